@@ -2,13 +2,17 @@
 """Headline benchmark: Mask R-CNN training throughput (images/s, whole job) and detect latency on
 synthetic 256x256 3-class radio tiles, float32, on N MI355X of one node (one process per GPU).
 Default workload = the one BASELINE.json's metric is quoted on (ResNet-101 256x256, nimg_per_gpu=4, i.e.
-configs[2] per GPU); at N=1 the line also carries configs[1] (ResNet-50, nimg_per_gpu=2) as a second leg.
+configs[2] per GPU); at N=1 a --full line also carries configs[1] (ResNet-50, nimg_per_gpu=2) as a second leg.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = forward + backward + gradient all-reduce (N > 1) + SGD update on IMAGES_PER_GPU images per
 rank, inputs resident in HBM.  Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+A plain run measures the headline only (set up, W warm-up steps, K timed steps); --full adds every other
+leg (positive-quota / 16-bit / direct-kernel steps, detect, train loop, rooflines, CPU baseline, configs[1]
+and configs[4], the exchange's cost at N > 1).  --dump-outputs DIR writes what the last timed step computed
+(see dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -205,6 +209,27 @@ def _train_loop_leg(args, res, model, cfg, nimg, world, rank, loader_threads=Non
              "exact_zero_skip; feed-inclusive, never `value`")
 
 
+DUMP_SAMPLE = 1 << 21                               # flat entries of params / grads kept by dump_outputs (8 MB each)
+
+
+def dump_outputs(out_dir, eng, losses):
+    """What the last timed step computed, for comparing two builds output for output: the five losses it returned
+    (losses), and one fixed, seeded set of up to DUMP_SAMPLE positions of the flat weight vector after its SGD update
+    (params_sample) and of its gradient buffer (grads_sample); the whole vectors are ~250 MB each at ResNet-101.
+    All float32.  The inputs are seeded and that step starts from the seeded initial weights (measure), so two runs with
+    the same arguments agree to rounding."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(eng.params.numel())
+    idx = np.unique(np.random.RandomState(0).randint(0, n, DUMP_SAMPLE))       # sorted, duplicates dropped
+    idx_d = torch.from_numpy(idx).to(eng.params.device)
+    arrays = {"losses": losses.detach().float().cpu().numpy(),
+              "params_sample": eng.params[idx_d].cpu().numpy(),
+              "grads_sample": eng.grads[idx_d].cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 TRAFFIC_PER_LAUNCH = {1024: None, 2048: 1.810e9}   # mask-head conv, PMC passes: profiles/r01_pmc_conv_traffic.md
 TRAFFIC_WGRAD_PER_LAUNCH = {1024: None, 2048: 4.55e9}   # its weight gradient (same file)
 # (ROIs, tiling) -> HBM-side bytes per launch of the roofline leg's GEMM: 2 x FETCH_SIZE (gfx950 reports half of wide reads, guide) +
@@ -212,8 +237,9 @@ TRAFFIC_WGRAD_PER_LAUNCH = {1024: None, 2048: 4.55e9}   # its weight gradient (s
 TRAFFIC_WINOGRAD_GEMM = {(2048, 6): 1.594e9}
 
 
-def measure(args, backbone, nimg, rank, local_rank, world, full):
-    """Train-step throughput (+ detect latency, roofline, cpu_baseline when ``full``) of one workload."""
+def measure(args, backbone, nimg, rank, local_rank, world, full, headline_only=False, dump_dir=None):
+    """Train-step throughput (+ detect latency, roofline, cpu_baseline when ``full``) of one workload.
+    ``headline_only``: the timed headline steps and nothing else (a plain bench run); ``dump_dir``: dump_outputs there."""
     import torch
     import torch.distributed as dist
     from caesar_mrcnn_amd import ops
@@ -229,7 +255,9 @@ def measure(args, backbone, nimg, rank, local_rank, world, full):
         model = MaskRCNN("training", cfg, "/tmp/mrcnn_bench_logs", device=dev, seed=0)
         model.compile(cfg.LEARNING_RATE, cfg.LEARNING_MOMENTUM)
     batch = synthetic_batch(cfg, nimg, seed=1234 + rank)
-    dev_inputs = model._to_device(batch)
+    # the proposal sampling keys seeded too: the same arguments give the same inputs run after run
+    keys = np.random.RandomState(99 + rank).uniform(0, 1, (nimg, cfg.POST_NMS_ROIS_TRAINING))
+    dev_inputs = model._to_device(batch, rand_keys=keys)
     eng = model.engine
     reducer = GradReducer(eng.grads, world, rank=rank, timing=True) if world > 1 else None
     eng.grad_ready = reducer.ready if reducer else None
@@ -258,13 +286,40 @@ def measure(args, backbone, nimg, rank, local_rank, world, full):
             dt_ = float(t.item())
         return dt_, ls
 
+    def set_state(state):
+        """Weights, momentum and skipped-step counter as the engine restores them after its own settle passes."""
+        eng.params.copy_(state[0])
+        eng.momentum.copy_(state[1])
+        eng.skipped_steps.copy_(state[2])
+        eng.wt_valid = eng._h16_valid = False
+        eng.fold_bn()
+
+    # the float atomics of the gradients make the weights drift apart from run to run within a few steps (the proposal and
+    # ROI selections amplify rounding), so the LAST timed step starts again from the seeded initial state: what it computes
+    # (dump_outputs, losses_last_step) then depends on the arguments alone.  Its work is that of every other step (fixed ROI
+    # counts); the restore itself is kept off the clock.
+    initial = (eng.params.clone(), eng.momentum.clone(), eng.skipped_steps.clone())
     # headline: every multiplication of the reference graph is executed (dense mask-head backward)
     eng.sparse_mask_bwd = False
     for _ in range(args.warmup):
         step()
     if reducer:
         reducer.pop_timing()
-    dt, losses = timed(args.steps)
+    dt = 0.0
+    if args.steps > 1:
+        dt, _ = timed(args.steps - 1)
+    trained = None if headline_only else (eng.params.clone(), eng.momentum.clone(), eng.skipped_steps.clone())
+    set_state(initial)
+    dt_last, losses = timed(1)
+    dt += dt_last
+    del initial
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, eng, losses)
+    if headline_only:
+        return {"backbone": backbone, "nimg": nimg, "ms_per_step": dt / args.steps * 1e3,
+                "images_per_s": nimg * world * args.steps / dt, "losses": [float(v) for v in losses.cpu().numpy()]}
+    set_state(trained)                                  # the other legs go on from the trained weights, as before
+    del trained
     comm = None
     if reducer:
         # what the gradient exchange costs: time on the exchange stream (HIP events around every range), bytes per range,
@@ -700,7 +755,16 @@ def main():
     ap.add_argument("--detect-iters", type=int, default=10)
     ap.add_argument("--dense-only", action="store_true", help="skip the exact-zero-skip timing loop (profiling)")
     ap.add_argument("--no-config4", action="store_true", help="skip the configs[4] leg (ResNet-101 512x512, 16-bit)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg besides the headline: positive-quota / 16-bit / direct-kernel steps, detect, train loop, "
+                         "rooflines, CPU baseline, configs[1], configs[4], exchange cost (N > 1); the --no-* / --dense-only / "
+                         "--detect-iters options act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (losses, seeded samples of the "
+                         "updated weights and of the gradients)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -712,9 +776,10 @@ def main():
     torch.cuda.set_device(torch.device("cuda", int(os.environ.get("MRCNN_FORCE_DEVICE", local_rank))))
 
     r_model_refs = []
-    r = measure(args, args.backbone, args.nimg, rank, local_rank, world, full=True)
+    r = measure(args, args.backbone, args.nimg, rank, local_rank, world, full=True, headline_only=not args.full,
+                dump_dir=args.dump_outputs)
     second = None
-    if world == 1 and not args.no_secondary and (args.backbone, args.nimg) != ("resnet50", 2):
+    if args.full and world == 1 and not args.no_secondary and (args.backbone, args.nimg) != ("resnet50", 2):
         torch.cuda.empty_cache()
         try:
             second = measure(args, "resnet50", 2, rank, local_rank, world, full=False)
@@ -722,7 +787,7 @@ def main():
             sys.stderr.write("configs[1] leg failed: %r\n" % (e,))
 
     cfg4 = None
-    if world == 1 and not args.no_config4 and not args.dense_only:
+    if args.full and world == 1 and not args.no_config4 and not args.dense_only:
         del r_model_refs[:]
         torch.cuda.empty_cache()
         try:
@@ -744,31 +809,35 @@ def main():
                                                                        "+RCCL all-reduce" if world > 1 else ""),
                        "global_batch": args.nimg * world, "parallelism": "dp%d" % world,
                        "weights": "random init (Keras defaults)"},
-            "detect_ms_per_image": rnd(r["detect_ms"]), "detect_ms_per_image_eager": rnd(r["detect_eager_ms"]),
-            "detect_ms_per_image_batch8": rnd(r["detect_ms_b8"]),
-            "detect_ms_per_image_f16_stages": rnd(r.get("detect_ms_f16")),
-            "detect_e2e_ms_per_image": (r.get("detect_e2e") or {}).get("ms_per_image"),
-            "detect_e2e": r.get("detect_e2e"),
-            "value_direct_conv_kernels": None if r.get("images_per_s_direct") is None else round(r["images_per_s_direct"], 3),
-            "note_direct_conv_kernels": "the same step with the Winograd path of the mask head switched off (direct 3x3 implicit-GEMM "
-                                        "kernels, MRCNN_WINOGRAD=0): `value` computes the same layers in float32 through F(4x4,3x3) tiles plus "
-                                        "a last row / column of 4x2, 2x4, 2x2 tiles -- 3.6x fewer matrix multiplications on 14x14 maps, "
-                                        "1.3e-5 of the direct result's range; F(2x2,3x3) under MRCNN_WINOGRAD_TILE=2: 2.25x, 1.6e-6 "
-                                        "(DESIGN.md 4.1d)",
-            "value_exact_zero_skip": None if args.dense_only else round(r["images_per_s_sparse"], 3),
-            "note_exact_zero_skip": "same step with the mask head (forward and backward) run on the <=168 positive-quota ROI "
-                                    "rows per image only: the other rows are never read by the loss and carry exactly-zero "
-                                    "gradient (identical losses and gradients, "
-                                    "tests/test_engine_gpu.py::test_sparse_mask_backward_equals_dense); product default, "
-                                    "never the headline value",
-            "value_f16_mask_head": None if args.dense_only else round(r["images_per_s_f16_mask_head"], 3),
-            "note_f16_mask_head": "BASELINE configs[4], stages 1-2: the headline (dense) step with the mask head (four 3x3 convolutions, "
-                                  "transposed convolution, output stage; forward, data and weight gradient) on the fp16 matrix "
-                                  "cores, float32 master weights / accumulation / gradients, loss scale 4096; reduced precision, "
-                                  "never the headline value",
-            "losses_last_step": [round(v, 5) for v in r["losses"]],
-            "roofline": r["roofline"],
         }
+        if args.full:
+            out.update({
+                "detect_ms_per_image": rnd(r["detect_ms"]), "detect_ms_per_image_eager": rnd(r["detect_eager_ms"]),
+                "detect_ms_per_image_batch8": rnd(r["detect_ms_b8"]),
+                "detect_ms_per_image_f16_stages": rnd(r.get("detect_ms_f16")),
+                "detect_e2e_ms_per_image": (r.get("detect_e2e") or {}).get("ms_per_image"),
+                "detect_e2e": r.get("detect_e2e"),
+                "value_direct_conv_kernels": None if r.get("images_per_s_direct") is None else round(r["images_per_s_direct"], 3),
+                "note_direct_conv_kernels": "the same step with the Winograd path of the mask head switched off (direct 3x3 implicit-GEMM "
+                                            "kernels, MRCNN_WINOGRAD=0): `value` computes the same layers in float32 through F(4x4,3x3) tiles plus "
+                                            "a last row / column of 4x2, 2x4, 2x2 tiles -- 3.6x fewer matrix multiplications on 14x14 maps, "
+                                            "1.3e-5 of the direct result's range; F(2x2,3x3) under MRCNN_WINOGRAD_TILE=2: 2.25x, 1.6e-6 "
+                                            "(DESIGN.md 4.1d)",
+                "value_exact_zero_skip": None if args.dense_only else round(r["images_per_s_sparse"], 3),
+                "note_exact_zero_skip": "same step with the mask head (forward and backward) run on the <=168 positive-quota ROI "
+                                        "rows per image only: the other rows are never read by the loss and carry exactly-zero "
+                                        "gradient (identical losses and gradients, "
+                                        "tests/test_engine_gpu.py::test_sparse_mask_backward_equals_dense); product default, "
+                                        "never the headline value",
+                "value_f16_mask_head": None if args.dense_only else round(r["images_per_s_f16_mask_head"], 3),
+                "note_f16_mask_head": "BASELINE configs[4], stages 1-2: the headline (dense) step with the mask head (four 3x3 convolutions, "
+                                      "transposed convolution, output stage; forward, data and weight gradient) on the fp16 matrix "
+                                      "cores, float32 master weights / accumulation / gradients, loss scale 4096; reduced precision, "
+                                      "never the headline value",
+            })
+        out["losses_last_step"] = [round(v, 5) for v in r["losses"]]
+        if args.full:
+            out["roofline"] = r["roofline"]
         for k in ("roofline_wgrad", "roofline_direct_conv", "roofline_direct_wgrad"):
             if k in r:
                 out[k] = r[k]

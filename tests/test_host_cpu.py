@@ -531,3 +531,29 @@ def test_resize_plan_matches_resize_image():
             s2, (oh, ow), pad2, win2 = utils.resize_plan(img.shape, min_dim, max_dim, 0, mode)
             assert s2 == scale and tuple(win2) == tuple(window) and [tuple(p) for p in pad2] == [tuple(p) for p in padding], (mode, h, w)
             assert out.shape[:2] == (oh + pad2[0][0] + pad2[0][1], ow + pad2[1][0] + pad2[1][1])
+
+
+def test_bench_dump_outputs_and_step_count(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files within 64 MB, the same seeded sample positions run after run; --steps < 1
+    is refused before any GPU work."""
+    import types
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 3 * bench.DUMP_SAMPLE
+    eng = types.SimpleNamespace(params=torch.arange(n, dtype=torch.float32), grads=-torch.arange(n, dtype=torch.float32))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), eng, torch.tensor([1.0, 2.0, 3.0, 4.0, 5.0]))
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == ["grads_sample.npy", "losses.npy", "params_sample.npy"]
+    total = 0
+    for f in names:
+        a, b = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert a.dtype == np.float32 and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    p = np.load(str(tmp_path / "a" / "params_sample.npy"))
+    assert 0.8 * bench.DUMP_SAMPLE < p.size <= bench.DUMP_SAMPLE and np.all(np.diff(p) > 0)
+    np.testing.assert_array_equal(np.load(str(tmp_path / "a" / "grads_sample.npy")), -p)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr
