@@ -12,6 +12,7 @@ Gradient plumbing conventions
 """
 import contextlib
 import gc
+import operator
 import os
 import numpy as np
 import torch
@@ -29,6 +30,65 @@ H16_WIDE_LAYERS = ("fpn_p2", "fpn_p3", "fpn_p4", "fpn_p5", "rpn_conv_shared", "m
 
 LOSS_NAMES = ("rpn_class_loss", "rpn_bbox_loss", "mrcnn_class_loss", "mrcnn_bbox_loss", "mrcnn_mask_loss")
 
+
+_on = lambda s: s != "0"        # an environment switch is on unless it is "0"
+
+# The engine's switches: (attribute, environment variable or None, default, parser, paths that read it: "t" the training step,
+# "i" inference, "" construction only).  __init__ reads them once; they stay plain attributes that tests and bench.py flip
+# between calls, so a recorded step is keyed by the "t" switches (_mode_key) and a captured inference graph by the "i" ones.
+SWITCHES = (
+    # BASELINE configs[4], stage 1: torch.float16 / torch.bfloat16 runs the four 3x3 convolutions of the mask head (forward, data
+    # and weight gradient) on the 16-bit matrix cores; master weights, accumulation and every gradient buffer stay float32.
+    # None = float32 everywhere.  loss_scale guards float16 gradients.
+    ("head_dtype", None, None, None, "ti"),
+    ("sparse_mask_bwd", None, True, None, "t"),                 # skip the exactly-zero rows of the mask-head backward
+    ("h16_wide", "MRCNN_H16_WIDE", True, _on, "ti"),            # False: only the mask head in 16 bits (round-1 stages 1-2)
+    ("h16_blocks", "MRCNN_H16_BLOCKS", True, _on, "ti"),        # bottleneck blocks in 16 bits (stage 4)
+    ("h16_all_blocks", "MRCNN_H16_ALL_BLOCKS", True, _on, "ti"),    # False: only the identity blocks of res4 / res5
+    ("h16_fused_bwd", "MRCNN_H16_FUSED_BWD", True, _on, "t"),   # 16-bit data gradients carry the lower layer's epilogue backward
+    ("h16_roialign", "MRCNN_H16_ROIALIGN", True, _on, "ti"),    # ROI heads gather from the 16-bit pyramid (mrcnn_roialign_*_h16)
+    # the persistent 256 x 256 16-bit kernel for the mask head's DATA gradients too (they run beside the weight gradients of the
+    # other stream; False keeps them on the small-LDS kernel that shares CUs)
+    ("h16_phase_bwd", "MRCNN_H16_PHASE_BWD", True, _on, "t"),
+    # Winograd F(2x2, 3x3) for the float32 3x3 convolutions of the mask head (forward and data gradients): 2.25 x fewer
+    # matrix-core flops through three launches per layer; False keeps the direct kernels
+    ("winograd", "MRCNN_WINOGRAD", True, _on, "ti"),
+    ("winograd_wgrad", "MRCNN_WINOGRAD_WGRAD", True, _on, "t"),     # weight gradients through the same domain
+    # the trunk's large 3x3 layers (FPN smoothing, RPN shared convolution on levels of >= trunk_winograd_min_rows pixels)
+    # through F(2x2, 3x3) in the forward pass (A/B switch, see DESIGN 4.1e for the measurement)
+    ("trunk_winograd", "MRCNN_WINOGRAD_TRUNK", True, _on, "ti"),
+    ("trunk_winograd_min_rows", "MRCNN_WINOGRAD_TRUNK_MIN_ROWS", 4096, int, "ti"),
+    # the mask head of the inference graph: 4 = uniform F(4x4, 3x3) tiles (16 overhanging tiles per 14 x 14 map: 36 x 1600 GEMM rows
+    # for 100 detections where F(2x2) has 16 x 4900; 1.3e-5 of the result's range instead of 1.6e-6, on probabilities that are
+    # thresholded at 0.5) -- detect graph 2.73 -> 2.60 ms; 2 = F(2x2) as in rounds 1-2
+    ("infer_mask_tile", "MRCNN_WINOGRAD_INFER_MASK_TILE", 4, int, "i"),
+    # forward as two half-batch chains on two streams: +0.7 ms with the F(2x2) layers, level with the uniform F(4x4) tiling, a loss with
+    # the mixed tiling (its small tile groups halve again: ResNet-101 / 4 images 37.6 -> 37.4 ms, ResNet-50 / 2 images 20.8 -> 20.0) -> off
+    ("winograd_split", "MRCNN_WINOGRAD_SPLIT", False, _on, "ti"),
+    # the 16 x 16-tile single-launch kernel for the layers of a few hundred pixels of the inference trunk (see infer)
+    ("sk16_infer", "MRCNN_SK16_INFER", True, _on, "i"),
+    ("fused_mask_out_bwd", None, True, None, "t"),              # single-pass backward of the mask-head output stage
+    ("fused_dgrad_epilogue", None, True, None, "t"),            # mask-head data-gradient convs apply the lower layer's epilogue bwd
+    # A/B switch, default OFF (measured, DESIGN.md "rejected"): the mask head's weight gradients feed nothing in the
+    # backward chain, so they can be held back and issued (auxiliary stream) when the backbone's backward pass starts,
+    # to fill the chip beside its ~330 small launches; "wgrad_lds_pad" then keeps one workgroup slot per CU free for
+    # those.  Result on ResNet-101, 4 images, dense: 60.56 -> 60.26 ms (pad 0), 60.81 (pad 8192): the small kernels are
+    # paced by the matrix pipe of their SIMD (serial K chains of 64-cycle fp32 MFMAs), which the large kernel keeps
+    # 88 % busy -- beside it they run 4x slower (18 -> 73 us) and the large kernels 1.45x slower: zero sum.
+    ("defer_mask_wgrad", "MRCNN_DEFER_MASK_WGRAD", False, _on, "t"),
+    ("defer_lds_pad", "MRCNN_DEFER_LDS_PAD", 8192, int, "t"),
+    ("gather_roialign_bwd", "MRCNN_GATHER_ROIALIGN_BWD", True, _on, "t"),   # class-head ROIAlign adjoint in gather form
+    ("multi_launch", "MRCNN_MULTI_LAUNCH", True, _on, "ti"),    # independent small convolutions share launches
+    # stream priorities (HIP: -1 high, 0 normal, 1 low where the runtime has three levels): the weight gradients are off the
+    # critical path, so their stream may be given a lower priority than the chain of data gradients it runs beside
+    ("wgrad_prio", "MRCNN_WGRAD_PRIO", 0, int, ""),
+    ("aux_prio", "MRCNN_AUX_PRIO", 0, int, ""),
+)
+_TRAIN_SWITCHES = operator.attrgetter(*(s[0] for s in SWITCHES if "t" in s[4]))
+_INFER_SWITCHES = operator.attrgetter(*(s[0] for s in SWITCHES if "i" in s[4]))
+# config values infer() passes by value into its launches (with RPN_BBOX_STD_DEV / BBOX_STD_DEV: infer_graphed's key)
+_INFER_CFG = operator.attrgetter("PRE_NMS_LIMIT", "POST_NMS_ROIS_INFERENCE", "RPN_NMS_THRESHOLD", "DETECTION_MAX_INSTANCES",
+                                 "DETECTION_MIN_CONFIDENCE", "DETECTION_NMS_THRESHOLD")
 
 
 @contextlib.contextmanager
@@ -115,9 +175,6 @@ class ConvOp(object):
         x = ctx[0]
         kh, kw, cin, cout = self.wshape
         N, H, W, _ = x.shape
-        fresh = self.model.wt_valid                     # refreshed for all layers at once (refresh_wt)
-        if not fresh and not (self.padding == "valid" and kh > 1):
-            ops.weight_flip_transpose(self.w, self.wt)
         res = out if accumulate else None
         rm = RES_SAME if accumulate else RES_NONE
         if self.stride == 1 and self.padding == "same":
@@ -140,8 +197,6 @@ class ConvOp(object):
             if out is None:
                 out = ops.empty_like(x)
             wt2 = self.wt.view(1, 1, cout, kh * kw * cin)
-            if not fresh:
-                ops.weight_flip_transpose(self.w.view(1, 1, kh * kw * cin, cout), wt2)
             ops.conv2d(dz.view(N, 1, 1, cout), wt2, res=None if res is None else res.view(N, 1, 1, -1), stride=1,
                        padding="valid", res_mode=rm, out=out.view(N, 1, 1, kh * kw * cin))
         else:
@@ -216,7 +271,7 @@ class MaskRCNNEngine(object):
             from . import _hip
             _hip.set_device_index(torch.device(device).index if torch.device(device).index is not None
                                   else torch.cuda.current_device())
-        self.wt_valid = False
+        self._gen, self._wt_gen = 0, -1     # weight generation (params_changed) and the one the flipped kernels were built from
         self.set_trainable("all")
         self.set_weights(weights if weights is not None else init_weights(L, seed))
         self._anchor_cache = {}
@@ -232,63 +287,20 @@ class MaskRCNNEngine(object):
                             2: (s2, s3), "head": (0, s2), "bn": (L.gamma_offset, L.total)}
         self.grad_ready = None          # callable(start, end) or None
         self.forced_rpn_rois = None     # test hook: [B, POST_NMS_ROIS_TRAINING, 4] used instead of the ProposalLayer's output
-        self.sparse_mask_bwd = True     # skip the exactly-zero rows of the mask-head backward
-        # BASELINE configs[4], stage 1: torch.float16 / torch.bfloat16 runs the four 3x3 convolutions of the mask head
-        # (forward, data and weight gradient) on the 16-bit matrix cores; master weights, accumulation and every
-        # gradient buffer stay float32.  None (default) = float32 everywhere.  loss_scale guards float16 gradients.
-        self.head_dtype = None
         self.loss_scale = 4096.0
         self.skipped_steps = torch.zeros(1, dtype=torch.int32, device=device)   # steps the guarded optimiser refused (float16)
         self._skipped_seen = 0
-        self.h16_wide = os.environ.get("MRCNN_H16_WIDE", "1") != "0"   # False: only the mask head in 16 bits (round-1 stages 1-2)
-        self.h16_blocks = os.environ.get("MRCNN_H16_BLOCKS", "1") != "0"   # bottleneck blocks in 16 bits (stage 4)
-        self.h16_all_blocks = os.environ.get("MRCNN_H16_ALL_BLOCKS", "1") != "0"   # 0: only the identity blocks of res4 / res5
-        self.h16_fused_bwd = os.environ.get("MRCNN_H16_FUSED_BWD", "1") != "0"     # 16-bit data gradients carry the lower layer's epilogue backward
-        self.h16_roialign = os.environ.get("MRCNN_H16_ROIALIGN", "1") != "0"       # ROI heads gather from the 16-bit pyramid (mrcnn_roialign_fwd_h16 / _bwd_h16)
-        self._h16 = {}
-        # Winograd F(2x2, 3x3) for the float32 3x3 convolutions of the mask head (forward and data gradients): 2.25 x fewer
-        # matrix-core flops through three launches per layer; MRCNN_WINOGRAD=0 keeps the direct kernels
-        self.winograd = os.environ.get("MRCNN_WINOGRAD", "1") != "0"
-        self.winograd_wgrad = os.environ.get("MRCNN_WINOGRAD_WGRAD", "1") != "0"    # weight gradients through the same domain
-        # the trunk's large 3x3 layers (FPN smoothing, RPN shared convolution on levels of >= 16 384 pixels) through F(2x2, 3x3)
-        # in the forward pass (A/B switch, see DESIGN 4.1e for the measurement)
-        self.sk16_infer = os.environ.get("MRCNN_SK16_INFER", "1") != "0"
-        # the mask head of the inference graph: 4 = uniform F(4x4, 3x3) tiles (16 overhanging tiles per 14 x 14 map: 36 x 1600 GEMM rows
-        # for 100 detections where F(2x2) has 16 x 4900; 1.3e-5 of the result's range instead of 1.6e-6, on probabilities that are
-        # thresholded at 0.5) -- detect graph 2.73 -> 2.60 ms; 2 = F(2x2) as in rounds 1-2
-        self.infer_mask_tile = int(os.environ.get("MRCNN_WINOGRAD_INFER_MASK_TILE", "4"))
-        self.trunk_winograd = os.environ.get("MRCNN_WINOGRAD_TRUNK", "1") != "0"
-        self.trunk_winograd_min_rows = int(os.environ.get("MRCNN_WINOGRAD_TRUNK_MIN_ROWS", "4096"))
-        # forward as two half-batch chains on two streams: +0.7 ms with the F(2x2) layers, level with the uniform F(4x4) tiling, a loss with
-        # the mixed tiling (its small tile groups halve again: ResNet-101 / 4 images 37.6 -> 37.4 ms, ResNet-50 / 2 images 20.8 -> 20.0) -> off
-        self.winograd_split = os.environ.get("MRCNN_WINOGRAD_SPLIT", "0") != "0"
+        for name, env, default, parse, _ in SWITCHES:
+            v = os.environ.get(env) if env else None
+            setattr(self, name, default if v is None else parse(v))
+        self._h16, self._h16_gen = {}, None     # 16-bit images of head_dtype, and the (weight generation, dtype) they hold
         self._wino_V = {}               # layer -> input transform V of this step's forward pass
-        self._wino = {}                 # layer -> [U forward, U data gradient] (allocated once, refreshed after weight updates)
-        self._wino_valid = {}           # layer -> [forward valid, data-gradient valid]
+        self._wino = {}                 # (layer, tile, 0 forward / 1 data gradient) -> [U, weight generation]; stable addresses
+        self._wino_reads = set()        # keys of _wino read since infer_graphed last cleared it
         self._h16_store = {}            # dtype -> {layer: (W^T image, data-gradient image)}, stable addresses
         self._h16_tables = {}           # (dtype, layer names) -> table of the one-launch refresh (ops.h16_image_table)
-        self._h16_valid = False
-        self.fused_mask_out_bwd = True  # single-pass backward of the mask-head output stage
-        # the persistent 256 x 256 16-bit kernel for the mask head's DATA gradients too (they run beside the weight gradients
-        # of the other stream; MRCNN_H16_PHASE_BWD=0 keeps them on the small-LDS kernel that shares CUs)
-        self.h16_phase_bwd = os.environ.get("MRCNN_H16_PHASE_BWD", "1") != "0"
-        self.fused_dgrad_epilogue = True  # data-gradient convs of the mask head apply the lower layer's epilogue backward
-        # stream priorities (HIP: -1 high, 0 normal, 1 low where the runtime has three levels): the weight gradients are off the
-        # critical path, so their stream may be given a lower priority than the chain of data gradients it runs beside
-        wprio = int(os.environ.get("MRCNN_WGRAD_PRIO", "0"))
-        aprio = int(os.environ.get("MRCNN_AUX_PRIO", "0"))
-        self.wgrad_stream, self.aux_stream = _side_streams(device, wprio, aprio)
-        # A/B switch, default OFF (measured, DESIGN.md "rejected"): the mask head's weight gradients feed nothing in the
-        # backward chain, so they can be held back and issued (auxiliary stream) when the backbone's backward pass starts,
-        # to fill the chip beside its ~330 small launches; "wgrad_lds_pad" then keeps one workgroup slot per CU free for
-        # those.  Result on ResNet-101, 4 images, dense: 60.56 -> 60.26 ms (pad 0), 60.81 (pad 8192): the small kernels are
-        # paced by the matrix pipe of their SIMD (serial K chains of 64-cycle fp32 MFMAs), which the large kernel keeps
-        # 88 % busy -- beside it they run 4x slower (18 -> 73 us) and the large kernels 1.45x slower: zero sum.
-        self.defer_mask_wgrad = os.environ.get("MRCNN_DEFER_MASK_WGRAD", "0") != "0"
-        self.defer_lds_pad = int(os.environ.get("MRCNN_DEFER_LDS_PAD", "8192"))
+        self.wgrad_stream, self.aux_stream = _side_streams(device, self.wgrad_prio, self.aux_prio)
         self._deferred = []
-        self.gather_roialign_bwd = os.environ.get("MRCNN_GATHER_ROIALIGN_BWD", "1") != "0"   # class-head ROIAlign adjoint in gather form
-        self.multi_launch = os.environ.get("MRCNN_MULTI_LAUNCH", "1") != "0"     # independent small convolutions share launches
 
     def op(self, name):
         return self._ops[name]
@@ -342,32 +354,45 @@ class MaskRCNNEngine(object):
         dz.record_stream(ws)
         x.record_stream(ws)
 
-    # every site that invalidates the 16-bit weight images (optimiser step, set_weights, graph / tape replay, warm-up roll
-    # back) changes the weights: the Winograd-domain kernels go stale with them
-    @property
-    def _h16_valid(self):
-        return self._h16_valid_flag
+    # ---- images derived from the weights ------------------------------------------------------------
+    # The flipped / transposed kernels (wt), the 16-bit operand images and the Winograd-domain kernels U remember the weight
+    # generation they were built from; where one is read while stale it is rebuilt in place (captured graphs and recorded
+    # tapes hold its address).  The folded BatchNorm is rebuilt at once.
+    def params_changed(self, fold=True):
+        """The one way a change of `params` (set_weights, the optimiser step, a replayed step, a roll-back) reaches the derived
+        images: a new weight generation.  fold=False: the replayed step already folded BatchNorm inside the recording."""
+        self._gen += 1
+        if fold:
+            self.fold_bn()
 
-    @_h16_valid.setter
-    def _h16_valid(self, v):
-        self._h16_valid_flag = bool(v)
-        if not v:
-            self._wino_valid = {}
+    # compatibility shim: an assignment to either marks every derived image stale (`eng.wt_valid = eng._h16_valid = False`,
+    # then fold_bn(), after writing params directly)
+    wt_valid = _h16_valid = property(fset=lambda self, _: self.params_changed(fold=False))
+
+    def refresh_wt(self):
+        """Flipped / transposed kernels of every layer from the current parameters (one launch), when stale."""
+        if self._wt_gen != self._gen:
+            ops.weight_flip_transpose_batched(self.params, self.wt, self._flip_table)
+            self._wt_gen = self._gen
 
     def _wino_U(self, op, which, xshape, train=True, infer_tile=2):
         """Winograd-domain kernel of layer `op` for an input of shape xshape (in training the shape picks the tile size; inference
         takes `infer_tile`, whatever the batch: F(2x2, 3x3) for the trunk -- the RPN scores feed index-exact proposal selection --,
-        the uniform F(4x4, 3x3) tiling for the mask head, whose output is thresholded at 0.5): which = 0 forward (from op.w), 1 data
-        gradient (from the flipped / transposed op.wt, which must be current).  Refreshed lazily after every weight update, in place."""
-        tile = ops.winograd_tile(tuple(xshape)) if train else infer_tile
-        key = (op.name, tile)
+        the uniform F(4x4, 3x3) tiling for the mask head, whose output is thresholded at 0.5): which = 0 forward, 1 data gradient."""
+        key = (op.name, ops.winograd_tile(tuple(xshape)) if train else infer_tile, which)
+        self._wino_reads.add(key)
+        return self._wino_fresh(key)
+
+    def _wino_fresh(self, key):
+        """The U of `key`, rebuilt in place when stale: from op.w (forward) or from the flipped / transposed op.wt."""
         ent = self._wino.setdefault(key, [None, None])
-        ok = self._wino_valid.setdefault(key, [False, False])
-        if not ok[which]:
-            src = op.w if which == 0 else op.wt
-            ent[which] = ops.winograd_weights(src, out=ent[which], tile=tile)
-            ok[which] = True
-        return ent[which]
+        if ent[1] != self._gen:
+            name, tile, which = key
+            op = self.op(name)
+            assert which == 0 or self._wt_gen == self._gen
+            ent[0] = ops.winograd_weights(op.w if which == 0 else op.wt, out=ent[0], tile=tile)
+            ent[1] = self._gen
+        return ent[0]
 
     def _wino_ok(self, op, xshape, min_rows=None):
         return (self.winograd and self.head_dtype is None and
@@ -381,7 +406,7 @@ class MaskRCNNEngine(object):
 
     def _ensure_h16(self):
         """16-bit operand images (W^T and the rotated data-gradient image) of the mask-head convolutions."""
-        if self._h16_valid and self._h16.get("dtype") == self.head_dtype:
+        if self._h16_gen == (self._gen, self.head_dtype):
             return
         # one set of images per dtype, allocated once and refreshed IN PLACE: captured HIP graphs (infer_graphed) hold
         # their addresses, so a weight update must never move them
@@ -402,8 +427,7 @@ class MaskRCNNEngine(object):
             for op, wn in tab[1]:
                 kh, kw, cin, cout = op.wshape
                 ops.cast_to_h16(op.w.view(kh * kw * cin, cout), self.head_dtype, out=wn)
-            self._h16 = dict(imgs, dtype=self.head_dtype)
-            self._h16_valid = True
+            self._h16, self._h16_gen = imgs, (self._gen, self.head_dtype)
             return
         for name in names:
             op = self.op(name)
@@ -430,8 +454,7 @@ class MaskRCNNEngine(object):
             self._h16_tables[tkey] = (ops.h16_image_table(self.params, entries, self.dev), casts)
         except AssertionError:
             pass                                            # a kernel that is not a view into the flat buffer: stay layer by layer
-        self._h16 = dict(imgs, dtype=self.head_dtype)
-        self._h16_valid = True
+        self._h16, self._h16_gen = imgs, (self._gen, self.head_dtype)
 
     @staticmethod
     def _h16_shape_ok(op):
@@ -616,7 +639,7 @@ class MaskRCNNEngine(object):
         """[ConvOp.dgrad(dz, ctx, out, accumulate)] for stride-1 SAME / 1x1 layers as one launch (else the loop)."""
         outs = list(outs) if outs is not None else [None] * len(layers)
         accs = list(accumulate) if isinstance(accumulate, (list, tuple)) else [accumulate] * len(layers)
-        ok = self.multi_launch and self.wt_valid and 1 < len(layers) <= 5 and all(
+        ok = self.multi_launch and 1 < len(layers) <= 5 and all(
             op.stride == 1 and (op.padding == "same" or (op.wshape[0] == 1 and op.wshape[1] == 1)) for op in layers)
         if ok:
             probs = []
@@ -733,15 +756,8 @@ class MaskRCNNEngine(object):
             self._aux_pending = False
 
     # ---- weights in / out (Keras layouts at this boundary) --------------------------------------
-    def refresh_wt(self):
-        """Flipped / transposed kernels of every layer from the current parameters (one launch)."""
-        ops.weight_flip_transpose_batched(self.params, self.wt, self._flip_table)
-        self.wt_valid = True
-
     def set_weights(self, weights, strict=True):
         L = self.layout
-        self.wt_valid = False
-        self._h16_valid = False
         for name, (off, n, shape) in L.offsets.items():
             if name not in weights:
                 if strict:
@@ -760,7 +776,7 @@ class MaskRCNNEngine(object):
                     buf[c0:c0 + c].copy_(torch.from_numpy(np.asarray(weights[l.bn + "/" + key], dtype=np.float32)))
                 elif strict:
                     raise KeyError("missing weight tensor %s/%s" % (l.bn, key))
-        self.fold_bn()
+        self.params_changed()
 
     def get_weights(self, grads=False):
         L = self.layout
@@ -1076,10 +1092,12 @@ class MaskRCNNEngine(object):
                 "rpn_class": rpn_probs, "rpn_bbox": rpn_bbox, "pyramid": pyr}
 
     def infer_graphed(self, images, windows_norm):
-        """infer() replayed from a HIP graph (one capture per input shape): the ~450 launches of a
+        """infer() replayed from a HIP graph (one capture per input shape and mode): the ~450 launches of a
         batch-1 detect pass are host-bound when issued one by one.  `images` / `windows_norm` may be host
         or device tensors; they are copied into the graph's static input buffers."""
-        key = (tuple(images.shape), tuple(windows_norm.shape), id(self.cfg), self.head_dtype)
+        cfg = self.cfg              # the key: what the capture bakes in besides its buffers (cfg is mutable: patched in place)
+        key = (tuple(images.shape), tuple(windows_norm.shape), id(cfg), _INFER_SWITCHES(self), _INFER_CFG(cfg),
+               np.asarray(cfg.RPN_BBOX_STD_DEV, np.float32).tobytes(), np.asarray(cfg.BBOX_STD_DEV, np.float32).tobytes())
         entry = self._infer_graphs.get(key)
         if self.head_dtype is not None:
             self._ensure_h16()      # outside the graph: the 16-bit weight images follow set_weights / apply_gradients in place
@@ -1095,11 +1113,14 @@ class MaskRCNNEngine(object):
                     self.infer(sx, sw)
             _hip_mod.stream_wait(torch.cuda.current_stream(self.dev), side)
             graph = torch.cuda.CUDAGraph()
+            self._wino_reads.clear()
             with _capture(graph):
                 out = self.infer(sx, sw)
-            entry = (graph, sx, sw, out)
+            entry = (graph, sx, sw, out, tuple(self._wino_reads))
             self._infer_graphs[key] = entry
-        graph, sx, sw, out = entry
+        graph, sx, sw, out, wino_keys = entry
+        for k in wino_keys:         # and so do the Winograd-domain kernels the capture reads
+            self._wino_fresh(k)
         sx.copy_(images, non_blocking=True)
         sw.copy_(windows_norm, non_blocking=True)
         graph.replay()
@@ -1145,15 +1166,13 @@ class MaskRCNNEngine(object):
                     self._ensure_h16()                 # 16-bit weight images: first needed by the FPN (wide mode) / after the trunk
                     h16_ev = _hip_mod.ev_record(self.wgrad_stream)
                 ops.fill_zero(self.grads)
-                if not self.wt_valid:
-                    self.refresh_wt()
+                self.refresh_wt()
             prep_ev = _hip_mod.ev_record(self.wgrad_stream)
             if h16_ev is not None and self.h16_wide:
                 _hip_mod.ev_wait(torch.cuda.current_stream(self.dev), h16_ev)
         else:
             ops.fill_zero(self.grads)
-            if not self.wt_valid:
-                self.refresh_wt()
+            self.refresh_wt()
         pyr, tape = self._trunk_fwd(images, True)
         rpn_logits, rpn_probs, rpn_bbox, rpn_tape = self._rpn_fwd(pyr, True)
         anchors = self.anchors((H, W, images.shape[3]))
@@ -1208,6 +1227,7 @@ class MaskRCNNEngine(object):
         losses, d_rpn_logits, d_rpn_bbox, d_logits, d_mbbox, d_mmask = out
         if prep_ev is not None:
             _hip_mod.ev_wait(main, prep_ev)
+        assert self._wt_gen == self._gen, "the backward pass reads the flipped kernels of the current weights"
 
         # ---- pyramid gradient accumulators ------------------------------------------------------
         dP = [ops.empty_like(p) for p in pyr[:4]]
@@ -1299,8 +1319,6 @@ class MaskRCNNEngine(object):
             dzg = ops.pixel_unshuffle2(dzu)                             # [M,14,14,1024]
         if d16 is None:
             self._mask_wgrad("f32", x_in, dzg, dc.wshape, 1, "valid", dc.dw, False)
-            if not self.wt_valid:
-                ops.weight_flip_transpose(dc.w, dc.wt)
         if self.head_dtype is None:
             # every data-gradient convolution applies the epilogue backward of the layer below in its own epilogue
             # (mrcnn_conv2d_dgrad_ep): the gradient w.r.t. the activated output is never written or re-read
@@ -1315,12 +1333,8 @@ class MaskRCNNEngine(object):
                     self._mask_wgrad("f32", *op.wgrad_item(dz, c))
                 kh, kw, cin, cout = op.wshape
                 wino = self._wino_ok(op, c[0].shape)
-                if wino and not self.wt_valid:
-                    ops.weight_flip_transpose(op.w, op.wt)
                 if k + 1 < len(chain):
                     below, bctx = chain[k + 1]
-                    if not self.wt_valid and not wino:
-                        ops.weight_flip_transpose(op.w, op.wt)
                     if wino and self.fused_dgrad_epilogue and below.bn is not None:
                         _, bz, bout, bact = bctx
                         dz = ops.conv2d_dgrad_ep_winograd(dz, self._wino_U(op, 1, dz.shape), bout if bact != ACT_NONE else None, bz, below.scale,
@@ -1403,7 +1417,7 @@ class MaskRCNNEngine(object):
         B, A = d_logits.shape[0], d_logits.shape[1]
         shared, cls, box = self.op("rpn_conv_shared"), self.op("rpn_class_raw"), self.op("rpn_bbox_pred")
         dP6 = None
-        if self.multi_launch and self.wt_valid and len(rpn_tape) == 5:
+        if self.multi_launch and len(rpn_tape) == 5:
             # level by level only what is elementwise; the data-gradient convolutions of the five levels share launches
             n = len(rpn_tape)
             dzl, dzb, heads = [], [], []
@@ -1551,9 +1565,6 @@ class MaskRCNNEngine(object):
             dzc, dy = blk.c2c.epilogue_bwd(d_out, cc, want_dy=True)
         # 2c -> 2b -> 2a: each data-gradient convolution (or its split-K reduction) applies the epilogue backward of
         # the layer below (mrcnn_conv2d_dgrad_ep)
-        if not self.wt_valid:
-            ops.weight_flip_transpose(blk.c2c.w, blk.c2c.wt)
-            ops.weight_flip_transpose(blk.c2b.w, blk.c2b.wt)
         dzb = self._dgrad_ep(dzc, blk.c2c.wt, "valid", blk.c2b, cb)
         dza = self._dgrad_ep(dzb, blk.c2b.wt, (1, 1), blk.c2a, ca)
         # the block's weight gradients travel together (they trail the data gradients on their stream anyway)
@@ -1576,7 +1587,7 @@ class MaskRCNNEngine(object):
         """dx = dgrad_2a(dza) + acc with the output epilogue backward of the block below fused into the split-K reduction:
         returns (dz of below's 2c convolution, masked gradient for below's shortcut), or None when that data gradient is not
         a dense stride-1 split-K layer (the caller then takes the two-launch route)."""
-        if below is None or not self.fused_dgrad_epilogue or not self.wt_valid or blk.c2a.stride != 1:
+        if below is None or not self.fused_dgrad_epilogue or blk.c2a.stride != 1:
             return None
         pblk, pcc = below
         op = pblk.c2c
@@ -1591,19 +1602,24 @@ class MaskRCNNEngine(object):
     # =========================================================================================
     #  the whole training step as one HIP graph
     # =========================================================================================
-    _MODE_ATTRS = ("sparse_mask_bwd", "h16_wide", "h16_blocks", "h16_all_blocks", "h16_fused_bwd", "h16_phase_bwd", "winograd",
-                   "winograd_wgrad", "winograd_split", "fused_mask_out_bwd", "fused_dgrad_epilogue", "defer_mask_wgrad",
-                   "gather_roialign_bwd", "multi_launch", "h16_roialign", "trunk_winograd", "trunk_winograd_min_rows")
-
     def _mode_key(self):
         """Every engine switch a captured graph / recorded launch tape bakes in besides the tensors: a replay is only valid for the
         mode it was made in (tests and tools flip these attributes between steps of one engine)."""
         # ... and what a launch bakes in by VALUE: the loss weights and the clip norm are scalar arguments of recorded calls
         # (cfg is mutable: run.py patches it in place).  The trainable mask / weight decay live in gran_coef, a buffer with a
         # stable address that set_trainable refreshes in place, so recordings survive a change of `layers`.
-        return tuple(getattr(self, a, None) for a in self._MODE_ATTRS) + (
-            float(self.loss_scale), self.forced_rpn_rois is not None, tuple(self.loss_weights()),
-            float(self.cfg.GRADIENT_CLIP_NORM))
+        return _TRAIN_SWITCHES(self) + (float(self.loss_scale), self.forced_rpn_rois is not None, tuple(self.loss_weights()),
+                                        float(self.cfg.GRADIENT_CLIP_NORM))
+
+    @contextlib.contextmanager
+    def _rolled_back(self):
+        """Settle passes (they size every workspace, arena slot and weight image before a capture or recording) are no training
+        steps: weights, momentum and the skipped-step counter (a float16 overflow there is no skipped step) are restored."""
+        keep = (self.params.clone(), self.momentum.clone(), self.skipped_steps.clone())
+        yield
+        for t, k in zip((self.params, self.momentum, self.skipped_steps), keep):
+            t.copy_(k)
+        self.params_changed()
 
     def step_graphed(self, dev_inputs, learning_rate, momentum):
         """forward_backward + apply_gradients (single rank) replayed from a HIP graph: one capture per input signature,
@@ -1612,8 +1628,8 @@ class MaskRCNNEngine(object):
         step (main, weight gradients, auxiliary) fork from and re-join the capturing stream, so the graph keeps their
         concurrency.  Inputs are copied into the graph's static buffers; the returned losses tensor is the graph's static
         output (valid until the next replay).  Nothing on this path may use memset / memcpy nodes."""
-        key = (tuple((tuple(t.shape), t.dtype) for t in dev_inputs), float(learning_rate), float(momentum), self.head_dtype,
-               id(self.cfg), self._mode_key())
+        key = (tuple((tuple(t.shape), t.dtype) for t in dev_inputs), float(learning_rate), float(momentum), id(self.cfg),
+               self._mode_key())
         entry = self._train_graphs.get(key)
         main = torch.cuda.current_stream(self.dev)
         if entry is None:
@@ -1621,21 +1637,14 @@ class MaskRCNNEngine(object):
             static = [torch.empty_like(t) for t in dev_inputs]
             for s_, t in zip(static, dev_inputs):
                 s_.copy_(t)
-            # two eager steps size every workspace, arena slot and weight image; they must not count as training steps
-            keep = (self.params.clone(), self.momentum.clone(), self.skipped_steps.clone())
-            side = torch.cuda.Stream(device=self.dev)
-            _hip_mod.stream_wait(side, main)
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self.forward_backward(*static)
-                    self.apply_gradients(learning_rate, momentum, 1)
-                self.params.copy_(keep[0])
-                self.momentum.copy_(keep[1])
-                self.skipped_steps.copy_(keep[2])
-                self.wt_valid = self._h16_valid = False
-                self.fold_bn()
-            _hip_mod.stream_wait(main, side)
-            del keep
+            with self._rolled_back():                       # two eager steps on a side stream
+                side = torch.cuda.Stream(device=self.dev)
+                _hip_mod.stream_wait(side, main)
+                with torch.cuda.stream(side):
+                    for _ in range(2):
+                        self.forward_backward(*static)
+                        self.apply_gradients(learning_rate, momentum, 1)
+                _hip_mod.stream_wait(main, side)
             graph = torch.cuda.CUDAGraph()
             with _capture(graph):
                 losses = self.forward_backward(*static)
@@ -1647,8 +1656,7 @@ class MaskRCNNEngine(object):
             if s_.data_ptr() != t.data_ptr():
                 s_.copy_(t, non_blocking=True)
         graph.replay()
-        # the captured step ends with the optimiser: the flipped / 16-bit weight images are stale for eager callers
-        self.wt_valid = self._h16_valid = False
+        self.params_changed(fold=False)                     # the captured step ends with the optimiser
         return losses
 
     def step_taped(self, dev_inputs, learning_rate, momentum, world_size=1, reducer=None):
@@ -1663,8 +1671,8 @@ class MaskRCNNEngine(object):
         data-parallel step is re-issued like a single-rank one.  The settle pass runs WITHOUT the hooks (local, rolled
         back): every call of this function then enters exactly one set of collectives whether it records or replays, so ranks
         that record in different steps cannot desynchronise."""
-        key = (tuple((tuple(t.shape), t.dtype) for t in dev_inputs), float(learning_rate), float(momentum), self.head_dtype,
-               id(self.cfg), torch.cuda.current_stream(self.dev).cuda_stream, self._mode_key(), int(world_size),
+        key = (tuple((tuple(t.shape), t.dtype) for t in dev_inputs), float(learning_rate), float(momentum), id(self.cfg),
+               torch.cuda.current_stream(self.dev).cuda_stream, self._mode_key(), int(world_size),
                None if reducer is None else id(reducer))
         entry = self._train_tapes.get(key)
         if entry is None:
@@ -1672,20 +1680,13 @@ class MaskRCNNEngine(object):
             static = [torch.empty_like(t) for t in dev_inputs]
             for s_, t in zip(static, dev_inputs):
                 s_.copy_(t)
-            # one eager step settles arena slots, workspaces and weight images (rolled back: it is not a training step)
-            keep = (self.params.clone(), self.momentum.clone(), self.skipped_steps.clone())
-            hook, self.grad_ready = self.grad_ready, None
-            try:
-                self.forward_backward(*static)
-            finally:
-                self.grad_ready = hook
-            self.apply_gradients(learning_rate, momentum, 1)
-            self.params.copy_(keep[0])
-            self.momentum.copy_(keep[1])
-            self.skipped_steps.copy_(keep[2])               # a settle pass that overflowed in float16 is not a skipped training step
-            self.wt_valid = self._h16_valid = False
-            self.fold_bn()
-            del keep
+            with self._rolled_back():                       # one eager step
+                hook, self.grad_ready = self.grad_ready, None
+                try:
+                    self.forward_backward(*static)
+                finally:
+                    self.grad_ready = hook
+                self.apply_gradients(learning_rate, momentum, 1)
             _hip_mod.tape_begin()
             try:
                 losses = self.forward_backward(*static)
@@ -1703,7 +1704,7 @@ class MaskRCNNEngine(object):
             if s_.data_ptr() != t.data_ptr():
                 s_.copy_(t, non_blocking=True)
         _hip_mod.tape_replay(tape)
-        self.wt_valid = self._h16_valid = False
+        self.params_changed(fold=False)                     # the recorded step ends with the optimiser
         return losses
 
     # =========================================================================================
@@ -1734,6 +1735,4 @@ class MaskRCNNEngine(object):
         guard = self.skipped_steps if self.head_dtype == torch.float16 else None
         ops.sgd_momentum(self.params, self.momentum, self.grads, self.sumsq, cfg.GRADIENT_CLIP_NORM, learning_rate,
                          momentum, self.gran_coef, skipped=guard)
-        self.wt_valid = False
-        self._h16_valid = False
-        self.fold_bn()
+        self.params_changed()

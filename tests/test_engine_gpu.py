@@ -679,6 +679,50 @@ def test_graph_replay_with_multiworkgroup_topk_512(dev):
     assert np.abs(eager["rpn_rois"]).sum() > 0
 
 
+def test_graph_replay_follows_weights_modes_and_config(dev):
+    """float32 HIP-graph inference after a change of the weights, of an inference switch or of a config value patched in place
+    must return what eager infer() returns now (and each change must change that result).  Custom backbone at 256 x 256 with
+    100 detections: the trunk's P2 layers (4 096 pixels) and the mask head (19 600 rows) both take the Winograd path, whose
+    weight transforms the captured graph reads."""
+    from caesar_mrcnn_amd.model import MaskRCNN
+    cfg = _small_cfg("custom", 256, mode="inference", DETECTION_MAX_INSTANCES=100)
+    w1, w2 = _weights(cfg, 3), _weights(cfg, 4)
+    eng = MaskRCNN("inference", cfg, "/tmp/mrcnn_logs", device=dev, weights=w1).engine
+    x = torch.tensor(np.random.default_rng(2).uniform(0, 255, (1, 256, 256, 3)).astype(np.float32), device=dev)
+    win = torch.tensor([[0., 0., 1., 1.]], device=dev)
+
+    def run(graphed):
+        out = (eng.infer_graphed if graphed else eng.infer)(x, win)
+        return {k: out[k].cpu().numpy().copy() for k in ("detections", "mrcnn_mask")}
+
+    prev = run(False)
+    assert {("fpn_p2", 2), ("rpn_conv_shared", 2), ("mrcnn_mask_conv1", 4)} <= {k[:2] for k in eng._wino}   # (layer, tile) of U
+    g = run(True)
+    assert all(np.array_equal(g[k], prev[k]) for k in g)
+
+    def confidence_above_best():                             # no current detection passes (the random heads score 1.0)
+        d = prev["detections"][0]
+        s = d[d[:, 4] > 0, 5]
+        assert len(s) > 0
+        cfg.DETECTION_MIN_CONFIDENCE = float(np.nextafter(s.max(), np.float32(2)))
+
+    changes = [("weights", lambda: eng.set_weights(w2)),
+               ("infer_mask_tile", lambda: setattr(eng, "infer_mask_tile", 2)),
+               ("trunk_winograd", lambda: setattr(eng, "trunk_winograd", False)),
+               ("DETECTION_MIN_CONFIDENCE", confidence_above_best)]
+    for name, change in changes:
+        change()
+        g = run(True)
+        if name == "weights":                                # the replay itself had to refresh the weight images in place
+            assert len(eng._infer_graphs) == 1
+            eng.set_weights(w2)                              # again, so that eager infer() rebuilds its own
+        e = run(False)
+        assert not np.array_equal(e["mrcnn_mask"], prev["mrcnn_mask"]), name
+        for k in e:
+            assert np.array_equal(g[k], e[k]), (name, k)
+        prev = e
+
+
 @pytest.mark.parametrize("how", ["graph", "tape"])
 @pytest.mark.parametrize("head_dtype", [None, "float16"])
 def test_graphed_training_steps_equal_eager(dev, head_dtype, how):
