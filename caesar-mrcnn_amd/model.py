@@ -284,6 +284,9 @@ class MaskRCNN(object):
             for ds in (train_dataset, val_dataset):
                 if hasattr(ds, "load_image") and hasattr(ds, "zscale_contrasts"):     # SourceDataset: FITS -> uint8 RGB on the GPU
                     ds.device = self.engine.dev
+        from .augment import ReferenceAugmenter
+        if isinstance(augmentation, ReferenceAugmenter) and augmentation.device is None:
+            augmentation.device = self.engine.dev             # its warps on the loader stream (augment.py)
         train_gen = Prefetcher([data_generator(train_dataset, cfg, shuffle=True, augmentation=augmentation,
                                                batch_size=cfg.IMAGES_PER_GPU, no_augmentation_sources=no_augmentation_sources,
                                                rank=rank, world_size=world, seed=1234 + 1000 * k, device_targets=dev_t)

@@ -718,6 +718,43 @@ def mold_image_u8(src, out_hw, pad_tl, canvas_hw, mean_pixel, out=None):
     return out
 
 
+def _augment_matrix(m):
+    import numpy as np
+    m = np.asarray(m, dtype=np.float64).reshape(-1)
+    assert m.shape == (6,) and np.all(np.isfinite(m)), "m must be a finite 2 x 3 inverse map"
+    return (C.c_double * 6)(*[float(v) for v in m])
+
+
+def augment_warp_u8(src, m, out=None):
+    """One stage of the reference's training augmentation (scripts/run.py:1091-1100) on the device: src [H, W, C] uint8 (C <= 4)
+    -> uint8 [H, W, C] sampled bilinearly (float64, zero outside, rint) at the inverse map m (2 x 3 doubles: (sx, sy) =
+    m @ (x, y, 1)); byte-identical to augment.warp_host(..., "image")."""
+    _need_cuda(src, out)
+    assert src.dtype == torch.uint8 and src.dim() == 3 and 1 <= src.shape[2] <= 4
+    H, W, C_ = src.shape
+    if out is None:
+        out = torch.empty_like(src)
+    assert out.shape == src.shape and out.dtype == torch.uint8 and out.data_ptr() != src.data_ptr()
+    check(_hip.lib().mrcnn_augment_warp_u8(ptr(src), H, W, C_, _augment_matrix(m), ptr(out), current_stream()),
+          "mrcnn_augment_warp_u8")
+    return out
+
+
+def augment_warp_mask_bits(packed, m, out=None):
+    """The same stage on bit-packed instance masks: packed [H, W, nbytes] uint8 (numpy.packbits(mask, axis=-1,
+    bitorder="little")) -> [H, W, nbytes], warped without unpacking; a bit is set where the bilinear value of its 0 / 1 plane
+    is > 0.5 (augment.warp_host(..., "mask"))."""
+    _need_cuda(packed, out)
+    assert packed.dtype == torch.uint8 and packed.dim() == 3 and packed.shape[2] >= 1
+    H, W, nb = packed.shape
+    if out is None:
+        out = torch.empty_like(packed)
+    assert out.shape == packed.shape and out.dtype == torch.uint8 and out.data_ptr() != packed.data_ptr()
+    check(_hip.lib().mrcnn_augment_warp_mask_bits(ptr(packed), H, W, nb, _augment_matrix(m), ptr(out), current_stream()),
+          "mrcnn_augment_warp_mask_bits")
+    return out
+
+
 def fill_zero(t):
     _need_cuda(t)
     check(_hip.lib().mrcnn_fill_zero(ptr(t), t.numel() * t.element_size(), current_stream()), "mrcnn_fill_zero")

@@ -185,6 +185,19 @@ int mrcnn_fill_zero(void* dst, size_t bytes, void* stream);
  * >= n_used are written as zeros.                                                                                           */
 int mrcnn_unpack_mask_bits(const void* packed, void* out, int64_t npix, int nbytes_per_pixel, int n_used, int G, void* stream);
 
+/* Training augmentation (the reference's default pipeline, scripts/run.py:1091-1100: imgaug SomeOf((0, 2), [Fliplr, Flipud,
+ * Affine(rotate=(-90, 90)), Affine(translate_percent=(-0.3, 0.3))], mode='constant', cval=0), applied by load_image_gt to the
+ * image and the instance masks, mrcnn/model.py:1323-1359): ONE stage of a plan.  m = 6 doubles on the HOST, the inverse map
+ * (sx, sy) = (m0 x + m1 y + m2, m3 x + m4 y + m5) of output pixel (x, y); float64 bilinear sampling, taps outside the image
+ * read 0 -- identical to the host statement caesar-mrcnn_amd/augment.py:warp_host [imgaug bit-parity unpinned].  src and dst
+ * are distinct device buffers of the same shape.
+ *   _u8:        [H, W, C] uint8 image, C <= 4; rint (half to even).
+ *   _mask_bits: [H, W, nbytes_per_pixel] instance masks bit-packed as for mrcnn_unpack_mask_bits (instance j = bit j & 7 of
+ *               byte j >> 3), warped without unpacking; a bit is set when the value is > 0.5.  Any nbytes_per_pixel (32-bit
+ *               words when it is a multiple of 4).                                                                         */
+int mrcnn_augment_warp_u8(const void* src, int H, int W, int C, const double* m, void* dst, void* stream);
+int mrcnn_augment_warp_mask_bits(const void* src, int H, int W, int nbytes_per_pixel, const double* m, void* dst, void* stream);
+
 /* detect() post-processing (MaskRCNN.unmold_detections, mrcnn/model.py:2607-2619; utils.unmold_mask, mrcnn/utils.py:629-645;
  * utils.resize -> skimage.transform.resize(order=1, mode='constant', cval=0, clip=True), mrcnn/utils.py:957-978): for each of
  * the n detections of ONE image, resize the class channel of its MH x MW mask to its integer pixel box (float64, half-pixel

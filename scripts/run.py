@@ -74,6 +74,9 @@ def parse_args(argv=None):
     p.add_argument('--exclude_first_layer_weights', action='store_true', default=False)
     p.add_argument('--head_dtype', type=str, default="", help="extension: float16 | bfloat16 mask-head convolutions")
     p.add_argument('--no_augmentation', dest='use_augmentation', action='store_false', default=True)
+    p.add_argument('--reference_augmentation', action='store_true', default=False,
+                   help="extension: augment with the reference's imgaug pipeline (0-2 of flip lr / flip ud / rotate -90..90 / "
+                        "translate +-30%%), warped on the GPU; default: flips + 90-degree rotations")
     p.add_argument('--scoreThr', type=float, default=0.7)
     p.add_argument('--iouThr', type=float, default=0.6)
     p.add_argument('--image', type=str, default=None)
@@ -151,6 +154,29 @@ def make_dataset(args, path):
     return ds
 
 
+def build_augmentation(args):
+    """The training augmentation: None with --no_augmentation; with --reference_augmentation the reference's pipeline
+    (run.py:1091-1100, caesar_mrcnn_amd.augment.ReferenceAugmenter, warped on the training GPU); else flips + 90-degree
+    rotations."""
+    if not args.use_augmentation:
+        return None
+    if args.reference_augmentation:
+        from caesar_mrcnn_amd.augment import ReferenceAugmenter
+        return ReferenceAugmenter(seed=0)
+    rng = np.random.RandomState(0)
+
+    def aug(image, mask):        # flips + 90-degree rotations (imgaug SomeOf in run.py:1091-1100)
+        if rng.rand() < 0.5:
+            image, mask = np.fliplr(image), np.fliplr(mask)
+        if rng.rand() < 0.5:
+            image, mask = np.flipud(image), np.flipud(mask)
+        k = rng.randint(0, 4)
+        if image.shape[0] == image.shape[1]:
+            image, mask = np.rot90(image, k), np.rot90(mask, k)
+        return np.ascontiguousarray(image), np.ascontiguousarray(mask)
+    return aug
+
+
 def train(args, model, cfg):
     src = args.datadir if args.dataloader == 'datadir_json' else (args.datalist_train or args.datalist)
     ds_train = make_dataset(args, src)
@@ -160,19 +186,7 @@ def train(args, model, cfg):
     world = max(1, cfg.GPU_COUNT)
     cfg.STEPS_PER_EPOCH = args.epoch_length or max(1, len(ds_train.image_ids) // (cfg.IMAGES_PER_GPU * world))
     cfg.VALIDATION_STEPS = args.nvalidation_steps or max(1, len(ds_val.image_ids) // (cfg.IMAGES_PER_GPU * world))
-    aug = None
-    if args.use_augmentation:
-        rng = np.random.RandomState(0)
-
-        def aug(image, mask):        # flips + 90-degree rotations (imgaug SomeOf in run.py:1091-1100)
-            if rng.rand() < 0.5:
-                image, mask = np.fliplr(image), np.fliplr(mask)
-            if rng.rand() < 0.5:
-                image, mask = np.flipud(image), np.flipud(mask)
-            k = rng.randint(0, 4)
-            if image.shape[0] == image.shape[1]:
-                image, mask = np.rot90(image, k), np.rot90(mask, k)
-            return np.ascontiguousarray(image), np.ascontiguousarray(mask)
+    aug = build_augmentation(args)
     model.train(ds_train, ds_val, learning_rate=cfg.LEARNING_RATE, epochs=args.nepochs, layers='all', augmentation=aug,
                 n_worker_threads=args.nthreads, class_weights=ds_train.compute_class_weights() if args.weight_classes else None)
     return 0
