@@ -755,6 +755,98 @@ def augment_warp_mask_bits(packed, m, out=None):
     return out
 
 
+def tile_upload(pool, desc, device):
+    """Sources of a mosaic for tile_adjacency / tile_union (include/mrcnn_hip.h: mrcnn_tile_source): pool = uint32 words (NumPy),
+    desc [n, 6] int32 = (x0, y0, w, h, word_offset, words_per_row).  Checks every descriptor against the pool and uploads both
+    once; returns (pool, desc) device tensors (int32 views)."""
+    import numpy as np
+    pool = np.ascontiguousarray(pool, dtype=np.uint32).reshape(-1)
+    desc = np.ascontiguousarray(desc, dtype=np.int32).reshape(-1, 6)
+    if desc.shape[0]:
+        w, h, off, wpr = (desc[:, k].astype(np.int64) for k in (2, 3, 4, 5))
+        ok = (w > 0) & (h > 0) & (off >= 0) & (wpr >= (w + 31) // 32) & (off + h * wpr <= pool.size)
+        if not ok.all():
+            raise _hip.HipPathError("tile source %d does not fit the pool of %d words" % (int(np.flatnonzero(~ok)[0]), pool.size))
+    pool_t = torch.from_numpy(pool.view(np.int32) if pool.size else np.zeros(1, np.int32)).to(device)
+    desc_t = torch.from_numpy(desc if desc.shape[0] else np.zeros((1, 6), np.int32)).to(device)
+    return pool_t, desc_t
+
+
+def tile_adjacency(pool, desc, pairs):
+    """SFinder.merge_edge_sources' pixel-pair loops (mrcnn/sfinder.py:787-810) for all candidate pairs in one launch: pool, desc from
+    tile_upload; pairs [P, 2] int32 (NumPy or device) source indices -> int32 [P] device, 1 where some pixel of the first and some
+    pixel of the second source have |dx| <= 1 and |dy| <= 1."""
+    import numpy as np
+    _need_cuda(pool, desc)
+    n = desc.shape[0]
+    if not torch.is_tensor(pairs):
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if pairs.size and (pairs.min() < 0 or pairs.max() >= n):
+            raise _hip.HipPathError("tile_adjacency: pair index outside [0, %d)" % n)
+        pairs = torch.from_numpy(pairs).to(pool.device)
+    _need_cuda(pairs)
+    assert pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2
+    P = pairs.shape[0]
+    out = torch.empty((P,), dtype=torch.int32, device=pool.device)
+    if P:
+        check(_hip.lib().mrcnn_tile_adjacency(ptr(pool), pool.numel(), ptr(desc), n, ptr(pairs), P, ptr(out), current_stream()),
+              "mrcnn_tile_adjacency")
+    return out
+
+
+def tile_union_plan(desc_host, comp_offsets, member_ids):
+    """Output layout of tile_union, from the boxes alone: (out_offsets [C], out_words, fresh_offsets [M], fresh_words), int64."""
+    import numpy as np
+    d = np.asarray(desc_host, dtype=np.int64).reshape(-1, 6)
+    co = np.asarray(comp_offsets, dtype=np.int64)
+    ids = np.asarray(member_ids, dtype=np.int64)
+    C_, M = co.size - 1, ids.size
+    if C_ < 0 or co[0] != 0 or co[-1] != M or np.any(np.diff(co) < 0) or (M and (ids.min() < 0 or ids.max() >= d.shape[0])):
+        raise _hip.HipPathError("tile_union: malformed component list")
+    m = d[ids]
+    fresh_sizes = m[:, 3] * m[:, 5]
+    fresh_offsets = np.concatenate([[0], np.cumsum(fresh_sizes)])
+    out_sizes = np.zeros(C_, np.int64)
+    nonempty = np.flatnonzero(np.diff(co) > 0)
+    if nonempty.size:
+        starts = co[:-1][nonempty]
+        x0 = np.minimum.reduceat(m[:, 0], starts)
+        y0 = np.minimum.reduceat(m[:, 1], starts)
+        x1 = np.maximum.reduceat(m[:, 0] + m[:, 2], starts)
+        y1 = np.maximum.reduceat(m[:, 1] + m[:, 3], starts)
+        out_sizes[nonempty] = (y1 - y0) * ((x1 - x0 + 31) // 32)
+    out_offsets = np.concatenate([[0], np.cumsum(out_sizes)])
+    return out_offsets[:-1].copy(), int(out_offsets[-1]), fresh_offsets[:-1].copy(), int(fresh_offsets[-1])
+
+
+def tile_union(pool, desc, desc_host, comp_offsets, member_ids):
+    """The pixel union of SFinder.merge_edge_sources (mrcnn/sfinder.py:848-884) for all components in one launch.  Components in
+    CSR form (comp_offsets [C + 1], member_ids [M], NumPy, members in the reference's visiting order); desc_host = the NumPy
+    descriptors behind `desc`.  Returns a dict of device tensors: out_desc [C, 6] (box of the set bits, word_offset into
+    out_pool), out_count [C], out_pool, fresh_pool (int32 views of the words) and the NumPy offsets out_offsets [C],
+    fresh_offsets [M] (member position q's fresh bitmap: h * words_per_row words of member q's own box)."""
+    import numpy as np
+    _need_cuda(pool, desc)
+    out_offsets, out_words, fresh_offsets, fresh_words = tile_union_plan(desc_host, comp_offsets, member_ids)
+    C_, M = len(comp_offsets) - 1, len(member_ids)
+    dev = pool.device
+    res = {"out_offsets": out_offsets, "fresh_offsets": fresh_offsets,
+           "out_desc": torch.zeros((C_, 6), dtype=torch.int32, device=dev), "out_count": torch.zeros((C_,), dtype=torch.int32, device=dev),
+           "out_pool": torch.zeros((max(out_words, 1),), dtype=torch.int32, device=dev),
+           "fresh_pool": torch.zeros((max(fresh_words, 1),), dtype=torch.int32, device=dev)}
+    if C_ == 0:
+        return res
+    meta = np.concatenate([out_offsets, fresh_offsets]).astype(np.int64)
+    meta_t = torch.from_numpy(meta).to(dev)
+    csr_t = torch.from_numpy(np.concatenate([np.asarray(comp_offsets, np.int32), np.asarray(member_ids, np.int32)])).to(dev)
+    check(_hip.lib().mrcnn_tile_union(ptr(pool), pool.numel(), ptr(desc), desc.shape[0], csr_t.data_ptr(), csr_t.data_ptr() + 4 * (C_ + 1),
+                                      C_, M, meta_t.data_ptr(), meta_t.data_ptr() + 8 * C_, ptr(res["out_desc"]), ptr(res["out_count"]),
+                                      ptr(res["out_pool"]), out_words, ptr(res["fresh_pool"]), fresh_words, current_stream()),
+          "mrcnn_tile_union")
+    res["_keep"] = (meta_t, csr_t)          # alive until the caller has synchronised on the results
+    return res
+
+
 def fill_zero(t):
     _need_cuda(t)
     check(_hip.lib().mrcnn_fill_zero(ptr(t), t.numel() * t.element_size(), current_stream()), "mrcnn_fill_zero")

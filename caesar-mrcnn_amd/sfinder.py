@@ -1,0 +1,638 @@
+"""Tiled source finding: cut a mosaic into tiles, detect per tile, stitch the sources that straddle tile borders back
+together and write one catalogue.  Restates ``TileTask`` and ``SFinder`` of mrcnn/sfinder.py for the path scripts/run.py
+uses (create_tile_tasks :1216, find_sources_at_edge :643, merge_edge_sources :711, run_parallel :549), rule by rule, quirks
+included (each carries the reference line).  The merge has two implementations behind ``SFinder.merge_device``:
+
+  * ``merge_edge_sources_host``    the literal statement in Python / NumPy -- the CPU-testable statement and the yardstick of
+                                   the kernels;
+  * ``merge_edge_sources_device``  the pixel-pair test and the pixel union on bit masks on the GPU (csrc/tilemerge.hip through
+                                   ops.tile_adjacency / ops.tile_union); candidate pairs, the component search, contours and
+                                   JSON stay on the host.
+
+Both give equal catalogues (tests/test_sfinder_gpu.py).  Ranks are RANK / WORLD_SIZE processes (no mpi4py): tiles go round
+robin over the ranks, the per-tile result dicts are gathered on rank 0 with torch.distributed.gather_object, rank 0 merges
+and writes.  Not restated: compute_source_params (:994-1211: needs astropy.stats / astropy.wcs), plots.
+"""
+import logging
+import os
+import time
+
+import numpy as np
+
+from . import analyze
+from . import fits
+from .analyze import Analyzer
+
+logger = logging.getLogger("mrcnn")
+
+
+class MergedSourceInfo(object):
+    """Helper of merge_edge_sources (sfinder.py:44-49): source index within its tile entry, index of the tile entry."""
+
+    def __init__(self, sindex, tindex):
+        self.sindex = sindex
+        self.tindex = tindex
+
+
+# ===============================
+#        TileTask
+# ===============================
+class TileTask(object):
+    """One tile of the mosaic (sfinder.py:54-259)."""
+
+    def __init__(self, tile_coords, model, config):
+        self.model = model
+        self.config = config
+        self.coords = tile_coords
+        self.ix_min, self.ix_max, self.iy_min, self.iy_max = tile_coords[0], tile_coords[1], tile_coords[2], tile_coords[3]
+        self.wid = -1
+        self.tid = 0
+        self.sname_tag = ""
+        self.neighborTaskId = []
+        self.neighborTaskIndex = []
+        self.neighborWorkerId = []
+        self.imgdata = None
+        self.imgheader = None
+        self.image_id = os.path.splitext(os.path.basename(os.path.abspath(self.config.IMG_PATH)))[0]
+        self.det_sources = {}
+        self.bboxes_det = self.scores_det = self.classid_det = self.masks_det = None
+        self.save_json = False
+        self.save_regions = False
+        self.procId = 0
+
+    def set_worker_id(self, wid):
+        self.wid = wid
+
+    def set_task_id(self, tid):
+        self.tid = tid
+        self.sname_tag = "t" + str(tid)
+
+    def is_task_tile_adjacent(self, aTask):
+        # sfinder.py:127-129: "adjacent" = touching in x AND in y, where an identical span counts as touching
+        ax = (self.ix_max == aTask.ix_min - 1 or self.ix_min == aTask.ix_max + 1 or
+              (self.ix_min == aTask.ix_min and self.ix_max == aTask.ix_max))
+        ay = (self.iy_max == aTask.iy_min - 1 or self.iy_min == aTask.iy_max + 1 or
+              (self.iy_min == aTask.iy_min and self.iy_max == aTask.iy_max))
+        return ax and ay
+
+    def is_task_tile_overlapping(self, aTask):
+        # sfinder.py:141-150: strict tests on inclusive-looking corners; tiles that only share their border column overlap
+        if self.ix_max < aTask.ix_min or self.ix_min > aTask.ix_max:
+            return False
+        if self.iy_max < aTask.iy_min or self.iy_min > aTask.iy_max:
+            return False
+        return True
+
+    def is_task_tile_neighbor(self, aTask):
+        return self.is_task_tile_adjacent(aTask) or self.is_task_tile_overlapping(aTask)      # sfinder.py:153-159
+
+    def add_neighbor_info(self, tid, tindex, wid):
+        self.neighborTaskId.append(tid)
+        self.neighborTaskIndex.append(tindex)
+        self.neighborWorkerId.append(wid)
+
+    def find_sources(self):
+        """Read the tile and run the Analyzer on it (sfinder.py:169-259); fills det_sources.  0 / -1."""
+        cfg = self.config
+        self.bboxes_det = self.scores_det = self.classid_det = self.masks_det = None
+        res = fits.read_fits(cfg.IMG_PATH, self.ix_min, self.ix_max, self.iy_min, self.iy_max, stretch=cfg.ZSCALE_STRETCH,
+                             zscale_contrasts=cfg.ZSCALE_CONTRASTS, normalize=cfg.NORMALIZE_IMG, convertToRGB=cfg.IMG_TO_RGB,
+                             to_uint8=cfg.IMG_TO_UINT8, stretch_biascontrast=cfg.BIAS_CONTRAST_STRETCH, bias=cfg.IMG_BIAS,
+                             contrast=cfg.IMG_CONTRAST)
+        if res is None:
+            logger.warning("[PROC %d] Failed to read tile image for task %d!" % (self.procId, self.tid))
+            return -1
+        self.imgdata, self.imgheader = res
+        analyzer = Analyzer(self.model, cfg)
+        analyzer.draw = False
+        analyzer.iou_thr, analyzer.score_thr = cfg.IOU_THR, cfg.SCORE_THR
+        analyzer.write_to_json = self.save_json
+        analyzer.outfile_json = 'catalog_' + self.image_id + '_tid' + str(self.tid) + '.json'
+        analyzer.write_to_ds9 = self.save_regions
+        analyzer.outfile_ds9 = 'catalog_' + self.image_id + '_tid' + str(self.tid) + '.reg'
+        analyzer.obj_name_tag = self.sname_tag
+        if analyzer.predict(self.imgdata, self.image_id, header=self.imgheader, xmin=self.ix_min, ymin=self.iy_min) < 0:
+            logger.error("[PROC %d] Failed to run model prediction on tile image for task %d!" % (self.procId, self.tid))
+            return -1
+        if not analyzer.bboxes:                                   # sfinder.py:221-224: det_sources stays empty
+            logger.info("[PROC %d] No object detected in tile image for task %d ..." % (self.procId, self.tid))
+            return 0
+        self.bboxes_det, self.scores_det = analyzer.bboxes, analyzer.scores_final
+        self.classid_det, self.masks_det = analyzer.class_ids_final, analyzer.masks_final
+        self.det_sources = analyzer.results
+        self.det_sources["workerId"] = self.wid
+        self.det_sources["tileId"] = self.tid
+        self.det_sources["neighborTileIds"] = self.neighborTaskId
+        self.det_sources["xmin"], self.det_sources["xmax"] = self.ix_min, self.ix_max
+        self.det_sources["ymin"], self.det_sources["ymax"] = self.iy_min, self.iy_max
+        logger.info("[PROC %d] #%d objects found in tile image for task %d ..." % (self.procId, len(self.bboxes_det), self.tid))
+        return 0
+
+
+# ===============================
+#        bit masks of the edge sources
+# ===============================
+def pack_sources(pixel_lists):
+    """Edge sources -> the layout of include/mrcnn_hip.h (mrcnn_tile_source): every source as the row-major bit mask of the
+    bounding box of its pixels ([y, x] lists, mosaic coordinates), numpy.packbits little-endian, rows padded to 32-bit words,
+    all in one pool.  Returns (pool uint32 [words], desc int32 [n, 6] = x0, y0, w, h, word_offset, words_per_row).  A source
+    without pixels becomes an empty 1 x 1 box at the origin."""
+    n = len(pixel_lists)
+    desc = np.zeros((n, 6), np.int32)
+    chunks, off = [], 0
+    for s, pixels in enumerate(pixel_lists):
+        p = np.asarray(pixels, dtype=np.int64).reshape(-1, 2)
+        if p.shape[0] == 0:
+            y0 = x0 = 0
+            h = w = 1
+        else:
+            y0, x0 = p.min(axis=0)
+            h, w = p.max(axis=0) - (y0, x0) + 1
+        wpr = (int(w) + 31) // 32
+        m = np.zeros((int(h), wpr * 32), np.uint8)
+        if p.shape[0]:
+            m[p[:, 0] - y0, p[:, 1] - x0] = 1
+        chunks.append(np.packbits(m, axis=1, bitorder="little").view("<u4").reshape(-1))
+        desc[s] = (x0, y0, w, h, off, wpr)
+        off += int(h) * wpr
+    if off > 0x7FFFFFFF:
+        raise ValueError("edge sources need %d mask words: more than one pool holds" % off)
+    pool = np.concatenate(chunks).astype(np.uint32) if chunks else np.zeros(0, np.uint32)
+    return pool, desc
+
+
+def unpack_bitmap(words, h, w, wpr):
+    """Inverse of one pack_sources entry: h * wpr uint32 words -> bool [h, w]."""
+    b = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8).reshape(h, wpr * 4), axis=1, bitorder="little")
+    return b[:, :w].astype(bool)
+
+
+# ===============================
+#        SFinder
+# ===============================
+class SFinder(object):
+    """sfinder.py:264-1500 for the run.py path.  ``tile_sources`` holds the per-tile result dicts (Analyzer.results + tile
+    info), ``sources`` the final catalogue {"sources": [...]}."""
+
+    # Fewer edge sources than this are merged on the host even with merge_device on.  0: measured, the device path wins from
+    # the smallest merging case up (4 edge sources: 2.1 ms against 48 ms).
+    MERGE_DEVICE_MIN_SOURCES = 0
+
+    def __init__(self, model, config):
+        self.config = config
+        self.model = model
+        self.header = None
+        self.image_id = ""
+        self.nx = self.ny = -1
+        self.read_subimg = False
+        self.xmin = self.xmax = self.ymin = self.ymax = -1
+        self.tileSizeX = self.tileSizeY = -1
+        self.tileStepSizeX = self.tileStepSizeY = 1
+        self.mpiEnabled = False
+        self.comm = None                  # the gather's process group when WORLD_SIZE > 1
+        self.nproc = 1
+        self.tasks_per_worker = []
+        self.procId = 0
+        self.MASTER_ID = 0
+        self.tile_sources = {"sources": []}
+        self.sources = {"sources": []}
+        self.save_tile_regions = False    # the reference defaults to one JSON + region file per tile as well (:314, :331)
+        self.save_tile_json = False
+        self.write_to_ds9 = True
+        self.use_polygon_regions = True
+        self.sregions = []
+        self.outfile_ds9 = ""
+        self.write_to_json = True
+        self.outfile_json = ""
+        self.merge_device = self._has_gpu()
+        self.merge_device_min_sources = self.MERGE_DEVICE_MIN_SOURCES
+        self.merge_timing = {}
+
+    def _device(self):
+        dev = getattr(getattr(self.model, "engine", None), "device", None)
+        if dev is not None:
+            return dev
+        import torch
+        return torch.device("cuda", torch.cuda.current_device())
+
+    def _has_gpu(self):
+        dev = getattr(getattr(self.model, "engine", None), "device", None)
+        if dev is not None:
+            return getattr(dev, "type", "") == "cuda"
+        try:
+            import torch
+            return bool(torch.cuda.is_available())
+        except Exception:
+            return False
+
+    # ---- image / tile parameters (sfinder.py:336-444) -------------------------------------------------------
+    def set_img_size_params(self):
+        cfg = self.config
+        self.header = fits.get_fits_header(cfg.IMG_PATH)
+        if self.header is None:
+            logger.error("[PROC %d] Header read from image %s is None!" % (self.procId, cfg.IMG_PATH))
+            return -1
+        xmin, xmax, ymin, ymax = cfg.IMG_XMIN, cfg.IMG_XMAX, cfg.IMG_YMIN, cfg.IMG_YMAX
+        if xmin >= 0 and xmax >= 0 and ymin >= 0 and ymax >= 0:
+            self.read_subimg = True
+            # sfinder.py:353-354: the size is taken from the range BEFORE it is assigned (1 x 1 on a fresh object); as written
+            self.nx = (self.xmax - self.xmin + 1)
+            self.ny = (self.ymax - self.ymin + 1)
+            self.xmin, self.xmax, self.ymin, self.ymax = xmin, xmax, ymin, ymax
+        else:
+            self.read_subimg = False
+            if 'NAXIS1' not in self.header or 'NAXIS2' not in self.header:
+                logger.error("[PROC %d] NAXIS1 / NAXIS2 keyword missing in header!" % self.procId)
+                return -1
+            self.nx, self.ny = self.header['NAXIS1'], self.header['NAXIS2']
+            self.xmin, self.xmax, self.ymin, self.ymax = 0, self.nx - 1, 0, self.ny - 1
+        self.tileSizeX, self.tileSizeY = self.nx, self.ny
+        self.tileStepSizeX = self.tileStepSizeY = 1
+        if cfg.SPLIT_IMG_IN_TILES:
+            self.tileSizeX, self.tileSizeY = cfg.TILE_XSIZE, cfg.TILE_YSIZE
+            self.tileStepSizeX, self.tileStepSizeY = cfg.TILE_XSTEP, cfg.TILE_YSTEP
+        self.image_id = os.path.splitext(os.path.basename(os.path.abspath(cfg.IMG_PATH)))[0]
+        return 0
+
+    # ---- single image (sfinder.py:450-523) ------------------------------------------------------------------
+    def run(self):
+        cfg = self.config
+        if self.set_img_size_params() < 0:
+            logger.error("Failed to set image size parameters!")
+            return -1
+        res = fits.read_fits(cfg.IMG_PATH, cfg.IMG_XMIN, cfg.IMG_XMAX, cfg.IMG_YMIN, cfg.IMG_YMAX, stretch=cfg.ZSCALE_STRETCH,
+                             zscale_contrasts=cfg.ZSCALE_CONTRASTS, normalize=cfg.NORMALIZE_IMG, convertToRGB=cfg.IMG_TO_RGB,
+                             to_uint8=cfg.IMG_TO_UINT8, stretch_biascontrast=cfg.BIAS_CONTRAST_STRETCH, bias=cfg.IMG_BIAS,
+                             contrast=cfg.IMG_CONTRAST)
+        if res is None:
+            logger.error("Failed to read image %s!" % cfg.IMG_PATH)
+            return -1
+        image_data, _ = res
+        analyzer = Analyzer(self.model, cfg)
+        analyzer.write_to_json = True
+        analyzer.outfile_json = self.outfile_json or cfg.OUTFILE_JSON
+        analyzer.outfile_ds9 = self.outfile_ds9
+        analyzer.iou_thr, analyzer.score_thr = cfg.IOU_THR, cfg.SCORE_THR
+        if analyzer.predict(image_data, self.image_id) < 0:               # sfinder.py:493: no offsets, no header
+            logger.error("Failed to run model prediction on image %s!" % cfg.IMG_PATH)
+            return -1
+        if not analyzer.bboxes:
+            logger.info("No object detected in image %s ..." % cfg.IMG_PATH)
+            return 0
+        logger.info("#%d objects found in image %s ..." % (len(analyzer.bboxes), cfg.IMG_PATH))
+        return 0
+
+    # ---- ranks ------------------------------------------------------------------------------------------------
+    def init_mpi(self):
+        """The reference's MPI set-up (sfinder.py:528-546) with RANK / WORLD_SIZE processes: torch.distributed from
+        parallel.init_distributed(); the gather runs over a gloo group (object collectives need no GPU)."""
+        world = int(os.environ.get("WORLD_SIZE", "1"))
+        if world <= 1:
+            self.mpiEnabled, self.nproc, self.procId, self.comm = False, 1, 0, None
+            return
+        import torch.distributed as dist
+        from . import parallel
+        rank, _, world = parallel.init_distributed()
+        self.comm = dist.group.WORLD if dist.get_backend() == "gloo" else dist.new_group(backend="gloo")
+        self.mpiEnabled, self.nproc, self.procId = True, world, rank
+
+    # ---- tiles (sfinder.py:549-638) ---------------------------------------------------------------------------
+    def run_parallel(self):
+        self.init_mpi()
+        t0 = time.time()
+        status = 0
+        if self.set_img_size_params() < 0:
+            logger.error("[PROC %d] Failed to set image size parameters!" % self.procId)
+            status = -2
+        elif self.create_tile_tasks() < 0:
+            logger.warning("[PROC %d] Failure in create tile tasks, exit..." % self.procId)
+            status = -2
+        if status == 0:
+            tasks = self.tasks_per_worker[self.procId]
+            for j, task in enumerate(tasks):
+                logger.info("[PROC %d] Start processing of task id %d (%d/%d) ..." % (self.procId, task.tid, j + 1, len(tasks)))
+                try:
+                    rc = task.find_sources()
+                except Exception as e:              # a failing tile must not keep this rank out of the gather below
+                    logger.error("[PROC %d] Task id %d raised %s: %s" % (self.procId, task.tid, type(e).__name__, e))
+                    task.det_sources = {}
+                    rc = -1
+                if rc < 0:                          # sfinder.py:583-586: log, remember, next tile
+                    logger.error("[PROC %d] Failed to find sources in task no. %d, skip to next!" % (self.procId, j))
+                    status = -1
+                    continue
+                self.find_sources_at_edge(j)
+            if status < 0:
+                logger.warning("[PROC %d] One or more errors occurred in source finding tasks..." % self.procId)
+        # every rank arrives here, whatever happened above (the reference returns early on a set-up error and leaves the others
+        # in the barrier): a rank whose set-up failed contributes nothing
+        if self.gather_task_data_from_workers(skip_local=(status == -2)) < 0:
+            return -1
+        if status == -2:
+            return -1
+        if self.procId == self.MASTER_ID:
+            logger.info("[PROC %d] Merging sources at tile edges ..." % self.procId)
+            self.merge_edge_sources()
+            self.save()
+            logger.info("[PROC %d] Run completed in %d seconds" % (self.procId, time.time() - t0))
+        return 0
+
+    # ---- edge flags (sfinder.py:643-706) ----------------------------------------------------------------------
+    def find_sources_at_edge(self, tindex):
+        tileData = self.tasks_per_worker[self.procId][tindex]
+        sourceTileData = tileData.det_sources
+        if not sourceTileData or not sourceTileData["objs"]:
+            logger.warning("[PROC %d] No sources for this tile, nothing to be done..." % self.procId)
+            return
+        sources = sourceTileData["objs"]
+        xmin, xmax, ymin, ymax = tileData.ix_min, tileData.ix_max, tileData.iy_min, tileData.iy_max
+        for source in sources:
+            xmin_s, xmax_s, ymin_s, ymax_s = source["x1"], source["x2"], source["y1"], source["y2"]
+            # sfinder.py:676-682: the box touches the tile's own frame (x2 / y2 are exclusive, ix_max / iy_max as generated)
+            if xmin_s == xmin or xmax_s == xmax or ymin_s == ymin or ymax_s == ymax:
+                source["edge"] = True
+                continue
+            # sfinder.py:685-706: the box intersects a neighbour tile.  A flag the Analyzer already set is never cleared.
+            for tindex_n, windex_n in zip(tileData.neighborTaskIndex, tileData.neighborWorkerId):
+                t = self.tasks_per_worker[windex_n][tindex_n]
+                if xmax_s < t.ix_min or xmin_s > t.ix_max or ymax_s < t.iy_min or ymin_s > t.iy_max:
+                    continue
+                source["edge"] = True
+                break
+
+    # ---- gather (sfinder.py:940-988) --------------------------------------------------------------------------
+    def gather_task_data_from_workers(self, skip_local=False):
+        """tile_sources = the non-empty det_sources of every worker's tasks, worker by worker (rank 0 only when there are
+        several ranks).  The serial reference never fills tile_sources (the call sits under `if self.mpiEnabled`, :599) and so
+        merges nothing; here one process runs the local half of the gather, which is what the MPI run of one rank does."""
+        self.tile_sources = {"sources": []}
+        if not skip_local and self.tasks_per_worker:
+            for task in self.tasks_per_worker[self.procId]:
+                if task.det_sources:
+                    self.tile_sources["sources"].append(task.det_sources)
+        if not self.mpiEnabled:
+            return 0
+        import torch.distributed as dist
+        gathered = [None] * self.nproc if self.procId == self.MASTER_ID else None
+        dist.gather_object(self.tile_sources, gathered, dst=self.MASTER_ID, group=self.comm)
+        if self.procId == self.MASTER_ID:
+            for i in range(1, self.nproc):                  # :963-972: appended in rank order
+                self.tile_sources["sources"].extend(gathered[i]["sources"])
+        return 0
+
+    # ---- merge (sfinder.py:711-935) ---------------------------------------------------------------------------
+    def merge_edge_sources(self):
+        if self.procId != self.MASTER_ID:
+            return 0
+        # measured: the device path wins from the smallest merging case up (4 edge sources: 2.1 ms against 48 ms),
+        # so there is no size below which the host statement is preferred
+        return self.merge_edge_sources_device() if self.merge_device else self.merge_edge_sources_host()
+
+    def _split_edge_sources(self):
+        """:719-730: non-edge sources go to the catalogue as they are (merged = False), edge sources are listed for merging."""
+        sourcesToBeMerged = []
+        self.sources["sources"] = []
+        for tile_index, tileData in enumerate(self.tile_sources["sources"]):
+            for j, s in enumerate(tileData["objs"]):
+                if not s["edge"]:
+                    s["merged"] = False
+                    self.sources["sources"].append(s)
+                    continue
+                sourcesToBeMerged.append(MergedSourceInfo(j, tile_index))
+        return sourcesToBeMerged
+
+    def _edge_source(self, info):
+        return self.tile_sources["sources"][info.tindex]["objs"][info.sindex]
+
+    def _finish_merge(self, sourcesToBeMerged, cc, merged_of):
+        """:821-933: components of one keep their object; larger ones become the object merged_of(i, members) builds; then
+        every source is renamed S1..Sn."""
+        for i, comp in enumerate(cc):
+            if not comp:
+                continue
+            if len(comp) == 1:
+                source = self._edge_source(sourcesToBeMerged[comp[0]])
+                source["name"] = "S" + str(i + 1) + "_merged"
+                source["merged"] = False
+                self.sources["sources"].append(source)
+            else:
+                self.sources["sources"].append(merged_of(i, comp))
+        for i, s in enumerate(self.sources["sources"]):                   # :928-933
+            s["name"] = "S" + str(i + 1)
+        return 0
+
+    @staticmethod
+    def _merged_source(name, last, pixels_merged, mask, xmin, ymin):
+        """:864-924 from the union's pixels: `mask` = the union in its tight box [ymin.., xmin..]."""
+        dy, dx = mask.shape
+        xmax, ymax = xmin + dx - 1, ymin + dy - 1                         # :879-882: pixel max, i.e. INCLUSIVE (unmerged: exclusive)
+        offset = 10                                                       # :887
+        padded_mask = np.zeros((dy + 2 * offset, dx + 2 * offset), dtype=np.uint8)
+        padded_mask[offset:offset + dy, offset:offset + dx] = mask
+        vertexes = []
+        for verts in analyze.find_contours(padded_mask, 0.5):
+            verts = np.fliplr(verts)                                      # :902: (y, x) -> (x, y), padding kept ...
+            verts = verts.tolist()
+            for v in verts:                                               # :906-909: ... and removed here
+                v[0] += xmin - offset
+                v[1] += ymin - offset
+            vertexes.append(verts)
+        # :865-870: class / score of `sourcesToBeMerged[index]` with index the LAST member visited (index_largest is computed
+        # and never used)
+        return {"name": name, "x1": int(xmin), "x2": int(xmax), "y1": int(ymin), "y2": int(ymax), "edge": True, "merged": True,
+                "score": last["score"], "class_name": last["class_name"], "class_id": last["class_id"],
+                "pixels": pixels_merged, "vertexes": vertexes}
+
+    # -- host statement ------------------------------------------------------------------------------------------
+    def merge_edge_sources_host(self):
+        """The reference's algorithm as written: every pair j > i of edge sources, neighbour-tile test, box test, pixel-pair
+        test, components, first-seen pixel union.  The two innermost loops are NumPy expressions of the same predicates (the
+        pixel-pair test by broadcasting, the `x not in pixels_merged` scan through a set): same results, same order."""
+        if self.procId != self.MASTER_ID:
+            return 0
+        todo = self._split_edge_sources()
+        N = len(todo)
+        tiles = self.tile_sources["sources"]
+        srcs = [self._edge_source(t) for t in todo]
+        pix = [np.asarray(s["pixels"], dtype=np.int64).reshape(-1, 2) for s in srcs]
+        edges = []
+        for i in range(N):
+            s = srcs[i]
+            tids_neighbor = tiles[todo[i].tindex]["neighborTileIds"]
+            xmin, xmax, ymin, ymax = s["x1"], s["x2"], s["y1"], s["y2"]
+            for j in range(i + 1, N):
+                sj = srcs[j]
+                if tiles[todo[j].tindex]["tileId"] not in tids_neighbor:             # :771: one-sided, as written
+                    continue
+                if xmax < sj["x1"] or xmin > sj["x2"] or ymax < sj["y1"] or ymin > sj["y2"]:     # :776-781
+                    continue
+                if self._pixels_adjacent(pix[i], pix[j]):                            # :787-810
+                    edges.append((i, j))
+        cc = analyze.connected_components(N, edges)                                  # :820, mrcnn/graph.py
+
+        def merged_of(i, comp):
+            pixels_merged, seen = [], set()
+            for index in comp:                                                        # :848-862: first-seen order
+                for p in srcs[index]["pixels"]:
+                    key = (p[0], p[1])
+                    if key not in seen:
+                        seen.add(key)
+                        pixels_merged.append(p)
+            arr = np.asarray(pixels_merged, dtype=np.int64)
+            ymin, xmin = arr.min(axis=0)
+            ymax, xmax = arr.max(axis=0)
+            mask = np.zeros((ymax - ymin + 1, xmax - xmin + 1), np.uint8)
+            mask[arr[:, 0] - ymin, arr[:, 1] - xmin] = 1
+            return self._merged_source("S" + str(i + 1) + "_merged", srcs[comp[-1]], pixels_merged, mask, int(xmin), int(ymin))
+
+        return self._finish_merge(todo, cc, merged_of)
+
+    @staticmethod
+    def _pixels_adjacent(a, b, chunk=512):
+        """:787-810: some pixel of a and some pixel of b with |dx| <= 1 and |dy| <= 1 ([y, x] rows)."""
+        if a.shape[0] == 0 or b.shape[0] == 0:
+            return False
+        for k in range(0, a.shape[0], chunk):
+            d = np.abs(a[k:k + chunk, None, :] - b[None, :, :])
+            if np.any((d[..., 0] <= 1) & (d[..., 1] <= 1)):
+                return True
+        return False
+
+    # -- device path ---------------------------------------------------------------------------------------------
+    def candidate_pairs(self, todo):
+        """The pairs the reference's double loop hands to the pixel test (:756-781), without visiting all N^2: per pair of
+        tile entries (a before b in tile_sources, b's tile id among a's neighbour ids) the box test on integer arrays.
+        Returned sorted by (i, j), the order in which the reference adds graph edges."""
+        tiles = self.tile_sources["sources"]
+        by_tile = {}
+        for k, t in enumerate(todo):
+            by_tile.setdefault(t.tindex, []).append(k)
+        box = np.array([[s["x1"], s["x2"], s["y1"], s["y2"]] for s in (self._edge_source(t) for t in todo)], dtype=np.int64).reshape(-1, 4)
+        order = sorted(by_tile)
+        out = []
+        for ai, ta in enumerate(order):
+            ia = np.asarray(by_tile[ta])
+            neighbors = set(tiles[ta]["neighborTileIds"])
+            for tb in order[ai + 1:]:
+                if tiles[tb]["tileId"] not in neighbors:
+                    continue
+                ib = np.asarray(by_tile[tb])
+                A, B = box[ia][:, None, :], box[ib][None, :, :]
+                disjoint = (A[..., 1] < B[..., 0]) | (A[..., 0] > B[..., 1]) | (A[..., 3] < B[..., 2]) | (A[..., 2] > B[..., 3])
+                ii, jj = np.nonzero(~disjoint)
+                if ii.size:
+                    out.append(np.stack([ia[ii], ib[jj]], axis=1))
+        if not out:
+            return np.zeros((0, 2), np.int32)
+        pairs = np.concatenate(out)
+        return pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))].astype(np.int32)
+
+    def merge_edge_sources_device(self):
+        """Same catalogue as merge_edge_sources_host; the pixel-pair test and the pixel union run on the GPU on bit masks."""
+        if self.procId != self.MASTER_ID:
+            return 0
+        import torch
+        from . import ops
+        clock = time.perf_counter
+        t = [clock()]
+        todo = self._split_edge_sources()
+        N = len(todo)
+        srcs = [self._edge_source(t_) for t_ in todo]
+        if N == 0:
+            return self._finish_merge(todo, [], None)
+        dev = self._device()
+        pairs = self.candidate_pairs(todo)
+        t.append(clock())
+        pool, desc = pack_sources([s["pixels"] for s in srcs])
+        t.append(clock())
+        pool_t, desc_t = ops.tile_upload(pool, desc, dev)
+        adj = ops.tile_adjacency(pool_t, desc_t, pairs).cpu().numpy() if len(pairs) else np.zeros(0, np.int32)
+        t.append(clock())
+        edges = [(int(i), int(j)) for i, j in pairs[adj != 0]]
+        cc = analyze.connected_components(N, edges)
+        multi = [k for k, comp in enumerate(cc) if len(comp) > 1]
+        t.append(clock())
+        result = {}
+        if multi:
+            members = [cc[k] for k in multi]
+            comp_offsets = np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.int32)
+            member_ids = np.concatenate(members).astype(np.int32)
+            u = ops.tile_union(pool_t, desc_t, desc, comp_offsets, member_ids)
+            out_desc = u["out_desc"].cpu().numpy()
+            out_count = u["out_count"].cpu().numpy()
+            out_pool = u["out_pool"].cpu().numpy().view(np.uint32)
+            fresh_pool = u["fresh_pool"].cpu().numpy().view(np.uint32)        # .cpu() synchronises with the launches
+            t.append(clock())
+            for c, k in enumerate(multi):
+                parts = []
+                for q in range(comp_offsets[c], comp_offsets[c + 1]):
+                    x0, y0, w, h, _, wpr = (int(v) for v in desc[member_ids[q]])
+                    fo = int(u["fresh_offsets"][q])
+                    parts.append(np.argwhere(unpack_bitmap(fresh_pool[fo:fo + h * wpr], h, w, wpr)) + (y0, x0))
+                pixels = np.concatenate(parts)
+                x0, y0, w, h, off, wpr = (int(v) for v in out_desc[c])
+                assert pixels.shape[0] == int(out_count[c]), "tile_union: fresh bitmaps and union count disagree"
+                result[k] = (pixels.tolist(), unpack_bitmap(out_pool[off:off + h * wpr], h, w, wpr), x0, y0)
+        else:
+            t.append(clock())
+        t.append(clock())
+        self.merge_timing = {"edge_sources": N, "pairs": int(len(pairs)), "edges": len(edges), "components_merged": len(multi),
+                             "pool_words": int(pool.size)}
+        for name, a, b in zip(("candidate_pairs", "pack", "upload_adjacency_download", "components", "union_download", "pixel_lists"),
+                              t[:-1], t[1:]):
+            self.merge_timing[name + "_ms"] = round(1e3 * (b - a), 3)
+
+        def merged_of(i, comp):
+            pixels, mask, x0, y0 = result[i]
+            return self._merged_source("S" + str(i + 1) + "_merged", srcs[comp[-1]], pixels, mask.astype(np.uint8), x0, y0)
+
+        return self._finish_merge(todo, cc, merged_of)
+
+    # ---- tile grid (sfinder.py:1216-1384) ---------------------------------------------------------------------
+    def create_tile_tasks(self):
+        tileGrid = fits.generate_tiles(self.xmin, self.xmax, self.ymin, self.ymax, self.tileSizeX, self.tileSizeY,
+                                       self.tileStepSizeX, self.tileStepSizeY)
+        if tileGrid is None:
+            return -1
+        self.tasks_per_worker = [[] for _ in range(self.nproc)]
+        workerCounter = 0
+        for tid, coords in enumerate(tileGrid):                           # :1235-1251: round robin
+            tileTask = TileTask(coords, self.model, self.config)
+            tileTask.set_worker_id(workerCounter)
+            tileTask.set_task_id(tid)
+            tileTask.procId = self.procId
+            tileTask.save_regions = self.save_tile_regions
+            tileTask.save_json = self.save_tile_json
+            self.tasks_per_worker[workerCounter].append(tileTask)
+            workerCounter = 0 if workerCounter >= self.nproc - 1 else workerCounter + 1
+        for i in range(len(self.tasks_per_worker)):                       # :1256-1293: neighbour lists, in this insertion order
+            tasks_i = self.tasks_per_worker[i]
+            for j, task in enumerate(tasks_i):
+                for k in range(j + 1, len(tasks_i)):                      # first the later tasks of the same worker
+                    task_N = tasks_i[k]
+                    if task.is_task_tile_neighbor(task_N):
+                        task.add_neighbor_info(task_N.tid, k, i)
+                        task_N.add_neighbor_info(task.tid, j, i)
+                for s in range(i + 1, len(self.tasks_per_worker)):        # then the tasks of the later workers
+                    for t, task_N in enumerate(self.tasks_per_worker[s]):
+                        if task.is_task_tile_neighbor(task_N):
+                            task.add_neighbor_info(task_N.tid, t, s)
+                            task_N.add_neighbor_info(task.tid, j, i)
+        for tasks in self.tasks_per_worker:                               # :1372-1382
+            if len(tasks) > self.config.MAX_NTASKS_PER_WORKER:
+                logger.warning("[PROC %d] Too many tasks per worker exceeded (thr=%d)!" % (self.procId, self.config.MAX_NTASKS_PER_WORKER))
+                return -1
+        return 0
+
+    # ---- output (sfinder.py:1389-1500), through the Analyzer's writers -------------------------------------
+    def save(self):
+        if self.procId != self.MASTER_ID:
+            return
+        writer = Analyzer(self.model, self.config)
+        writer.results = {"image_id": self.image_id, "objs": self.sources["sources"]}
+        if self.write_to_json:
+            writer.write_json_results(self.outfile_json or 'catalog_' + str(self.image_id) + '.json')
+        writer.make_ds9_regions(self.use_polygon_regions)
+        self.sregions = writer.obj_regions
+        if self.write_to_ds9:
+            writer.write_ds9_regions(self.outfile_ds9 or 'ds9_' + str(self.image_id) + '.reg')

@@ -198,6 +198,37 @@ int mrcnn_unpack_mask_bits(const void* packed, void* out, int64_t npix, int nbyt
 int mrcnn_augment_warp_u8(const void* src, int H, int W, int C, const double* m, void* dst, void* stream);
 int mrcnn_augment_warp_mask_bits(const void* src, int H, int W, int nbytes_per_pixel, const double* m, void* dst, void* stream);
 
+/* Stitching of sources across tile borders (SFinder.merge_edge_sources, mrcnn/sfinder.py:711-935).  Sources are row-major bit
+ * masks of their bounding boxes in mosaic coordinates: ONE pool of 32-bit words and a descriptor per source; pixel (x, y) of a
+ * source is bit (x - x0) & 31 of word word_offset + (y - y0) * words_per_row + ((x - x0) >> 5), least significant bit first
+ * (numpy.packbits(..., bitorder="little"), as for mrcnn_unpack_mask_bits); bits past w in a row's last word are ignored.
+ * Rows, words and addresses outside a source or outside the pool read as zero; pool_words is the pool's length (at most
+ * 2^31 - 1 words, else MRCNN_ERR_UNSUPPORTED).  All pointers are device pointers; nothing is allocated on the device.
+ *   mrcnn_tile_adjacency  replaces the pixel-pair loops :787-810: out[p] = 1 iff some pixel of source pairs[p][0] and some pixel of
+ *                         source pairs[p][1] have |dx| <= 1 and |dy| <= 1 (:797-799), else 0.  One wavefront per pair; only the
+ *                         intersection of j's box with i's box grown by one pixel is read.  An index outside [0, n) gives 0.
+ *   mrcnn_tile_union      replaces the membership-test union :848-862 and the pixel min / max box :873-884.  Components in CSR
+ *                         form: the members of component c are member_ids[comp_offsets[c] .. comp_offsets[c + 1]) (M ids in all),
+ *                         in the order the reference visits them.  Per component: out_desc[c] = the box of the set bits
+ *                         (w = h = 0 when there are none) with word_offset = out_offsets[c], the union bitmap in that box at
+ *                         out_pool + out_offsets[c], out_count[c] = its pixel count.  Per member position q: at fresh_pool +
+ *                         fresh_offsets[q], in the member's OWN box and row pitch, member AND NOT (the members before it) -- the
+ *                         set bits of the fresh bitmaps, member after member in raster order, are the reference's first-seen
+ *                         pixel list.  The caller sizes both pools from the boxes: out_offsets[c] leaves room for the members'
+ *                         common box (rows x ceil(width / 32) words), fresh_offsets[q] for h * words_per_row of the member;
+ *                         writes past out_pool_words / fresh_pool_words are dropped.                                            */
+typedef struct mrcnn_tile_source {
+    int32_t x0, y0, w, h;            /* bounding box in mosaic pixels: columns x0 .. x0 + w - 1, rows y0 .. y0 + h - 1 */
+    int32_t word_offset;             /* first word of row 0 in the pool */
+    int32_t words_per_row;           /* >= ceil(w / 32) */
+} mrcnn_tile_source;
+int mrcnn_tile_adjacency(const void* pool, int64_t pool_words, const mrcnn_tile_source* desc, int n, const int32_t* pairs, int P,
+                         int32_t* out, void* stream);
+int mrcnn_tile_union(const void* pool, int64_t pool_words, const mrcnn_tile_source* desc, int n, const int32_t* comp_offsets,
+                     const int32_t* member_ids, int C, int M, const int64_t* out_offsets, const int64_t* fresh_offsets,
+                     mrcnn_tile_source* out_desc, int32_t* out_count, void* out_pool, int64_t out_pool_words, void* fresh_pool,
+                     int64_t fresh_pool_words, void* stream);
+
 /* detect() post-processing (MaskRCNN.unmold_detections, mrcnn/model.py:2607-2619; utils.unmold_mask, mrcnn/utils.py:629-645;
  * utils.resize -> skimage.transform.resize(order=1, mode='constant', cval=0, clip=True), mrcnn/utils.py:957-978): for each of
  * the n detections of ONE image, resize the class channel of its MH x MW mask to its integer pixel box (float64, half-pixel

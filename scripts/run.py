@@ -11,6 +11,8 @@ Multi-GPU training: ``torchrun --nproc-per-node NGPU scripts/run.py train --ngpu
 post-processing (caesar_mrcnn_amd/analyze.py: score filter, connected-mask merging, best-of-overlapping
 selection) on every tile and writes the objects as JSON (`out_<image>.json`: image_id, objs[name, x1, x2,
 y1, y2, class_id, class_name, score, pixels, vertexes, edge]) and DS9 regions.  Plots are not produced.
+`detect --split_img_in_tiles --merge_tile_sources` is the reference's SFinder (caesar_mrcnn_amd/sfinder.py): sources that
+straddle tile borders are merged and one catalogue (objects gain `merged`, names S1..Sn) is written by rank 0.
 """
 import argparse
 import json
@@ -89,6 +91,10 @@ def parse_args(argv=None):
     p.add_argument('--tile_ysize', type=int, default=512)
     p.add_argument('--tile_xstep', type=float, default=1.0)
     p.add_argument('--tile_ystep', type=float, default=1.0)
+    p.add_argument('--merge_tile_sources', action='store_true', default=False,
+                   help="with --split_img_in_tiles: the reference's SFinder -- sources cut by tile borders or seen in several "
+                        "overlapping tiles are merged (on the GPU) and ONE catalogue is written by rank 0; default: per-tile "
+                        "objects concatenated")
     return p.parse_args(argv)
 
 
@@ -235,11 +241,30 @@ def test(args, model, cfg):
     return 0
 
 
+def detect_merged(args, model, cfg):
+    """--split_img_in_tiles --merge_tile_sources: SFinder.run_parallel (mrcnn/sfinder.py:549-638; the reference's run.py:1420-1437
+    drives it the same way).  Tiles go round robin over the RANK / WORLD_SIZE processes; rank 0 gathers, merges and writes."""
+    from caesar_mrcnn_amd.sfinder import SFinder
+    base = os.path.splitext(os.path.basename(args.image))[0]
+    sf = SFinder(model, cfg)
+    sf.outfile_json = args.detect_outfile_json or ("out_%s.json" % base)
+    sf.outfile_ds9 = os.path.splitext(sf.outfile_json)[0] + ".reg"
+    if sf.run_parallel() < 0:
+        logger.error("Failed to run the tiled source finder on image %s!" % args.image)
+        return -1
+    if sf.procId == sf.MASTER_ID:
+        n_merged = sum(1 for s in sf.sources["sources"] if s["merged"])
+        print("%d sources (%d merged across tiles) written to %s" % (len(sf.sources["sources"]), n_merged, sf.outfile_json))
+    return 0
+
+
 def detect(args, model, cfg):
     from caesar_mrcnn_amd import fits
     if not args.image:
         logger.error("No input image given (--image)")
         return -1
+    if cfg.SPLIT_IMG_IN_TILES and args.merge_tile_sources:
+        return detect_merged(args, model, cfg)
     tiles = [(args.xmin, args.xmax, args.ymin, args.ymax)]
     if cfg.SPLIT_IMG_IN_TILES:
         size = fits.get_fits_size(args.image)
