@@ -1416,7 +1416,8 @@ __global__ __launch_bounds__(256) void mask_out_fwd_h16_kernel(const T* __restri
     }
 }
 
-// C <= 4 (the repo's 3 classes + background), Cd = 256: a 16-lane group owns one pixel (16 channels = 32 bytes per lane),
+// C <= 4 (run.py's default class dictionary of 3 classes + background, or fewer: the class count is a user parameter; larger
+// ones take the kernel above), Cd = 256: a 16-lane group owns one pixel (16 channels = 32 bytes per lane),
 // four pixels per wave at a time; the 4 dot products are reduced inside the group (4 xor steps).
 template <typename T>
 __global__ __launch_bounds__(256) void mask_out_fwd_h16_c4_kernel(const T* __restrict__ up, const float* __restrict__ wm,

@@ -956,7 +956,7 @@ class MaskRCNNEngine(object):
                 x16 = ops.cast_to_h16(x, self.head_dtype)
             h1, c1 = self._h16_fwd(self.op("mrcnn_class_conv1"), x16, ACT_RELU, train)
             h2_16, c2 = self._h16_fwd(self.op("mrcnn_class_conv2"), h1, ACT_RELU, train)
-            h2 = ops.cast_from_h16(h2_16)                        # the 4- / 16-column output layers stay float32
+            h2 = ops.cast_from_h16(h2_16)                        # the C- / 4C-column output layers (C = NUM_CLASSES) stay float32
         else:
             h1, c1 = self.op("mrcnn_class_conv1").forward(x, ACT_RELU, train=train)
             h2, c2 = self.op("mrcnn_class_conv2").forward(h1, ACT_RELU, train=train)

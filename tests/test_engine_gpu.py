@@ -10,86 +10,9 @@ import pytest
 import torch
 
 import mrcnn_oracle as orc
+from model_cases import _scene, _small_cfg, _train_inputs, _weights  # noqa: F401  (other test modules and the smoke run reach them through this module)
 
 pytestmark = pytest.mark.gpu
-
-
-def _small_cfg(backbone="custom", size=128, mode="training", **kw):
-    from caesar_mrcnn_amd.config import run_py_config
-    cfg = run_py_config(backbone=backbone, imgsize=size, mode=mode)
-    cfg.POST_NMS_ROIS_TRAINING = 1500
-    cfg.POST_NMS_ROIS_INFERENCE = 200
-    cfg.TRAIN_ROIS_PER_IMAGE = 48
-    cfg.MAX_GT_INSTANCES = 20
-    cfg.RPN_TRAIN_ANCHORS_PER_IMAGE = 64
-    cfg.DETECTION_MAX_INSTANCES = 30
-    for k, v in kw.items():
-        setattr(cfg, k, v)
-    return cfg
-
-
-def _scene(cfg, B, seed):
-    """Synthetic tiles: noise + bright boxes.  Every GT instance is laid over a (pixel-rounded) anchor of
-    scale >= 8 px so that, with RPN deltas kept small, some proposals reach IoU >= 0.5 and the
-    detection-target / mask / bbox branches are exercised."""
-    rng = np.random.default_rng(seed)
-    S = int(cfg.IMAGE_SHAPE[0])
-    G = cfg.MAX_GT_INSTANCES
-    anchors = orc.generate_pyramid_anchors(cfg.RPN_ANCHOR_SCALES, cfg.RPN_ANCHOR_RATIOS,
-                                           orc.compute_backbone_shapes(cfg.BACKBONE_STRIDES, cfg.IMAGE_SHAPE),
-                                           cfg.BACKBONE_STRIDES, cfg.RPN_ANCHOR_STRIDE)
-    ok = np.where((anchors[:, 0] >= 0) & (anchors[:, 1] >= 0) & (anchors[:, 2] <= S) & (anchors[:, 3] <= S) &
-                  ((anchors[:, 2] - anchors[:, 0]) >= 6) & ((anchors[:, 3] - anchors[:, 1]) >= 6))[0]
-    images = rng.normal(0, 8, (B, S, S, 3)).astype(np.float32) + 20
-    gt_masks = np.zeros((B, S, S, G), bool)
-    gt_boxes = np.zeros((B, G, 4), np.int32)
-    gt_cls = np.zeros((B, G), np.int32)
-    for b in range(B):
-        for g in range(G - 4 - b):
-            y1, x1, y2, x2 = np.round(anchors[rng.choice(ok)]).astype(int)
-            gt_masks[b, y1:y2, x1:x2, g] = True
-            gt_masks[b, (y1 + y2) // 2, (x1 + x2) // 2, g] = False
-            images[b, y1:y2, x1:x2] += rng.uniform(60, 200)
-            gt_boxes[b, g] = [y1, x1, y2, x2]
-            gt_cls[b, g] = rng.integers(1, cfg.NUM_CLASSES)
-    return images, gt_cls, gt_boxes, gt_masks
-
-
-def _train_inputs(cfg, B, seed):
-    images, gt_cls, gt_boxes, gt_masks = _scene(cfg, B, seed)
-    anchors_px = orc.generate_pyramid_anchors(cfg.RPN_ANCHOR_SCALES, cfg.RPN_ANCHOR_RATIOS,
-                                              orc.compute_backbone_shapes(cfg.BACKBONE_STRIDES, cfg.IMAGE_SHAPE),
-                                              cfg.BACKBONE_STRIDES, cfg.RPN_ANCHOR_STRIDE)
-    rng = np.random.RandomState(seed)
-    rpn_match = np.zeros((B, anchors_px.shape[0], 1), np.int32)
-    rpn_bbox = np.zeros((B, cfg.RPN_TRAIN_ANCHORS_PER_IMAGE, 4), np.float32)
-    for b in range(B):
-        n = int((gt_cls[b] > 0).sum())
-        m, bb = orc.build_rpn_targets(anchors_px, gt_cls[b, :n], gt_boxes[b, :n], cfg.RPN_TRAIN_ANCHORS_PER_IMAGE,
-                                      cfg.RPN_BBOX_STD_DEV, rng)
-        rpn_match[b, :, 0], rpn_bbox[b] = m, bb
-    meta = np.stack([orc.compose_image_meta(b, images[b].shape, images[b].shape, (0, 0) + images[b].shape[:2], 1.0,
-                                            np.ones(cfg.NUM_CLASSES, np.int32)) for b in range(B)])
-    keys = np.random.default_rng(seed + 1).uniform(0, 1, (B, cfg.POST_NMS_ROIS_TRAINING)).astype(np.float32)
-    return [images, meta, rpn_match, rpn_bbox, gt_cls, gt_boxes, gt_masks], keys
-
-
-def _weights(cfg, seed, damp=None):
-    """damp: factor on the BatchNorm gamma that closes every bottleneck branch.  ResNet-101 sums 33 residual branches;
-    with unit-scale random branches the activations grow ~2x in variance per block and the RPN saturates (all proposals
-    clip to the full tile, no positive ROI): 0.25 keeps the trunk's output in range so that every branch of the training
-    graph carries signal."""
-    from caesar_mrcnn_amd.params import ParamLayout, init_weights, deconv_gemm_to_keras
-    w = init_weights(ParamLayout(cfg), seed=seed, perturb_bn=True)
-    if damp is not None:
-        for k in w:
-            if k.endswith("_branch2c/gamma"):
-                w[k] = w[k] * np.float32(damp)
-    w["mrcnn_mask_deconv/kernel"] = deconv_gemm_to_keras(w["mrcnn_mask_deconv/kernel"])   # Keras layout at the boundary
-    # keep RPN box deltas small so proposals stay near their anchors and some reach IoU >= 0.5 with the GT
-    w["rpn_bbox_pred/kernel"] = w["rpn_bbox_pred/kernel"] * np.float32(0.02)
-    w["rpn_bbox_pred/bias"] = w["rpn_bbox_pred/bias"] * np.float32(0.02)
-    return w
 
 
 def _check_gradients(g, o, names, tag=""):
@@ -125,10 +48,9 @@ def _close(got, ref, rtol, name):
     assert err <= rtol, "%s: max error %.3g of max |ref| %.3g (allowed %.3g)" % (name, err, scale, rtol)
 
 
-@pytest.mark.parametrize("backbone,size", [("custom", 128), ("resnet50", 128)])
-def test_inference_graph_staged(dev, backbone, size):
+def _inference_staged(dev, backbone, size, num_classes=4):
     from caesar_mrcnn_amd.model import MaskRCNN
-    cfg = _small_cfg(backbone, size, mode="inference")
+    cfg = _small_cfg(backbone, size, mode="inference", num_classes=num_classes)
     w = _weights(cfg, 3)
     model = MaskRCNN("inference", cfg, "/tmp/mrcnn_logs", device=dev, weights=w)
     images, _, _, _ = _scene(cfg, 1, 7)
@@ -174,6 +96,39 @@ def test_inference_graph_staged(dev, backbone, size):
     res = model.detect([images[0].astype(np.float32)])[0]
     assert set(res) == {"rois", "class_ids", "scores", "masks"}
     assert res["masks"].shape[:2] == images[0].shape[:2] and res["masks"].shape[2] == res["rois"].shape[0]
+    assert tuple(out["mrcnn_class"].shape[2:]) == (num_classes,) and tuple(out["mrcnn_bbox"].shape[2:]) == (num_classes, 4)
+    assert out["mrcnn_mask"].shape[-1] == num_classes and det_ref[:, 4].max() < num_classes
+    return model, images, det_ref
+
+
+@pytest.mark.parametrize("backbone,size", [("custom", 128), ("resnet50", 128)])
+def test_inference_graph_staged(dev, backbone, size):
+    _inference_staged(dev, backbone, size)
+
+
+@pytest.mark.parametrize("num_classes", [2, 6])
+def test_inference_graph_staged_class_counts(dev, num_classes):
+    """The staged inference comparison at NUM_CLASSES = 2 (the tiled source finder's model) and 6 (the reference's 1 + 5): class
+    logits / softmax over C columns, C * 4 box deltas, C mask planes, the detection layer's argmax and class-specific deltas --
+    same checks and tolerances as at four classes.  At 6 also the public detect() on a uint8 image: class ids in range and the
+    device un-mold of every detection equal to the host statement (utils.unmold_mask) on the plane of ITS class."""
+    from caesar_mrcnn_amd import utils
+    model, images, det_ref = _inference_staged(dev, "custom", 128, num_classes)
+    assert (det_ref[:, 4] > 0).sum() > 0                       # the oracle's detection layer kept something to compare
+    if num_classes != 6:
+        return
+    img = np.clip(images[0], 0, 255).astype(np.uint8)
+    res = model.detect([img])[0]
+    n = res["rois"].shape[0]
+    assert n > 0 and res["class_ids"].min() >= 1 and res["class_ids"].max() < num_classes
+    molded, metas, windows = model.mold_inputs([img])
+    graph_out = model._predict_molded(molded, metas)
+    det, mm = graph_out[0][0], graph_out[3][0]
+    assert mm.shape[-1] == num_classes
+    boxes, class_ids, scores, rows = model._unmold_boxes(det, img.shape, molded[0].shape, windows[0])
+    want = np.stack([utils.unmold_mask(mm[r, :, :, c], b, img.shape) for r, c, b in zip(rows, class_ids, boxes)], axis=-1)
+    assert np.array_equal(res["rois"], boxes) and np.array_equal(res["class_ids"], class_ids) and np.array_equal(res["scores"], scores)
+    assert res["masks"].dtype == np.bool_ and np.array_equal(res["masks"], want) and want.any()
 
 
 @pytest.mark.parametrize("backbone,size,dice", [("custom", 128, False), ("resnet50", 128, False), ("custom", 128, True)])
@@ -872,3 +827,162 @@ def test_overfit_one_batch_then_detect_it(dev):
                     found += 1
                     break
     assert total > 0 and 3 * found >= total, (found, total)
+
+
+def _spy(monkeypatch, module, names):
+    """Count the calls of `module.<name>` (the engine calls its kernels through the ops module) without changing them."""
+    calls = {n: 0 for n in names}
+    for n in names:
+        real = getattr(module, n)
+
+        def wrapper(*a, _real=real, _n=n, **k):
+            calls[_n] += 1
+            return _real(*a, **k)
+        monkeypatch.setattr(module, n, wrapper)
+    return calls
+
+
+@pytest.mark.parametrize("num_classes", [2, 6, 17])
+def test_training_step_staged_class_counts(dev, num_classes, monkeypatch):
+    """One float32 training step at NUM_CLASSES = 2, 6 and 17 against the oracle, staged like test_training_step_staged: the
+    sampled ROIs / targets exactly, the five losses at rtol 2e-3, every parameter gradient through _check_gradients.  The class
+    count is the width of mrcnn_class_logits (C), mrcnn_bbox_fc (4 C) and mrcnn_mask (C) -- their forward, weight- and
+    data-gradient kernels -- and selects the backward of the mask head's output stage: the fused mask_out_bwd_kernel<4> / <8>
+    at 2 / 6, and at 17 (more than the fused kernel's 16) the unfused chain (sigmoid epilogue backward, 1x1 weight and data
+    gradient, ReLU epilogue backward, pixel_unshuffle2).  Which one ran is observed from outside the engine.  At 6 both the
+    dense mask head and the positive-quota one (the class-plane gather of its rows) against ONE oracle pass, as in test_cfg3."""
+    from caesar_mrcnn_amd import ops
+    from caesar_mrcnn_amd.model import MaskRCNN
+    cfg = _small_cfg("custom", 128, num_classes=num_classes)
+    cfg.LOSS_WEIGHTS = dict(cfg.LOSS_WEIGHTS, rpn_bbox_loss=0.7, mrcnn_mask_loss=1.3)
+    B, size = 2, 128
+    w = _weights(cfg, 11)
+    assert w["mrcnn_class_logits/kernel"].shape[-1] == num_classes and w["mrcnn_bbox_fc/kernel"].shape[-1] == 4 * num_classes
+    assert w["mrcnn_mask/kernel"].shape[-1] == num_classes
+    inputs, keys = _train_inputs(cfg, B, 5)
+    images, meta, rpn_match, rpn_bbox_t, gt_cls, gt_boxes, gt_masks = inputs
+    assert meta.shape[1] == 12 + num_classes and gt_cls.max() < num_classes
+    calls = _spy(monkeypatch, ops, ["mask_out_bwd", "pixel_unshuffle2"])
+    runs = {}
+    for mode in (("dense", "sparse") if num_classes == 6 else ("sparse",)):
+        model = MaskRCNN("training", cfg, "/tmp/mrcnn_logs", device=dev, weights=w)
+        eng = model.engine
+        assert eng.fused_mask_out_bwd and eng.head_dtype is None
+        eng.sparse_mask_bwd = mode == "sparse"
+        losses = model.train_on_batch(inputs, rand_keys=keys, apply=False, keep_outputs=True)
+        torch.cuda.synchronize()
+        last = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in eng.last.items() if k != "pyramid"}
+        eng.apply_gradients(0.0, 0.0, world_size=1)      # lr = 0: adds the L2 term, leaves the gradient in eng.grads
+        torch.cuda.synchronize()
+        runs[mode] = (losses.cpu().numpy(), eng.get_weights(grads=True), last)
+        names = list(eng.layout.offsets)
+        del model, eng
+    # which output-stage backward ran (engine._mask_head_bwd_rows_impl: fused only up to 16 classes)
+    if num_classes <= 16:
+        assert calls["mask_out_bwd"] >= len(runs) and calls["pixel_unshuffle2"] == 0, calls
+    else:
+        assert calls["mask_out_bwd"] == 0 and calls["pixel_unshuffle2"] >= len(runs), calls
+    last = runs["sparse"][2]
+    o = orc.OracleMaskRCNN(cfg, w, requires_grad=True)
+    gtn = ((gt_boxes.astype(np.float32) - np.array([0, 0, 1, 1], np.float32)) / np.float32(size - 1)).astype(np.float32)
+    npos = 0
+    for b in range(B):
+        r_rois, r_cls, r_bb, r_m, (P, N) = o.detection_targets(last["rpn_rois"][b], gt_cls[b], gtn[b], gt_masks[b], keys[b])
+        assert tuple(last["counts"][b]) == (P, N)
+        np.testing.assert_array_equal(last["rois"][b], r_rois)
+        np.testing.assert_array_equal(last["target_class_ids"][b], r_cls)
+        np.testing.assert_allclose(last["target_bbox"][b], r_bb, rtol=1e-5, atol=1e-5)
+        np.testing.assert_array_equal(last["target_mask"][b], r_m)
+        npos += P
+    assert npos > 0, "scene produced no positive ROIs; the mask/bbox losses would be untested"
+    if num_classes > 2:
+        assert len(set(last["target_class_ids"][last["target_class_ids"] > 0].tolist())) > 1        # more than one class plane read
+    for mode in runs:
+        for k in ("rois", "target_class_ids", "target_bbox", "target_mask"):
+            np.testing.assert_array_equal(runs[mode][2][k], last[k])
+    forced = {k: last[k] for k in ("rois", "target_class_ids", "target_bbox", "target_mask")}
+    ref = o.forward_training(images, rpn_match, rpn_bbox_t.astype(np.float32), gt_cls, gt_boxes, gt_masks,
+                             meta[:, 12:].astype(np.int32), orc.get_anchors(cfg, images.shape[1:]), keys, forced=forced)
+    want = np.array([float(l.detach()) for l in ref["losses"]])
+    assert np.all(want > 0)
+    o.total_loss(ref["losses"]).backward()
+    quota = int(cfg.TRAIN_ROIS_PER_IMAGE * cfg.ROI_POSITIVE_RATIO)
+    for mode, (losses, g, lst) in runs.items():
+        _close(lst["mrcnn_class_logits"], ref["mrcnn_class_logits"].detach(), 1e-3, "mrcnn_class_logits")
+        rows = quota if mode == "sparse" else cfg.TRAIN_ROIS_PER_IMAGE
+        _close(lst["mrcnn_mask"][:, :rows], ref["mrcnn_mask"].detach().numpy()[:, :rows], 1e-3, "mrcnn_mask")
+        assert not lst["mrcnn_mask"][:, rows:].any()
+        print("[training step C=%d %s] losses max rel err %.3g (rtol 2e-3)" % (
+            num_classes, mode, float(np.max(np.abs(losses - want) / np.maximum(want, 1e-5)))))
+        np.testing.assert_allclose(losses, want, rtol=2e-3, atol=1e-5, err_msg=mode)
+        _check_gradients(g, o, names, "C=%d %s" % (num_classes, mode))
+        for name in ("mrcnn_class_logits/kernel", "mrcnn_bbox_fc/kernel", "mrcnn_mask/kernel", "mrcnn_mask/bias", "mrcnn_mask_deconv/bias"):
+            assert np.abs(g[name]).max() > 0, name
+
+
+@pytest.mark.parametrize("how", ["graph", "tape"])
+def test_replayed_training_steps_keep_class_counts_apart(dev, how):
+    """Two models in one process, NUM_CLASSES = 4 and 6, each stepping through its own HIP graph / launch tape in turn: every
+    model's replayed steps equal its own eager steps at the float32 bars of test_graphed_training_steps_equal_eager (losses rtol
+    2e-4, parameters 2e-4, momentum 5e-3 of the maximum -- float atomics, not bit-exactness, bound a replay), and the two
+    trajectories differ.  Each engine keeps its own recordings, so no key can collide across models; what the two models share
+    is the ops module's per-stream workspaces, the pair of side streams and the allocator, and that is what stepping them in
+    turn exercises: a recording must survive the other model's steps (workspaces grown or replaced, side streams reused).
+    Both runs take their proposals from one fixed set per batch (engine.forced_rpn_rois: this model's own proposals at the
+    initial weights, refreshed in place before every step), as the 16-bit case of test_graphed_training_steps_equal_eager does
+    and for its reason: from the second step on the weights of two runs differ by the order of the float atomics, an RPN score
+    that moves in its last bits can re-order one NMS / top-k decision, and a single sampled negative ROI that differs moves
+    mrcnn_class_loss (a mean over 96 rows with logits of tens) by percents -- two different problems, whatever issued the
+    launches.  The proposal layer's own replay is compared bit for bit by the inference-graph tests."""
+    from caesar_mrcnn_amd.model import MaskRCNN
+    counts = (4, 6)
+    cfgs = {c: _small_cfg("custom", 128, num_classes=c) for c in counts}
+    ws = {c: _weights(cfgs[c], 71) for c in counts}
+    batches = {c: [_train_inputs(cfgs[c], 2, 73), _train_inputs(cfgs[c], 2, 75)] for c in counts}
+    steps = 3
+    forced = {}
+    for c in counts:
+        m0 = MaskRCNN("training", cfgs[c], "/tmp/mrcnn_logs", device=dev, weights=ws[c])
+        forced[c] = []
+        for inputs, keys in batches[c]:
+            m0.train_on_batch(inputs, rand_keys=keys, apply=False, keep_outputs=True)
+            forced[c].append(m0.engine.last["rpn_rois"].clone())
+            assert int(m0.engine.last["counts"][:, 0].sum()) > 0          # positive ROIs: every loss carries signal
+        del m0
+
+    def run(replayed):
+        models = {c: MaskRCNN("training", cfgs[c], "/tmp/mrcnn_logs", device=dev, weights=ws[c]) for c in counts}
+        losses = {c: [] for c in counts}
+        for c in counts:
+            models[c].compile(0.002, 0.9)
+            models[c].engine.forced_rpn_rois = torch.empty_like(forced[c][0])
+        for s in range(steps):
+            for c in counts:                                   # interleaved: 4, 6, 4, 6, ...
+                eng = models[c].engine
+                di = models[c]._to_device(*batches[c][s % 2])
+                eng.forced_rpn_rois.copy_(forced[c][s % 2])
+                if replayed:
+                    ls = (eng.step_graphed if how == "graph" else eng.step_taped)(di, 0.002, 0.9)
+                else:
+                    ls = eng.forward_backward(*di)
+                    eng.apply_gradients(0.002, 0.9, 1)
+                losses[c].append(ls.cpu().numpy().copy())
+        torch.cuda.synchronize()
+        if replayed:
+            for c in counts:
+                assert len(models[c].engine._train_graphs if how == "graph" else models[c].engine._train_tapes) == 1
+        return {c: (np.stack(losses[c]), models[c].engine.params.cpu().numpy().copy(), models[c].engine.momentum.cpu().numpy().copy())
+                for c in counts}
+
+    eager, replay = run(False), run(True)
+    tol = 2e-4
+    for c in counts:
+        print("[replay %s C=%d] losses max rel diff per step %s (rtol 2e-4); parameters %.3g, momentum %.3g of their maximum (2e-4, 5e-3)" % (
+            how, c, np.max(np.abs(replay[c][0] - eager[c][0]) / np.maximum(np.abs(eager[c][0]), 1e-5), axis=1),
+            np.abs(replay[c][1] - eager[c][1]).max() / np.abs(eager[c][1]).max(), np.abs(replay[c][2] - eager[c][2]).max() / np.abs(eager[c][2]).max()))
+        np.testing.assert_allclose(replay[c][0], eager[c][0], rtol=tol, atol=1e-5, err_msg="C=%d" % c)
+        for k, t in ((1, tol), (2, max(tol, 5e-3))):
+            scale = np.abs(eager[c][k]).max()
+            assert np.abs(replay[c][k] - eager[c][k]).max() <= t * scale, (c, k)
+        assert np.abs(eager[c][2]).max() > 0
+    assert eager[4][1].shape != eager[6][1].shape and not np.allclose(eager[4][0], eager[6][0], rtol=1e-3)

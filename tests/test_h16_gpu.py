@@ -395,22 +395,94 @@ def test_mixed_precision_training_step(dev, dtype, backbone, wide):
         assert np.abs(g).max() > 0 and np.isfinite(g).all(), name
 
 
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("num_classes", [6, 17])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_mixed_precision_training_step_class_counts(dev, dtype, num_classes, wide, monkeypatch):
+    """engine.head_dtype at NUM_CLASSES = 6 and 17 (custom backbone, the comparison and per-dtype bars of
+    test_mixed_precision_training_step: losses to 1e-2 / 4e-2, every gradient tensor to 4x that of its maximum -- with the 16-bit
+    trunk blocks of `wide`, 10x in L2 -- and the median L2 error to 2.5x), with the float32 ORACLE as the reference, fed the ROIs and
+    targets this engine sampled.  At 6 the output stage stays on the 16-bit tensors and takes the general kernels
+    (mask_out_fwd_h16_kernel, mask_out_bwd_h16_kernel<T, 8>); at 17 those refuse and the engine runs the mixed path: 16-bit
+    convolutions, float32 deconvolution and unfused output stage, the gradient cast back to 16 bits with the loss scale.  Which
+    one ran is observed from outside the engine.  float16: no overflow on these inputs, so the step is not skipped and the
+    loss scale is not lowered."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_engine_gpu as T
+    from caesar_mrcnn_amd import ops
+    from caesar_mrcnn_amd.model import MaskRCNN
+    cfg = T._small_cfg("custom", 128, num_classes=num_classes)
+    w = T._weights(cfg, 31)
+    inputs, keys = T._train_inputs(cfg, 2, 33)
+    images, meta, rpn_match, rpn_bbox_t, gt_cls, gt_boxes, gt_masks = inputs
+    calls = T._spy(monkeypatch, ops, ["mask_out_fwd_h16", "mask_out_bwd_h16", "mask_out_bwd", "pixel_unshuffle2", "deconv2x2", "deconv2x2_h16"])
+    model = MaskRCNN("training", cfg, "/tmp/mrcnn_logs", device=dev, weights=w)
+    eng = model.engine
+    eng.head_dtype, eng.h16_wide = dtype, wide
+    scale0 = float(eng.loss_scale)
+    losses = model.train_on_batch(inputs, rand_keys=keys, apply=False, keep_outputs=True)
+    torch.cuda.synchronize()
+    n16 = sum(eng._h16_block(b) for st in eng.stages for b in st)
+    assert eng._h16_layer("mrcnn_class_conv1") == wide and (n16 > 0) == wide
+    if num_classes <= 16:
+        assert calls["mask_out_fwd_h16"] >= 1 and calls["mask_out_bwd_h16"] >= 1 and calls["deconv2x2_h16"] >= 1, calls
+        assert calls["mask_out_bwd"] == 0 and calls["pixel_unshuffle2"] == 0 and calls["deconv2x2"] == 0, calls
+    else:
+        assert calls["mask_out_fwd_h16"] == 0 and calls["mask_out_bwd_h16"] == 0 and calls["deconv2x2_h16"] == 0, calls
+        assert calls["mask_out_bwd"] == 0 and calls["pixel_unshuffle2"] >= 1 and calls["deconv2x2"] >= 1, calls
+    last = {k: v.cpu().numpy() for k, v in eng.last.items() if torch.is_tensor(v)}
+    assert int(last["counts"][:, 0].sum()) > 0, "no positive ROIs: the mask / bbox branches would be untested"
+    eng.apply_gradients(0.0, 0.0, world_size=1)              # lr 0: adds the L2 term; float16: the guarded step looks at the norm
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(eng.grads).all())
+    if dtype == torch.float16:
+        assert eng.skipped_step_count() == 0 and eng.adapt_loss_scale() == 0 and float(eng.loss_scale) == scale0 and scale0 > 1.0
+    g = eng.get_weights(grads=True)
+    names = list(eng.layout.offsets)
+    o = orc.OracleMaskRCNN(cfg, w, requires_grad=True)
+    forced = {k: last[k] for k in ("rois", "target_class_ids", "target_bbox", "target_mask")}
+    ref = o.forward_training(images, rpn_match, rpn_bbox_t.astype(np.float32), gt_cls, gt_boxes, gt_masks,
+                             meta[:, 12:].astype(np.int32), orc.get_anchors(cfg, images.shape[1:]), keys, forced=forced)
+    o.total_loss(ref["losses"]).backward()
+    want = np.array([float(l.detach()) for l in ref["losses"]])
+    tol = 1e-2 if dtype == torch.float16 else 4e-2
+    got = losses.cpu().numpy()
+    bad, l2s, worst = [], [], 0.0
+    for name in names:
+        rg = o.w[name].grad.numpy().astype(np.float64)
+        d = g[name].astype(np.float64) - rg
+        err = float(np.abs(d).max()) / max(float(np.abs(rg).max()), 1e-10)
+        l2 = float(np.linalg.norm(d)) / max(float(np.linalg.norm(rg)), 1e-12)
+        l2s.append(l2)
+        worst = max(worst, l2 / (10 * tol) if n16 else err / (4 * tol))
+        if (l2 > 10 * tol) if n16 else (err > 4 * tol):
+            bad.append((name, err, l2))
+    print("[mixed precision C=%d %s wide=%s] losses max rel err %.3g (rtol %.3g); worst gradient tensor %.3g of its bar; median L2 %.3g (bar %.3g)" % (
+        num_classes, dtype, wide, float(np.max(np.abs(got - want) / np.abs(want))), tol, worst, np.median(l2s), 2.5 * tol))
+    np.testing.assert_allclose(got, want, rtol=tol)
+    assert not bad, bad[:6]
+    assert np.median(l2s) <= 2.5 * tol, np.median(l2s)
+    for name in ("mrcnn_mask_conv2/kernel", "mrcnn_mask/kernel", "mrcnn_mask_deconv/kernel", "mrcnn_class_logits/kernel", "mrcnn_bbox_fc/kernel"):
+        assert np.abs(g[name]).max() > 0 and np.isfinite(g[name]).all(), name
+
+
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_deconv_and_mask_output_stage_h16(dev, dtype, h16_tile):
-    """16-bit deconvolution (pixel-shuffle store; 256 x 128 tile kernel and the phased kernel's row-store form) + mask 1x1
-    conv + sigmoid, and the one-pass backward of that stage, against the float32 ops of the package (themselves checked
-    against the oracle) on the same 16-bit-rounded tensors."""
+    """16-bit deconvolution (pixel-shuffle store; 256 x 128 tile kernel and the phased kernel's row-store form) against the oracle's
+    Conv2DTranspose on the same 16-bit-rounded tensors; then mask 1x1 conv + sigmoid and the one-pass backward of that stage on the
+    deconvolution's output against their float64 statement (test_kernels_gpu._mask_out_ref64)."""
     ops = _ops()
     if h16_tile == "big":
         pytest.skip("the ring kernel has no pixel-shuffle store")
-    from caesar_mrcnn_amd.params import deconv_keras_to_gemm
+    from caesar_mrcnn_amd.params import deconv_keras_to_gemm, deconv_gemm_to_keras
     rng = np.random.default_rng(17)
     M, Cd, C = 37, 256, 4
     x = torch.tensor(rng.standard_normal((M, 14, 14, 256)).astype(np.float32)).to(dtype)
     k = (rng.standard_normal((2, 2, Cd, 256)) * 0.05).astype(np.float32)                  # Keras (2,2,out,in)
     wg = torch.tensor(deconv_keras_to_gemm(k).reshape(256, 4 * Cd)).to(dtype)            # GEMM matrix [Cin, 4*Cd], rounded
     b = torch.tensor(rng.standard_normal(Cd).astype(np.float32) * 0.1)
-    up_ref = ops.deconv2x2(x.float().to(dev), wg.float().to(dev), b.to(dev), 1)           # float32 kernel, same operands
+    k16 = torch.tensor(deconv_gemm_to_keras(wg.float().numpy().reshape(256, 2, 2, Cd)))  # the rounded weights, Keras layout
+    up_ref = torch.relu(orc.conv2d_transpose_2x2(x.float(), k16, b)).to(dev)              # the oracle on the same operands
     wt, _ = ops.weights_to_h16(wg.float().to(dev).view(1, 1, 256, 4 * Cd), dtype, want_dgrad=False)
     up = ops.deconv2x2_h16(x.to(dev), wt, b.to(dev), Cd, 1)
     torch.cuda.synchronize()
@@ -419,23 +491,87 @@ def test_deconv_and_mask_output_stage_h16(dev, dtype, h16_tile):
     assert err <= TOL[dtype], err
     wm = torch.tensor(rng.standard_normal((Cd, C)).astype(np.float32) * 0.1, device=dev)
     bm = torch.tensor(rng.standard_normal(C).astype(np.float32) * 0.1, device=dev)
-    m_ref = ops.conv2d(up.float(), wm.view(1, 1, Cd, C), bm, stride=1, padding="valid", act=2)
+    g = torch.tensor(rng.standard_normal((M, 28, 28, C)).astype(np.float32) * 1e-3, device=dev)
+    _check_mask_output_stage_h16(dev, dtype, up, wm, bm, g, "C=4 Cd=256 %s" % h16_tile)
+
+
+def _check_mask_output_stage_h16(dev, dtype, up, wm, bm, g, tag, up_bwd=None):
+    """mrcnn_mask_out_fwd_h16 / mrcnn_mask_out_bwd_h16 on the 16-bit `up` against the float64 statement of the stage
+    (test_kernels_gpu._mask_out_ref64) on the same 16-bit-rounded `up`: forward rtol = atol = 1e-5; dzg, divided by the loss
+    scale, TOL[dtype] of its maximum (one 16-bit rounding); the three float32 sums rtol 1e-4, atol 1e-4 max |ref|, accumulated
+    onto non-zero buffers.  up_bwd: the tensor the backward reads (the same values at another address)."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_kernels_gpu as K
+    ops = _ops()
+    M, H, W, Cd = up.shape
+    C = wm.shape[1]
+    ref = K._mask_out_ref64(up.cpu(), wm.cpu(), bm.cpu(), g.cpu())
     m = ops.mask_out_fwd_h16(up, wm, bm)
     torch.cuda.synchronize()
-    torch.testing.assert_close(m, m_ref, rtol=1e-5, atol=1e-5)
-    # backward of the output stage
-    g = torch.tensor(rng.standard_normal((M, 28, 28, C)).astype(np.float32) * 1e-3, device=dev)
-    ref_dw, ref_dbm, ref_dbd = torch.zeros_like(wm), torch.zeros(C, device=dev), torch.zeros(Cd, device=dev)
-    dzg_ref = ops.mask_out_bwd(g, m, up.float(), wm, ref_dw, ref_dbm, ref_dbd)
-    dw, dbm, dbd = torch.zeros_like(wm), torch.zeros(C, device=dev), torch.zeros(Cd, device=dev)
+    assert m.dtype == torch.float32 and tuple(m.shape) == (M, H, W, C)
+    fe = (m.cpu().double() - ref["mask"]).abs()
+    msg = ["fwd %.3g of its bar" % float((fe / (1e-5 + 1e-5 * ref["mask"].abs())).max())]
+    torch.testing.assert_close(m.cpu().double(), ref["mask"], rtol=1e-5, atol=1e-5)
+    # backward of the output stage: it reads a stored float32 mask -- here the float64 mask rounded to float32 (not the output of
+    # the forward kernel above), and the reference takes its sigmoid' from exactly that tensor
+    m = ref["mask"].float().to(dev)
+    ref = K._mask_out_ref64(up.cpu(), wm.cpu(), bm.cpu(), g.cpu(), m.cpu())
+    gen = torch.Generator().manual_seed(C * 1000 + Cd)
+    init = [torch.randn(shape, generator=gen) * 0.05 for shape in ((Cd, C), (C,), (Cd,))]
+    dw, dbm, dbd = (t.clone().to(dev) for t in init)
     S = 1024.0
-    dzg = ops.mask_out_bwd_h16(g, m, up, wm, dw, dbm, dbd, S)
+    dzg = ops.mask_out_bwd_h16(g, m, up if up_bwd is None else up_bwd, wm, dw, dbm, dbd, S)
     torch.cuda.synchronize()
-    assert dzg.dtype == dtype
-    err = float((dzg.float() / S - dzg_ref).abs().max()) / float(dzg_ref.abs().max())
-    assert err <= TOL[dtype], err
-    for a, r in ((dw, ref_dw), (dbm, ref_dbm), (dbd, ref_dbd)):
-        torch.testing.assert_close(a, r, rtol=1e-4, atol=1e-4 * float(r.abs().max()))
+    assert dzg.dtype == dtype and tuple(dzg.shape) == (M, H // 2, W // 2, 4 * Cd)
+    assert float((ref["dzg"] == 0).double().mean()) > 0.3 and float(ref["dzg"].abs().max()) > 0          # the ReLU mask bites
+    err = float((dzg.cpu().double() / S - ref["dzg"]).abs().max()) / float(ref["dzg"].abs().max())
+    msg.append("dzg %.3g (allowed %.3g)" % (err, TOL[dtype]))
+    fails = [] if err <= TOL[dtype] else ["dzg"]
+    for name, a, start in (("dWm", dw, init[0]), ("dbm", dbm, init[1]), ("dbd", dbd, init[2])):
+        r = start.double() + ref[name]
+        e = (a.cpu().double() - r).abs()
+        rel = float((e / (1e-4 * float(r.abs().max()) + 1e-4 * r.abs())).max())
+        msg.append("%s %.3g of its bar" % (name, rel))
+        if rel > 1.0:
+            fails.append(name)
+    print("[mask output stage %s %s] %s" % (dtype, tag, ", ".join(msg)))
+    assert not fails, (fails, msg)
+
+
+MASK_STAGE_H16_CASES = [
+    # C, Cd, M, `up` of the backward 8 bytes off a 16-byte boundary
+    (2, 256, 37, False),         # forward: the 16-lanes-per-pixel kernel (C <= 4, Cd = 256); backward: the 16-byte kernel <T, 4>
+    (5, 256, 37, False),         # forward: general kernel, one 256-channel segment, weights in registers; backward: <T, 8>
+    (6, 256, 37, False),
+    (9, 256, 37, False),         # backward: <T, 16>
+    (16, 256, 37, False),        # the cap of both entry points
+    (2, 512, 5, False),          # Cd = 512: forward with two segments, weights read from memory; backward <T, 4> (no 16-byte form)
+    (6, 512, 5, False),
+    (2, 256, 37, True),          # misaligned for 16-byte accesses: the 16-byte backward declines, the one-channel-per-thread <T, 4> runs
+    (4, 256, 37, True),
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("num_classes,Cd,M,offset", MASK_STAGE_H16_CASES)
+def test_mask_output_stage_h16_class_counts(dev, dtype, num_classes, Cd, M, offset):
+    """The 16-bit mask output stage at NUM_CLASSES = 2, 5, 6, 9, 16 (test_deconv_and_mask_output_stage_h16 runs it at 4 behind a
+    real deconvolution): which kernel each case takes is in MASK_STAGE_H16_CASES.  M * 784 pixels are ragged against the 512-pixel
+    workgroups of the backward (and the 64 / 256 of the forward); `up` holds zeros and negatives."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_kernels_gpu as K
+    C = num_classes
+    rng = np.random.default_rng(9000 + 17 * C + Cd + int(offset))
+    assert (M * 784) % 512 != 0 and (M * 784) % 256 != 0
+    up, wm, bm, g = K._mask_out_inputs(rng, M, 28, 28, Cd, C, dtype)
+    up, wm, bm, g = up.to(dev), wm.to(dev), bm.to(dev), g.to(dev)
+    up_bwd = None
+    if offset:
+        buf = torch.empty(up.numel() + 8, dtype=dtype, device=dev)
+        up_bwd = buf[4:4 + up.numel()].view(up.shape)
+        up_bwd.copy_(up)
+        assert up.data_ptr() % 16 == 0 and up_bwd.data_ptr() % 16 == 8 and up_bwd.is_contiguous()
+    _check_mask_output_stage_h16(dev, dtype, up, wm, bm, g, "C=%d Cd=%d%s" % (C, Cd, " offset" if offset else ""), up_bwd)
 
 
 def test_graph_replay_follows_weight_updates_h16(dev):

@@ -173,6 +173,101 @@ def test_weight_file_roundtrip_and_exclude_quirk(tmp_path):
     assert "conv1/kernel" not in kept and "bn_conv1/gamma" in kept and "mrcnn_mask_conv1/kernel" in kept
 
 
+@pytest.mark.parametrize("num_classes", [2, 6, 17])
+def test_param_layout_and_weight_files_follow_the_class_count(tmp_path, num_classes):
+    """NUM_CLASSES (run.py --classdict) is the width of three layers: mrcnn_class_logits [1024, C], mrcnn_bbox_fc [1024, 4 C] (Dense
+    layers, kept as 1 x 1 kernels) and mrcnn_mask [1, 1, 256, C].  Whatever C is, every tensor of the flat buffer starts on a 64-float
+    granule, the buffer is a whole number of granules (the optimiser kernels' ABI), nothing overlaps, the granule table covers the
+    three tensors, and both weight containers return the tensors bit for bit."""
+    from caesar_mrcnn_amd import hdf5_min, weights_io
+    from caesar_mrcnn_amd.config import run_py_config
+    from caesar_mrcnn_amd.params import ALIGN, ParamLayout, deconv_gemm_to_keras, granule_coefficients, init_weights
+    C_ = num_classes
+    cfg = run_py_config(num_classes=C_, backbone="custom", imgsize=128)
+    assert cfg.NUM_CLASSES == C_ and cfg.IMAGE_META_SIZE == 12 + C_
+    L = ParamLayout(cfg)
+    heads = {"mrcnn_class_logits": (1024, C_), "mrcnn_bbox_fc": (1024, 4 * C_), "mrcnn_mask": (256, C_)}
+    for name, (cin, cout) in heads.items():
+        assert L.by_name[name].shape == (1, 1, cin, cout)
+        assert L.offsets[name + "/kernel"][1:] == (cin * cout, (1, 1, cin, cout)) and L.offsets[name + "/bias"][1:] == (cout, (cout,))
+    assert ALIGN == 64 and L.total % 64 == 0 and L.gamma_offset % 64 == 0 and L.beta_offset % 64 == 0
+    segs = sorted(L.segments, key=lambda s_: s_[1])
+    assert all(s_[1] % 64 == 0 for s_ in segs)
+    assert all(a[1] + a[2] <= b[1] for a, b in zip(segs[:-1], segs[1:])) and segs[-1][1] + segs[-1][2] <= L.total
+    base = ParamLayout(run_py_config(num_classes=4, backbone="custom", imgsize=128))
+    grow = lambda c: sum((n + 63) // 64 * 64 for n in (1024 * c, c, 1024 * 4 * c, 4 * c, 256 * c, c))
+    assert L.total - base.total == grow(C_) - grow(4)                      # nothing but the three layers depends on C
+    gran = granule_coefficients(L, 1e-4, L.trainable_mask("all"))
+    assert gran.shape == (L.total // 64,)
+    for name in heads:
+        off, n, _ = L.offsets[name + "/kernel"]
+        assert (gran[off // 64:(off + n + 63) // 64] == np.float32(2e-4 / n)).all()
+        assert off + n == (off + n + 63) // 64 * 64 or gran[(off + n) // 64] == np.float32(2e-4 / n)      # a partial last granule is the tensor's
+    w = init_weights(L, seed=3, perturb_bn=True)
+    assert w["mrcnn_class_logits/kernel"].reshape(1024, C_).shape == (1024, C_) and w["mrcnn_class_logits/bias"].shape == (C_,)
+    assert w["mrcnn_bbox_fc/kernel"].shape[-2:] == (1024, 4 * C_) and w["mrcnn_mask/kernel"].shape == (1, 1, 256, C_)
+    assert all(np.abs(w[n + "/kernel"]).max() > 0 for n in heads)
+    w["mrcnn_mask_deconv/kernel"] = deconv_gemm_to_keras(w["mrcnn_mask_deconv/kernel"])
+    for ext in (".npz", ".h5"):
+        p = str(tmp_path / ("mask_rcnn_c%d%s" % (C_, ext)))
+        weights_io.save(p, w, L)
+        back = weights_io.load(p)
+        assert set(back) == set(w) and all(np.array_equal(back[k], w[k]) and back[k].shape == w[k].shape for k in w)
+    f = hdf5_min.H5File(str(tmp_path / ("mask_rcnn_c%d.h5" % C_)))
+    assert f.read(f.get(f.root, "mrcnn_bbox_fc/mrcnn_bbox_fc/kernel:0")).shape[-2:] == (1024, 4 * C_)
+
+
+def test_class_count_preconditions_of_gpu_cases():
+    """The GPU parity tests at other class counts assert data-dependent preconditions from the reference side; here the same seeded
+    inputs (tests/model_cases.py) go through the oracle alone, so the seeds are known to be good without a GPU: the detection layer
+    keeps more than 10 detections per image at both confidence settings and every foreground class occurs among them; the class
+    loss sees both active and inactive predictions, with a positive normaliser, and every class among its targets."""
+    import mrcnn_oracle as orc
+    import model_cases as M
+    from caesar_mrcnn_amd.config import run_py_config
+    for num_classes, seed, scale in [(4, 21, 2.0)] + M.DETECTION_CLASS_CASES:
+        cfg = run_py_config(mode="inference", num_classes=num_classes)
+        rois, probs, deltas, windows = M.detection_layer_inputs(num_classes, seed, scale)
+        o = orc.OracleMaskRCNN(cfg, {})
+        seen = set()
+        for minconf in (0, 0.5):
+            cfg.DETECTION_MIN_CONFIDENCE = minconf
+            for b in range(rois.shape[0]):
+                ref = o.refine_detections(rois[b], probs[b], deltas[b], windows[b])
+                assert (ref[:, 4] > 0).sum() > 10, (num_classes, minconf, b)
+                assert minconf == 0 or ref[ref[:, 4] > 0, 5].min() >= 0.5
+                seen |= set(ref[ref[:, 4] > 0, 4].astype(int).tolist())
+        assert seen == set(range(1, num_classes)), (num_classes, seen)
+    for num_classes, cycle in ((4, False), (2, True), (5, True), (6, True), (17, True)):
+        d = M.losses_inputs(num_classes, cycle)
+        assert set(d["pred_active"].tolist()) == {0, 1} and d["pred_active"].sum() > 0, num_classes
+        if cycle:
+            assert set(d["tcls"].reshape(-1).tolist()) == set(range(num_classes))
+
+
+def test_oracle_training_graph_at_six_classes():
+    """OracleMaskRCNN.forward_training on the small test configuration at NUM_CLASSES = 6 (the reference's documented 1 + 5): five
+    finite losses, head outputs C / 4 C / C wide, target class ids of more than one foreground class below C."""
+    import torch
+    import mrcnn_oracle as orc
+    import model_cases as T
+    cfg = T._small_cfg("custom", 128, num_classes=6)
+    w = T._weights(cfg, 11)
+    inputs, keys = T._train_inputs(cfg, 2, 5)
+    images, meta, rpn_match, rpn_bbox_t, gt_cls, gt_boxes, gt_masks = inputs
+    assert meta.shape == (2, 18) and set(np.unique(gt_cls)) <= set(range(6)) and len(set(gt_cls[gt_cls > 0].tolist())) == 5
+    o = orc.OracleMaskRCNN(cfg, w)
+    with torch.no_grad():
+        ref = o.forward_training(images, rpn_match, rpn_bbox_t.astype(np.float32), gt_cls, gt_boxes, gt_masks,
+                                 meta[:, 12:].astype(np.int32), orc.get_anchors(cfg, images.shape[1:]), keys)
+    losses = np.array([float(l) for l in ref["losses"]])
+    assert losses.shape == (5,) and np.isfinite(losses).all() and (losses > 0).all(), losses
+    assert tuple(ref["mrcnn_class_logits"].shape) == (2, cfg.TRAIN_ROIS_PER_IMAGE, 6)
+    assert tuple(ref["mrcnn_bbox"].shape) == (2, cfg.TRAIN_ROIS_PER_IMAGE, 6, 4) and tuple(ref["mrcnn_mask"].shape[2:]) == (28, 28, 6)
+    tc = ref["target_class_ids"]
+    assert sum(c[0] for c in ref["counts"]) > 0 and tc.max() < 6 and len(set(tc[tc > 0].tolist())) > 1
+
+
 def test_set_log_dir_epoch_parsing():
     from caesar_mrcnn_amd.model import MaskRCNN
     from caesar_mrcnn_amd.config import run_py_config

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import mrcnn_oracle as orc
+from model_cases import DETECTION_CLASS_CASES, _rand, _random_rois, detection_layer_inputs, losses_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -18,10 +19,6 @@ F32 = dict(rtol=2e-4, atol=2e-4)     # fp32 contractions with a different summat
 def _ops():
     from caesar_mrcnn_amd import ops
     return ops
-
-
-def _rand(rng, *shape, scale=1.0):
-    return (rng.standard_normal(shape) * scale).astype(np.float32)
 
 
 def _cfg(**kw):
@@ -58,6 +55,15 @@ CONV_CASES = [
     (1, 7, 9, 256, 128, 3, 1, "same", 0, False, 1),      # ragged M (63 = 3 x 16 + 15), odd map, residual, no BN
     (1, 16, 16, 512, 256, 1, 2, "valid", 1, True, 0),    # stride-2 1 x 1 (first block of a stage): 64 pixels out
 ]
+# the three layers whose width is the class count (NUM_CLASSES = 2, 5, 6, 17): mask logits + sigmoid on 5 ROIs (3920 rows: ragged
+# for the 32-, 64- and 128-row tiles; 784 rows per ROI are always a multiple of 16) and on 5 maps of 7 x 7 (245 rows: ragged
+# for the 16-row tile too), class logits and the bbox FC on 77 ROIs (ragged for every tile).  Cout = 5, 17, 68 ...: rows that are no multiple of 8 or 16 bytes, scalar B loads
+HEAD_CLASS_COUNTS = (2, 5, 6, 17)
+for _nc in HEAD_CLASS_COUNTS:
+    CONV_CASES += [(5, 28, 28, 256, _nc, 1, 1, "valid", 2, False, 0),
+                   (5, 7, 7, 256, _nc, 1, 1, "valid", 2, False, 0),
+                   (77, 1, 1, 1024, _nc, 1, 1, "valid", 0, False, 0),
+                   (77, 1, 1, 1024, 4 * _nc, 1, 1, "valid", 0, False, 0)]
 
 
 @pytest.fixture
@@ -376,6 +382,11 @@ WGRAD_CASES = [
     (90, 13, 11, 128, 256, 3, 1, "same"),       # LDS-DMA wgrad + LDS-DMA dgrad, ragged M
     (459, 13, 11, 128, 128, 3, 1, "same"),      # M = 65637 >= 65536: pixel-table addressing, tail inside a step
 ]
+# weight and data gradients of the class-count-wide layers (see CONV_CASES): Cout & 3 != 0 in the weight gradient, Cin = K = 2, 5,
+# 6, 17 / 8, 20, 24, 68 in the data gradient (no 32-channel fast path)
+for _nc in HEAD_CLASS_COUNTS:
+    WGRAD_CASES += [(5, 28, 28, 256, _nc, 1, 1, "valid"), (5, 7, 7, 256, _nc, 1, 1, "valid"), (77, 1, 1, 1024, _nc, 1, 1, "valid"),
+                    (77, 1, 1, 1024, 4 * _nc, 1, 1, "valid")]
 
 
 @pytest.mark.parametrize("case", WGRAD_CASES)
@@ -471,6 +482,127 @@ def test_epilogue_bwd(dev, M, C, act, bn):
         torch.testing.assert_close(dbet.cpu(), be.grad, **tol)
 
 
+def _mask_out_inputs(rng, M, H, W, Cd, C, dtype=None):
+    """Seeded operands of the mask head's output stage.  `up` stands for relu(deconv): about half of its entries positive, one in
+    eight exactly zero and the rest NEGATIVE (a real ReLU output has none, the kernels' mask `up > 0` must not care), so the
+    ReLU mask bites; with `dtype` it is rounded to that 16-bit type first.  Returns float32 / 16-bit CPU tensors."""
+    up = _rand(rng, M, H, W, Cd)
+    up[rng.uniform(0, 1, up.shape) < 0.125] = 0.0
+    up = torch.tensor(up)
+    if dtype is not None:
+        up = up.to(dtype)
+    wm = torch.tensor(_rand(rng, Cd, C, scale=0.1))
+    bm = torch.tensor(_rand(rng, C, scale=0.1))
+    d_mask = torch.tensor(_rand(rng, M, H, W, C, scale=1e-3))
+    frac = float((up.float() > 0).float().mean())
+    assert 0.3 < frac < 0.6 and bool((up.float() == 0).any()) and bool((up.float() < 0).any()), frac      # ReLU mask not trivial
+    return up, wm, bm, d_mask
+
+
+def _mask_out_ref64(up, wm, bm, d_mask, mask32=None):
+    """float64 statement of the output stage of build_fpn_mask_graph and of its backward pass, on the operands the kernels read
+    (all promoted exactly):  mask = sigmoid(up Wm + bm);  dz = d_mask * mask * (1 - mask);  dWm = up^T dz, dbm = sum dz (torch
+    autograd of the affine map);  dzu = (dz Wm^T) * (up > 0), dbd = sum dzu;  dzg = 2 x 2 pixel-unshuffle of dzu in the (a, b, co)
+    column order of params.deconv_keras_to_gemm.  The backward kernels read the STORED float32 mask, so dz uses `mask32` when
+    given (the derivative q (1 - q) amplifies a rounding of q near 1).  Also the magnitude sums the tolerances are built from:
+    sum_c |dz_c w_c| per dzg element and sum |terms| of the three reduced gradients."""
+    M, H, W, Cd = up.shape
+    C = wm.shape[1]
+    u = up.double().reshape(-1, Cd).requires_grad_(True)
+    w = wm.double().clone().requires_grad_(True)
+    b = bm.double().clone().requires_grad_(True)
+    z = u @ w + b
+    mask = torch.sigmoid(z.detach())
+    q = mask if mask32 is None else mask32.double().reshape(-1, C)
+    dz = d_mask.double().reshape(-1, C) * q * (1 - q)
+    z.backward(dz)
+    relu = (u.detach() > 0).double()
+    dzu = u.grad * relu
+    regroup = lambda t: t.reshape(M, H // 2, 2, W // 2, 2, Cd).permute(0, 1, 3, 2, 4, 5).reshape(M, H // 2, W // 2, 4 * Cd)
+    return dict(mask=mask.reshape(M, H, W, C), dzg=regroup(dzu), dWm=w.grad, dbm=b.grad, dbd=dzu.sum(0),
+                dzg_abs=regroup((dz.abs() @ wm.double().abs().t()) * relu),
+                dWm_abs=float((u.detach().abs().t() @ dz.abs()).max()), dbm_abs=float(dz.abs().sum(0).max()),
+                dbd_abs=float(dzu.abs().sum(0).max()))
+
+
+MASK_OUT_BWD_CASES = ([(3, 28, 28, Cd, C) for C in (2, 4, 5, 6, 8, 9, 16) for Cd in (256, 64, 320)] +
+                      [(37, 6, 6, 256, 5), (37, 6, 6, 64, 4)])
+
+
+@pytest.mark.parametrize("M,H,W,Cd,num_classes", MASK_OUT_BWD_CASES)
+def test_mask_out_bwd(dev, M, H, W, Cd, num_classes):
+    """mrcnn_mask_out_bwd (float32) against the float64 statement above.  C <= 4 with Cd / 4 a power of two (256, 64) takes
+    mask_out_bwd_vec_kernel<4>; Cd = 320 (80 channel groups) the scalar mask_out_bwd_kernel<4>; C = 5, 6, 8 kernel<8>; C = 9, 16
+    kernel<16>.  M * H * W = 2352 / 1332 pixels: four / two full 512-pixel workgroups and a ragged one; the 6 x 6 maps have an odd
+    number (9) of 2 x 2 groups per ROI.  The three reduced gradients ACCUMULATE onto non-zero buffers.
+    dzg element-wise: a C-term float32 dot product of float32 products whose factors dz = g q (1 - q) carry three roundings:
+    |err| <= 2 (C + 4) 2^-24 sum_c |dz_c w_c|.  dWm, dbm, dbd: the rule of test_epilogue_bwd for channel sums (rtol 1e-3, atol 1e-3
+    max(1, max sum |terms|))."""
+    ops = _ops()
+    C = num_classes
+    rng = np.random.default_rng(7000 + 131 * C + Cd + H)
+    assert (M * H * W) % 512 != 0
+    up, wm, bm, d_mask = _mask_out_inputs(rng, M, H, W, Cd, C)
+    mask32 = _mask_out_ref64(up, wm, bm, d_mask)["mask"].float()           # what the forward pass stored
+    ref = _mask_out_ref64(up, wm, bm, d_mask, mask32)
+    init = [torch.tensor(_rand(rng, *shape, scale=0.05)) for shape in ((Cd, C), (C,), (Cd,))]
+    dWm, dbm, dbd = (t.clone().to(dev) for t in init)
+    dzg = ops.mask_out_bwd(d_mask.to(dev), mask32.to(dev), up.to(dev), wm.to(dev), dWm, dbm, dbd)
+    torch.cuda.synchronize()
+    assert tuple(dzg.shape) == (M, H // 2, W // 2, 4 * Cd)
+    err = (dzg.cpu().double() - ref["dzg"]).abs()
+    bound = 2.0 * (C + 4) * 2.0 ** -24 * ref["dzg_abs"]
+    assert float(ref["dzg"].abs().max()) > 0 and float((ref["dzg"] == 0).double().mean()) > 0.3
+    worst = float((err / bound.clamp_min(1e-300)).max())
+    msg = ["dzg %.3f of its bound" % worst]
+    assert bool((err <= bound).all()), "dzg: max |err| / bound = %.3g" % worst
+    fails = []
+    for name, got, start in (("dWm", dWm, init[0]), ("dbm", dbm, init[1]), ("dbd", dbd, init[2])):
+        want = start.double() + ref[name]
+        atol = 1e-3 * max(1.0, ref[name + "_abs"])
+        e = (got.cpu().double() - want).abs()
+        rel = float((e / (atol + 1e-3 * want.abs())).max())
+        msg.append("%s %.2e of its bar" % (name, rel))
+        if rel > 1.0:
+            fails.append(name)
+    print("[mask_out_bwd C=%d Cd=%d %dx%dx%d] max error relative to the bar: %s" % (C, Cd, M, H, W, ", ".join(msg)))
+    assert not fails, (fails, msg)
+    # the bar of test_epilogue_bwd is an absolute 1e-3 on sums of this size; the float32 summation itself is bounded much lower: a
+    # thread adds at most 512 products in sequence ((n - 1) 2^-24 sum |terms|, plus the roundings of the products and of dz: 16
+    # more), and at most 8 partial sums meet the non-zero start value in atomics (2^-24 of the running total each)
+    for name, got, start in (("dWm", dWm, init[0]), ("dbm", dbm, init[1]), ("dbd", dbd, init[2])):
+        e = float((got.cpu().double() - start.double() - ref[name]).abs().max())
+        assert e <= 2.0 ** -24 * (528 * ref[name + "_abs"] + 8 * (float(start.abs().max()) + ref[name + "_abs"])), (name, e)
+
+
+def test_mask_out_bwd_refuses_more_than_16_classes(dev):
+    """C = 17 is outside the fused output-stage kernels (register-resident weight rows for at most 16 classes): the entry points
+    return MRCNN_ERR_ARG (-1) and launch nothing -- the engine takes its unfused path there
+    (test_engine_gpu.py::test_training_step_staged_class_counts[17], test_h16_gpu.py::test_mixed_precision_training_step_class_counts)."""
+    ops = _ops()
+    lib = ops._hip.lib()
+    M, H, W, Cd, C = 1, 4, 4, 256, 17
+    z = lambda *s: torch.zeros(s, device=dev)
+    dzg = torch.full((M, H // 2, W // 2, 4 * Cd), 7.0, device=dev)
+    dW = z(Cd, C)
+    g, m, up, wm, dbm, dbd = z(M, H, W, C), z(M, H, W, C), z(M, H, W, Cd), z(Cd, C), z(C), z(Cd)
+    rc = lib.mrcnn_mask_out_bwd(ops.ptr(g), ops.ptr(m), ops.ptr(up), ops.ptr(wm), ops.ptr(dzg), ops.ptr(dW), ops.ptr(dbm), ops.ptr(dbd),
+                                M, H, W, Cd, C, ops.current_stream())
+    torch.cuda.synchronize()
+    assert rc == -1 and float(dzg.min()) == 7.0 and float(dW.abs().max()) == 0.0
+    with pytest.raises(ops._hip.HipPathError):
+        ops.mask_out_bwd(z(M, H, W, C), z(M, H, W, C), z(M, H, W, Cd), z(Cd, C), dW, z(C), z(Cd))
+    for dtype in (torch.float16, torch.bfloat16):
+        up16 = torch.zeros((M, H, W, Cd), dtype=dtype, device=dev)
+        with pytest.raises(ops._hip.HipPathError):
+            ops.mask_out_fwd_h16(up16, z(Cd, C), z(C))
+        with pytest.raises(ops._hip.HipPathError):
+            ops.mask_out_bwd_h16(z(M, H, W, C), z(M, H, W, C), up16, z(Cd, C), dW, z(C), z(Cd), 1.0)
+    ok = ops.mask_out_bwd(z(M, H, W, 16), z(M, H, W, 16), z(M, H, W, Cd), z(Cd, 16), z(Cd, 16), z(16), z(Cd))      # 16 is served
+    torch.cuda.synchronize()
+    assert tuple(ok.shape) == (M, H // 2, W // 2, 4 * Cd)
+
+
 def test_pool_and_resample(dev):
     ops = _ops()
     rng = np.random.default_rng(11)
@@ -498,21 +630,24 @@ def test_pool_and_resample(dev):
     torch.testing.assert_close(dsrc.cpu(), ref, rtol=1e-6, atol=1e-6)
     lg = torch.tensor(_rand(rng, 1000, 4, scale=3))
     torch.testing.assert_close(ops.softmax_rows(lg.to(dev)).cpu(), torch.softmax(lg, -1), rtol=1e-6, atol=1e-7)
+    # other class counts (NUM_CLASSES = 2, 6, 17), against float64; the first 64 rows hold logits of magnitude 80, the next 64 of
+    # magnitude 100, where float32 expf itself overflows: a kernel without the max-subtraction returns inf / inf there
+    for num_classes in (2, 6, 17):
+        lg = _rand(rng, 1003, num_classes, scale=3)
+        lg[:64] = 80.0 * np.sign(lg[:64])
+        lg[64:128] = 100.0 * np.sign(lg[64:128])
+        lg[:8] = 80.0
+        lg[64:72] = 100.0
+        lg = torch.tensor(lg)
+        ref = torch.softmax(lg.double(), -1)
+        assert bool(torch.isinf(torch.exp(lg[64:72])).all())                   # float32 exp of those logits is not finite
+        got = ops.softmax_rows(lg.to(dev)).cpu()
+        assert bool(torch.isfinite(got).all())
+        print("[softmax_rows C=%d] max |err| %.3g (atol 1e-7 + rtol 1e-6)" % (num_classes, float((got.double() - ref).abs().max())))
+        torch.testing.assert_close(got.double(), ref, rtol=1e-6, atol=1e-7)
     a = torch.tensor(_rand(rng, 100000)); b = torch.tensor(_rand(rng, 100000))
     ad = a.to(dev); ops.add_inplace(ad, b.to(dev))
     assert torch.equal(ad.cpu(), a + b)
-
-
-def _random_rois(rng, B, R, zero_tail=0):
-    """log-uniform sizes covering all four pyramid levels, some ROIs touching the border."""
-    size = np.exp(rng.uniform(np.log(0.01), np.log(0.9), (B, R, 2)))
-    ctr = rng.uniform(0, 1, (B, R, 2))
-    y1 = np.clip(ctr[..., 0] - size[..., 0] / 2, 0, 1); y2 = np.clip(ctr[..., 0] + size[..., 0] / 2, 0, 1)
-    x1 = np.clip(ctr[..., 1] - size[..., 1] / 2, 0, 1); x2 = np.clip(ctr[..., 1] + size[..., 1] / 2, 0, 1)
-    rois = np.stack([y1, x1, y2, x2], -1).astype(np.float32)
-    if zero_tail:
-        rois[:, -zero_tail:] = 0
-    return rois
 
 
 @pytest.mark.parametrize("pool", [7, 14])
@@ -665,18 +800,13 @@ def test_proposal_selection_survives_stale_counters(dev):
         assert np.array_equal(g, b_)
 
 
-def test_detection_layer(dev):
+def _detection_layer_case(dev, num_classes, seed, logit_scale):
     ops = _ops()
-    rng = np.random.default_rng(21)
-    cfg = _cfg(mode="inference")
-    B, R, C = 2, 1000, cfg.NUM_CLASSES
-    rois = _random_rois(rng, B, R, zero_tail=50)
-    lg = _rand(rng, B, R, C, scale=2.0)
-    probs = np.exp(lg) / np.exp(lg).sum(-1, keepdims=True)
-    probs = np.round(probs, 2).astype(np.float32)            # score ties
-    deltas = _rand(rng, B, R, C, 4, scale=0.5)
-    windows = np.array([[0, 0, 1, 1], [0.1, 0.05, 0.9, 0.95]], np.float32)
+    cfg = _cfg(mode="inference", num_classes=num_classes)
+    B, C = 2, cfg.NUM_CLASSES
+    rois, probs, deltas, windows = detection_layer_inputs(num_classes, seed, logit_scale)
     o = orc.OracleMaskRCNN(cfg, {})
+    seen = set()
     for minconf in (0, 0.5):
         cfg.DETECTION_MIN_CONFIDENCE = minconf
         out = ops.detections(torch.tensor(rois, device=dev), torch.tensor(probs, device=dev),
@@ -690,15 +820,26 @@ def test_detection_layer(dev):
             assert np.array_equal(got[:, 5], ref[:, 5])
             np.testing.assert_allclose(got[:, :4], ref[:, :4], rtol=0, atol=2e-6)
             assert (ref[:, 4] > 0).sum() > 10
+            seen |= set(ref[ref[:, 4] > 0, 4].astype(int).tolist())
+    assert seen == set(range(1, C)), seen                         # every foreground class among the kept detections
 
 
-@pytest.mark.parametrize("mini", [False, True])
-def test_detection_targets(dev, mini):
-    """mini=True: config.USE_MINI_MASK -- gt_masks hold each instance cropped to its box and resized to MINI_MASK_SHAPE
-    (56x56) and the ROI is re-expressed in the GT box's frame before crop_and_resize (mrcnn/model.py:670-682)."""
+def test_detection_layer(dev):
+    _detection_layer_case(dev, 4, 21, 2.0)
+
+
+@pytest.mark.parametrize("num_classes,seed,logit_scale", DETECTION_CLASS_CASES)
+def test_detection_layer_class_counts(dev, num_classes, seed, logit_scale):
+    """refine_detections at NUM_CLASSES = 2 (one foreground class: every kept ROI meets every other in ONE suppression), 6 and 17
+    (argmax over rows that are no multiple of 16 bytes, class-specific deltas at stride C * 4, per-class suppression between many
+    classes): indices and class ids exact, boxes to 2e-6, as at four classes."""
+    _detection_layer_case(dev, num_classes, seed, logit_scale)
+
+
+def _detection_targets_case(dev, mini, num_classes):
     ops = _ops()
     rng = np.random.default_rng(31)
-    cfg = _cfg()
+    cfg = _cfg(num_classes=num_classes)
     cfg.USE_MINI_MASK = mini
     B, R, G, T, HW = 2, 2000, cfg.MAX_GT_INSTANCES, cfg.TRAIN_ROIS_PER_IMAGE, 64
     gt_boxes = np.zeros((B, G, 4), np.float32); gt_cls = np.zeros((B, G), np.int32)
@@ -736,6 +877,23 @@ def test_detection_targets(dev, mini):
         # order without contraction and rounds half to even like tf.round (rintf); the oracle does the same in torch
         np.testing.assert_array_equal(tmask[b], r_m)
         assert r_m.sum() > 0 and (r_m[:P] == 0).sum() > 0
+        assert r_cls.max() < num_classes and (r_cls[:P] > 0).all()
+        if num_classes > 2:
+            assert len(set(r_cls[:P].tolist())) > 1                # targets of more than one class
+
+
+@pytest.mark.parametrize("mini", [False, True])
+def test_detection_targets(dev, mini):
+    """mini=True: config.USE_MINI_MASK -- gt_masks hold each instance cropped to its box and resized to MINI_MASK_SHAPE
+    (56x56) and the ROI is re-expressed in the GT box's frame before crop_and_resize (mrcnn/model.py:670-682)."""
+    _detection_targets_case(dev, mini, 4)
+
+
+@pytest.mark.parametrize("num_classes", [2, 6, 17])
+def test_detection_targets_class_counts(dev, num_classes):
+    """The same scene with the ground-truth class ids drawn from NUM_CLASSES = 2, 6 and 17: the sampled target class ids are the
+    assigned GT's, everything else as at four classes."""
+    _detection_targets_case(dev, False, num_classes)
 
 
 @pytest.mark.parametrize("case", ["golden", "crowded", "big_image", "no_overlap_gt"])
@@ -799,36 +957,46 @@ def test_rpn_targets_device(dev, case):
         np.testing.assert_array_equal(bbox[2], bbox[0])
 
 
-@pytest.mark.parametrize("dice", [False, True])
-def test_losses(dev, dice):
+def _losses_case(dev, dice, num_classes, cycle):
     ops = _ops()
-    rng = np.random.default_rng(41)
-    cfg = _cfg()
+    cfg = _cfg(num_classes=num_classes)
     cfg.MASK_LOSS_FUNCTION = "dice_coef_loss" if dice else "binary_crossentropy"
-    B, A, T, C = 2, 4092, 64, cfg.NUM_CLASSES
-    rpn_match = rng.choice([-1, 0, 1], size=(B, A, 1), p=[0.1, 0.85, 0.05]).astype(np.int32)
-    maxpos = int((rpn_match == 1).sum(1).max()) + 5
-    rpn_bbox_t = _rand(rng, B, maxpos, 4)
-    rpn_logits = torch.tensor(_rand(rng, B, A, 2, scale=2), requires_grad=True)
-    rpn_bbox = torch.tensor(_rand(rng, B, A, 4, scale=1.5), requires_grad=True)
-    tcls = np.zeros((B, T), np.int32); tcls[:, :20] = rng.integers(1, C, (B, 20))
-    tbbox = _rand(rng, B, T, 4); tmask = (rng.uniform(0, 1, (B, T, 28, 28)) > 0.5).astype(np.float32)
-    active = np.ones((B, C), np.int32); active[:, 2] = 0
-    logits = torch.tensor(_rand(rng, B, T, C, scale=2), requires_grad=True)
-    mbbox = torch.tensor(_rand(rng, B, T, C, 4, scale=1.5), requires_grad=True)
-    mm = rng.uniform(0, 1, (B, T, 28, 28, C)).astype(np.float32); mm[0, 0, 0, :4, :] = [[0.0] * C, [1.0] * C, [1e-9] * C, [0.5] * C]
-    mmask = torch.tensor(mm, requires_grad=True)
+    C = cfg.NUM_CLASSES
+    d = losses_inputs(num_classes, cycle)
+    rpn_match, rpn_bbox_t, tcls, tbbox, tmask, active = (d[n] for n in ("rpn_match", "rpn_bbox_t", "tcls", "tbbox", "tmask", "active"))
+    rpn_logits, rpn_bbox, logits, mbbox, mmask = (torch.tensor(d[n], requires_grad=True) for n in ("rpn_logits", "rpn_bbox", "logits", "mbbox", "mmask"))
     w = [1.0, 0.5, 1.0, 2.0, 1.5]
     o = orc.OracleMaskRCNN(cfg, {})
+    pred_active = d["pred_active"]
+    assert set(pred_active.tolist()) == {0, 1} and pred_active.sum() > 0       # both kinds of prediction in the class loss
     ls = o.losses(rpn_match, rpn_bbox_t, rpn_logits, rpn_bbox, tcls, tbbox, tmask, active, logits, mbbox, mmask)
     sum(wi * li for wi, li in zip(w, ls)).backward()
     D = lambda a: torch.tensor(np.ascontiguousarray(a), device=dev) if isinstance(a, np.ndarray) else a.detach().to(dev)
     out = ops.losses_fwd_bwd(D(rpn_match), D(rpn_bbox_t), D(rpn_logits), D(rpn_bbox), D(tcls), D(tbbox), D(tmask),
                              D(active[0].copy()), D(logits), D(mbbox), D(mmask), w, dice)
     torch.cuda.synchronize()
+    want = np.array([float(l) for l in ls])
+    print("[losses C=%d dice=%s] max rel err of the five losses %.3g (rtol 2e-5)" % (
+        C, dice, float(np.max(np.abs(out[0].cpu().numpy() - want) / np.maximum(np.abs(want), 1e-6)))))
     np.testing.assert_allclose(out[0].cpu().numpy(), [float(l) for l in ls], rtol=2e-5, atol=1e-6)
-    for got, ref in zip(out[1:], (rpn_logits, rpn_bbox, logits, mbbox, mmask)):
+    for got, ref, name in zip(out[1:], (rpn_logits, rpn_bbox, logits, mbbox, mmask), ("rpn_logits", "rpn_bbox", "logits", "mbbox", "mmask")):
+        assert float(ref.grad.abs().max()) > 0
+        err = (got.cpu() - ref.grad).abs() - 1e-4 * ref.grad.abs()
+        print("[losses C=%d dice=%s] d_%s: max (|err| - rtol |ref|) %.3g (atol 1e-7)" % (C, dice, name, float(err.max())))
         torch.testing.assert_close(got.cpu(), ref.grad, rtol=1e-4, atol=1e-7)
+
+
+@pytest.mark.parametrize("dice", [False, True])
+def test_losses(dev, dice):
+    _losses_case(dev, dice, 4, cycle=False)
+
+
+@pytest.mark.parametrize("dice", [False, True])
+@pytest.mark.parametrize("num_classes", [2, 5, 6, 17])
+def test_losses_class_counts(dev, num_classes, dice):
+    """The five losses and their gradients at NUM_CLASSES = 2, 5, 6, 17 (heads_loss_*_kernel index `i % C`, `i < C * 4`,
+    `active[argmax]`): every foreground class among the targets, one inactive class, both mask losses; tolerances of test_losses."""
+    _losses_case(dev, dice, num_classes, cycle=True)
 
 
 @pytest.mark.parametrize("n_used,G", [(0, 12), (1, 12), (7, 12), (8, 8), (13, 300), (300, 300)])
@@ -879,17 +1047,11 @@ def _unmold_boxes_for_test(rng, n, H, W):
     return boxes
 
 
-@pytest.mark.parametrize("packed", [False, True])
-def test_unmold_masks(dev, packed):
-    """mrcnn_unmold_masks against the host statement of mrcnn/utils.py:629-645 (caesar_mrcnn_amd.utils.unmold_mask: float64
-    bilinear resize of the 28 x 28 class mask to the integer box, clip to the mask's range, `>= 0.5`, paste): 1040 boxes in
-    batches of 104 detections (13 bytes in the packed form, the last one partial) on a 96 x 80 image -- 1-pixel, edge-touching,
-    full-tile, down- / up-sampled boxes; masks with all values above / below the threshold (the clip decides those) and one
-    with a NaN.  Boolean output identical, both layouts; class channel and row indirection exercised."""
+def _unmold_masks_case(dev, packed, C_):
     ops = _ops()
     from caesar_mrcnn_amd import utils
     rng = np.random.default_rng(77)
-    H, W, C_, R, n = 96, 80, 4, 120, 104
+    H, W, R, n = 96, 80, 120, 104
     for batch in range(10):
         mm = 1.0 / (1.0 + np.exp(-_rand(rng, R, 28, 28, C_, scale=2.0)))
         mm = mm.astype(np.float32)
@@ -901,6 +1063,9 @@ def test_unmold_masks(dev, packed):
         rows = rng.permutation(R)[:n].astype(np.int32)
         rows[:6] = (3, 4, 5, 3, 4, 5)
         boxes[:3] = ((0, 0, H, W), (10, 5, 60, 70), (2, 3, 50, 40))
+        if C_ != 4:
+            cls = rng.permutation(np.arange(n) % C_).astype(np.int32)        # every class id occurs, 0 included
+            assert set(cls.tolist()) == set(range(C_))
         dets = np.concatenate([boxes, cls[:, None], rows[:, None]], axis=1).astype(np.int32)
         got = ops.unmold_masks(torch.tensor(mm, device=dev), torch.tensor(dets, device=dev), (H, W), packed=packed)
         torch.cuda.synchronize()
@@ -913,9 +1078,42 @@ def test_unmold_masks(dev, packed):
             want = np.stack([utils.unmold_mask(mm[rows[i], :, :, cls[i]], boxes[i], (H, W, 3)) for i in range(n)], axis=-1)
         assert want[..., 0].all() and not want[..., 1].any() and not want[..., 2].any()      # the clip / NaN cases as intended
         np.testing.assert_array_equal(got.view(np.bool_), want)
+        if batch == 0:
+            # the class planes of a row are independent random patterns: for every detection whose box is large enough to show
+            # them (>= 8 x 8 pixels; not the all-set / all-clear / NaN rows 3, 4 and 5), the plane of ANY other class un-molds to a
+            # different boolean image, so a kernel that read a wrong plane could not have passed the comparison above
+            checked = 0
+            for i in range(n):
+                y1, x1, y2, x2 = boxes[i]
+                if rows[i] in (3, 4, 5) or y2 - y1 < 8 or x2 - x1 < 8:
+                    continue
+                with np.errstate(invalid="ignore"):
+                    for c in range(C_):
+                        if c != cls[i]:
+                            assert not np.array_equal(utils.unmold_mask(mm[rows[i], :, :, c], boxes[i], (H, W, 3)), want[..., i]), (i, c)
+                checked += 1
+            assert checked > 20
     # no detections: an empty result, nothing launched
     e = ops.unmold_masks(torch.tensor(mm, device=dev), torch.zeros((0, 6), dtype=torch.int32, device=dev), (H, W), packed=packed)
     assert tuple(e.shape) == (H, W, 0)
+
+
+@pytest.mark.parametrize("num_classes", [2, 6, 17])
+def test_unmold_masks_class_counts(dev, num_classes):
+    """mrcnn_unmold_masks at NUM_CLASSES = 2, 6, 17: the class plane of every detection is selected by its class id (stride C in the
+    innermost dimension of mrcnn_mask); every class id occurs and no other plane of the same row gives the same image."""
+    _unmold_masks_case(dev, False, num_classes)
+    _unmold_masks_case(dev, True, num_classes)
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_unmold_masks(dev, packed):
+    """mrcnn_unmold_masks against the host statement of mrcnn/utils.py:629-645 (caesar_mrcnn_amd.utils.unmold_mask: float64
+    bilinear resize of the 28 x 28 class mask to the integer box, clip to the mask's range, `>= 0.5`, paste): 1040 boxes in
+    batches of 104 detections (13 bytes in the packed form, the last one partial) on a 96 x 80 image -- 1-pixel, edge-touching,
+    full-tile, down- / up-sampled boxes; masks with all values above / below the threshold (the clip decides those) and one
+    with a NaN.  Boolean output identical, both layouts; class channel and row indirection exercised."""
+    _unmold_masks_case(dev, packed, 4)
 
 
 def test_guarded_sgd_skips_non_finite_steps(dev):
