@@ -13,6 +13,7 @@ Gradient plumbing conventions
 import contextlib
 import gc
 import operator
+from functools import partial
 import os
 import numpy as np
 import torch
@@ -107,6 +108,20 @@ def _capture(graph):
         if was:
             gc.enable()
 
+
+@contextlib.contextmanager
+def _tuning(key, value, restore, on=True):
+    """A process-wide tuning value of the kernel library (ops.tuning_set) for the launches issued inside, put back to
+    `restore` afterwards; on=False leaves it alone."""
+    if on:
+        ops.tuning_set(key, value)
+    try:
+        yield
+    finally:
+        if on:
+            ops.tuning_set(key, restore)
+
+
 class ConvOp(object):
     """One named Conv2D/Dense(+BatchNorm) layer: views into the flat buffers + fwd/bwd launches."""
 
@@ -136,6 +151,12 @@ class ConvOp(object):
             self.mean, self.rstd = model.bn_mean[c0:c0 + c], model.bn_rstd[c0:c0 + c]
             self.dgamma = model.grads[L.gamma_offset + c0:L.gamma_offset + c0 + c]
             self.dbeta = model.grads[L.beta_offset + c0:L.beta_offset + c0 + c]
+
+    @property
+    def dgrad_padding(self):
+        """Padding of this layer's stride-1 data-gradient convolution (the flipped / transposed kernel over dz)."""
+        kh, kw = self.wshape[:2]
+        return ((kh - 1) // 2, (kw - 1) // 2) if self.padding == "same" else "valid"
 
     # ---- forward ---------------------------------------------------------------------------
     def forward(self, x, act=ACT_NONE, res=None, res_mode=RES_NONE, train=False):
@@ -177,14 +198,10 @@ class ConvOp(object):
         N, H, W, _ = x.shape
         res = out if accumulate else None
         rm = RES_SAME if accumulate else RES_NONE
-        if self.stride == 1 and self.padding == "same":
+        if self.stride == 1 and (self.padding == "same" or (kh == 1 and kw == 1)):
             if out is None:
                 out = ops.empty_like(x)
-            ops.conv2d(dz, self.wt, res=res, stride=1, padding=((kh - 1) // 2, (kw - 1) // 2), res_mode=rm, out=out)
-        elif kh == 1 and kw == 1 and self.stride == 1:
-            if out is None:
-                out = ops.empty_like(x)
-            ops.conv2d(dz, self.wt, res=res, stride=1, padding="valid", res_mode=rm, out=out)
+            ops.conv2d(dz, self.wt, res=res, stride=1, padding=self.dgrad_padding, res_mode=rm, out=out)
         elif kh == 1 and kw == 1 and self.stride == 2:
             if out is None:
                 out = ops.empty_like(x)
@@ -300,10 +317,33 @@ class MaskRCNNEngine(object):
         self._h16_store = {}            # dtype -> {layer: (W^T image, data-gradient image)}, stable addresses
         self._h16_tables = {}           # (dtype, layer names) -> table of the one-launch refresh (ops.h16_image_table)
         self.wgrad_stream, self.aux_stream = _side_streams(device, self.wgrad_prio, self.aux_prio)
+        if self.wgrad_stream is None:           # the step is written for three streams: there is no single-stream form of it
+            raise _hip_mod.HipPathError("MaskRCNNEngine needs a GPU device for its side streams, not %r" % (device,))
         self._deferred = []
 
     def op(self, name):
         return self._ops[name]
+
+    # ---- work on a side stream ---------------------------------------------------------------------
+    def _fork(self, side, body, *operands, ev=None):
+        """body() on the stream `side`, behind everything the current stream has been given so far (or behind `ev`, an event
+        already recorded on it); returns what body returns.  `operands`: the tensors of the current stream that body reads,
+        kept from reuse until `side` is done with them.  The ONE place where work leaves the main stream (besides the
+        two-chain forward of _mask_convs_fwd_split); joining again -- join_wgrad, join_aux, a stream_wait -- is the caller's."""
+        if ev is None:
+            ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(side):
+            _hip_mod.ev_wait(side, ev)
+            out = body()
+        for t in operands:
+            t.record_stream(side)
+        return out
+
+    def _settle(self, body):
+        """body() on a fresh stream beside the current one, which then waits for it: the eager passes before a capture."""
+        side = torch.cuda.Stream(device=self.dev)
+        self._fork(side, body)
+        _hip_mod.stream_wait(torch.cuda.current_stream(self.dev), side)
 
     # ---- weight gradients on a second stream -------------------------------------------------------
     def wgrad_async(self, x, dz, wshape, stride, padding, dw, accumulate):
@@ -311,48 +351,17 @@ class MaskRCNNEngine(object):
         launched on a side stream so that it overlaps the data-gradient convolution of the same layer: the
         partial last round of one grid (and the small grids of the backbone) fill the CUs the other leaves
         idle.  All weight gradients share that one stream (and its slab workspace), in program order."""
-        ws = self.wgrad_stream
-        if ws is None:
-            ops.conv2d_wgrad(x, dz, wshape, stride, padding, dw=dw, accumulate=accumulate)
-            return
-        ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(ws):
-            _hip_mod.ev_wait(ws, ev)
-            ops.conv2d_wgrad(x, dz, wshape, stride, padding, dw=dw, accumulate=accumulate)
-        dz.record_stream(ws)
-        x.record_stream(ws)
+        self._fork(self.wgrad_stream, partial(ops.conv2d_wgrad, x, dz, wshape, stride, padding, dw=dw, accumulate=accumulate),
+                   x, dz)
 
     def wgrad_group(self, items):
         """Weight gradients of several layers (ConvOp.wgrad_item) behind one event: one shared launch when they all
         fit the LDS-DMA kernel (the three convolutions of a bottleneck block on the small feature maps), else one by one."""
-        ws = self.wgrad_stream
-
         def run():
             if not (self.multi_launch and 1 < len(items) <= 4 and ops.conv2d_wgrad_multi(items)):
                 for x, dz, wshape, stride, padding, dw, acc in items:
                     ops.conv2d_wgrad(x, dz, wshape, stride, padding, dw=dw, accumulate=acc)
-        if ws is None:
-            run()
-            return
-        ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(ws):
-            _hip_mod.ev_wait(ws, ev)
-            run()
-        for x, dz, *_ in items:
-            dz.record_stream(ws)
-            x.record_stream(ws)
-
-    def wgrad_h16_async(self, x, dz, wshape, dw, multiplier, padding="same", accumulate=False):
-        ws = self.wgrad_stream
-        if ws is None:
-            ops.conv2d_wgrad_h16(x, dz, wshape, 1, padding, dw=dw, accumulate=accumulate, multiplier=multiplier)
-            return
-        ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(ws):
-            _hip_mod.ev_wait(ws, ev)
-            ops.conv2d_wgrad_h16(x, dz, wshape, 1, padding, dw=dw, accumulate=accumulate, multiplier=multiplier)
-        dz.record_stream(ws)
-        x.record_stream(ws)
+        self._fork(self.wgrad_stream, run, *(t for item in items for t in item[:2]))
 
     # ---- images derived from the weights ------------------------------------------------------------
     # The flipped / transposed kernels (wt), the 16-bit operand images and the Winograd-domain kernels U remember the weight
@@ -489,28 +498,11 @@ class MaskRCNNEngine(object):
         got = ops.epilogue_bwd_h16(d16, y if act != ACT_NONE else None, z, op.scale, op.mean, op.rstd, op.dgamma, op.dbeta, op.db,
                                    act, 1.0 / S, want_dy=want_dy)
         dz, dy = got if want_dy else (got, None)
-        if self._h16_shape_ok(op):
-            self.wgrad_h16_async(x16, dz, op.wshape, op.dw, 1.0 / S, op.padding, accumulate_w)
-        else:
-            self._wgrad_from_h16(op, x16, dz, 1.0 / S, accumulate_w)
+        self._h16_wgrad(op, x16, dz, S, accumulate_w)
         if not need_dx:
             return (dz, dy) if want_dy else dz                    # the caller issues the data gradient itself
         dx = self._h16_dgrad(op, dz, dx_res)
         return (dx, dy) if want_dy else dx
-
-    def _wgrad_from_h16(self, op, x16, dz16, mult, accumulate):
-        """Weight gradient of a layer whose channel counts are below the 16-bit weight-gradient kernel's 256-channel tile
-        (res2 / res3, the first block of a stage): both operands are widened to float32 ON THE WEIGHT-GRADIENT STREAM and the
-        float32 kernel runs there -- off the critical path, which stays in 16 bits."""
-        ws = self.wgrad_stream
-        ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(ws):
-            _hip_mod.ev_wait(ws, ev)
-            x32 = ops.cast_from_h16(x16)
-            dz32 = ops.cast_from_h16(dz16, mult)
-            ops.conv2d_wgrad(x32, dz32, op.wshape, op.stride, op.padding, dw=op.dw, accumulate=accumulate)
-        for t in (x16, dz16):
-            t.record_stream(ws)
 
     def _h16_dgrad(self, op, dz, dx_res=None, out=None, out_strides=None):
         kh, kw, cin, cout = op.wshape
@@ -519,9 +511,8 @@ class MaskRCNNEngine(object):
             dx = ops.conv2d_h16(dz.view(M, 1, 1, cout), self._h16[op.name][1], (1, 1, cout, kh * kw * cin), None, None, None, 1,
                                 "valid", ACT_NONE)
             return dx.view(M, kh, kw, cin)
-        return ops.conv2d_h16(dz, self._h16[op.name][1], (kh, kw, cout, cin), None, None, None, 1,
-                              ((kh - 1) // 2, (kw - 1) // 2) if op.padding == "same" else "valid", ACT_NONE, res=dx_res, out=out,
-                              out_strides=out_strides)
+        return ops.conv2d_h16(dz, self._h16[op.name][1], (kh, kw, cout, cin), None, None, None, 1, op.dgrad_padding, ACT_NONE,
+                              res=dx_res, out=out, out_strides=out_strides)
 
     # ---- identity bottleneck blocks in 16 bits (configs[4], stage 4) ------------------------------------------
     def _h16_block(self, blk):
@@ -529,7 +520,7 @@ class MaskRCNNEngine(object):
         kernel (channel counts multiples of 64: all of ResNet-50 / 101's 16 / 33 blocks) -- identity blocks and the first
         block of each stage (projection shortcut, stride 2 on the 1x1 convolutions)."""
         ops_ = [blk.c2a, blk.c2b, blk.c2c] + ([blk.c1] if blk.c1 is not None else [])
-        return (self.head_dtype is not None and self.h16_wide and self.h16_blocks and self.wgrad_stream is not None and
+        return (self.head_dtype is not None and self.h16_wide and self.h16_blocks and
                 all(self._h16_fwd_ok(o) for o in ops_) and (self.h16_all_blocks or
                                                              (blk.c1 is None and all(self._h16_shape_ok(o) for o in ops_))))
 
@@ -541,19 +532,26 @@ class MaskRCNNEngine(object):
         return y, ("h16", ca, cb, cc, c1c)
 
     def _h16_wgrad(self, op, x16, dz, S, accumulate=False):
+        """Weight gradient of a 16-bit layer from its input and dz (16 bit, times S), on the weight-gradient stream.  A layer
+        whose channel counts are below the 16-bit weight-gradient kernel's 256-channel tile (res2 / res3, the first block of a
+        stage) has both operands widened to float32 ON THAT STREAM and takes the float32 kernel there -- off the critical
+        path, which stays in 16 bits."""
         if self._h16_shape_ok(op):
-            self.wgrad_h16_async(x16, dz, op.wshape, op.dw, 1.0 / S, op.padding, accumulate)
+            launch = partial(ops.conv2d_wgrad_h16, x16, dz, op.wshape, 1, op.padding, dw=op.dw, accumulate=accumulate,
+                             multiplier=1.0 / S)
         else:
-            self._wgrad_from_h16(op, x16, dz, 1.0 / S, accumulate)
+            def launch():
+                ops.conv2d_wgrad(ops.cast_from_h16(x16), ops.cast_from_h16(dz, 1.0 / S), op.wshape, op.stride, op.padding,
+                                 dw=op.dw, accumulate=accumulate)
+        self._fork(self.wgrad_stream, launch, x16, dz)
 
     def _h16_dgrad_ep(self, op, dz, below, below_ctx, S):
         """dz of layer `below` from the dz of layer `op` above it: the 16-bit data gradient with `below`'s epilogue
         backward in its own epilogue (mrcnn_conv2d_dgrad_ep_h16); the two launches when the shape has no fused kernel."""
         kh, kw, cin, cout = op.wshape
         _, z, y, act = below_ctx
-        pad = ((kh - 1) // 2, (kw - 1) // 2) if op.padding == "same" else "valid"
         if self.h16_fused_bwd and op.stride == 1:
-            got = ops.conv2d_dgrad_ep_h16(dz, self._h16[op.name][1], (kh, kw, cout, cin), pad, y if act != ACT_NONE else None, z,
+            got = ops.conv2d_dgrad_ep_h16(dz, self._h16[op.name][1], (kh, kw, cout, cin), op.dgrad_padding, y if act != ACT_NONE else None, z,
                                           below.scale, below.mean, below.rstd, below.dgamma, below.dbeta, below.db, act, 1.0 / S)
             if got is not None:
                 return got
@@ -644,13 +642,11 @@ class MaskRCNNEngine(object):
         if ok:
             probs = []
             for i, (op, dz, ctx) in enumerate(zip(layers, dzs, ctxs)):
-                kh, kw = op.wshape[0], op.wshape[1]
                 if outs[i] is None:
                     assert not accs[i]
                     outs[i] = ops.empty_like(ctx[0])
-                probs.append(dict(x=dz, w=op.wt, padding=((kh - 1) // 2, (kw - 1) // 2) if op.padding == "same" else "valid",
-                                  res=outs[i] if accs[i] else None, res_mode=RES_SAME if accs[i] else RES_NONE,
-                                  out=outs[i]))
+                probs.append(dict(x=dz, w=op.wt, padding=op.dgrad_padding, res=outs[i] if accs[i] else None,
+                                  res_mode=RES_SAME if accs[i] else RES_NONE, out=outs[i]))
             if ops.conv2d_multi(probs) is not None:
                 return outs
         return [op.dgrad(dz, ctx, out=o, accumulate=a) for op, dz, ctx, o, a in zip(layers, dzs, ctxs, outs, accs)]
@@ -671,7 +667,8 @@ class MaskRCNNEngine(object):
             self.wgrad_group([layers[i].wgrad_item(dzs[i], ctxs[i]) for i in rest])
         for i in range(n):                                  # (shared weights: in layer order, each adding to the one before)
             if Vs[i] is not None:
-                self._wino_wgrad_async(Vs[i], tuple(ctxs[i][0].shape), dzs[i], layers[i].dw, wacc[i])   # never deferred: trunk
+                self._fork(self.wgrad_stream, partial(ops.conv2d_wgrad_winograd, Vs[i], tuple(ctxs[i][0].shape), dzs[i],
+                                                      layers[i].dw, accumulate=wacc[i]), Vs[i], dzs[i])   # never deferred: trunk
             elif any(wacc):
                 self.wgrad_async(*layers[i].wgrad_item(dzs[i], ctxs[i], accumulate=wacc[i]))
         if rest:
@@ -691,63 +688,30 @@ class MaskRCNNEngine(object):
         return outs
 
     def join_wgrad(self):
-        if self.wgrad_stream is not None:
-            _hip_mod.stream_wait(torch.cuda.current_stream(self.dev), self.wgrad_stream)
+        _hip_mod.stream_wait(torch.cuda.current_stream(self.dev), self.wgrad_stream)
 
     # ---- deferred mask-head weight gradients ----------------------------------------------------------
-    def _mask_wgrad(self, kind, *args):
-        """A weight gradient of the mask head: now (on the weight-gradient stream) or, with ``defer_mask_wgrad``, beside
-        the backbone's backward pass (``_flush_deferred``).  kind "f32": ConvOp.wgrad_item tuple; "h16": the arguments of
-        wgrad_h16_async."""
-        if self.defer_mask_wgrad and self.aux_stream is not None:
-            self._deferred.append((kind, args))
-        elif kind == "f32":
-            self.wgrad_async(*args)
-        elif kind == "wino":
-            self._wino_wgrad_async(*args)
+    def _mask_wgrad(self, launch, *operands):
+        """A weight gradient of the mask head (`launch`: the ops call with its arguments bound, `operands`: the tensors it
+        reads): now, on the weight-gradient stream, or, with ``defer_mask_wgrad``, beside the backbone's backward pass
+        (``_flush_deferred``)."""
+        if self.defer_mask_wgrad:
+            self._deferred.append((launch, operands))
         else:
-            self.wgrad_h16_async(*args)
-
-    def _wino_wgrad_async(self, V, xshape, dz, dw, acc):
-        """Weight gradient from a kept Winograd input transform, on the weight-gradient stream behind the current one."""
-        ws = self.wgrad_stream
-        if ws is None:
-            ops.conv2d_wgrad_winograd(V, xshape, dz, dw, accumulate=acc)
-            return
-        ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(ws):
-            _hip_mod.ev_wait(ws, ev)
-            ops.conv2d_wgrad_winograd(V, xshape, dz, dw, accumulate=acc)
-        dz.record_stream(ws)
-        V.record_stream(ws)
+            self._fork(self.wgrad_stream, launch, *operands)
 
     def _flush_deferred(self):
         """Issue the deferred weight gradients on the auxiliary stream, behind everything the main stream has done so far."""
         if not self._deferred:
             return
-        aux, main = self.aux_stream, torch.cuda.current_stream(self.dev)
-        ev = _hip_mod.ev_record(main)
-        if self.defer_lds_pad:
-            ops.tuning_set("wgrad_lds_pad", self.defer_lds_pad)
-        try:
-            with torch.cuda.stream(aux):
-                _hip_mod.ev_wait(aux, ev)
-                for kind, a in self._deferred:
-                    if kind == "f32":
-                        x, dz, wshape, stride, padding, dw, acc = a
-                        ops.conv2d_wgrad(x, dz, wshape, stride, padding, dw=dw, accumulate=acc)
-                    elif kind == "wino":
-                        x, xshape, dz, dw, acc = a
-                        ops.conv2d_wgrad_winograd(x, xshape, dz, dw, accumulate=acc)
-                    else:
-                        x, dz, wshape, dw, mult = a
-                        ops.conv2d_wgrad_h16(x, dz, wshape, 1, "same", dw=dw, multiplier=mult)
-                    dz.record_stream(aux)
-                    x.record_stream(aux)
-        finally:
-            if self.defer_lds_pad:
-                ops.tuning_set("wgrad_lds_pad", 0)
-        self._deferred = []
+        deferred, self._deferred = self._deferred, []
+
+        def run():
+            for launch, _ in deferred:
+                launch()
+        ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))    # before the tuning call: a launch tape reads as it always has
+        with _tuning("wgrad_lds_pad", self.defer_lds_pad, 0, on=bool(self.defer_lds_pad)):
+            self._fork(self.aux_stream, run, *(t for _, operands in deferred for t in operands), ev=ev)
         self._aux_pending = True
 
     def join_aux(self):
@@ -978,7 +942,7 @@ class MaskRCNNEngine(object):
             pooled = ops.roialign(rois, fms, cfg.MASK_POOL_SIZE, image_area)
             x = pooled.view(B * R, cfg.MASK_POOL_SIZE, cfg.MASK_POOL_SIZE, -1)
         ctxs = []
-        if self.head_dtype is None and self.winograd_split and self.wgrad_stream is not None and x.shape[0] >= 512 and \
+        if self.head_dtype is None and self.winograd_split and x.shape[0] >= 512 and \
                 all(self._wino_ok(self.op("mrcnn_mask_conv%d" % i), (x.shape[0] // 2,) + tuple(x.shape[1:3]) + (self.op("mrcnn_mask_conv%d" % i).wshape[2],))
                     for i in range(1, 5)):
             x, ctxs = self._mask_convs_fwd_split(x, train)
@@ -1072,12 +1036,9 @@ class MaskRCNNEngine(object):
         area = float(H * W)
         # layers of a few hundred pixels (res4 / res5 / P5 / P6 at batch 1) take the 16 x 16-tile single-launch kernel while the
         # inference trunk is issued: detect graph 3.01 -> 2.73 ms (ResNet-101), 2.35 -> 2.23 (ResNet-50).  Training keeps its kernels.
-        ops.tuning_set("sk16", 1 if self.sk16_infer else 0)
-        try:
+        with _tuning("sk16", 1 if self.sk16_infer else 0, 0):
             pyr, _ = self._trunk_fwd(images, False)
             _, rpn_probs, rpn_bbox, _ = self._rpn_fwd(pyr, False)
-        finally:
-            ops.tuning_set("sk16", 0)
         anchors = self.anchors((H, W, images.shape[3]))
         rois = ops.proposals(rpn_probs, rpn_bbox, anchors, cfg.PRE_NMS_LIMIT, cfg.POST_NMS_ROIS_INFERENCE,
                              cfg.RPN_NMS_THRESHOLD, np.asarray(cfg.RPN_BBOX_STD_DEV, np.float32))
@@ -1106,12 +1067,10 @@ class MaskRCNNEngine(object):
             sw = ops.empty(tuple(windows_norm.shape), torch.float32, self.dev)
             sx.copy_(images)
             sw.copy_(windows_norm)
-            side = torch.cuda.Stream(device=self.dev)
-            _hip_mod.stream_wait(side, torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
+            def settle():
                 for _ in range(2):                      # sizes every workspace / caches the anchors
                     self.infer(sx, sw)
-            _hip_mod.stream_wait(torch.cuda.current_stream(self.dev), side)
+            self._settle(settle)
             graph = torch.cuda.CUDAGraph()
             self._wino_reads.clear()
             with _capture(graph):
@@ -1156,23 +1115,20 @@ class MaskRCNNEngine(object):
         area = float(H * W)
         # gradient zeroing and the flipped / transposed weight images are only needed by the backward pass: they run on
         # the weight-gradient stream beside the forward pass (0.2 ms off the critical path)
-        prep_ev = None
-        if self.wgrad_stream is not None:
-            ev0 = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))
+        main, aux = torch.cuda.current_stream(self.dev), self.aux_stream
+
+        def prep():
             h16_ev = None
-            with torch.cuda.stream(self.wgrad_stream):
-                _hip_mod.ev_wait(self.wgrad_stream, ev0)
-                if self.head_dtype is not None:
-                    self._ensure_h16()                 # 16-bit weight images: first needed by the FPN (wide mode) / after the trunk
-                    h16_ev = _hip_mod.ev_record(self.wgrad_stream)
-                ops.fill_zero(self.grads)
-                self.refresh_wt()
-            prep_ev = _hip_mod.ev_record(self.wgrad_stream)
-            if h16_ev is not None and self.h16_wide:
-                _hip_mod.ev_wait(torch.cuda.current_stream(self.dev), h16_ev)
-        else:
+            if self.head_dtype is not None:
+                self._ensure_h16()                     # 16-bit weight images: first needed by the FPN (wide mode) / after the trunk
+                h16_ev = _hip_mod.ev_record(self.wgrad_stream)
             ops.fill_zero(self.grads)
             self.refresh_wt()
+            return h16_ev
+        h16_ev = self._fork(self.wgrad_stream, prep)
+        prep_ev = _hip_mod.ev_record(self.wgrad_stream)
+        if h16_ev is not None and self.h16_wide:
+            _hip_mod.ev_wait(main, h16_ev)
         pyr, tape = self._trunk_fwd(images, True)
         rpn_logits, rpn_probs, rpn_bbox, rpn_tape = self._rpn_fwd(pyr, True)
         anchors = self.anchors((H, W, images.shape[3]))
@@ -1185,7 +1141,6 @@ class MaskRCNNEngine(object):
             cfg.ROI_POSITIVE_RATIO, cfg.BBOX_STD_DEV, cfg.MASK_SHAPE, cfg.USE_MINI_MASK)
         # the two heads are independent: the (small) class/box head runs on the auxiliary stream beside the
         # mask head, forward and backward
-        main, aux = torch.cuda.current_stream(self.dev), self.aux_stream
         # The mask loss only sees positive ROIs (mrcnn_mask_loss_graph, model.py:1250-1257) and
         # DetectionTargetLayer puts them first (model.py:696), at most int(T * ROI_POSITIVE_RATIO) per image:
         # the mask-head outputs of every other row are never read and their gradient rows are exactly zero.
@@ -1200,21 +1155,13 @@ class MaskRCNNEngine(object):
             ops.copy2d(rois_m.data_ptr(), quota * 16, rois.data_ptr(), T * 16, quota * 16, B)
         else:
             rois_m = rois
-        if prep_ev is not None and self.head_dtype is not None:
+        if self.head_dtype is not None:
             _hip_mod.ev_wait(main, prep_ev)                    # the mask head reads the 16-bit weight images prepared on the side stream
-        if aux is not None:
-            ev = _hip_mod.ev_record(main)
-            with torch.cuda.stream(aux):
-                _hip_mod.ev_wait(aux, ev)
-                logits, probs, mbbox, ctx_cls = self._class_head_fwd(rois, pyr[:4], area, True)
-            mmask, ctx_mask = self._mask_head_fwd(rois_m, pyr[:4], area, True)
-            _hip_mod.stream_wait(main, aux)
-            for t in (logits, probs, mbbox):
-                t.record_stream(main)
-            rois.record_stream(aux)
-        else:
-            logits, probs, mbbox, ctx_cls = self._class_head_fwd(rois, pyr[:4], area, True)
-            mmask, ctx_mask = self._mask_head_fwd(rois_m, pyr[:4], area, True)
+        logits, probs, mbbox, ctx_cls = self._fork(aux, lambda: self._class_head_fwd(rois, pyr[:4], area, True), rois)
+        mmask, ctx_mask = self._mask_head_fwd(rois_m, pyr[:4], area, True)
+        _hip_mod.stream_wait(main, aux)
+        for t in (logits, probs, mbbox):
+            t.record_stream(main)
         if sparse:                                   # rows [quota, T) of the loss input: zeros, never read as positives
             row = int(np.prod(mmask.shape[2:])) * 4
             full = ops.empty((B, T) + tuple(mmask.shape[2:]), torch.float32, self.dev)
@@ -1225,32 +1172,23 @@ class MaskRCNNEngine(object):
                                  logits, mbbox, mmask, self.loss_weights(),
                                  cfg.MASK_LOSS_FUNCTION == "dice_coef_loss")
         losses, d_rpn_logits, d_rpn_bbox, d_logits, d_mbbox, d_mmask = out
-        if prep_ev is not None:
-            _hip_mod.ev_wait(main, prep_ev)
+        _hip_mod.ev_wait(main, prep_ev)
         assert self._wt_gen == self._gen, "the backward pass reads the flipped kernels of the current weights"
 
         # ---- pyramid gradient accumulators ------------------------------------------------------
         dP = [ops.empty_like(p) for p in pyr[:4]]
         for t in dP:
             ops.fill_zero(t)
-        if aux is not None:
-            ev = _hip_mod.ev_record(main)
-            with torch.cuda.stream(aux):
-                _hip_mod.ev_wait(aux, ev)
-                self._class_head_bwd(d_logits, d_mbbox, ctx_cls, rois, dP, area)
-                # the RPN backward needs nothing from the heads: it follows the class head on this stream, beside the
-                # (much longer) mask head.  Its data gradients add to dP with plain read-modify-writes, so the mask head's
-                # ROIAlign adjoint (atomics on the same maps, last thing on the main stream) waits for this event.
-                dP6 = self._rpn_bwd(d_rpn_logits, d_rpn_bbox, rpn_tape, dP)
-                ev_aux = _hip_mod.ev_record(aux)
-            self._mask_head_bwd(d_mmask, ctx_mask, rois_m, dP, area, before_adjoint=ev_aux)
-            _hip_mod.stream_wait(main, aux)
-            for t in (d_logits, d_mbbox, d_rpn_logits, d_rpn_bbox):
-                t.record_stream(aux)
-        else:
-            self._mask_head_bwd(d_mmask, ctx_mask, rois_m, dP, area)
+
+        def heads_bwd():
             self._class_head_bwd(d_logits, d_mbbox, ctx_cls, rois, dP, area)
-            dP6 = self._rpn_bwd(d_rpn_logits, d_rpn_bbox, rpn_tape, dP)
+            # the RPN backward needs nothing from the heads: it follows the class head on this stream, beside the
+            # (much longer) mask head.  Its data gradients add to dP with plain read-modify-writes, so the mask head's
+            # ROIAlign adjoint (atomics on the same maps, last thing on the main stream) waits for this event.
+            return self._rpn_bwd(d_rpn_logits, d_rpn_bbox, rpn_tape, dP), _hip_mod.ev_record(aux)
+        dP6, ev_aux = self._fork(aux, heads_bwd, d_logits, d_mbbox, d_rpn_logits, d_rpn_bbox)
+        self._mask_head_bwd(d_mmask, ctx_mask, rois_m, dP, area, ev_aux)
+        _hip_mod.stream_wait(main, aux)
         deferred = bool(self._deferred)
         self._flush_deferred()
         if self.grad_ready and not deferred:     # ~2/3 of the gradient bytes (FC1 alone is 51 MB) are final here,
@@ -1268,9 +1206,10 @@ class MaskRCNNEngine(object):
         return losses
 
     # ---- head backward --------------------------------------------------------------------------
-    def _mask_head_bwd(self, d_mmask, ctxs, rois, dP, area, before_adjoint=None):
+    def _mask_head_bwd(self, d_mmask, ctxs, rois, dP, area, before_adjoint):
         """Backward of build_fpn_mask_graph on the rows the forward ran on: ``rois`` is [B, R, 4] with R = T
-        (all train ROIs) or the positive quota (see forward_backward); d_mmask is always [B, T, ...]."""
+        (all train ROIs) or the positive quota (see forward_backward); d_mmask is always [B, T, ...].  The ROIAlign adjoint
+        at its end waits for the event ``before_adjoint``."""
         B, T, R = d_mmask.shape[0], d_mmask.shape[1], rois.shape[1]
         if R == T:
             g = d_mmask
@@ -1278,30 +1217,22 @@ class MaskRCNNEngine(object):
             row = int(np.prod(d_mmask.shape[2:])) * 4
             g = ops.empty((B, R) + tuple(d_mmask.shape[2:]), torch.float32, self.dev)
             ops.copy2d(g.data_ptr(), R * row, d_mmask.data_ptr(), T * row, R * row, B)
-        self._mask_head_bwd_rows(g.view((B * R,) + tuple(g.shape[2:])), ctxs, rois, dP, area, before_adjoint)
+        with _tuning("h16_phase", 0, 1, on=not self.h16_phase_bwd):
+            self._mask_head_bwd_rows(g.view((B * R,) + tuple(g.shape[2:])), ctxs, rois, dP, area, before_adjoint)
 
-    def _mask_head_bwd_rows(self, g, ctxs, rois, dP, area, before_adjoint=None):
-        if not self.h16_phase_bwd:
-            ops.tuning_set("h16_phase", 0)
-        try:
-            self._mask_head_bwd_rows_impl(g, ctxs, rois, dP, area, before_adjoint)
-        finally:
-            if not self.h16_phase_bwd:
-                ops.tuning_set("h16_phase", 1)
-
-    def _mask_head_bwd_rows_impl(self, g, ctxs, rois, dP, area, before_adjoint=None):
+    def _mask_head_bwd_rows(self, g, ctxs, rois, dP, area, before_adjoint):
         cfg = self.cfg
         c1, c2, c3, c4, cdec, cm = ctxs
         mop, dc = self.op("mrcnn_mask"), self.op("mrcnn_mask_deconv")
         x_in, _, up, _ = cdec
         C_ = cm[2].shape[-1]
-        S = float(self.loss_scale) if self.head_dtype == torch.float16 else 1.0
+        S = self._S()
         d16 = None
         if up.dtype != torch.float32:
             # output stage and deconvolution on the 16-bit tensors: dzg comes out scaled, in 16 bits
             dzg = ops.mask_out_bwd_h16(g, cm[2], up, mop.w.view(mop.wshape[2], mop.wshape[3]),
                                        mop.dw.view(mop.wshape[2], mop.wshape[3]), mop.db, dc.db, S)
-            self._mask_wgrad("h16", x_in, dzg, dc.wshape, dc.dw, 1.0 / S)
+            self._mask_wgrad(partial(ops.conv2d_wgrad_h16, x_in, dzg, dc.wshape, 1, "same", dw=dc.dw, multiplier=1.0 / S), x_in, dzg)
             d16 = ops.conv2d_h16(dzg, self._h16[dc.name][1], (1, 1, dc.wshape[3], dc.wshape[2]), None, None, None, 1, "valid",
                                  ACT_NONE)
         elif self.fused_mask_out_bwd and C_ <= 16 and up.shape[-1] % 64 == 0 and up.shape[-1] <= 1024:
@@ -1318,7 +1249,7 @@ class MaskRCNNEngine(object):
             ops.epilogue_bwd(d_up, up, None, None, None, None, None, dzu, None, None, dc.db, ACT_RELU)
             dzg = ops.pixel_unshuffle2(dzu)                             # [M,14,14,1024]
         if d16 is None:
-            self._mask_wgrad("f32", x_in, dzg, dc.wshape, 1, "valid", dc.dw, False)
+            self._mask_wgrad(partial(ops.conv2d_wgrad, x_in, dzg, dc.wshape, 1, "valid", dw=dc.dw), x_in, dzg)
         if self.head_dtype is None:
             # every data-gradient convolution applies the epilogue backward of the layer below in its own epilogue
             # (mrcnn_conv2d_dgrad_ep): the gradient w.r.t. the activated output is never written or re-read
@@ -1328,10 +1259,10 @@ class MaskRCNNEngine(object):
                 Vs = self._wino_V.pop(op.name, None)
                 if Vs is not None and self.winograd_wgrad:
                     for vi, (V, a, b) in enumerate(Vs):                  # one call per forward chain (whole batch, or two halves)
-                        self._mask_wgrad("wino", V, (b - a,) + tuple(c[0].shape[1:]), dz[a:b], op.dw, vi > 0)
+                        self._mask_wgrad(partial(ops.conv2d_wgrad_winograd, V, (b - a,) + tuple(c[0].shape[1:]), dz[a:b], op.dw,
+                                                 accumulate=vi > 0), V, dz)
                 else:
-                    self._mask_wgrad("f32", *op.wgrad_item(dz, c))
-                kh, kw, cin, cout = op.wshape
+                    self._mask_wgrad(partial(ops.conv2d_wgrad, c[0], dz, op.wshape, op.stride, op.padding, dw=op.dw), c[0], dz)
                 wino = self._wino_ok(op, c[0].shape)
                 if k + 1 < len(chain):
                     below, bctx = chain[k + 1]
@@ -1343,7 +1274,7 @@ class MaskRCNNEngine(object):
                     elif wino:
                         dz = below.epilogue_bwd(ops.conv2d_winograd(dz, self._wino_U(op, 1, dz.shape)), bctx)[0]
                     else:
-                        dz = self._dgrad_ep(dz, op.wt, ((kh - 1) // 2, (kw - 1) // 2), below, bctx)
+                        dz = self._dgrad_ep(dz, op.wt, op.dgrad_padding, below, bctx)
                 elif wino:
                     d = ops.conv2d_winograd(dz, self._wino_U(op, 1, dz.shape))
                 else:
@@ -1357,13 +1288,11 @@ class MaskRCNNEngine(object):
                 kh, kw, cin, cout = op.wshape
                 xin, z, y, _ = c
                 dz = ops.epilogue_bwd_h16(d16, y, z, op.scale, op.mean, op.rstd, op.dgamma, op.dbeta, op.db, ACT_RELU, 1.0 / S)
-                self._mask_wgrad("h16", xin, dz, op.wshape, op.dw, 1.0 / S)
-                d16 = ops.conv2d_h16(dz, self._h16[op.name][1], (kh, kw, cout, cin), None, None, None, 1,
-                                     ((kh - 1) // 2, (kw - 1) // 2), ACT_NONE)
+                self._mask_wgrad(partial(ops.conv2d_wgrad_h16, xin, dz, op.wshape, 1, "same", dw=op.dw, multiplier=1.0 / S), xin, dz)
+                d16 = ops.conv2d_h16(dz, self._h16[op.name][1], (kh, kw, cout, cin), None, None, None, 1, op.dgrad_padding, ACT_NONE)
             d = None if self.h16_roialign else ops.cast_from_h16(d16, 1.0 / S)
         B, R = rois.shape[0], rois.shape[1]
-        if before_adjoint is not None:
-            _hip_mod.ev_wait(torch.cuda.current_stream(self.dev), before_adjoint)
+        _hip_mod.ev_wait(torch.cuda.current_stream(self.dev), before_adjoint)
         if self.head_dtype is not None and d is None:     # the 16-bit gradient goes straight into the float32 pyramid gradients
             ops.roialign_bwd_h16(rois, d16.view(B, R, cfg.MASK_POOL_SIZE, cfg.MASK_POOL_SIZE, -1), dP, cfg.MASK_POOL_SIZE, area, 1.0 / S)
             return
@@ -1621,6 +1550,17 @@ class MaskRCNNEngine(object):
             t.copy_(k)
         self.params_changed()
 
+    @staticmethod
+    def _static_inputs(dev_inputs, static=None):
+        """The static input buffers of a captured / recorded step, holding `dev_inputs`: new ones, or `static` with the inputs
+        copied in unless they already are these buffers."""
+        if static is None:
+            static = [torch.empty_like(t) for t in dev_inputs]
+        for s_, t in zip(static, dev_inputs):
+            if s_.data_ptr() != t.data_ptr():
+                s_.copy_(t, non_blocking=True)
+        return static
+
     def step_graphed(self, dev_inputs, learning_rate, momentum):
         """forward_backward + apply_gradients (single rank) replayed from a HIP graph: one capture per input signature,
         learning rate / momentum and engine mode.  A step is ~670 launches in float32 and ~930 with the 16-bit blocks; issued
@@ -1631,20 +1571,16 @@ class MaskRCNNEngine(object):
         key = (tuple((tuple(t.shape), t.dtype) for t in dev_inputs), float(learning_rate), float(momentum), id(self.cfg),
                self._mode_key())
         entry = self._train_graphs.get(key)
-        main = torch.cuda.current_stream(self.dev)
         if entry is None:
             assert self.grad_ready is None, "graph replay is single-rank: gradient hooks cannot be captured"
-            static = [torch.empty_like(t) for t in dev_inputs]
-            for s_, t in zip(static, dev_inputs):
-                s_.copy_(t)
+            static = self._static_inputs(dev_inputs)
+
+            def settle():
+                for _ in range(2):
+                    self.forward_backward(*static)
+                    self.apply_gradients(learning_rate, momentum, 1)
             with self._rolled_back():                       # two eager steps on a side stream
-                side = torch.cuda.Stream(device=self.dev)
-                _hip_mod.stream_wait(side, main)
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self.forward_backward(*static)
-                        self.apply_gradients(learning_rate, momentum, 1)
-                _hip_mod.stream_wait(main, side)
+                self._settle(settle)
             graph = torch.cuda.CUDAGraph()
             with _capture(graph):
                 losses = self.forward_backward(*static)
@@ -1652,9 +1588,7 @@ class MaskRCNNEngine(object):
             entry = (graph, static, losses)
             self._train_graphs[key] = entry
         graph, static, losses = entry
-        for s_, t in zip(static, dev_inputs):
-            if s_.data_ptr() != t.data_ptr():
-                s_.copy_(t, non_blocking=True)
+        self._static_inputs(dev_inputs, static)
         graph.replay()
         self.params_changed(fold=False)                     # the captured step ends with the optimiser
         return losses
@@ -1677,9 +1611,7 @@ class MaskRCNNEngine(object):
         entry = self._train_tapes.get(key)
         if entry is None:
             assert (self.grad_ready is None) == (reducer is None), "gradient hooks are recorded through their GradReducer"
-            static = [torch.empty_like(t) for t in dev_inputs]
-            for s_, t in zip(static, dev_inputs):
-                s_.copy_(t)
+            static = self._static_inputs(dev_inputs)
             with self._rolled_back():                       # one eager step
                 hook, self.grad_ready = self.grad_ready, None
                 try:
@@ -1700,9 +1632,7 @@ class MaskRCNNEngine(object):
             self._train_tapes[key] = (tape, static, losses, list(self.arena.slots), list(ops._ws_cache.values()), reducer)
             return losses                                   # the recording pass was this step
         tape, static, losses = entry[:3]
-        for s_, t in zip(static, dev_inputs):
-            if s_.data_ptr() != t.data_ptr():
-                s_.copy_(t, non_blocking=True)
+        self._static_inputs(dev_inputs, static)
         _hip_mod.tape_replay(tape)
         self.params_changed(fold=False)                     # the recorded step ends with the optimiser
         return losses

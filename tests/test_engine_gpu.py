@@ -877,7 +877,7 @@ def test_training_step_staged_class_counts(dev, num_classes, monkeypatch):
         runs[mode] = (losses.cpu().numpy(), eng.get_weights(grads=True), last)
         names = list(eng.layout.offsets)
         del model, eng
-    # which output-stage backward ran (engine._mask_head_bwd_rows_impl: fused only up to 16 classes)
+    # which output-stage backward ran (engine._mask_head_bwd_rows: fused only up to 16 classes)
     if num_classes <= 16:
         assert calls["mask_out_bwd"] >= len(runs) and calls["pixel_unshuffle2"] == 0, calls
     else:

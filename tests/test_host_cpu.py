@@ -84,6 +84,17 @@ def test_product_path_has_no_cpu_fallback():
             assert "mrcnn_oracle" not in open(os.path.join(pkg, fn)).read(), fn
 
 
+@pytest.mark.parametrize("backbone", ["custom", "resnet50"])
+def test_engine_cannot_be_built_on_cpu(backbone):
+    """The training step is written for three streams and has no single-stream form: an engine on a device without streams
+    must not come into being (MaskRCNNEngine.__init__ raises before it returns)."""
+    import model_cases as T
+    from caesar_mrcnn_amd import _hip
+    from caesar_mrcnn_amd.engine import MaskRCNNEngine
+    with pytest.raises(_hip.HipPathError):
+        MaskRCNNEngine(T._small_cfg(backbone, 128), "cpu")
+
+
 def test_same_padding_is_tf_asymmetric():
     from caesar_mrcnn_amd.ops import same_padding
     assert same_padding(128, 3, 2) == (64, 0)       # stem max-pool: pad 0 before / 1 after
