@@ -348,43 +348,67 @@ def conv2d_transpose_2x2(x, k_keras, bias):
     return y.permute(0, 2, 3, 1)
 
 
+class _CropAndResize(torch.autograd.Function):
+    """Forward: TF's CropAndResize CPU functor (lerp x first, then y).  Backward: TF's CropAndResizeBackpropImage functor, the
+    gradient the reference trains with: dtop = (1 - y_lerp) * g, image[top, left] += (1 - x_lerp) * dtop, ... -- products of the
+    weights, every term accurate relative to |g * w|.  torch's chain rule through t + (b - t) * y_lerp would form the same term
+    as (g - g * y_lerp) - (g - g * y_lerp) * x_lerp, accurate only relative to |g| (tests/test_roialign_cpu.py)."""
+
+    @staticmethod
+    def forward(ctx, image, boxes, box_idx, crop_h, crop_w):
+        H, W = image.shape[1], image.shape[2]
+        y1, x1, y2, x2 = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
+        fH, fW = torch.tensor(float(H - 1)), torch.tensor(float(W - 1))
+        if crop_h > 1:
+            hs = (y2 - y1) * fH / float(crop_h - 1)
+            in_y = (y1 * fH)[:, None] + torch.arange(crop_h, dtype=torch.float32)[None, :] * hs[:, None]
+        else:
+            in_y = (0.5 * (y1 + y2) * fH)[:, None]
+        if crop_w > 1:
+            ws = (x2 - x1) * fW / float(crop_w - 1)
+            in_x = (x1 * fW)[:, None] + torch.arange(crop_w, dtype=torch.float32)[None, :] * ws[:, None]
+        else:
+            in_x = (0.5 * (x1 + x2) * fW)[:, None]
+        vy = ~((in_y < 0) | (in_y > fH))
+        vx = ~((in_x < 0) | (in_x > fW))
+        iy = torch.where(vy, in_y, torch.zeros_like(in_y))
+        ix = torch.where(vx, in_x, torch.zeros_like(in_x))
+        top, bot = torch.floor(iy).long()[:, :, None], torch.ceil(iy).long()[:, :, None]
+        lef, rig = torch.floor(ix).long()[:, None, :], torch.ceil(ix).long()[:, None, :]
+        yl = (iy - torch.floor(iy))[:, :, None, None]
+        xl = (ix - torch.floor(ix))[:, None, :, None]
+        bi = box_idx[:, None, None]
+        tl = image[bi, top, lef]
+        tr = image[bi, top, rig]
+        bl = image[bi, bot, lef]
+        br = image[bi, bot, rig]
+        t = tl + (tr - tl) * xl
+        b = bl + (br - bl) * xl
+        out = t + (b - t) * yl
+        valid = (vy[:, :, None] & vx[:, None, :])[..., None]
+        ctx.save_for_backward(bi, top, bot, lef, rig, yl, xl, valid)
+        ctx.image_shape, ctx.image_dtype = image.shape, image.dtype
+        return torch.where(valid, out, torch.zeros_like(out))
+
+    @staticmethod
+    def backward(ctx, g):
+        bi, top, bot, lef, rig, yl, xl, valid = ctx.saved_tensors
+        g = torch.where(valid, g, torch.zeros_like(g))
+        yl, xl = yl.to(g.dtype), xl.to(g.dtype)
+        grad = torch.zeros(ctx.image_shape, dtype=ctx.image_dtype)
+        dtop, dbot = (1 - yl) * g, yl * g
+        for rows, d in ((top, dtop), (bot, dbot)):
+            grad.index_put_((bi, rows, lef), (1 - xl) * d, accumulate=True)
+            grad.index_put_((bi, rows, rig), xl * d, accumulate=True)
+        return grad, None, None, None, None
+
+
 def crop_and_resize(image, boxes, box_idx, crop_h, crop_w):
     """tf.image.crop_and_resize(method='bilinear', extrapolation_value=0) on NHWC torch `image`;
     boxes [n,4] float32 (NumPy or torch, no gradient), box_idx [n].  Differentiable w.r.t. image."""
     boxes = torch.as_tensor(boxes, dtype=torch.float32)
     box_idx = torch.as_tensor(np.asarray(box_idx), dtype=torch.long)
-    H, W = image.shape[1], image.shape[2]
-    n = boxes.shape[0]
-    y1, x1, y2, x2 = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
-    fH, fW = torch.tensor(float(H - 1)), torch.tensor(float(W - 1))
-    if crop_h > 1:
-        hs = (y2 - y1) * fH / float(crop_h - 1)
-        in_y = (y1 * fH)[:, None] + torch.arange(crop_h, dtype=torch.float32)[None, :] * hs[:, None]
-    else:
-        in_y = (0.5 * (y1 + y2) * fH)[:, None]
-    if crop_w > 1:
-        ws = (x2 - x1) * fW / float(crop_w - 1)
-        in_x = (x1 * fW)[:, None] + torch.arange(crop_w, dtype=torch.float32)[None, :] * ws[:, None]
-    else:
-        in_x = (0.5 * (x1 + x2) * fW)[:, None]
-    vy = ~((in_y < 0) | (in_y > fH))
-    vx = ~((in_x < 0) | (in_x > fW))
-    iy = torch.where(vy, in_y, torch.zeros_like(in_y))
-    ix = torch.where(vx, in_x, torch.zeros_like(in_x))
-    top, bot = torch.floor(iy).long(), torch.ceil(iy).long()
-    lef, rig = torch.floor(ix).long(), torch.ceil(ix).long()
-    yl = (iy - torch.floor(iy))[:, :, None, None]
-    xl = (ix - torch.floor(ix))[:, None, :, None]
-    bi = box_idx[:, None, None]
-    tl = image[bi, top[:, :, None], lef[:, None, :]]
-    tr = image[bi, top[:, :, None], rig[:, None, :]]
-    bl = image[bi, bot[:, :, None], lef[:, None, :]]
-    br = image[bi, bot[:, :, None], rig[:, None, :]]
-    t = tl + (tr - tl) * xl
-    b = bl + (br - bl) * xl
-    out = t + (b - t) * yl
-    valid = (vy[:, :, None] & vx[:, None, :])[..., None]
-    return torch.where(valid, out, torch.zeros_like(out))
+    return _CropAndResize.apply(image, boxes, box_idx, crop_h, crop_w)
 
 
 def roi_levels(boxes, image_area):
