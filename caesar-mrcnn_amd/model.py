@@ -62,6 +62,9 @@ class MaskRCNN(object):
         # callers that drop each result before asking for many more -- results that are KEPT then keep pinned memory
         self.detect_zero_copy = False
         self._mask_staging = {}
+        # per image of the last detect: the [H, W, n] uint8 device tensor behind r['masks'] (None without detections); the
+        # Analyzer works on it in place.  It holds H * W * n bytes of device memory per image until the next detect.
+        self.last_masks_device = []
 
     def print_model(self):
         print(self.keras_model.summary())
@@ -426,7 +429,9 @@ class MaskRCNN(object):
             dets = np.empty((n, 6), np.int32)
             dets[:, :4], dets[:, 4], dets[:, 5] = boxes, class_ids, rows
             d = torch.from_numpy(dets).to(mrcnn_mask_dev.device, non_blocking=True)
-            host.copy_(ops.unmold_masks(mrcnn_mask_dev, d, (H, W)), non_blocking=True)
+            masks_dev = ops.unmold_masks(mrcnn_mask_dev, d, (H, W))
+            host.copy_(masks_dev, non_blocking=True)
+            self.last_masks_device[slot] = masks_dev       # the callers have sized the list
         return host
 
     def unmold_detections(self, detections, mrcnn_mask, original_image_shape, image_shape, window):
@@ -435,6 +440,7 @@ class MaskRCNN(object):
         GPU (utils.unmold_mask is the host statement of the same arithmetic, tests/test_kernels_gpu.py::test_unmold_masks)."""
         import torch
         detections = np.asarray(detections)
+        self.last_masks_device = [None]
         boxes, class_ids, scores, rows = self._unmold_boxes(detections, original_image_shape, image_shape, window)
         if not torch.is_tensor(mrcnn_mask):
             mrcnn_mask = torch.from_numpy(np.ascontiguousarray(mrcnn_mask, dtype=np.float32))
@@ -483,6 +489,7 @@ class MaskRCNN(object):
         if timing is not None:
             timing["graph_done"] = time.perf_counter()
         pending = []
+        self.last_masks_device = [None] * len(shapes)
         for i in range(len(shapes)):
             boxes, class_ids, scores, rows = self._unmold_boxes(detections[i], shapes[i], molded_shapes[i], windows[i])
             host = self._unmold_masks_device(boxes, class_ids, rows, out["mrcnn_mask"][i], shapes[i], slot=i) if boxes.shape[0] else None

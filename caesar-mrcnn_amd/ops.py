@@ -847,6 +847,74 @@ def tile_union(pool, desc, desc_host, comp_offsets, member_ids):
     return res
 
 
+class MaskPlanes(object):
+    """The masks of one frame as bit planes on the device (include/mrcnn_hip.h, "mask graph"): words [n, H, ceil(W / 32)] int32
+    (views of the 32-bit words), count [n] int32 = set pixels, box [n, 4] int32 = (y1, x1, y2, x2) as utils.extract_bboxes."""
+
+    def __init__(self, words, count, box, W):
+        self.words, self.count, self.box, self.W = words, count, box, int(W)
+        self.n, self.H, self.wpr = (int(v) for v in words.shape)
+
+
+def mask_planes_pack(masks):
+    """masks [H, W, n] uint8 / bool device tensor (nonzero = set; what unmold_masks returns) -> MaskPlanes."""
+    _need_cuda(masks)
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    assert masks.dtype == torch.uint8 and masks.dim() == 3
+    H, W, n = (int(v) for v in masks.shape)
+    if n <= 0 or H <= 0 or W <= 0:
+        raise _hip.HipPathError("mask_planes_pack: empty request %r" % ((H, W, n),))
+    dev = masks.device
+    words = torch.empty((n, H, (W + 31) // 32), dtype=torch.int32, device=dev)
+    count = torch.empty((n,), dtype=torch.int32, device=dev)
+    box = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    check(_hip.lib().mrcnn_mask_planes_pack(ptr(masks), H, W, n, ptr(words), ptr(count), ptr(box), current_stream()),
+          "mrcnn_mask_planes_pack")
+    return MaskPlanes(words, count, box, W)
+
+
+def mask_pair_stats(planes, pairs):
+    """For pairs [P, 2] int32 (NumPy or device) of plane indices: (inter [P], touch [P]) int32 device tensors -- the pixels two
+    planes share and analyze.masks_touch4 (== Analyzer.are_mask_connected) of the two.  An index outside [0, n) gives 0, 0."""
+    import numpy as np
+    _need_cuda(planes.words, planes.box)
+    dev = planes.words.device
+    if not torch.is_tensor(pairs):
+        pairs = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)).to(dev)
+    _need_cuda(pairs)
+    assert pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2
+    P = pairs.shape[0]
+    inter = torch.empty((P,), dtype=torch.int32, device=dev)
+    touch = torch.empty((P,), dtype=torch.int32, device=dev)
+    if P:
+        check(_hip.lib().mrcnn_mask_pair_stats(ptr(planes.words), ptr(planes.box), planes.n, planes.H, planes.W, ptr(pairs), P,
+                                               ptr(inter), ptr(touch), current_stream()), "mrcnn_mask_pair_stats")
+    return inter, touch
+
+
+def mask_union(planes, comp_offsets, member_ids):
+    """OR of the member planes of every component (CSR: comp_offsets [C + 1], member_ids [M], NumPy) -> MaskPlanes of the C unions,
+    an empty component giving a zero plane."""
+    import numpy as np
+    _need_cuda(planes.words)
+    co = np.ascontiguousarray(comp_offsets, dtype=np.int32).reshape(-1)
+    ids = np.ascontiguousarray(member_ids, dtype=np.int32).reshape(-1)
+    C_, M = co.size - 1, ids.size
+    if C_ < 0 or co[0] != 0 or co[-1] != M or np.any(np.diff(co) < 0):
+        raise _hip.HipPathError("mask_union: malformed component list")
+    dev = planes.words.device
+    words = torch.empty((C_, planes.H, planes.wpr), dtype=torch.int32, device=dev)
+    count = torch.empty((C_,), dtype=torch.int32, device=dev)
+    box = torch.empty((C_, 4), dtype=torch.int32, device=dev)
+    if C_:
+        csr_t = torch.from_numpy(np.concatenate([co, ids, np.zeros(1, np.int32)])).to(dev)
+        check(_hip.lib().mrcnn_mask_union(ptr(planes.words), planes.n, planes.H, planes.W, csr_t.data_ptr(),
+                                          csr_t.data_ptr() + 4 * (C_ + 1), C_, M, ptr(words), ptr(count), ptr(box), current_stream()),
+              "mrcnn_mask_union")
+    return MaskPlanes(words, count, box, planes.W)
+
+
 def fill_zero(t):
     _need_cuda(t)
     check(_hip.lib().mrcnn_fill_zero(ptr(t), t.numel() * t.element_size(), current_stream()), "mrcnn_fill_zero")

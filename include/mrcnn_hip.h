@@ -229,6 +229,30 @@ int mrcnn_tile_union(const void* pool, int64_t pool_words, const mrcnn_tile_sour
                      mrcnn_tile_source* out_desc, int32_t* out_count, void* out_pool, int64_t out_pool_words, void* fresh_pool,
                      int64_t fresh_pool_words, void* stream);
 
+/* The mask graph of Analyzer.extract_det_masks (mrcnn/analyze.py:1162-1496): which detection masks of a frame overlap or touch,
+ * and the unions of those that are merged.  The masks of ONE frame are bit planes, planes[n][H][wpr] 32-bit words, wpr =
+ * ceil(W / 32): pixel x of a row is bit x & 31 of word x >> 5, least significant bit first (numpy.packbits(...,
+ * bitorder="little"), as for mrcnn_unpack_mask_bits); the bits past W in a row's last word are always zero.  A box is
+ * (y1, x1, y2, x2) as utils.extract_bboxes gives it: y2 / x2 exclusive, all four 0 for an empty plane.  Integer arithmetic
+ * throughout; all pointers are device pointers; nothing is allocated on the device.  n, H or W <= 0: MRCNN_ERR_ARG.
+ *   mrcnn_mask_planes_pack  masks [H, W, n] uint8 (nonzero = set: what mrcnn_unmold_masks writes) -> planes, count[n] (set pixels
+ *                           per plane) and box[n, 4].
+ *   mrcnn_mask_pair_stats   for pairs[P, 2] (plane indices a, b): inter[p] = popcount(a & b) -- the caller forms the union of
+ *                           mask_iou as count_a + count_b - inter -- and touch[p] = 1 iff some pixel of a equals or is a
+ *                           4-neighbour (up, down, left, right; NOT diagonal) of some pixel of b, which is
+ *                           Analyzer.are_mask_connected(a, b) (analyze.masks_touch4 is the NumPy statement).  box = the planes'
+ *                           boxes from _pack / _union: only b's box intersected with a's box grown by one pixel is read.  One
+ *                           wavefront per pair.  An index outside [0, n) gives 0, 0.
+ *   mrcnn_mask_union        components in CSR form as for mrcnn_tile_union (members of component c: member_ids[comp_offsets[c] ..
+ *                           comp_offsets[c + 1]), M ids in all): out_planes[C][H][wpr] = OR of the members (merge_masks chains),
+ *                           with out_count[C] and out_box[C, 4].  An empty component gives a zero plane; members may repeat; ids
+ *                           outside [0, n) are skipped.  out_planes must not be planes.                                        */
+int mrcnn_mask_planes_pack(const void* masks, int H, int W, int n, void* planes, int32_t* count, int32_t* box, void* stream);
+int mrcnn_mask_pair_stats(const void* planes, const int32_t* box, int n, int H, int W, const int32_t* pairs, int P, int32_t* inter,
+                          int32_t* touch, void* stream);
+int mrcnn_mask_union(const void* planes, int n, int H, int W, const int32_t* comp_offsets, const int32_t* member_ids, int C, int M,
+                     void* out_planes, int32_t* out_count, int32_t* out_box, void* stream);
+
 /* detect() post-processing (MaskRCNN.unmold_detections, mrcnn/model.py:2607-2619; utils.unmold_mask, mrcnn/utils.py:629-645;
  * utils.resize -> skimage.transform.resize(order=1, mode='constant', cval=0, clip=True), mrcnn/utils.py:957-978): for each of
  * the n detections of ONE image, resize the class channel of its MH x MW mask to its integer pixel box (float64, half-pixel
