@@ -256,6 +256,93 @@ def test_class_count_preconditions_of_gpu_cases():
             assert set(d["tcls"].reshape(-1).tolist()) == set(range(num_classes))
 
 
+def test_count_case_preconditions_of_gpu_cases():
+    """The count-dependent GPU cases (tests/test_counts_gpu.py) assert their preconditions from the oracle side; here the same
+    seeded inputs (tests/model_cases.py) go through the oracle alone.  Detection targets: the counts (P, N) every scene is built for
+    -- the sweep's P = min(b, 66) with N and its float32 steps, P below the quota, scarce negatives, P = N = 0, R = 1, the caps --
+    and the threshold scene's float32 IoUs of exactly 0.5 and either side of 0.001.  Detection layer: nvalid of every case, the zero
+    tail, the cut inside a chunk.  Losses: which register groups of the RPN kernel hold positives, the emptied sides, the surplus."""
+    import model_cases as M
+    from caesar_mrcnn_amd.config import run_py_config
+    for name in M.DT_SCENES:
+        M.check_detection_target_case(name)
+    for name in M.DT_MINI_SCENES:
+        M.check_detection_target_case(name, True)
+    seen = set()
+    for R, n, maxi, minconf in M.DETECTION_COUNT_CASES:
+        inp, cfg, ref, nvalid = M.detection_count_case(R, n, maxi, minconf)
+        assert inp[0].shape == (2, R, 4) and (minconf != 0 or nvalid == list(n))
+        seen |= set(nvalid)
+    assert {0, 1, 63, 64, 65, 128, 129, 2048} <= seen
+    cfg = run_py_config(num_classes=4)
+    for A in M.RANK_CASE_ANCHORS:
+        d = M.losses_rank_inputs(A)
+        m = d["rpn_match"][:, :, 0]
+        per_group = M.rank_case_group_positives(d)
+        assert per_group.shape == (2, -(-A // M.LOSS_GROUP)) and (per_group.sum(0) > 0).all()          # every group, in some image
+        assert per_group[0, 0] == 0 and (per_group[0, 1:] > 0).all()                                     # empty first group
+        assert per_group[1, -1] == 0 and (per_group[1, :-1] > 0).all()                                   # empty last group
+        assert ((m == 1).sum(1) <= 256).all() and ((m != 0).sum(1) <= 512).all() and (m != 0).sum() > 900
+        for a in (0, 32767, 32768, 65535, 65536, 98303, 98304, A - 1):
+            if a < A:
+                assert (m[:, a] == 1).any() and (m[:, a] != 0).all(), a
+        assert len(np.unique(d["rpn_bbox_t"], axis=1)[0]) == d["rpn_bbox_t"].shape[1] >= (m == 1).sum(1).max()
+    for case in M.EMPTY_SIDE_CASES:
+        d = M.losses_empty_inputs(case)
+        ls, grads = M.losses_reference(cfg, d)
+        zero = {"a": [1], "b": [0, 1], "c": [], "d": [3, 4], "e": [], "f": [], "g": []}[case]
+        assert all(ls[i] == 0 for i in zero) and all(ls[i] > 0 for i in range(5) if i not in zero and not (case == "g" and i == 2))
+        assert np.isnan(ls[2]) == (case == "g") and np.isnan(grads["logits"]).all() == (case == "g")
+        assert int((d["tcls"] > 0).sum()) == {"d": 0, "e": 1, "f": d["tcls"].size}.get(case, 40)
+    d, match_box = M.losses_surplus_inputs()
+    npos = (d["rpn_match"][:, :, 0] == 1).sum(1)
+    assert npos.max() == d["rpn_bbox_t"].shape[1] + 3 and ((match_box[:, :, 0] == 1).sum(1) <= d["rpn_bbox_t"].shape[1]).all()
+    ls, grads = M.losses_reference(cfg, d, rpn_match_box=match_box)
+    assert np.isfinite(ls).all() and (grads["rpn_bbox"][match_box[:, :, 0] != 1] == 0).all()
+
+
+@pytest.mark.parametrize("A", [33797, 98309])
+def test_rank_carry_perturbation_fails_the_loss_comparison(A):
+    """The multi-group loss case can see a lost rank carry: a float64 statement of the RPN box loss with the ranks written out
+    (model_cases.rpn_bbox_loss_statement) passes the GPU test's comparison with the oracle; the same statement with the ranks of
+    the second register group shifted by one fails it, in the loss and in the gradient."""
+    import model_cases as M
+    from caesar_mrcnn_amd.config import run_py_config
+    d = M.losses_rank_inputs(A)
+    ls, grads = M.losses_reference(run_py_config(num_classes=4), d)
+
+    def compare(shift_group):
+        l1, g = M.rpn_bbox_loss_statement(d, shift_group)
+        got = ls.copy(); got[1] = l1
+        M.assert_losses_close(got, {"rpn_bbox": g}, ls, grads, names=["rpn_bbox"], which=[1])
+        return l1, g
+
+    compare(None)
+    with pytest.raises(AssertionError):
+        compare(1)
+    l1, g = M.rpn_bbox_loss_statement(d, 1)
+    assert abs(l1 - ls[1]) > 100 * (M.LOSS_TOL["atol"] + M.LOSS_TOL["rtol"] * abs(ls[1]))               # not a near miss
+    with pytest.raises(AssertionError):
+        np.testing.assert_allclose(g, grads["rpn_bbox"], **M.GRAD_TOL)
+
+
+@pytest.mark.parametrize("mini", [False, True])
+def test_compacted_mask_plane_perturbation_changes_the_targets(mini):
+    """The layout scene can see a kernel that reads GT mask plane g of the compacted order instead of the original row gorig[g]:
+    with the planes moved that way the oracle's mask targets change (and nothing else does)."""
+    import mrcnn_oracle as orc
+    import model_cases as M
+    s, cfg, ref = M.detection_target_case("layout", mini)
+    wrong = M.layout_compacted_planes(s)
+    o = orc.OracleMaskRCNN(cfg, {})
+    for b, r in enumerate(ref):
+        p = o.detection_targets(s["props"][b], s["gt_cls"][b], s["gt_boxes"][b], wrong[b].astype(bool), s["keys"][b])
+        P = r[4][0]
+        assert p[4] == r[4] and np.array_equal(p[0], r[0]) and np.array_equal(p[1], r[1]) and np.array_equal(p[2], r[2])
+        differs = (p[3][:P] != r[3][:P]).any(axis=(1, 2))
+        assert differs.mean() > 0.9, differs.mean()                  # (almost) every positive row: random planes
+
+
 def test_oracle_training_graph_at_six_classes():
     """OracleMaskRCNN.forward_training on the small test configuration at NUM_CLASSES = 6 (the reference's documented 1 + 5): five
     finite losses, head outputs C / 4 C / C wide, target class ids of more than one foreground class below C."""
