@@ -10,6 +10,7 @@ Gradient plumbing conventions
     convolution can add an existing buffer in its epilogue (res_mode SAME, in place);
   * the ROIAlign adjoints scatter-add into zero-initialised pyramid gradients first.
 """
+import collections
 import contextlib
 import gc
 import operator
@@ -30,6 +31,16 @@ from .params import ParamLayout, deconv_gemm_to_keras, deconv_keras_to_gemm, gra
 H16_WIDE_LAYERS = ("fpn_p2", "fpn_p3", "fpn_p4", "fpn_p5", "rpn_conv_shared", "mrcnn_class_conv1", "mrcnn_class_conv2")
 
 LOSS_NAMES = ("rpn_class_loss", "rpn_bbox_loss", "mrcnn_class_loss", "mrcnn_bbox_loss", "mrcnn_mask_loss")
+
+
+# What a layer's forward pass leaves for its backward pass.  The forward pass is the only writer; the backward pass decides from
+# these fields alone, never from the engine's switches.  path: the kernels the forward ran -- the direct float32 ones, the
+# Winograd domain, or the 16-bit matrix cores (x, z, out are 16-bit tensors then).  V: the Winograd input transform kept for
+# the weight gradient (winograd_wgrad), else None.
+DIRECT, WINO, H16 = "direct", "winograd", "h16"
+Ctx = collections.namedtuple("Ctx", "x z out act path V", defaults=(DIRECT, None))
+# a bottleneck block: the contexts of its 2a, 2b, 2c and shortcut (None: identity) convolutions, and whether it ran in 16 bits
+BlockCtx = collections.namedtuple("BlockCtx", "a b c shortcut h16")
 
 
 _on = lambda s: s != "0"        # an environment switch is on unless it is "0"
@@ -63,21 +74,10 @@ SWITCHES = (
     # for 100 detections where F(2x2) has 16 x 4900; 1.3e-5 of the result's range instead of 1.6e-6, on probabilities that are
     # thresholded at 0.5) -- detect graph 2.73 -> 2.60 ms; 2 = F(2x2) as in rounds 1-2
     ("infer_mask_tile", "MRCNN_WINOGRAD_INFER_MASK_TILE", 4, int, "i"),
-    # forward as two half-batch chains on two streams: +0.7 ms with the F(2x2) layers, level with the uniform F(4x4) tiling, a loss with
-    # the mixed tiling (its small tile groups halve again: ResNet-101 / 4 images 37.6 -> 37.4 ms, ResNet-50 / 2 images 20.8 -> 20.0) -> off
-    ("winograd_split", "MRCNN_WINOGRAD_SPLIT", False, _on, "ti"),
     # the 16 x 16-tile single-launch kernel for the layers of a few hundred pixels of the inference trunk (see infer)
     ("sk16_infer", "MRCNN_SK16_INFER", True, _on, "i"),
     ("fused_mask_out_bwd", None, True, None, "t"),              # single-pass backward of the mask-head output stage
     ("fused_dgrad_epilogue", None, True, None, "t"),            # mask-head data-gradient convs apply the lower layer's epilogue bwd
-    # A/B switch, default OFF (measured, DESIGN.md "rejected"): the mask head's weight gradients feed nothing in the
-    # backward chain, so they can be held back and issued (auxiliary stream) when the backbone's backward pass starts,
-    # to fill the chip beside its ~330 small launches; "wgrad_lds_pad" then keeps one workgroup slot per CU free for
-    # those.  Result on ResNet-101, 4 images, dense: 60.56 -> 60.26 ms (pad 0), 60.81 (pad 8192): the small kernels are
-    # paced by the matrix pipe of their SIMD (serial K chains of 64-cycle fp32 MFMAs), which the large kernel keeps
-    # 88 % busy -- beside it they run 4x slower (18 -> 73 us) and the large kernels 1.45x slower: zero sum.
-    ("defer_mask_wgrad", "MRCNN_DEFER_MASK_WGRAD", False, _on, "t"),
-    ("defer_lds_pad", "MRCNN_DEFER_LDS_PAD", 8192, int, "t"),
     ("gather_roialign_bwd", "MRCNN_GATHER_ROIALIGN_BWD", True, _on, "t"),   # class-head ROIAlign adjoint in gather form
     ("multi_launch", "MRCNN_MULTI_LAUNCH", True, _on, "ti"),    # independent small convolutions share launches
     # stream priorities (HIP: -1 high, 0 normal, 1 low where the runtime has three levels): the weight gradients are off the
@@ -166,34 +166,32 @@ class ConvOp(object):
         if train and self.bn:
             z = ops.empty_like(out)
         ops.conv2d(x, self.w, self.b, self.scale, self.shift, res, out=out, z_out=z, desc=d)
-        ctx = (x, z, out, act) if train else None
-        return out, ctx
+        return out, (Ctx(x, z, out, act) if train else None)
 
     # ---- backward pieces ---------------------------------------------------------------------
     def epilogue_bwd(self, dout, ctx, want_dy=False):
         """Returns (dz, dy): gradient w.r.t. the raw conv output, and (optionally) the gradient after
         the activation mask, which is what a residual input receives."""
-        x, z, out, act = ctx
-        if self.bn is None and act == ACT_NONE:
+        if self.bn is None and ctx.act == ACT_NONE:
             ops.epilogue_bwd(dout, dbias=self.db)
             return dout, dout
         dz = ops.empty_like(dout)
         dy = ops.empty_like(dout) if want_dy else None
-        ops.epilogue_bwd(dout, out if act != ACT_NONE else None, z, self.scale, self.mean, self.rstd, dy, dz,
-                         self.dgamma, self.dbeta, self.db, act)
+        ops.epilogue_bwd(dout, ctx.out if ctx.act != ACT_NONE else None, ctx.z, self.scale, self.mean, self.rstd, dy, dz,
+                         self.dgamma, self.dbeta, self.db, ctx.act)
         return dz, dy
 
     def wgrad(self, dz, ctx, accumulate=False):
-        self.model.wgrad_async(ctx[0], dz, self.wshape, self.stride, self.padding, self.dw, accumulate)
+        self.model.wgrad_async(ctx.x, dz, self.wshape, self.stride, self.padding, self.dw, accumulate)
 
     def wgrad_item(self, dz, ctx, accumulate=False):
         """The arguments of this layer's weight gradient, for MaskRCNNEngine.wgrad_group."""
-        return (ctx[0], dz, self.wshape, self.stride, self.padding, self.dw, accumulate)
+        return (ctx.x, dz, self.wshape, self.stride, self.padding, self.dw, accumulate)
 
     def dgrad(self, dz, ctx, out=None, accumulate=False):
         """dx = adjoint of the convolution applied to dz.  `out` (shape of x) receives the result;
         accumulate=True adds to what `out` already holds (in place)."""
-        x = ctx[0]
+        x = ctx.x
         kh, kw, cin, cout = self.wshape
         N, H, W, _ = x.shape
         res = out if accumulate else None
@@ -311,7 +309,6 @@ class MaskRCNNEngine(object):
             v = os.environ.get(env) if env else None
             setattr(self, name, default if v is None else parse(v))
         self._h16, self._h16_gen = {}, None     # 16-bit images of head_dtype, and the (weight generation, dtype) they hold
-        self._wino_V = {}               # layer -> input transform V of this step's forward pass
         self._wino = {}                 # (layer, tile, 0 forward / 1 data gradient) -> [U, weight generation]; stable addresses
         self._wino_reads = set()        # keys of _wino read since infer_graphed last cleared it
         self._h16_store = {}            # dtype -> {layer: (W^T image, data-gradient image)}, stable addresses
@@ -319,19 +316,16 @@ class MaskRCNNEngine(object):
         self.wgrad_stream, self.aux_stream = _side_streams(device, self.wgrad_prio, self.aux_prio)
         if self.wgrad_stream is None:           # the step is written for three streams: there is no single-stream form of it
             raise _hip_mod.HipPathError("MaskRCNNEngine needs a GPU device for its side streams, not %r" % (device,))
-        self._deferred = []
 
     def op(self, name):
         return self._ops[name]
 
     # ---- work on a side stream ---------------------------------------------------------------------
-    def _fork(self, side, body, *operands, ev=None):
-        """body() on the stream `side`, behind everything the current stream has been given so far (or behind `ev`, an event
-        already recorded on it); returns what body returns.  `operands`: the tensors of the current stream that body reads,
-        kept from reuse until `side` is done with them.  The ONE place where work leaves the main stream (besides the
-        two-chain forward of _mask_convs_fwd_split); joining again -- join_wgrad, join_aux, a stream_wait -- is the caller's."""
-        if ev is None:
-            ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))
+    def _fork(self, side, body, *operands):
+        """body() on the stream `side`, behind everything the current stream has been given so far; returns what body returns.
+        `operands`: the tensors of the current stream that body reads, kept from reuse until `side` is done with them.  The ONE
+        place where work leaves the main stream; joining again -- join_wgrad, a stream_wait -- is the caller's."""
+        ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(side):
             _hip_mod.ev_wait(side, ev)
             out = body()
@@ -488,17 +482,16 @@ class MaskRCNNEngine(object):
         z = ops.empty((d.N, d.OH, d.OW, d.Cout), x16.dtype, x16.device) if (train and op.bn) else None
         y = ops.conv2d_h16(x16, self._h16[op.name][0], op.wshape, op.b, op.scale, op.shift, op.stride, op.padding, act, z_out=z,
                            res=res)
-        return y, ((x16, z, y, act) if train else None)
+        return y, (Ctx(x16, z, y, act, H16) if train else None)
 
     def _h16_bwd(self, op, d16, ctx, S, accumulate_w=False, need_dx=True, want_dy=False, dx_res=None):
         """Backward of _h16_fwd.  d16: gradient w.r.t. the activated output, 16 bit, times the loss scale S.  Bias / BN
         sums and the weight gradient land unscaled in the float32 gradient buffer; returns dx (16 bit, times S; plus
         dx_res when given), or (dx, dy) with want_dy: dy = d16 * act' is what a shortcut into this layer's Add receives."""
-        x16, z, y, act = ctx
-        got = ops.epilogue_bwd_h16(d16, y if act != ACT_NONE else None, z, op.scale, op.mean, op.rstd, op.dgamma, op.dbeta, op.db,
-                                   act, 1.0 / S, want_dy=want_dy)
+        got = ops.epilogue_bwd_h16(d16, ctx.out if ctx.act != ACT_NONE else None, ctx.z, op.scale, op.mean, op.rstd, op.dgamma,
+                                   op.dbeta, op.db, ctx.act, 1.0 / S, want_dy=want_dy)
         dz, dy = got if want_dy else (got, None)
-        self._h16_wgrad(op, x16, dz, S, accumulate_w)
+        self._h16_wgrad(op, ctx.x, dz, S, accumulate_w)
         if not need_dx:
             return (dz, dy) if want_dy else dz                    # the caller issues the data gradient itself
         dx = self._h16_dgrad(op, dz, dx_res)
@@ -529,7 +522,7 @@ class MaskRCNNEngine(object):
         b, cb = self._h16_fwd(blk.c2b, a, ACT_RELU, train)
         sc, c1c = (x16, None) if blk.c1 is None else self._h16_fwd(blk.c1, x16, ACT_NONE, train)
         y, cc = self._h16_fwd(blk.c2c, b, ACT_RELU, train, res=sc)
-        return y, ("h16", ca, cb, cc, c1c)
+        return y, BlockCtx(ca, cb, cc, c1c, True)
 
     def _h16_wgrad(self, op, x16, dz, S, accumulate=False):
         """Weight gradient of a 16-bit layer from its input and dz (16 bit, times S), on the weight-gradient stream.  A layer
@@ -549,7 +542,7 @@ class MaskRCNNEngine(object):
         """dz of layer `below` from the dz of layer `op` above it: the 16-bit data gradient with `below`'s epilogue
         backward in its own epilogue (mrcnn_conv2d_dgrad_ep_h16); the two launches when the shape has no fused kernel."""
         kh, kw, cin, cout = op.wshape
-        _, z, y, act = below_ctx
+        z, y, act = below_ctx.z, below_ctx.out, below_ctx.act
         if self.h16_fused_bwd and op.stride == 1:
             got = ops.conv2d_dgrad_ep_h16(dz, self._h16[op.name][1], (kh, kw, cout, cin), op.dgrad_padding, y if act != ACT_NONE else None, z,
                                           below.scale, below.mean, below.rstd, below.dgamma, below.dbeta, below.db, act, 1.0 / S)
@@ -564,20 +557,20 @@ class MaskRCNNEngine(object):
         main stream for an identity block (output-stage backward, two data gradients that carry the backward epilogue of the
         layer below, the last data gradient with the shortcut's gradient on its residual port); weight gradients on the side
         stream."""
-        _, ca, cb, cc, c1c = ctxs
+        ca, cb, cc, c1c = ctxs.a, ctxs.b, ctxs.c, ctxs.shortcut
         c2a, c2b, c2c = blk.c2a, blk.c2b, blk.c2c
-        dzc, dy = ops.epilogue_bwd_h16(d16, cc[2], cc[1], c2c.scale, c2c.mean, c2c.rstd, c2c.dgamma, c2c.dbeta, c2c.db, ACT_RELU,
+        dzc, dy = ops.epilogue_bwd_h16(d16, cc.out, cc.z, c2c.scale, c2c.mean, c2c.rstd, c2c.dgamma, c2c.dbeta, c2c.db, ACT_RELU,
                                        1.0 / S, want_dy=True)
-        self._h16_wgrad(c2c, cc[0], dzc, S)
+        self._h16_wgrad(c2c, cc.x, dzc, S)
         dzb = self._h16_dgrad_ep(c2c, dzc, c2b, cb, S)
-        self._h16_wgrad(c2b, cb[0], dzb, S)
+        self._h16_wgrad(c2b, cb.x, dzb, S)
         dza = self._h16_dgrad_ep(c2b, dzb, c2a, ca, S)
-        self._h16_wgrad(c2a, ca[0], dza, S)
+        self._h16_wgrad(c2a, ca.x, dza, S)
         if blk.c1 is None:
             return self._h16_dgrad(c2a, dza, dx_res=dy)           # identity shortcut: dx = dgrad_2a + dy
         # projection shortcut: dx = dgrad_1(dy) + dgrad_2a(dza); with stride 2 both 1x1 data gradients scatter into the
         # even pixels of a zeroed tensor (the second adds through the residual port, same strides)
-        x16 = ca[0]
+        x16 = ca.x
         N, H, W, C = x16.shape
         st = c2a.stride
         dz1 = self._h16_bwd(blk.c1, dy, c1c, S, need_dx=False)
@@ -593,24 +586,26 @@ class MaskRCNNEngine(object):
     def _S(self):
         return float(self.loss_scale) if self.head_dtype == torch.float16 else 1.0
 
+    def _wino_fwd(self, op, x, act, train, infer_tile=2):
+        """ConvOp.forward(x, act) of a 3 x 3 layer through the Winograd domain (tile: see _wino_U).  With winograd_wgrad the training
+        context keeps the input transform V: the layer's weight gradient contracts it with the transformed dz."""
+        out = ops.empty(tuple(x.shape[:3]) + (op.wshape[3],), torch.float32, x.device)
+        z = ops.empty_like(out) if (train and op.bn) else None
+        V = ops.empty((ops.winograd_v_floats(tuple(x.shape)),), torch.float32, x.device) if (train and self.winograd_wgrad) else None
+        ops.conv2d_winograd(x, self._wino_U(op, 0, x.shape, train, infer_tile), op.b, op.scale, op.shift, act, out=out, z_out=z, keep_v=V)
+        return out, (Ctx(x, z, out, act, WINO, V) if train else None)
+
     # ---- independent small convolutions in one launch (mrcnn_conv2d_fwd_multi) ------------------------
     def _forward_multi(self, layers, xs, act=ACT_NONE, train=False):
         """[ConvOp.forward(x, act) for layer, x in zip(layers, xs)] as one launch; falls back to the loop.  With trunk_winograd the
         3 x 3 layers large enough for the Winograd path (FPN smoothing / RPN shared convolution on P2, P3 of big inputs) leave the
-        group and run F(2x2, 3x3) on their own; their training contexts are the direct kernels' (the backward pass is unchanged)."""
+        group and run F(2x2, 3x3) on their own; _bwd_group takes those that kept their input transform through it again."""
         if self.trunk_winograd and any(self._wino_trunk_ok(op, x.shape) for op, x in zip(layers, xs)):
             res = [None] * len(layers)
             rest = []
             for i, (op, x) in enumerate(zip(layers, xs)):
                 if self._wino_trunk_ok(op, x.shape):
-                    out = ops.empty(tuple(x.shape[:3]) + (op.wshape[3],), torch.float32, x.device)
-                    z = ops.empty_like(out) if (train and op.bn) else None
-                    V = None
-                    if train and self.winograd_wgrad:       # the input transform is kept: the weight gradient contracts it with A dz A^T
-                        V = ops.empty((ops.winograd_v_floats(tuple(x.shape)),), torch.float32, x.device)
-                        self._wino_V[(op.name, tuple(x.shape))] = V
-                    ops.conv2d_winograd(x, self._wino_U(op, 0, x.shape, train), op.b, op.scale, op.shift, act, out=out, z_out=z, keep_v=V)
-                    res[i] = (out, (x, z, out, act) if train else None)
+                    res[i] = self._wino_fwd(op, x, act, train)
                 else:
                     rest.append(i)
             if rest:
@@ -630,7 +625,7 @@ class MaskRCNNEngine(object):
                                   padding=op.padding, act=act, out=out, z_out=z))
             outs = ops.conv2d_multi(probs)
             if outs is not None:
-                return [(o, (x, z, o, act) if train else None) for o, x, z in zip(outs, xs, zs)]
+                return [(o, Ctx(x, z, o, act) if train else None) for o, x, z in zip(outs, xs, zs)]
         return [op.forward(x, act, train=train) for op, x in zip(layers, xs)]
 
     def _dgrad_multi(self, layers, dzs, ctxs, outs=None, accumulate=False):
@@ -644,7 +639,7 @@ class MaskRCNNEngine(object):
             for i, (op, dz, ctx) in enumerate(zip(layers, dzs, ctxs)):
                 if outs[i] is None:
                     assert not accs[i]
-                    outs[i] = ops.empty_like(ctx[0])
+                    outs[i] = ops.empty_like(ctx.x)
                 probs.append(dict(x=dz, w=op.wt, padding=op.dgrad_padding, res=outs[i] if accs[i] else None,
                                   res_mode=RES_SAME if accs[i] else RES_NONE, out=outs[i]))
             if ops.conv2d_multi(probs) is not None:
@@ -653,7 +648,7 @@ class MaskRCNNEngine(object):
 
     def _bwd_group(self, layers, dzs, ctxs, outs=None, accumulate=False, wgrad_acc=None):
         """Weight gradients (weight-gradient stream) and data gradients of a group of stride-1 convolutions from their dz.  Layers
-        whose forward went through the Winograd path (trunk_winograd: a kept input transform under (name, input shape)) take it
+        whose forward went through the Winograd path and kept its input transform (trunk_winograd: a context with a V) take it
         here too -- weight gradient from V, data gradient F(2x2, 3x3) and, where the destination accumulates, one add pass --,
         the others share the multi-problem launches as before.  wgrad_acc[i]: the layer's weight gradient adds to dw (shared
         weights: the RPN convolution over the pyramid levels)."""
@@ -661,14 +656,14 @@ class MaskRCNNEngine(object):
         outs = list(outs) if outs is not None else [None] * n
         accs = list(accumulate) if isinstance(accumulate, (list, tuple)) else [accumulate] * n
         wacc = list(wgrad_acc) if wgrad_acc is not None else [False] * n
-        Vs = [self._wino_V.pop((op.name, tuple(c[0].shape)), None) for op, c in zip(layers, ctxs)]
+        Vs = [c.V for c in ctxs]
         rest = [i for i in range(n) if Vs[i] is None]
         if rest and not any(wacc):                          # independent weights: the direct ones of the group share a launch as before
             self.wgrad_group([layers[i].wgrad_item(dzs[i], ctxs[i]) for i in rest])
         for i in range(n):                                  # (shared weights: in layer order, each adding to the one before)
             if Vs[i] is not None:
-                self._fork(self.wgrad_stream, partial(ops.conv2d_wgrad_winograd, Vs[i], tuple(ctxs[i][0].shape), dzs[i],
-                                                      layers[i].dw, accumulate=wacc[i]), Vs[i], dzs[i])   # never deferred: trunk
+                self._fork(self.wgrad_stream, partial(ops.conv2d_wgrad_winograd, Vs[i], tuple(ctxs[i].x.shape), dzs[i],
+                                                      layers[i].dw, accumulate=wacc[i]), Vs[i], dzs[i])
             elif any(wacc):
                 self.wgrad_async(*layers[i].wgrad_item(dzs[i], ctxs[i], accumulate=wacc[i]))
         if rest:
@@ -689,35 +684,6 @@ class MaskRCNNEngine(object):
 
     def join_wgrad(self):
         _hip_mod.stream_wait(torch.cuda.current_stream(self.dev), self.wgrad_stream)
-
-    # ---- deferred mask-head weight gradients ----------------------------------------------------------
-    def _mask_wgrad(self, launch, *operands):
-        """A weight gradient of the mask head (`launch`: the ops call with its arguments bound, `operands`: the tensors it
-        reads): now, on the weight-gradient stream, or, with ``defer_mask_wgrad``, beside the backbone's backward pass
-        (``_flush_deferred``)."""
-        if self.defer_mask_wgrad:
-            self._deferred.append((launch, operands))
-        else:
-            self._fork(self.wgrad_stream, launch, *operands)
-
-    def _flush_deferred(self):
-        """Issue the deferred weight gradients on the auxiliary stream, behind everything the main stream has done so far."""
-        if not self._deferred:
-            return
-        deferred, self._deferred = self._deferred, []
-
-        def run():
-            for launch, _ in deferred:
-                launch()
-        ev = _hip_mod.ev_record(torch.cuda.current_stream(self.dev))    # before the tuning call: a launch tape reads as it always has
-        with _tuning("wgrad_lds_pad", self.defer_lds_pad, 0, on=bool(self.defer_lds_pad)):
-            self._fork(self.aux_stream, run, *(t for _, operands in deferred for t in operands), ev=ev)
-        self._aux_pending = True
-
-    def join_aux(self):
-        if getattr(self, "_aux_pending", False):
-            _hip_mod.stream_wait(torch.cuda.current_stream(self.dev), self.aux_stream)
-            self._aux_pending = False
 
     # ---- weights in / out (Keras layouts at this boundary) --------------------------------------
     def set_weights(self, weights, strict=True):
@@ -791,13 +757,15 @@ class MaskRCNNEngine(object):
     #  forward
     # =========================================================================================
     def _trunk_fwd(self, images, train):
-        """resnet_graph + FPN (model.py:175-210, 2005-2026).  Returns pyramid [P2..P6] and the tape."""
+        """resnet_graph + FPN (model.py:175-210, 2005-2026).  Returns the pyramid [P2..P6], its 16-bit twin (None unless the FPN
+        smoothing ran in 16 bits), the 16-bit P2..P5 for the ROI heads' 16-bit ROIAlign (configs[4]; None: float32 gathers) and
+        the tape."""
         tape = {}
         c1 = self.op("conv1")
         x, tape["conv1"] = c1.forward(images, ACT_RELU, train=train)
         if train:
             x, am = ops.maxpool3x3s2(x, want_argmax=True)
-            tape["pool"] = (am, tuple(tape["conv1"][2].shape))
+            tape["pool"] = (am, tuple(tape["conv1"].out.shape))
         else:
             x = ops.maxpool3x3s2(x)
         feats = []
@@ -824,7 +792,7 @@ class MaskRCNNEngine(object):
                     sc, c1c = x, None
                 x, cc = blk.c2c.forward(b, ACT_RELU, res=sc, res_mode=RES_SAME, train=train)
                 if train:
-                    tape[id(blk)] = (ca, cb, cc, c1c)
+                    tape[id(blk)] = BlockCtx(ca, cb, cc, c1c, False)
             if x is None:                           # stage output in float32 for the FPN lateral (x16 stays valid for the next block)
                 x = ops.cast_from_h16(x16)
             feats.append(x)
@@ -834,8 +802,6 @@ class MaskRCNNEngine(object):
         P3s, tape["fpn_c3p3"] = self.op("fpn_c3p3").forward(C3, res=P4s, res_mode=RES_UP2, train=train)
         P2s, tape["fpn_c2p2"] = self.op("fpn_c2p2").forward(C2, res=P3s, res_mode=RES_UP2, train=train)
         names = ("fpn_p2", "fpn_p3", "fpn_p4", "fpn_p5")
-        self._p16 = None
-        self._p16_heads = None                     # 16-bit P2..P5 of this pass for the ROI heads' 16-bit ROIAlign (configs[4])
         if all(self._h16_layer(n) for n in names):
             self._ensure_h16()
             outs, p16 = [], []
@@ -845,20 +811,18 @@ class MaskRCNNEngine(object):
                 outs.append(ops.cast_from_h16(y16))             # float32 copies for ROIAlign and P6
             P2, P3, P4, P5 = outs
             P6 = ops.subsample2(P5)
-            self._p16 = p16 + [ops.cast_to_h16(P6, self.head_dtype)]
-            if self.h16_roialign and all(t.shape[3] % 4 == 0 for t in p16):
-                self._p16_heads = list(p16)
-            return [P2, P3, P4, P5, P6], tape
+            p16h = p16 if self.h16_roialign and all(t.shape[3] % 4 == 0 for t in p16) else None
+            return [P2, P3, P4, P5, P6], p16 + [ops.cast_to_h16(P6, self.head_dtype)], p16h, tape
         res = self._forward_multi([self.op(n) for n in names], [P2s, P3s, P4s, P5s], train=train)
         (P2, P3, P4, P5) = [r[0] for r in res]
         for n, r in zip(names, res):
             tape[n] = r[1]
         P6 = ops.subsample2(P5)
-        return [P2, P3, P4, P5, P6], tape
+        return [P2, P3, P4, P5, P6], None, None, tape
 
-    def _rpn_fwd(self, pyramid, train):
+    def _rpn_fwd(self, pyramid, p16, train):
         """rpn_graph over the 5 levels with shared weights, outputs concatenated level-major
-        (model.py:916-957, 2040-2055)."""
+        (model.py:916-957, 2040-2055).  p16: the pyramid in 16 bits where _trunk_fwd has it, else None."""
         B = pyramid[0].shape[0]
         na = len(self.cfg.RPN_ANCHOR_RATIOS)
         A = sum(p.shape[1] * p.shape[2] * na for p in pyramid)
@@ -866,20 +830,19 @@ class MaskRCNNEngine(object):
         bbox = ops.empty((B, A, 4), torch.float32, self.dev)
         shared, cls, box = self.op("rpn_conv_shared"), self.op("rpn_class_raw"), self.op("rpn_bbox_pred")
         tape, off = [], 0
-        h16 = self._h16_layer("rpn_conv_shared") and self.multi_launch and len(pyramid) <= 5
-        if h16:
-            self._ensure_h16()
-            p16 = self._p16 if self._p16 is not None else [ops.cast_to_h16(p, self.head_dtype) for p in pyramid]
-            s16 = [self._h16_fwd(shared, x16, ACT_RELU, train) for x16 in p16]
-            ss = [ops.cast_from_h16(y) for y, _ in s16]          # the two small heads (6 / 12 columns) stay float32
         if self.multi_launch and len(pyramid) <= 5:
             # the levels are independent and P3..P6 are a handful of workgroups each: one launch per layer for all levels
-            if not h16:
-                if self.trunk_winograd and any(self._wino_trunk_ok(shared, p.shape) for p in pyramid):
-                    ss = [r[0] for r in self._forward_multi([shared] * len(pyramid), pyramid, ACT_RELU, train)]
-                else:
-                    ss = ops.conv2d_multi([dict(x=p, w=shared.w, bias=shared.b, act=ACT_RELU) for p in pyramid])
-            assert ss is not None                       # one weight tensor: the levels always share a launch shape
+            if self._h16_layer("rpn_conv_shared"):
+                self._ensure_h16()
+                s16, cs_ = zip(*[self._h16_fwd(shared, x16, ACT_RELU, train)
+                                 for x16 in (p16 if p16 is not None else [ops.cast_to_h16(p, self.head_dtype) for p in pyramid])])
+                ss = [ops.cast_from_h16(y) for y in s16]            # the two small heads (6 / 12 columns) stay float32
+            elif self.trunk_winograd and any(self._wino_trunk_ok(shared, p.shape) for p in pyramid):
+                ss, cs_ = zip(*self._forward_multi([shared] * len(pyramid), pyramid, ACT_RELU, train))
+            else:
+                ss = ops.conv2d_multi([dict(x=p, w=shared.w, bias=shared.b, act=ACT_RELU) for p in pyramid])
+                assert ss is not None                   # one weight tensor: the levels always share a launch shape
+                cs_ = [Ctx(p, None, s, ACT_RELU) if train else None for p, s in zip(pyramid, ss)]
             offs = []
             for p in pyramid:
                 offs.append(off)
@@ -888,27 +851,26 @@ class MaskRCNNEngine(object):
                                    out_strides=(A * 2, s.shape[2] * 2 * na, 2 * na)) for s, o in zip(ss, offs)])
             ops.conv2d_multi([dict(x=s, w=box.w, bias=box.b, padding="valid", out_ptr=bbox.data_ptr() + o * 4 * 4,
                                    out_strides=(A * 4, s.shape[2] * 4 * na, 4 * na)) for s, o in zip(ss, offs)])
-            for lvl, (p, s, o) in enumerate(zip(pyramid, ss, offs)):
-                cs = (s16[lvl][1] if h16 else (p, None, s, ACT_RELU)) if train else None
-                tape.append((cs, (s, None, None, ACT_NONE), o, p.shape[1], p.shape[2]))
-            self._p16 = None
+            for p, s, cs, o in zip(pyramid, ss, cs_, offs):
+                tape.append((cs, Ctx(s, None, None, ACT_NONE), o, p.shape[1], p.shape[2]))
             return logits, ops.softmax_rows(logits), bbox, tape
         for p in pyramid:
             s, cs = shared.forward(p, ACT_RELU, train=train)
             H, W = p.shape[1], p.shape[2]
             ops.conv2d_into(s, cls.w, cls.b, logits.data_ptr() + off * 2 * 4, A * 2, W * 2 * na, 2 * na, 1, "valid")
             ops.conv2d_into(s, box.w, box.b, bbox.data_ptr() + off * 4 * 4, A * 4, W * 4 * na, 4 * na, 1, "valid")
-            tape.append((cs, (s, None, None, ACT_NONE), off, H, W))
+            tape.append((cs, Ctx(s, None, None, ACT_NONE), off, H, W))
             off += H * W * na
         probs = ops.softmax_rows(logits)
         return logits, probs, bbox, tape
 
-    def _class_head_fwd(self, rois, fms, image_area, train):
-        """fpn_classifier_graph (model.py:986-1039)."""
+    def _class_head_fwd(self, rois, fms, p16h, image_area, train):
+        """fpn_classifier_graph (model.py:986-1039).  fms: P2..P5; p16h: the same in 16 bits for the 16-bit ROIAlign, or None."""
         cfg = self.cfg
         B, R = rois.shape[0], rois.shape[1]
         h16 = self._h16_layer("mrcnn_class_conv1") and self._h16_layer("mrcnn_class_conv2")
-        p16h = getattr(self, "_p16_heads", None) if h16 else None
+        if not h16:
+            p16h = None
         if p16h is not None:                       # 16-bit pyramid -> 16-bit pooled features: no float32 gather, no cast pass
             x16 = ops.roialign_h16(rois, p16h, cfg.POOL_SIZE, image_area).view(B * R, cfg.POOL_SIZE, cfg.POOL_SIZE, -1)
         else:
@@ -930,11 +892,10 @@ class MaskRCNNEngine(object):
         probs = ops.softmax_rows(logits)
         return logits, probs, bb.view(B, R, cfg.NUM_CLASSES, 4), (c1, c2, c3, c4)
 
-    def _mask_head_fwd(self, rois, fms, image_area, train):
-        """build_fpn_mask_graph (model.py:1042-1091)."""
+    def _mask_head_fwd(self, rois, fms, p16h, image_area, train):
+        """build_fpn_mask_graph (model.py:1042-1091).  fms, p16h: as for _class_head_fwd."""
         cfg = self.cfg
         B, R = rois.shape[0], rois.shape[1]
-        p16h = getattr(self, "_p16_heads", None) if self.head_dtype is not None else None
         if p16h is not None:
             x = None
             x16 = ops.roialign_h16(rois, p16h, cfg.MASK_POOL_SIZE, image_area).view(B * R, cfg.MASK_POOL_SIZE, cfg.MASK_POOL_SIZE, -1)
@@ -942,22 +903,11 @@ class MaskRCNNEngine(object):
             pooled = ops.roialign(rois, fms, cfg.MASK_POOL_SIZE, image_area)
             x = pooled.view(B * R, cfg.MASK_POOL_SIZE, cfg.MASK_POOL_SIZE, -1)
         ctxs = []
-        if self.head_dtype is None and self.winograd_split and x.shape[0] >= 512 and \
-                all(self._wino_ok(self.op("mrcnn_mask_conv%d" % i), (x.shape[0] // 2,) + tuple(x.shape[1:3]) + (self.op("mrcnn_mask_conv%d" % i).wshape[2],))
-                    for i in range(1, 5)):
-            x, ctxs = self._mask_convs_fwd_split(x, train)
-        elif self.head_dtype is None:
+        if self.head_dtype is None:
             for i in range(1, 5):
                 op = self.op("mrcnn_mask_conv%d" % i)
                 if self._wino_ok(op, x.shape):
-                    out = ops.empty(tuple(x.shape[:3]) + (op.wshape[3],), torch.float32, self.dev)
-                    z = ops.empty_like(out) if (train and op.bn) else None
-                    # training keeps the input transform: the layer's weight gradient contracts it with the transformed dz
-                    V = ops.empty((ops.winograd_v_floats(tuple(x.shape)),), torch.float32, self.dev) if (train and self.winograd_wgrad) else None
-                    if V is not None:
-                        self._wino_V[op.name] = [(V, 0, x.shape[0])]
-                    ops.conv2d_winograd(x, self._wino_U(op, 0, x.shape, train, self.infer_mask_tile), op.b, op.scale, op.shift, ACT_RELU, out=out, z_out=z, keep_v=V)
-                    x, c = out, ((x, z, out, ACT_RELU) if train else None)
+                    x, c = self._wino_fwd(op, x, ACT_RELU, train, self.infer_mask_tile)
                 else:
                     x, c = op.forward(x, ACT_RELU, train=train)
                 ctxs.append(c)
@@ -965,68 +915,24 @@ class MaskRCNNEngine(object):
             self._ensure_h16()
             h = x16 if p16h is not None else ops.cast_to_h16(x, self.head_dtype)
             for i in range(1, 5):
-                op = self.op("mrcnn_mask_conv%d" % i)
-                z = ops.empty(tuple(h.shape[:3]) + (op.wshape[3],), self.head_dtype, self.dev) if (train and op.bn) else None
-                y = ops.conv2d_h16(h, self._h16[op.name][0], op.wshape, op.b, op.scale, op.shift, 1, "same", ACT_RELU, z_out=z)
-                ctxs.append((h, z, y, ACT_RELU) if train else None)
-                h = y
+                h, c = self._h16_fwd(self.op("mrcnn_mask_conv%d" % i), h, ACT_RELU, train)
+                ctxs.append(c)
             dc, mop = self.op("mrcnn_mask_deconv"), self.op("mrcnn_mask")
             Cd = dc.wshape[3] // 4
             C_ = mop.wshape[3]
             if Cd % 256 == 0 and C_ <= 16:             # deconvolution + mask 1x1 conv + sigmoid on the 16-bit tensors too
                 up = ops.deconv2x2_h16(h, self._h16[dc.name][0], dc.b, Cd, ACT_RELU)
                 m = ops.mask_out_fwd_h16(up, mop.w.view(mop.wshape[2], C_), mop.b)
-                ctxs.append((h, None, up, ACT_RELU) if train else None)
-                ctxs.append((up, None, m, ACT_SIGMOID) if train else None)
+                ctxs.append(Ctx(h, None, up, ACT_RELU, H16) if train else None)
+                ctxs.append(Ctx(up, None, m, ACT_SIGMOID, H16) if train else None)
                 return m.view(B, R, m.shape[1], m.shape[2], m.shape[3]), ctxs
             x = ops.cast_from_h16(h)
         dc = self.op("mrcnn_mask_deconv")
         up = ops.deconv2x2(x, dc.w.view(dc.wshape[2], dc.wshape[3]), dc.b, ACT_RELU)
         m, cm = self.op("mrcnn_mask").forward(up, ACT_SIGMOID, train=train)
-        ctxs.append((x, None, up, ACT_RELU) if train else None)
+        ctxs.append(Ctx(x, None, up, ACT_RELU) if train else None)
         ctxs.append(cm)
         return m.view(B, R, m.shape[1], m.shape[2], m.shape[3]), ctxs
-
-    def _mask_convs_fwd_split(self, x, train):
-        """The four Winograd layers of the mask head on the two halves of the ROI rows, one half per stream (main and the
-        weight-gradient stream, idle during the forward pass) and the second half one transform behind the first: a layer is
-        a memory pass, a matrix-core pass and a memory pass in a row, so two chains that are out of phase keep both busy.
-        Activations / z are whole tensors (the backward pass and the transposed convolution see one batch); the input transforms
-        kept for the weight gradients are per half."""
-        main, side = torch.cuda.current_stream(self.dev), self.wgrad_stream
-        N = x.shape[0]
-        cut = (N // 2 + 3) // 4 * 4
-        halves = ((0, cut, main), (cut, N, side))
-        ops_ = [self.op("mrcnn_mask_conv%d" % i) for i in range(1, 5)]
-        hshape = lambda op, a, b: (b - a,) + tuple(x.shape[1:3]) + (op.wshape[2],)
-        Us = [[self._wino_U(op, 0, hshape(op, a, b), train, self.infer_mask_tile) for a, b, _ in halves] for op in ops_]   # weight transforms on the main stream, before the fork
-        outs, zs, ctxs = [], [], []
-        cur = x
-        for op in ops_:
-            out = ops.empty(tuple(x.shape[:3]) + (op.wshape[3],), torch.float32, self.dev)
-            z = ops.empty_like(out) if (train and op.bn) else None
-            outs.append(out); zs.append(z)
-            ctxs.append((cur, z, out, ACT_RELU) if train else None)
-            cur = out
-            if train and self.winograd_wgrad:
-                self._wino_V[op.name] = [(ops.empty((ops.winograd_v_floats(hshape(op, a, b)),), torch.float32, self.dev), a, b)
-                                         for a, b, _ in halves]
-        ev0 = _hip_mod.ev_record(main)                                   # x and the U's are ready
-        lag = []
-        for hi, (a, b, st) in enumerate(halves):
-            with torch.cuda.stream(st):
-                if st is not main:
-                    _hip_mod.ev_wait(st, ev0)
-                    _hip_mod.ev_wait(st, lag[0])                         # one input transform behind the first half
-                inp = x[a:b]
-                for li, op in enumerate(ops_):
-                    V = self._wino_V[op.name][hi][0] if (train and self.winograd_wgrad) else None
-                    mark = (lambda: lag.append(_hip_mod.ev_record(main))) if (st is main and li == 0) else None
-                    ops.conv2d_winograd(inp, Us[li][hi], op.b, op.scale, op.shift, ACT_RELU, out=outs[li][a:b],
-                                        z_out=None if zs[li] is None else zs[li][a:b], keep_v=V, after_input=mark)
-                    inp = outs[li][a:b]
-        _hip_mod.stream_wait(main, side)
-        return outs[-1], ctxs
 
     def infer(self, images, windows_norm):
         """Inference graph (model.py:2133-2159).  images [B,H,W,3] float32 device tensor (molded);
@@ -1037,18 +943,18 @@ class MaskRCNNEngine(object):
         # layers of a few hundred pixels (res4 / res5 / P5 / P6 at batch 1) take the 16 x 16-tile single-launch kernel while the
         # inference trunk is issued: detect graph 3.01 -> 2.73 ms (ResNet-101), 2.35 -> 2.23 (ResNet-50).  Training keeps its kernels.
         with _tuning("sk16", 1 if self.sk16_infer else 0, 0):
-            pyr, _ = self._trunk_fwd(images, False)
-            _, rpn_probs, rpn_bbox, _ = self._rpn_fwd(pyr, False)
+            pyr, p16, p16h, _ = self._trunk_fwd(images, False)
+            _, rpn_probs, rpn_bbox, _ = self._rpn_fwd(pyr, p16, False)
         anchors = self.anchors((H, W, images.shape[3]))
         rois = ops.proposals(rpn_probs, rpn_bbox, anchors, cfg.PRE_NMS_LIMIT, cfg.POST_NMS_ROIS_INFERENCE,
                              cfg.RPN_NMS_THRESHOLD, np.asarray(cfg.RPN_BBOX_STD_DEV, np.float32))
-        _, probs, bbox, _ = self._class_head_fwd(rois, pyr[:4], area, False)
+        _, probs, bbox, _ = self._class_head_fwd(rois, pyr[:4], p16h, area, False)
         det = ops.detections(rois, probs, bbox, windows_norm, cfg.DETECTION_MAX_INSTANCES,
                              cfg.DETECTION_MIN_CONFIDENCE, cfg.DETECTION_NMS_THRESHOLD,
                              np.asarray(cfg.BBOX_STD_DEV, np.float32))
         det_boxes = ops.empty((B, cfg.DETECTION_MAX_INSTANCES, 4), torch.float32, self.dev)
         ops.copy2d(det_boxes.data_ptr(), 16, det.data_ptr(), 24, 16, B * cfg.DETECTION_MAX_INSTANCES)
-        masks, _ = self._mask_head_fwd(det_boxes, pyr[:4], area, False)
+        masks, _ = self._mask_head_fwd(det_boxes, pyr[:4], p16h, area, False)
         return {"detections": det, "mrcnn_class": probs, "mrcnn_bbox": bbox, "mrcnn_mask": masks, "rpn_rois": rois,
                 "rpn_class": rpn_probs, "rpn_bbox": rpn_bbox, "pyramid": pyr}
 
@@ -1129,8 +1035,8 @@ class MaskRCNNEngine(object):
         prep_ev = _hip_mod.ev_record(self.wgrad_stream)
         if h16_ev is not None and self.h16_wide:
             _hip_mod.ev_wait(main, h16_ev)
-        pyr, tape = self._trunk_fwd(images, True)
-        rpn_logits, rpn_probs, rpn_bbox, rpn_tape = self._rpn_fwd(pyr, True)
+        pyr, p16, p16h, tape = self._trunk_fwd(images, True)
+        rpn_logits, rpn_probs, rpn_bbox, rpn_tape = self._rpn_fwd(pyr, p16, True)
         anchors = self.anchors((H, W, images.shape[3]))
         rpn_rois = ops.proposals(rpn_probs, rpn_bbox, anchors, cfg.PRE_NMS_LIMIT, cfg.POST_NMS_ROIS_TRAINING,
                                  cfg.RPN_NMS_THRESHOLD, np.asarray(cfg.RPN_BBOX_STD_DEV, np.float32))
@@ -1157,8 +1063,8 @@ class MaskRCNNEngine(object):
             rois_m = rois
         if self.head_dtype is not None:
             _hip_mod.ev_wait(main, prep_ev)                    # the mask head reads the 16-bit weight images prepared on the side stream
-        logits, probs, mbbox, ctx_cls = self._fork(aux, lambda: self._class_head_fwd(rois, pyr[:4], area, True), rois)
-        mmask, ctx_mask = self._mask_head_fwd(rois_m, pyr[:4], area, True)
+        logits, probs, mbbox, ctx_cls = self._fork(aux, lambda: self._class_head_fwd(rois, pyr[:4], p16h, area, True), rois)
+        mmask, ctx_mask = self._mask_head_fwd(rois_m, pyr[:4], p16h, area, True)
         _hip_mod.stream_wait(main, aux)
         for t in (logits, probs, mbbox):
             t.record_stream(main)
@@ -1189,15 +1095,10 @@ class MaskRCNNEngine(object):
         dP6, ev_aux = self._fork(aux, heads_bwd, d_logits, d_mbbox, d_rpn_logits, d_rpn_bbox)
         self._mask_head_bwd(d_mmask, ctx_mask, rois_m, dP, area, ev_aux)
         _hip_mod.stream_wait(main, aux)
-        deferred = bool(self._deferred)
-        self._flush_deferred()
-        if self.grad_ready and not deferred:     # ~2/3 of the gradient bytes (FC1 alone is 51 MB) are final here,
+        if self.grad_ready:                      # ~2/3 of the gradient bytes (FC1 alone is 51 MB) are final here,
             self.join_wgrad()
             self.grad_ready(*self.grad_ranges["heads"])     # with the whole FPN/backbone backward left to hide them
         self._trunk_bwd(dP, dP6, tape)
-        self.join_aux()
-        if self.grad_ready and deferred:         # the mask head's kernels became final beside the backbone's backward pass
-            self.grad_ready(*self.grad_ranges["heads"])
         if keep_outputs:
             self.last = {"rpn_class_logits": rpn_logits, "rpn_class": rpn_probs, "rpn_bbox": rpn_bbox,
                          "rpn_rois": rpn_rois, "rois": rois, "target_class_ids": tcls, "target_bbox": tbbox,
@@ -1224,21 +1125,22 @@ class MaskRCNNEngine(object):
         cfg = self.cfg
         c1, c2, c3, c4, cdec, cm = ctxs
         mop, dc = self.op("mrcnn_mask"), self.op("mrcnn_mask_deconv")
-        x_in, _, up, _ = cdec
-        C_ = cm[2].shape[-1]
+        x_in, up = cdec.x, cdec.out
+        C_ = cm.out.shape[-1]
         S = self._S()
+        wgrad = lambda launch, *operands: self._fork(self.wgrad_stream, launch, *operands)
         d16 = None
-        if up.dtype != torch.float32:
+        if cdec.path == H16:
             # output stage and deconvolution on the 16-bit tensors: dzg comes out scaled, in 16 bits
-            dzg = ops.mask_out_bwd_h16(g, cm[2], up, mop.w.view(mop.wshape[2], mop.wshape[3]),
+            dzg = ops.mask_out_bwd_h16(g, cm.out, up, mop.w.view(mop.wshape[2], mop.wshape[3]),
                                        mop.dw.view(mop.wshape[2], mop.wshape[3]), mop.db, dc.db, S)
-            self._mask_wgrad(partial(ops.conv2d_wgrad_h16, x_in, dzg, dc.wshape, 1, "same", dw=dc.dw, multiplier=1.0 / S), x_in, dzg)
+            wgrad(partial(ops.conv2d_wgrad_h16, x_in, dzg, dc.wshape, 1, "same", dw=dc.dw, multiplier=1.0 / S), x_in, dzg)
             d16 = ops.conv2d_h16(dzg, self._h16[dc.name][1], (1, 1, dc.wshape[3], dc.wshape[2]), None, None, None, 1, "valid",
                                  ACT_NONE)
         elif self.fused_mask_out_bwd and C_ <= 16 and up.shape[-1] % 64 == 0 and up.shape[-1] <= 1024:
             # one pass over `up`: sigmoid', 1x1 conv wgrad/dgrad/bias, ReLU mask, deconv bias, GEMM regrouping
             # (dw accumulates: the flat gradient buffer was zeroed at the start of the step)
-            dzg = ops.mask_out_bwd(g, cm[2], up, mop.w.view(mop.wshape[2], mop.wshape[3]),
+            dzg = ops.mask_out_bwd(g, cm.out, up, mop.w.view(mop.wshape[2], mop.wshape[3]),
                                    mop.dw.view(mop.wshape[2], mop.wshape[3]), mop.db, dc.db)
         else:
             dz, _ = mop.epilogue_bwd(g, cm)
@@ -1249,28 +1151,24 @@ class MaskRCNNEngine(object):
             ops.epilogue_bwd(d_up, up, None, None, None, None, None, dzu, None, None, dc.db, ACT_RELU)
             dzg = ops.pixel_unshuffle2(dzu)                             # [M,14,14,1024]
         if d16 is None:
-            self._mask_wgrad(partial(ops.conv2d_wgrad, x_in, dzg, dc.wshape, 1, "valid", dw=dc.dw), x_in, dzg)
-        if self.head_dtype is None:
+            wgrad(partial(ops.conv2d_wgrad, x_in, dzg, dc.wshape, 1, "valid", dw=dc.dw), x_in, dzg)
+        chain = [(self.op("mrcnn_mask_conv%d" % i), c) for i, c in ((4, c4), (3, c3), (2, c2), (1, c1))]
+        if c4.path != H16:
             # every data-gradient convolution applies the epilogue backward of the layer below in its own epilogue
             # (mrcnn_conv2d_dgrad_ep): the gradient w.r.t. the activated output is never written or re-read
-            chain = [(self.op("mrcnn_mask_conv%d" % i), c) for i, c in ((4, c4), (3, c3), (2, c2), (1, c1))]
             dz = self._dgrad_ep(dzg, dc.wt, "valid", chain[0][0], chain[0][1])
             for k, (op, c) in enumerate(chain):
-                Vs = self._wino_V.pop(op.name, None)
-                if Vs is not None and self.winograd_wgrad:
-                    for vi, (V, a, b) in enumerate(Vs):                  # one call per forward chain (whole batch, or two halves)
-                        self._mask_wgrad(partial(ops.conv2d_wgrad_winograd, V, (b - a,) + tuple(c[0].shape[1:]), dz[a:b], op.dw,
-                                                 accumulate=vi > 0), V, dz)
+                if c.V is not None:
+                    wgrad(partial(ops.conv2d_wgrad_winograd, c.V, tuple(c.x.shape), dz, op.dw), c.V, dz)
                 else:
-                    self._mask_wgrad(partial(ops.conv2d_wgrad, c[0], dz, op.wshape, op.stride, op.padding, dw=op.dw), c[0], dz)
-                wino = self._wino_ok(op, c[0].shape)
+                    wgrad(partial(ops.conv2d_wgrad, c.x, dz, op.wshape, op.stride, op.padding, dw=op.dw), c.x, dz)
+                wino = c.path == WINO
                 if k + 1 < len(chain):
                     below, bctx = chain[k + 1]
                     if wino and self.fused_dgrad_epilogue and below.bn is not None:
-                        _, bz, bout, bact = bctx
-                        dz = ops.conv2d_dgrad_ep_winograd(dz, self._wino_U(op, 1, dz.shape), bout if bact != ACT_NONE else None, bz, below.scale,
-                                                          below.mean, below.rstd, below.dgamma, below.dbeta, below.db, bact,
-                                                          fwd_shift=below.shift)
+                        dz = ops.conv2d_dgrad_ep_winograd(dz, self._wino_U(op, 1, dz.shape), bctx.out if bctx.act != ACT_NONE else None,
+                                                          bctx.z, below.scale, below.mean, below.rstd, below.dgamma, below.dbeta,
+                                                          below.db, bctx.act, fwd_shift=below.shift)
                     elif wino:
                         dz = below.epilogue_bwd(ops.conv2d_winograd(dz, self._wino_U(op, 1, dz.shape)), bctx)[0]
                     else:
@@ -1283,17 +1181,12 @@ class MaskRCNNEngine(object):
             if d16 is None:
                 d = ops.conv2d(dzg, dc.wt, stride=1, padding="valid")
                 d16 = ops.cast_to_h16(d, self.head_dtype, multiplier=S)
-            for i, c in ((4, c4), (3, c3), (2, c2), (1, c1)):
-                op = self.op("mrcnn_mask_conv%d" % i)
-                kh, kw, cin, cout = op.wshape
-                xin, z, y, _ = c
-                dz = ops.epilogue_bwd_h16(d16, y, z, op.scale, op.mean, op.rstd, op.dgamma, op.dbeta, op.db, ACT_RELU, 1.0 / S)
-                self._mask_wgrad(partial(ops.conv2d_wgrad_h16, xin, dz, op.wshape, 1, "same", dw=op.dw, multiplier=1.0 / S), xin, dz)
-                d16 = ops.conv2d_h16(dz, self._h16[op.name][1], (kh, kw, cout, cin), None, None, None, 1, op.dgrad_padding, ACT_NONE)
+            for op, c in chain:
+                d16 = self._h16_bwd(op, d16, c, S)
             d = None if self.h16_roialign else ops.cast_from_h16(d16, 1.0 / S)
         B, R = rois.shape[0], rois.shape[1]
         _hip_mod.ev_wait(torch.cuda.current_stream(self.dev), before_adjoint)
-        if self.head_dtype is not None and d is None:     # the 16-bit gradient goes straight into the float32 pyramid gradients
+        if d is None:                           # the 16-bit gradient goes straight into the float32 pyramid gradients
             ops.roialign_bwd_h16(rois, d16.view(B, R, cfg.MASK_POOL_SIZE, cfg.MASK_POOL_SIZE, -1), dP, cfg.MASK_POOL_SIZE, area, 1.0 / S)
             return
         # scatter form here: the gather form measured 2 ms slower on the positive rows (14x14 samples of ~150 overlapping
@@ -1303,7 +1196,7 @@ class MaskRCNNEngine(object):
     def _dgrad_ep(self, dz, wt, padding, below, below_ctx):
         """dz of layer `below` from the dz of the layer above: data-gradient convolution with `wt` fused with
         `below`'s epilogue backward when the layer is large enough for that kernel, the two separate calls otherwise."""
-        _, z, out, act = below_ctx
+        z, out, act = below_ctx.z, below_ctx.out, below_ctx.act
         if self.fused_dgrad_epilogue and below.bn is not None:
             got = ops.conv2d_dgrad_ep(dz, wt, padding, out if act != ACT_NONE else None, z, below.scale, below.mean, below.rstd,
                                       below.dgamma, below.dbeta, below.db, act)
@@ -1326,7 +1219,7 @@ class MaskRCNNEngine(object):
         bo.wgrad(dz, c4)
         bo.dgrad(dz, c4, out=d_h2, accumulate=True)
         op2, op1 = self.op("mrcnn_class_conv2"), self.op("mrcnn_class_conv1")
-        if c2[0].dtype != torch.float32:                        # the two FC layers ran in 16 bits
+        if c2.path == H16:                                      # the two FC layers ran in 16 bits
             S = self._S()
             d_h1 = self._h16_bwd(op2, ops.cast_to_h16(d_h2, self.head_dtype, multiplier=S), c2, S)
             d_pool = ops.cast_from_h16(self._h16_bwd(op1, d_h1, c1, S), 1.0 / S)
@@ -1364,7 +1257,7 @@ class MaskRCNNEngine(object):
                 heads.append(chead)
             d_s = self._dgrad_multi([cls] * n, dzl, heads)
             self._dgrad_multi([box] * n, dzb, heads, outs=d_s, accumulate=True)
-            if self._h16_layer("rpn_conv_shared") and rpn_tape[0][0][0].dtype != torch.float32:
+            if rpn_tape[0][0].path == H16:
                 S = self._S()
                 for lvl, (cs, chead, off, H, W) in enumerate(rpn_tape):
                     dx16 = self._h16_bwd(shared, ops.cast_to_h16(d_s[lvl], self.head_dtype, multiplier=S), cs, S, accumulate_w=lvl > 0)
@@ -1374,13 +1267,13 @@ class MaskRCNNEngine(object):
                         dP6 = ops.cast_from_h16(dx16, 1.0 / S)
                 return dP6
             dzs, ctxs = [], []
-            wino = any((shared.name, tuple(t[0][0].shape)) in self._wino_V for t in rpn_tape)
+            wino = any(t[0].V is not None for t in rpn_tape)
             for lvl, (cs, chead, off, H, W) in enumerate(rpn_tape):
                 dz, _ = shared.epilogue_bwd(d_s[lvl], cs)
                 if not wino:
                     shared.wgrad(dz, cs, accumulate=lvl > 0)
                 dzs.append(dz); ctxs.append(cs)
-            if wino:                                        # some level's forward took the Winograd path (trunk_winograd)
+            if wino:                                        # some level's forward kept its Winograd input transform (trunk_winograd)
                 return self._bwd_group([shared] * n, dzs, ctxs, outs=list(dP[:4]) + [None], accumulate=[True] * 4 + [False],
                                        wgrad_acc=[lvl > 0 for lvl in range(n)])[4]
             return self._dgrad_multi([shared] * n, dzs, ctxs, outs=list(dP[:4]) + [None], accumulate=[True] * 4 + [False])[4]
@@ -1409,7 +1302,7 @@ class MaskRCNNEngine(object):
         dP2, dP3, dP4, dP5 = dP
         ops.subsample2_bwd_acc(dP6, dP5)
         layers, dzs, cs = [], [], []
-        if tape["fpn_p5"][0].dtype != torch.float32:                 # smoothing convolutions ran in 16 bits
+        if tape["fpn_p5"].path == H16:                              # smoothing convolutions ran in 16 bits
             S = self._S()
             d16 = [self._h16_bwd(self.op(name), ops.cast_to_h16(g, self.head_dtype, multiplier=S), tape[name], S)
                    for name, g in (("fpn_p5", dP5), ("fpn_p4", dP4), ("fpn_p3", dP3), ("fpn_p2", dP2))]
@@ -1419,7 +1312,7 @@ class MaskRCNNEngine(object):
                 op, c = self.op(name), tape[name]
                 dz, _ = op.epilogue_bwd(g, c)
                 layers.append(op); dzs.append(dz); cs.append(c)
-            if any((op.name, tuple(c[0].shape)) in self._wino_V for op, c in zip(layers, cs)):
+            if any(c.V is not None for c in cs):
                 d5s, d4s, d3s, d2s = self._bwd_group(layers, dzs, cs)
             else:
                 self.wgrad_group([op.wgrad_item(dz, c) for op, dz, c in zip(layers, dzs, cs)])
@@ -1444,7 +1337,7 @@ class MaskRCNNEngine(object):
             stage = self.stages[si]
             for bi in range(len(stage) - 1, -1, -1):
                 blk = stage[bi]
-                if tape[id(blk)][0] == "h16":
+                if tape[id(blk)].h16:
                     if d16 is None:
                         d16 = ops.cast_to_h16(d_out, self.head_dtype, multiplier=S)
                     d16 = self._block_bwd_h16(blk, d16, tape[id(blk)], S)
@@ -1460,12 +1353,11 @@ class MaskRCNNEngine(object):
                 # convolution) rides on this block's last data gradient when that is a split-K layer
                 below = None
                 if bi > 0:
-                    below = (stage[bi - 1], tape[id(stage[bi - 1])][2])
+                    below = stage[bi - 1]
                 elif si > 0:
-                    prev = self.stages[si - 1][-1]
-                    below = (prev, tape[id(prev)][2])
-                if below is not None and tape[id(below[0])][0] == "h16":
-                    below = None                        # the block below runs in 16 bits: it differentiates its own output stage
+                    below = self.stages[si - 1][-1]
+                if below is not None:                   # (a block below that ran in 16 bits differentiates its own output stage)
+                    below = None if tape[id(below)].h16 else (below, tape[id(below)].c)
                 d_out = self._block_bwd(blk, d_out, tape[id(blk)], acc_buf, below)
             if self.grad_ready:
                 self.join_wgrad()
@@ -1487,7 +1379,7 @@ class MaskRCNNEngine(object):
         """Backward of one bottleneck block.  ``d_out``: gradient w.r.t. the block output, or the pair (dz of the 2c
         convolution, gradient after the output ReLU) when the block after it already applied this block's output
         epilogue backward (see ``below``).  Returns the gradient w.r.t. the block input, or such a pair for ``below``."""
-        ca, cb, cc, c1c = ctxs
+        ca, cb, cc, c1c = ctxs.a, ctxs.b, ctxs.c, ctxs.shortcut
         if isinstance(d_out, tuple):
             dzc, dy = d_out
         else:
@@ -1520,7 +1412,7 @@ class MaskRCNNEngine(object):
             return None
         pblk, pcc = below
         op = pblk.c2c
-        _, z, out, act = pcc
+        z, out, act = pcc.z, pcc.out, pcc.act
         if op.bn is None or act != ACT_RELU:
             return None
         dy_below = ops.empty_like(acc)

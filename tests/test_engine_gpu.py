@@ -505,33 +505,6 @@ def test_fused_mask_output_backward_equals_unfused(dev):
     assert np.abs(grads[0] - grads[1]).max() <= 2e-5 * scale
 
 
-@pytest.mark.parametrize("head_dtype", [None, "float16"])
-def test_deferred_mask_wgrad_equals_inline(dev, head_dtype):
-    """engine.defer_mask_wgrad (an A/B switch, off by default) only moves the mask head's weight-gradient launches (to the auxiliary stream, beside the
-    backbone's backward pass): same kernels on the same operands, so losses and the whole gradient buffer agree up to the
-    float atomics of the other kernels.  ResNet-50 256x256 so that the large LDS-DMA weight-gradient kernel (and its
-    occupancy cap) is the one that runs."""
-    from caesar_mrcnn_amd.model import MaskRCNN
-    cfg = _full_cfg("resnet50", 256)
-    w = _weights(cfg, 47)
-    inputs, keys = _train_inputs(cfg, 2, 49)
-    res = []
-    for defer in (True, False):
-        model = MaskRCNN("training", cfg, "/tmp/mrcnn_logs", device=dev, weights=w)
-        eng = model.engine
-        eng.defer_mask_wgrad = defer
-        eng.sparse_mask_bwd = False
-        if head_dtype:
-            eng.head_dtype = getattr(torch, head_dtype)
-        for _ in range(2):                                   # twice: the second step reuses the arena and every side stream
-            losses = model.train_on_batch(inputs, rand_keys=keys, apply=False)
-        torch.cuda.synchronize()
-        res.append((losses.cpu().numpy(), eng.grads.cpu().numpy().copy()))
-    np.testing.assert_allclose(res[0][0], res[1][0], rtol=1e-6)
-    scale = np.abs(res[1][1]).max()
-    assert np.abs(res[0][1] - res[1][1]).max() <= 2e-5 * scale and scale > 0
-
-
 def test_device_rpn_targets_in_training_step(dev):
     """A step fed with rpn_match / rpn_bbox = None (targets built on the GPU, only the used GT-mask planes
     uploaded) equals the step fed with the oracle's host-built targets for the same draw keys."""
@@ -590,24 +563,71 @@ def test_fused_dgrad_epilogue_equals_unfused(dev):
     assert np.abs(res[0][1] - res[1][1]).max() <= 2e-5 * scale and scale > 0
 
 
-def test_winograd_split_forward_equals_whole(dev):
-    """engine.winograd_split (the mask head's Winograd layers as two half-batch chains on two streams, off by default since the
-    mixed tiling) against the whole-batch chain: same losses, gradients equal up to the order of the float32 atomics and of the
-    two accumulating weight-gradient calls per layer.  ResNet-50 256x256, 2 images = 1024 ROI rows = two halves of 512."""
+def _tensors(obj):
+    """Every tensor in a nest of tuples (contexts included), lists and dicts."""
+    if torch.is_tensor(obj):
+        return [obj]
+    if isinstance(obj, dict):
+        obj = list(obj.values())
+    if isinstance(obj, (tuple, list)):
+        return [t for o in obj for t in _tensors(o)]
+    return []
+
+
+def _contexts(obj):
+    from caesar_mrcnn_amd.engine import Ctx
+    if isinstance(obj, Ctx):
+        return [obj]
+    if isinstance(obj, dict):
+        obj = list(obj.values())
+    if isinstance(obj, (tuple, list)):
+        return [c for o in obj for c in _contexts(o)]
+    return []
+
+
+def test_training_forward_without_backward_leaves_nothing_on_the_engine(dev):
+    """What a layer's forward leaves for its backward travels in the contexts the forward returns, never on the engine: a
+    training forward (trunk, RPN, mask head) whose backward never runs changes nothing about the next step -- same losses and
+    gradients as a fresh engine's, within the bound of the switch tests -- and no attribute of the engine is, or holds in a dict
+    or list, a tensor of the dropped contexts (the kept Winograd input transforms among them).  trunk_winograd_min_rows = 256 puts
+    P2 / P3 (2 x 32 x 32 and 2 x 16 x 16 pixels) on the Winograd path at this size."""
+    from caesar_mrcnn_amd import engine as E, ops
     from caesar_mrcnn_amd.model import MaskRCNN
-    cfg = _full_cfg("resnet50", 256)
-    w = _weights(cfg, 47)
-    inputs, keys = _train_inputs(cfg, 2, 49)
+    cfg = _small_cfg("custom", 128)
+    w = _weights(cfg, 19)
+    orphan, _ = _train_inputs(cfg, 2, 21)
+    inputs, keys = _train_inputs(cfg, 2, 23)
     res = []
-    for split in (True, False):
+    for with_orphan in (True, False):
         model = MaskRCNN("training", cfg, "/tmp/mrcnn_logs", device=dev, weights=w)
-        if not model.engine.winograd:
-            pytest.skip("MRCNN_WINOGRAD=0: nothing to split")
-        model.engine.winograd_split = split
-        model.engine.sparse_mask_bwd = False
+        eng = model.engine
+        eng.trunk_winograd_min_rows = 256
+        if with_orphan:
+            images = torch.tensor(orphan[0], dtype=torch.float32, device=dev)
+            rois = torch.tensor(np.random.default_rng(5).uniform(0, 1, (2, 16, 2)), dtype=torch.float32, device=dev)
+            rois = torch.cat([rois * 0.5, rois * 0.5 + 0.4], dim=2).contiguous()       # [y1, x1, y2, x2], y2 > y1 and x2 > x1
+            ops.set_arena(eng.arena)
+            eng.arena.begin()
+            try:
+                pyr, p16, p16h, tape = eng._trunk_fwd(images, True)
+                rpn_tape = eng._rpn_fwd(pyr, p16, True)[3]
+                ctx_mask = eng._mask_head_fwd(rois, pyr[:4], p16h, float(128 * 128), True)[1]
+            finally:
+                eng.arena.end()
+            ctxs = _contexts([tape, rpn_tape, ctx_mask])
+            assert any(c.path == E.WINO and c.V is not None for c in ctxs)
+            dropped = {t.data_ptr() for t in _tensors([tape, rpn_tape, ctx_mask])}
+            assert len(dropped) > 20
+            del pyr, p16, p16h, tape, rpn_tape, ctx_mask, ctxs
+
+            def held():
+                return [k for k, v in vars(eng).items() if any(t.data_ptr() in dropped for t in _tensors(v))]
+            assert held() == []
         losses = model.train_on_batch(inputs, rand_keys=keys, apply=False)
         torch.cuda.synchronize()
-        res.append((losses.cpu().numpy(), model.engine.grads.cpu().numpy().copy()))
+        if with_orphan:
+            assert held() == []
+        res.append((losses.cpu().numpy(), eng.grads.cpu().numpy().copy()))
     np.testing.assert_allclose(res[0][0], res[1][0], rtol=5e-6)
     scale = np.abs(res[1][1]).max()
     assert np.abs(res[0][1] - res[1][1]).max() <= 2e-5 * scale and scale > 0
