@@ -119,6 +119,8 @@ _SIGNATURES = {
     "mrcnn_augment_warp_mask_bits": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P]),
     "mrcnn_tile_adjacency": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, C.c_int, _P, _P]),
     "mrcnn_tile_union": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "mrcnn_source_params": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int, _P, _P, _P, C.c_int64, C.c_double,
+                                      C.c_int, _P, _P]),
     "mrcnn_mask_planes_pack": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mrcnn_mask_pair_stats": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "mrcnn_mask_union": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),

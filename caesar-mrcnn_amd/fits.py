@@ -155,6 +155,28 @@ def zscale_limits(values, contrast=0.25, nsamples=1000, max_reject=0.5, min_npix
     return vmin, vmax
 
 
+def sigma_clipped_stats(values, sigma=3.0, maxiters=5):
+    """astropy.stats.sigma_clipped_stats with its defaults (cenfunc median, stdfunc std with ddof 0) [3P; parity unpinned:
+    astropy cannot run here -- the algorithm is the documented one].  Non-finite values are dropped; every iteration takes
+    c = median and s = std of what is kept and keeps c - sigma s <= x <= c + sigma s; it stops when an iteration removed nothing
+    or after `maxiters`.  Works on the values as float64 (the median of an even count is the mean of the two middle values).
+    Returns (mean, median, std, kept count, iterations run) of what is left -- NaNs when nothing is."""
+    x = np.asarray(values).ravel()
+    x = x[np.isfinite(x)].astype(np.float64)
+    iters = 0
+    while iters < maxiters and x.size:
+        c, s = np.median(x), np.std(x)
+        keep = (x >= c - sigma * s) & (x <= c + sigma * s)
+        iters += 1
+        removed = x.size - int(keep.sum())
+        x = x[keep]
+        if not removed:
+            break
+    if not x.size:
+        return float("nan"), float("nan"), float("nan"), 0, iters
+    return float(np.mean(x)), float(np.median(x)), float(np.std(x)), int(x.size), iters
+
+
 def stretch_img(data, contrast=0.25):
     """ZScaleInterval(contrast)(data): map [vmin, vmax] to [0, 1] with clipping (utils.py:1166-1172)."""
     vmin, vmax = zscale_limits(data, contrast)
@@ -332,3 +354,99 @@ def generate_tiles(img_xmin, img_xmax, img_ymin, img_ymax, tileSizeX, tileSizeY,
         return out
     xs, ys = spans(Nx, tileSizeX, stepX), spans(Ny, tileSizeY, stepY)
     return [(img_xmin + x0, img_xmin + x1, img_ymin + y0, img_ymin + y1) for (y0, y1) in ys for (x0, x1) in xs]
+
+
+# ---- world coordinates -------------------------------------------------------------------------------------
+class SimpleWCS(object):
+    """astropy.wcs.WCS(header).all_pix2world for the celestial pair of axes, on the host in float64 [3P; parity unpinned:
+    astropy cannot run here -- the arithmetic is FITS WCS Paper I (linear part) and Paper II (zenithal deprojection, spherical
+    rotation)].  Linear part: CRPIXi, then CDi_j, or PCi_j with CDELTi, or CROTA2 with CDELTi, then CRVALi.  Projections: -TAN
+    and -SIN without PV terms; a pair of axes without a projection code is purely linear.  ``valid`` is False -- and the caller
+    writes -999 -- for any other projection code or a header without CRVAL / CDELT (CDi_j) of both axes.  ``naxis`` as the
+    reference uses it (sfinder.py:1079-1095): the number of axes of the header."""
+
+    def __init__(self, header):
+        h = header or {}
+        self.naxis = int(h.get("WCSAXES", h.get("NAXIS", 2)))
+        self.lng, self.lat, self.proj = 0, 1, ""
+        self.valid, self.why = True, ""
+        ctype = [str(h.get("CTYPE%d" % (i + 1), "")).upper() for i in range(max(self.naxis, 2))]
+        lng = [i for i, c in enumerate(ctype) if c[:4] in ("RA--", "GLON", "ELON") or c[1:4] == "LON"]
+        lat = [i for i, c in enumerate(ctype) if c[:4] in ("DEC-", "GLAT", "ELAT") or c[1:4] == "LAT"]
+        if lng and lat:
+            self.lng, self.lat = lng[0], lat[0]
+            codes = [c[5:8].rstrip("-") if len(c) > 5 and c[4] == "-" else "" for c in (ctype[self.lng], ctype[self.lat])]
+            self.proj = codes[0] if codes[0] == codes[1] else "?"
+        i, j = self.lng + 1, self.lat + 1
+        self.h = h
+        has_cd = any(("CD%d_%d" % (a, b)) in h for a in (i, j) for b in (i, j))
+        if not all(("CRVAL%d" % a) in h for a in (i, j)) or not (has_cd or all(("CDELT%d" % a) in h for a in (i, j))):
+            self.valid, self.why = False, "no CRVAL / CDELT for the celestial axes"
+        elif self.proj not in ("", "TAN", "SIN"):
+            self.valid, self.why = False, "projection %r not supported" % self.proj
+        elif self.proj == "SIN" and any(float(h.get("PV%d_%d" % (j, m), 0.0)) != 0.0 for m in (1, 2)):
+            self.valid, self.why = False, "SIN projection with PV terms not supported"
+        if not self.valid:
+            return
+        self.crpix = (float(h.get("CRPIX%d" % i, 0.0)), float(h.get("CRPIX%d" % j, 0.0)))
+        self.crval = (float(h["CRVAL%d" % i]), float(h["CRVAL%d" % j]))
+        if has_cd:
+            self.m = [[float(h.get("CD%d_%d" % (a, b), 0.0)) for b in (i, j)] for a in (i, j)]
+        else:
+            cd = (float(h["CDELT%d" % i]), float(h["CDELT%d" % j]))
+            if any(("PC%d_%d" % (a, b)) in h for a in (i, j) for b in (i, j)):
+                pc = [[float(h.get("PC%d_%d" % (a, b), 1.0 if a == b else 0.0)) for b in (i, j)] for a in (i, j)]
+            else:
+                rho = np.deg2rad(float(h.get("CROTA%d" % j, 0.0)))        # the AIPS convention: rotation on the latitude axis
+                c_, s_ = np.cos(rho), np.sin(rho)
+                pc = [[c_, -s_ * cd[1] / cd[0]], [s_ * cd[0] / cd[1], c_]] if rho != 0.0 else [[1.0, 0.0], [0.0, 1.0]]
+            self.m = [[cd[0] * pc[0][0], cd[0] * pc[0][1]], [cd[1] * pc[1][0], cd[1] * pc[1][1]]]
+        self.lonpole = float(h.get("LONPOLE", 0.0 if self.crval[1] >= 90.0 else 180.0))
+
+    @classmethod
+    def from_header(cls, header):
+        """SimpleWCS(header), or an invalid one (-999 for the sky keys) when the header's keywords cannot be used at all: a
+        non-numeric CRVAL / CDELT, CDELT = 0 under CROTA2."""
+        try:
+            with np.errstate(all="ignore"):
+                w = cls(header)
+            if w.valid and not np.all(np.isfinite(np.asarray(w.m + [list(w.crval), list(w.crpix)], dtype=np.float64))):
+                raise ValueError("non-finite transformation")
+            return w
+        except Exception as e:
+            w = cls({})
+            w.naxis = 2
+            w.valid, w.why = False, "unusable WCS keywords (%s: %s)" % (type(e).__name__, e)
+            return w
+
+    def pix2world(self, x, y):
+        """(longitude, latitude) in degrees of the 0-based pixel (x, y) along the celestial axes."""
+        p = (float(x) + 1.0 - self.crpix[0], float(y) + 1.0 - self.crpix[1])
+        u = self.m[0][0] * p[0] + self.m[0][1] * p[1]
+        v = self.m[1][0] * p[0] + self.m[1][1] * p[1]
+        if not self.proj:
+            return self.crval[0] + u, self.crval[1] + v
+        r = np.hypot(u, v)
+        phi = np.arctan2(u, -v) if r != 0.0 else 0.0
+        theta = np.arctan2(180.0 / np.pi, r) if self.proj == "TAN" else np.arccos(min(np.deg2rad(r), 1.0))
+        dphi = phi - np.deg2rad(self.lonpole)
+        dp = np.deg2rad(self.crval[1])
+        st, ct = np.sin(theta), np.cos(theta)
+        lng = self.crval[0] + np.rad2deg(np.arctan2(-ct * np.sin(dphi), st * np.cos(dp) - ct * np.sin(dp) * np.cos(dphi)))
+        lat = np.rad2deg(np.arcsin(max(-1.0, min(1.0, st * np.sin(dp) + ct * np.cos(dp) * np.cos(dphi)))))
+        return float(lng % 360.0), float(lat)
+
+    def all_pix2world(self, points, origin):
+        """Rows [x, y, ...] of pixel coordinates (origin 0 or 1) -> rows of world coordinates; the celestial pair is transformed,
+        any further axis linearly (CRVAL + CDELT (p - CRPIX))."""
+        out = []
+        for pt in points:
+            pt = [float(v) - float(origin) for v in pt]
+            row = list(pt)
+            row[self.lng], row[self.lat] = self.pix2world(pt[self.lng], pt[self.lat])
+            for k in range(len(pt)):
+                if k not in (self.lng, self.lat):
+                    row[k] = float(self.h.get("CRVAL%d" % (k + 1), 0.0)) + float(self.h.get("CDELT%d" % (k + 1), 1.0)) * (
+                        pt[k] + 1.0 - float(self.h.get("CRPIX%d" % (k + 1), 0.0)))
+            out.append(row)
+        return out

@@ -847,6 +847,53 @@ def tile_union(pool, desc, desc_host, comp_offsets, member_ids):
     return res
 
 
+def source_record_dtype():
+    """NumPy view of mrcnn_source_record (include/mrcnn_hip.h)."""
+    import numpy as np
+    return np.dtype([("s64", "<f8"), ("w00", "<f8"), ("w10", "<f8"), ("w01", "<f8"), ("clip_mean", "<f8"), ("clip_median", "<f8"),
+                     ("clip_std", "<f8"), ("m00", "<i8"), ("m10", "<i8"), ("m01", "<i8"), ("fill", "<f4"), ("smin", "<f4"),
+                     ("smax", "<f4"), ("n_mask", "<i4"), ("npix", "<i4"), ("clip_kept", "<i4"), ("clip_iters", "<i4"),
+                     ("n_gathered", "<i4")])
+
+
+def source_params(img, pool, desc, cutouts, sigma=3.0, maxiters=5, big_endian=False, desc_host=None):
+    """SFinder.compute_source_params' masked reductions (mrcnn/sfinder.py:1046-1075) for all sources of a mosaic in one launch
+    (include/mrcnn_hip.h: mrcnn_source_params).  img: the image plane [H, W] on the device, float32, or the file's big-endian
+    bytes as uint8 [H, W, 4] with big_endian=True; pool, desc from tile_upload; cutouts [n, 4] int32 (cx0, cy0, cx1, cy1), NumPy or
+    device; desc_host = the NumPy descriptors behind `desc` (read back when not given).  Returns the records as a device uint8
+    tensor [n, sizeof(mrcnn_source_record)]: `.cpu().numpy().view(source_record_dtype())` after which every field is an [n, 1]
+    column."""
+    import numpy as np
+    _need_cuda(img, pool, desc)
+    if big_endian:
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 4, "big-endian input: uint8 [H, W, 4]"
+    else:
+        assert img.dtype == torch.float32 and img.dim() == 2, "native input: float32 [H, W]"
+    H, W = int(img.shape[0]), int(img.shape[1])
+    n = int(desc.shape[0])
+    if not torch.is_tensor(cutouts):
+        cutouts = torch.from_numpy(np.ascontiguousarray(cutouts, dtype=np.int32).reshape(-1, 4)).to(pool.device)
+    _need_cuda(cutouts)
+    assert cutouts.dtype == torch.int32 and tuple(cutouts.shape) == (n, 4), "one cut-out rectangle per source"
+    if H <= 0 or W <= 0:
+        raise _hip.HipPathError("source_params: empty image")
+    d = np.asarray(desc.cpu().numpy() if desc_host is None else desc_host, dtype=np.int64).reshape(-1, 6)
+    assert d.shape[0] == n
+    # a slice per source for its gathered pixel values: the bits its mask rows hold always suffice
+    offs = np.concatenate([[0], np.cumsum(np.maximum(d[:, 3], 0) * np.maximum(d[:, 5], 0) * 32)]).astype(np.int64)
+    rec = source_record_dtype()
+    out = torch.zeros((n, rec.itemsize), dtype=torch.uint8, device=pool.device)
+    if n == 0:
+        return out
+    values = workspace(4 * max(int(offs[-1]), 1), pool.device, "srcparams")
+    offs_t = torch.from_numpy(offs).to(pool.device)
+    check(_hip.lib().mrcnn_source_params(ptr(img), 1 if big_endian else 0, H, W, ptr(pool), pool.numel(), ptr(desc), n, ptr(cutouts),
+                                         ptr(offs_t), ptr(values), values.numel() // 4, float(sigma), int(maxiters), ptr(out),
+                                         current_stream()), "mrcnn_source_params")
+    out._keep = (offs_t, cutouts)           # alive until the caller has synchronised on the result
+    return out
+
+
 class MaskPlanes(object):
     """The masks of one frame as bit planes on the device (include/mrcnn_hip.h, "mask graph"): words [n, H, ceil(W / 32)] int32
     (views of the 32-bit words), count [n] int32 = set pixels, box [n, 4] int32 = (y1, x1, y2, x2) as utils.extract_bboxes."""

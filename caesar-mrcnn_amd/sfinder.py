@@ -11,7 +11,19 @@ included (each carries the reference line).  The merge has two implementations b
 
 Both give equal catalogues (tests/test_sfinder_gpu.py).  Ranks are RANK / WORLD_SIZE processes (no mpi4py): tiles go round
 robin over the ranks, the per-tile result dicts are gathered on rank 0 with torch.distributed.gather_object, rank 0 merges
-and writes.  Not restated: compute_source_params (:994-1211: needs astropy.stats / astropy.wcs), plots.
+and writes.
+
+The step between merging and saving, compute_source_params (:613-622, :994-1211: pixel count, flux statistics, centroids, sky
+positions per source), runs when ``SFinder.compute_params`` is set (run.py --compute_source_params; the reference always runs
+it).  It has two implementations as well, behind ``SFinder.params_device``:
+
+  * ``compute_source_params``      the per-source statement in NumPy, rule by rule;
+  * ``compute_sources_params``     all sources at once: the image plane uploaded once, the masked reductions and the clipping
+                                   loop in one launch (csrc/srcparams.hip through ops.source_params), every ratio and the dicts
+                                   formed by the host code that also finishes the per-source statement.
+
+astropy.stats.sigma_clipped_stats and astropy.wcs.WCS are restated in fits.py (sigma_clipped_stats, SimpleWCS), unpinned;
+cv.moments is its defining sums.  Not restated: plots.
 """
 import logging
 import os
@@ -177,6 +189,12 @@ class SFinder(object):
     # Fewer edge sources than this are merged on the host even with merge_device on.  0: measured, the device path wins from
     # the smallest merging case up (4 edge sources: 2.1 ms against 48 ms).
     MERGE_DEVICE_MIN_SOURCES = 0
+    # Fewer sources than this get their parameters from the host statement even with params_device on.  Measured (DESIGN.md
+    # 4.8): on a 1024 x 1024 image the device path is behind at 1 and 4 sources (0.78 against 0.42 ms, 1.16 against 1.05 ms) and
+    # ahead at 116 (30.5 against 41.2 ms); 116 is the smallest count at which it was measured ahead on every mosaic.
+    PARAMS_DEVICE_MIN_SOURCES = 116
+    PARAM_KEYS = ("nPix", "X0", "Y0", "X0w", "Y0w", "X0_wcs", "Y0_wcs", "X0w_wcs", "Y0w_wcs", "Xmin", "Xmax", "Ymin", "Ymax",
+                  "Xmin_wcs", "Xmax_wcs", "Ymin_wcs", "Ymax_wcs", "S", "Smin", "Smax", "Smean", "Smedian", "Sstddev", "flux")
 
     def __init__(self, model, config):
         self.config = config
@@ -207,6 +225,15 @@ class SFinder(object):
         self.merge_device = self._has_gpu()
         self.merge_device_min_sources = self.MERGE_DEVICE_MIN_SOURCES
         self.merge_timing = {}
+        self.compute_params = False       # the reference always computes them (:613-622); here run.py --compute_source_params
+        self.params_device = self._has_gpu()
+        self.params_device_min_sources = self.PARAMS_DEVICE_MIN_SOURCES
+        self.params_sigma, self.params_maxiters = 3.0, 5          # astropy's sigma_clipped_stats defaults
+        self.params_timing = {}
+        self.beamArea = 0
+        self.wcs = None
+        self._plane = None                # (image plane as stored, path) while compute_sources_params runs
+        self._wcs_warned = False
 
     def _device(self):
         dev = getattr(getattr(self.model, "engine", None), "device", None)
@@ -252,6 +279,26 @@ class SFinder(object):
             self.tileSizeX, self.tileSizeY = cfg.TILE_XSIZE, cfg.TILE_YSIZE
             self.tileStepSizeX, self.tileStepSizeY = cfg.TILE_XSTEP, cfg.TILE_YSTEP
         self.image_id = os.path.splitext(os.path.basename(os.path.abspath(cfg.IMG_PATH)))[0]
+        # :400-439: the beam area in pixels, 0 unless all five keywords are there
+        self.beamArea = 0
+        found = True
+        for key, attr in (("CDELT1", "dX"), ("CDELT2", "dY"), ("BMAJ", "bmaj"), ("BMIN", "bmin"), ("BPA", "pa")):
+            if key not in self.header:
+                # (the reference warns on every run; here only a run that asked for the parameters hears about it)
+                logger.log(logging.WARNING if self.compute_params else logging.DEBUG,
+                           "[PROC %d] %s keyword missing in header!" % (self.procId, key))
+                found = False
+            else:
+                setattr(self, attr, self.header[key])
+        try:
+            if found:
+                self.pixelArea = np.abs(self.dX * self.dY)
+                self.beamArea = (np.pi * self.bmaj * self.bmin / (4 * np.log(2))) / self.pixelArea
+        except Exception as e:              # a non-numeric keyword must not fail a run that never asked for the parameters
+            logger.warning("[PROC %d] Beam area not computed (%s: %s)" % (self.procId, type(e).__name__, e))
+            self.beamArea = 0
+        self.wcs = fits.SimpleWCS.from_header(self.header)                # :442
+        self._plane = None
         return 0
 
     # ---- single image (sfinder.py:450-523) ------------------------------------------------------------------
@@ -333,6 +380,9 @@ class SFinder(object):
         if self.procId == self.MASTER_ID:
             logger.info("[PROC %d] Merging sources at tile edges ..." % self.procId)
             self.merge_edge_sources()
+            if self.compute_params:                                       # :613-622 (the reference: always)
+                logger.info("[PROC %d] Computing source parameters ..." % self.procId)
+                self.compute_sources_params()
             self.save()
             logger.info("[PROC %d] Run completed in %d seconds" % (self.procId, time.time() - t0))
         return 0
@@ -587,6 +637,194 @@ class SFinder(object):
             return self._merged_source("S" + str(i + 1) + "_merged", srcs[comp[-1]], pixels, mask.astype(np.uint8), x0, y0)
 
         return self._finish_merge(todo, cc, merged_of)
+
+    # ---- source parameters (sfinder.py:994-1211) --------------------------------------------------------------
+    def _image_plane(self):
+        """The plane utils.read_fits cuts from (utils.py:1061-1078: [0, 0] of a 4-D cube, a 2-D image as it is), read once and
+        left as the file stores it (an unscaled float32 image: the read-only big-endian view of the file's bytes -- the host
+        statement converts the cut-outs it takes, the device path uploads the bytes as they are).  compute_sources_params drops
+        it when it is done."""
+        path = self.config.IMG_PATH
+        if self._plane is None or self._plane[1] != path:
+            data, _ = fits.read_primary_hdu(path, native=False)
+            if data.ndim == 4:
+                data = data[0, 0]
+            elif data.ndim != 2:
+                raise ValueError("Invalid/unsupported number of channels found in file %s (nchan=%d)!" % (path, data.ndim))
+            self._plane = (data, path)
+        return self._plane[0]
+
+    def _cutout_geometry(self, source, offset=10):
+        """:1006-1016: (xmin, xmax, ymin, ymax, dx, dy, img_offset_x, img_offset_y).  dx = x2 - x1 + 1 whether x2 is the inclusive
+        pixel maximum (merged sources) or the exclusive box corner (all others), as written."""
+        xmin, xmax, ymin, ymax = source["x1"], source["x2"], source["y1"], source["y2"]
+        dx, dy = xmax - xmin + 1, ymax - ymin + 1
+        ox = min(min(offset, self.nx - 1 - xmax), min(offset, xmin))      # :1013
+        oy = min(min(offset, self.ny - 1 - ymax), min(offset, ymin))      # :1014
+        return xmin, xmax, ymin, ymax, dx, dy, ox, oy
+
+    def _finish_params(self, source, xoffset, yoffset, npix, S, Smin, Smax, clipped, m, mw):
+        """:1058-1211 from the sums: m = (sum 1, sum x, sum y) of the byte mask (cv.moments(smask, True)), mw = (sum I, sum x I,
+        sum y I) in float64 over the cut-out that is zero outside the mask (cv.moments(simg, False)); x, y relative to the
+        cut-out.  Values are plain Python numbers: write_json_results uses json.dump as it is."""
+        x0 = m[1] / m[0] + xoffset                                        # :1061-1063 (m00 == 0: ZeroDivisionError, as cv's dict gives)
+        y0 = m[2] / m[0] + yoffset
+        if mw[0] == 0:                                                    # :1068-1071
+            logger.warning("[PROC %d] Moment 00 is =0 for source %s, setting weighted centroid to non-weighted one..." % (
+                self.procId, source["name"]))
+            x0_w, y0_w = x0, y0
+        else:
+            x0_w = float(mw[1] / mw[0] + xoffset)                         # :1073-1075
+            y0_w = float(mw[2] / mw[0] + yoffset)
+        sky = [-999, -999, -999, -999]
+        wcs = self.wcs
+        if wcs is not None and wcs.valid:
+            pad = [0] * (wcs.naxis - 2) if wcs.naxis in (3, 4) else []   # :1079-1095
+            c, cw = wcs.all_pix2world([[x0, y0] + pad], 0), wcs.all_pix2world([[x0_w, y0_w] + pad], 0)
+            sky = [float(c[0][0]), float(c[0][1]), float(cw[0][0]), float(cw[0][1])]
+        elif not self._wcs_warned:
+            self._wcs_warned = True
+            logger.warning("[PROC %d] No sky positions (%s): the *_wcs keys are -999" % (
+                self.procId, wcs.why if wcs is not None else "set_img_size_params was not run"))
+        S = float(S)
+        return {"nPix": int(npix), "X0": float(x0), "Y0": float(y0), "X0w": x0_w, "Y0w": y0_w, "X0_wcs": sky[0], "Y0_wcs": sky[1],
+                "X0w_wcs": sky[2], "Y0w_wcs": sky[3], "Xmin": int(source["x1"]), "Xmax": int(source["x2"]), "Ymin": int(source["y1"]),
+                "Ymax": int(source["y2"]), "Xmin_wcs": -999, "Xmax_wcs": -999, "Ymin_wcs": -999, "Ymax_wcs": -999,      # :1195-1198
+                "S": S, "Smin": float(Smin), "Smax": float(Smax), "Smean": float(clipped[0]), "Smedian": float(clipped[1]),
+                "Sstddev": float(clipped[2]), "flux": float(S / self.beamArea) if self.beamArea > 0 else S}              # :1206-1209
+
+    def compute_source_params(self, source, offset=10):
+        """The reference's statement for one source (:994-1211), on the host.  Raises where the reference's arithmetic does (a
+        sub-image run: nx = ny = 1 makes the offsets hugely negative); compute_sources_params catches that per source."""
+        if self.procId != self.MASTER_ID:
+            return None
+        xmin, xmax, ymin, ymax, dx, dy, ox, oy = self._cutout_geometry(source, offset)
+        xoffset, yoffset = xmin - ox, ymin - oy                          # :1015-1016
+        smask = np.zeros((dy + 2 * oy, dx + 2 * ox), dtype=np.uint8)     # :1019
+        p = np.asarray(source["pixels"], dtype=np.int64).reshape(-1, 2)
+        smask[p[:, 0] - yoffset, p[:, 1] - xoffset] = 1                  # :1021-1026 (a negative index wraps, as in the loop)
+        # :1031-1042 = utils.read_fits with every stretch off (utils.py:1051-1091): the cut is made only when all four limits
+        # are >= 0, float32, NaN -> the nanmin of THIS cut-out
+        x0, x1, y0, y1 = xmin - ox, xmax + ox + 1, ymin - oy, ymax + oy + 1
+        plane = self._image_plane()
+        if x0 >= 0 and x1 >= 0 and y0 >= 0 and y1 >= 0:
+            if x1 <= x0 or y1 <= y0:
+                raise ValueError("xmax/ymax must be > xmin/ymin for tile reading!")
+            plane = plane[y0:y1, x0:x1]
+        simg = plane.astype(np.float32)
+        with np.errstate(all="ignore"):
+            simg[np.isnan(simg)] = np.nanmin(simg)
+            simg[smask == 0] = 0                                          # :1046
+            sdata = simg[smask > 0]                                       # :1047
+            S = np.nansum(sdata)                                          # :1052-1055, float32 as NumPy does them
+            npix = sdata.size - np.isnan(sdata).sum()
+            Smin, Smax = np.nanmin(sdata), np.nanmax(sdata)
+            clipped = fits.sigma_clipped_stats(sdata, self.params_sigma, self.params_maxiters)               # :1056
+            ys, xs = np.nonzero(smask)
+            m = (int(xs.size), int(xs.sum()), int(ys.sum()))              # :1060 cv.moments(smask, True)
+            I = simg.astype(np.float64)                                   # :1067 cv.moments(simg, False)
+            mw = (I.sum(), (I * np.arange(I.shape[1], dtype=np.float64)[None, :]).sum(),
+                  (I * np.arange(I.shape[0], dtype=np.float64)[:, None]).sum())
+            return self._finish_params(source, xoffset, yoffset, npix, S, Smin, Smax, clipped, m, mw)
+
+    def _host_params(self, source):
+        """The host statement for one catalogue entry; a source the reference's arithmetic fails on is logged and left without
+        parameters (the reference itself would stop the run there)."""
+        try:
+            sparams = self.compute_source_params(source)
+        except Exception as e:
+            logger.error("[PROC %d] Source %s: parameters not computed (%s: %s)" % (self.procId, source.get("name", "?"), type(e).__name__, e))
+            return False
+        if sparams:                                                       # :621-622
+            source.update(sparams)
+        return True
+
+    def compute_sources_params(self):
+        """:613-622 for the whole catalogue.  With params_device: one upload of the image plane, one launch for all sources
+        (ops.source_params), the dicts by _finish_params; sources whose offsets are negative (the wrap quirk), that have no pixels
+        or whose pixels leave their own cut-out take the host statement, as does everything when the device path is not there."""
+        if self.procId != self.MASTER_ID:
+            return 0
+        clock = time.perf_counter
+        sources = self.sources["sources"]
+        self.params_timing = {"sources": len(sources), "device_sources": 0, "host_sources": len(sources)}
+        t0 = clock()
+        host = list(range(len(sources)))
+        if self.params_device and len(sources) >= max(1, self.params_device_min_sources):
+            try:
+                host = self._params_device(sources)
+            except Exception as e:
+                from ._hip import HipPathError
+                if not isinstance(e, HipPathError):
+                    raise
+                logger.warning("[PROC %d] Source parameters on the host: %s" % (self.procId, e))
+        t1 = clock()
+        failed = sum(0 if self._host_params(sources[i]) else 1 for i in host)
+        self._plane = None                                                # the whole image: not kept beyond this step
+        self.params_timing.update({"host_sources": len(host), "device_sources": len(sources) - len(host), "failed_sources": failed,
+                                   "device_path_ms": round(1e3 * (t1 - t0), 3), "host_statement_ms": round(1e3 * (clock() - t1), 3)})
+        return 0
+
+    def _params_device(self, sources):
+        """Fills the sources the device path covers; returns the indices left to the host statement."""
+        import torch
+        from . import ops
+        clock = time.perf_counter
+        t = [clock()]
+        dev = self._device()
+        geo, pix, todo, host = [], [], [], []
+        for i, s in enumerate(sources):
+            p = np.asarray(s["pixels"], dtype=np.int64).reshape(-1, 2)
+            try:
+                g = self._cutout_geometry(s)
+            except Exception:
+                host.append(i)
+                continue
+            xmin, xmax, ymin, ymax, dx, dy, ox, oy = g
+            x0, x1, y0, y1 = xmin - ox, xmax + ox + 1, ymin - oy, ymax + oy + 1
+            inside = p.shape[0] and p[:, 1].min() >= x0 and p[:, 1].max() < x1 and p[:, 0].min() >= y0 and p[:, 0].max() < y1
+            if ox < 0 or oy < 0 or not inside or x1 > self.nx or y1 > self.ny:
+                host.append(i)
+                continue
+            todo.append(i)
+            pix.append(p)
+            geo.append((x0, y0, x1, y1))
+        if not todo:
+            return host
+        t.append(clock())
+        plane = self._image_plane()
+        if tuple(plane.shape) != (self.ny, self.nx):
+            from ._hip import HipPathError
+            raise HipPathError("image plane %r is not the %d x %d the header states" % (plane.shape, self.ny, self.nx))
+        big = plane.dtype == np.dtype(">f4")
+        if big:
+            raw = torch.from_numpy(np.array(plane, order="C", copy=True).view(np.uint8).reshape(self.ny, self.nx, 4))
+        else:
+            raw = torch.from_numpy(np.ascontiguousarray(plane, dtype=np.float32))
+        img_t = raw.to(dev)
+        t.append(clock())
+        pool, desc = pack_sources(pix)
+        t.append(clock())
+        pool_t, desc_t = ops.tile_upload(pool, desc, dev)
+        rec_t = ops.source_params(img_t, pool_t, desc_t, np.asarray(geo, np.int32), self.params_sigma, self.params_maxiters,
+                                  big_endian=big, desc_host=desc)
+        rec = rec_t.cpu().numpy().view(ops.source_record_dtype()).reshape(-1)          # .cpu() synchronises with the launch
+        t.append(clock())
+        for k, i in enumerate(todo):
+            r, s = rec[k], sources[i]
+            if int(r["n_gathered"]) != int(r["n_mask"]) or int(r["n_mask"]) == 0:
+                host.append(i)
+                continue
+            try:
+                s.update(self._finish_params(s, geo[k][0], geo[k][1], int(r["npix"]), np.float32(r["s64"]), r["smin"], r["smax"],
+                                             (r["clip_mean"], r["clip_median"], r["clip_std"]),
+                                             (int(r["m00"]), int(r["m10"]), int(r["m01"])), (r["w00"], r["w10"], r["w01"])))
+            except Exception:
+                host.append(i)
+        t.append(clock())
+        for name, a, b in zip(("select", "read_upload", "pack", "launch_download", "dicts"), t[:-1], t[1:]):
+            self.params_timing[name + "_ms"] = round(1e3 * (b - a), 3)
+        return sorted(host)
 
     # ---- tile grid (sfinder.py:1216-1384) ---------------------------------------------------------------------
     def create_tile_tasks(self):

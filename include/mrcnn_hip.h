@@ -229,6 +229,36 @@ int mrcnn_tile_union(const void* pool, int64_t pool_words, const mrcnn_tile_sour
                      mrcnn_tile_source* out_desc, int32_t* out_count, void* out_pool, int64_t out_pool_words, void* fresh_pool,
                      int64_t fresh_pool_words, void* stream);
 
+/* Source parameters of a tiled run (SFinder.compute_source_params, mrcnn/sfinder.py:994-1211): the masked reductions of all n
+ * sources of a mosaic in one launch, one workgroup per source.  Nothing is allocated, nothing synchronises.
+ *   img          the image plane [H, W] float32 on the device (big_endian != 0: the file's byte order, swapped on read);
+ *   pool, desc   the sources as for mrcnn_tile_adjacency (pixel masks in mosaic = image coordinates);
+ *   cutouts      [n, 4] int32 (cx0, cy0, cx1, cy1): the padded rectangle the reference cuts per source, columns cx0 .. cx1 - 1 and
+ *                rows cy0 .. cy1 - 1; clipped to the image as a NumPy slice is; mask pixels outside it are ignored;
+ *   val_offsets  [n + 1] int64: source s gathers its pixel values into values[val_offsets[s] .. val_offsets[s + 1]) (room for its
+ *                pixel count; h * words_per_row * 32 always suffices); values_len = length of `values` in floats.  Pixels past a
+ *                slice are counted but not gathered (n_gathered < n_mask: the clipped statistics then cover the gathered ones);
+ *   sigma, maxiters  of the clipping loop: non-finite values dropped; per iteration c = median, s = std (ddof 0) of the kept
+ *                values, keep c - sigma s <= x <= c + sigma s; stops when an iteration removes nothing or after maxiters.
+ * Per source one record.  NaN pixels are first replaced by `fill`, the minimum of the cut-out's non-NaN pixels (NaN if there
+ * are none), as utils.read_fits does (mrcnn/utils.py:1090-1091).  x, y below are relative to (cx0, cy0).  Sums only: the
+ * caller forms every ratio.  Results are bitwise reproducible (fixed-order reductions, no float atomics).                     */
+typedef struct mrcnn_source_record {
+    double s64;                      /* sum of the non-NaN masked values (np.nansum, in float64) */
+    double w00, w10, w01;            /* sum I, sum x I, sum y I over the masked pixels, IEEE propagation of NaN / inf */
+    double clip_mean, clip_median, clip_std;   /* of the values kept by the clipping (NaN when none is) */
+    int64_t m00, m10, m01;           /* sum 1, sum x, sum y over the masked pixels */
+    float fill;
+    float smin, smax;                /* np.nanmin / np.nanmax of the masked values (NaN when npix == 0) */
+    int32_t n_mask;                  /* masked pixels inside the cut-out */
+    int32_t npix;                    /* those that are not NaN after the fill */
+    int32_t clip_kept, clip_iters;   /* values kept at the end, iterations run */
+    int32_t n_gathered;              /* min(n_mask, slice length) */
+} mrcnn_source_record;
+int mrcnn_source_params(const void* img, int big_endian, int H, int W, const void* pool, int64_t pool_words,
+                        const mrcnn_tile_source* desc, int n, const int32_t* cutouts, const int64_t* val_offsets, void* values,
+                        int64_t values_len, double sigma, int maxiters, mrcnn_source_record* out, void* stream);
+
 /* The mask graph of Analyzer.extract_det_masks (mrcnn/analyze.py:1162-1496): which detection masks of a frame overlap or touch,
  * and the unions of those that are merged.  The masks of ONE frame are bit planes, planes[n][H][wpr] 32-bit words, wpr =
  * ceil(W / 32): pixel x of a row is bit x & 31 of word x >> 5, least significant bit first (numpy.packbits(...,

@@ -12,7 +12,8 @@ post-processing (caesar_mrcnn_amd/analyze.py: score filter, connected-mask mergi
 selection) on every tile and writes the objects as JSON (`out_<image>.json`: image_id, objs[name, x1, x2,
 y1, y2, class_id, class_name, score, pixels, vertexes, edge]) and DS9 regions.  Plots are not produced.
 `detect --split_img_in_tiles --merge_tile_sources` is the reference's SFinder (caesar_mrcnn_amd/sfinder.py): sources that
-straddle tile borders are merged and one catalogue (objects gain `merged`, names S1..Sn) is written by rank 0.
+straddle tile borders are merged and one catalogue (objects gain `merged`, names S1..Sn) is written by rank 0; with
+`--compute_source_params` every object also gains the reference's parameters (nPix, S .. flux, X0 .. Y0w_wcs, Xmin .. Ymax_wcs).
 """
 import argparse
 import json
@@ -95,6 +96,9 @@ def parse_args(argv=None):
                    help="with --split_img_in_tiles: the reference's SFinder -- sources cut by tile borders or seen in several "
                         "overlapping tiles are merged (on the GPU) and ONE catalogue is written by rank 0; default: per-tile "
                         "objects concatenated")
+    p.add_argument('--compute_source_params', action='store_true', default=False,
+                   help="with --merge_tile_sources: add the reference's source parameters (pixel count, flux statistics, "
+                        "centroids, sky positions) to every catalogue entry before it is written")
     return p.parse_args(argv)
 
 
@@ -249,6 +253,7 @@ def detect_merged(args, model, cfg):
     sf = SFinder(model, cfg)
     sf.outfile_json = args.detect_outfile_json or ("out_%s.json" % base)
     sf.outfile_ds9 = os.path.splitext(sf.outfile_json)[0] + ".reg"
+    sf.compute_params = bool(args.compute_source_params)
     if sf.run_parallel() < 0:
         logger.error("Failed to run the tiled source finder on image %s!" % args.image)
         return -1
