@@ -13,6 +13,13 @@ implementations behind ``Analyzer.postprocess_device``:
                                   (csrc/maskgraph.hip: ops.mask_planes_pack / mask_pair_stats / mask_union); the
                                   score filter, the graph searches, the clique walk and the captions stay host code.
 
+The tester -- ``ModelTester`` and ``Analyzer.inspect_results`` (``get_data``, ``extract_gt_masks``, ``compute_det_mask_pars``,
+``compute_performances``; analyze.py:65-406, :715-828, :907-1157, :1502-1861) -- is restated rule for rule as well: true and
+detected objects matched by mask IoU, confusion matrix and purity, one table row per true and per detected object.  Its pixel
+work, the mask IoU of every (true object, detection) pair and the flux sum under every detection mask, has two implementations
+behind ``Analyzer.eval_device``: ``mask_iou`` / ``np.nansum`` on full frames, or one launch each on bit planes
+(csrc/maskeval.hip: ops.mask_cross_stats / mask_plane_sums); the matching loops are the same code for both.
+
 Third-party pieces the reference imports and this file restates (absent here, so parity is UNPINNED for
 them; the semantics are the published ones):
   * skimage.measure.label(connectivity=1)      -> ``label_components`` (4-connected, raster-order numbering)
@@ -20,9 +27,15 @@ them; the semantics are the published ones):
   * sklearn.metrics.jaccard_score(binary)      -> ``mask_iou``
   * networkx.find_cliques                      -> ``maximal_cliques`` (Bron-Kerbosch with pivoting)
   * regions (DS9 writer)                       -> plain-text DS9 ``polygon`` / ``box`` lines, image coordinates
+  * cv.findContours + cv.minAreaRect / boundingRect -> ``min_area_rect`` (hull + calipers), ``utils.extract_bboxes``
+  * skimage.measure.label + regionprops (count)   -> ``count_islands`` (8-connected)
 """
+import collections
+import csv
 import json
 import logging
+import math
+import os
 import time
 from collections import deque
 
@@ -34,7 +47,10 @@ logger = logging.getLogger("mrcnn")
 
 NO_SPLIT_CLASSES = ('galaxy_C2', 'galaxy_C3', 'galaxy', 'extended-multisland')      # analyze.py:1221
 
+NO_SPLIT_CLASSES_GT = ('galaxy_C2', 'galaxy_C3', 'galaxy', 'extended', 'extended-multisland')      # analyze.py:1065
+
 _device_fallback_logged = False
+_eval_fallback_logged = False
 
 
 # ---- restated third-party helpers -----------------------------------------------------------------------
@@ -206,6 +222,91 @@ def connected_components(n, edges):
     return cc
 
 
+def convex_hull(points):
+    """Convex hull of integer points [n, 2] (x, y) by the monotone chain, counter-clockwise in (x, y) axes, collinear points
+    dropped; one or two points when the set is one point or lies on one line."""
+    pts = sorted(set((int(x), int(y)) for x, y in points))
+    if len(pts) <= 2:
+        return np.array(pts, dtype=np.float64).reshape(-1, 2)
+
+    def half(seq):
+        h = []
+        for p in seq:
+            while len(h) >= 2 and (h[-1][0] - h[-2][0]) * (p[1] - h[-2][1]) - (h[-1][1] - h[-2][1]) * (p[0] - h[-2][0]) <= 0:
+                h.pop()
+            h.append(p)
+        return h
+    lower, upper = half(pts), half(pts[::-1])
+    return np.array(lower[:-1] + upper[:-1], dtype=np.float64).reshape(-1, 2)
+
+
+def min_area_rect(mask):
+    """((cx, cy), (w, h), angle) of the minimum-area enclosing rectangle of a mask's set pixels, in coordinate measure (a single
+    pixel is 0 x 0, an a x b block is (a - 1) x (b - 1)); None for an empty mask.  Stands for cv.findContours(RETR_EXTERNAL,
+    CHAIN_APPROX_SIMPLE) followed by cv.minAreaRect on the merged contours (analyze.py:1562-1617), UNPINNED: that is the rectangle
+    of the convex hull of the pixels' integer coordinates -- the outer contours hold every hull vertex, holes and collinear
+    points never reach the hull.  Rotating calipers in float64: a minimum-area rectangle has a side along a hull edge, so for
+    every edge the hull's extent along and across it is taken and the first smallest area kept.  The angle follows OpenCV >= 4.5.1:
+    in (0, 90], the rotation of the side reported as the width from the x axis; nothing reads it."""
+    m = np.asarray(mask) != 0
+    ys, xs = np.nonzero(m)
+    if ys.size == 0:
+        return None
+    # the leftmost and rightmost set pixel of every row suffice for the hull (np.nonzero lists the pixels row by row)
+    starts = np.flatnonzero(np.r_[True, ys[1:] != ys[:-1]])
+    ends = np.r_[starts[1:], ys.size] - 1
+    hull = convex_hull(np.concatenate([np.stack([xs[starts], ys[starts]], 1), np.stack([xs[ends], ys[ends]], 1)]))
+    if len(hull) == 1:
+        return (float(hull[0, 0]), float(hull[0, 1])), (0.0, 0.0), 90.0
+    best = None
+    for k in range(len(hull) if len(hull) > 2 else 1):
+        e = hull[(k + 1) % len(hull)] - hull[k]
+        u = e / math.hypot(e[0], e[1])
+        along, across = hull @ u, hull @ np.array([-u[1], u[0]])
+        w, h = float(along.max() - along.min()), float(across.max() - across.min())
+        if best is None or w * h < best[0]:
+            ca, cc = 0.5 * (along.max() + along.min()), 0.5 * (across.max() + across.min())
+            best = (w * h, (float(ca * u[0] - cc * u[1]), float(ca * u[1] + cc * u[0])), w, h, math.degrees(math.atan2(u[1], u[0])))
+    _, centre, w, h, angle = best
+    angle %= 180.0                                   # a side's direction has no sign ...
+    if angle > 90.0:                                 # ... and the other side's direction is 90 degrees off: swap the sides
+        angle, w, h = angle - 90.0, h, w
+    elif angle == 0.0:
+        angle, w, h = 90.0, h, w
+    return centre, (w, h), angle
+
+
+def count_islands(bmap):
+    """Number of 8-connected components of a binary map: len(regionprops(skimage.measure.label(bmap))) (analyze.py:1567-1572;
+    label's default connectivity is the array's rank), UNPINNED.  Counted on the crop to the map's bounding box."""
+    m = np.asarray(bmap) != 0
+    ys, xs = np.nonzero(m)
+    if ys.size == 0:
+        return 0
+    m = m[ys.min():ys.max() + 1, xs.min():xs.max() + 1]
+    try:
+        from scipy import ndimage
+        return int(ndimage.label(m, structure=np.ones((3, 3), int))[1])
+    except ImportError:
+        seen = np.zeros(m.shape, bool)
+        H, W = m.shape
+        n = 0
+        for r, c in zip(*np.nonzero(m)):
+            if seen[r, c]:
+                continue
+            n += 1
+            seen[r, c] = True
+            q = deque([(r, c)])
+            while q:
+                y, x = q.popleft()
+                for yy in range(max(y - 1, 0), min(y + 2, H)):
+                    for xx in range(max(x - 1, 0), min(x + 2, W)):
+                        if m[yy, xx] and not seen[yy, xx]:
+                            seen[yy, xx] = True
+                            q.append((yy, xx))
+        return n
+
+
 # ---- the Analyzer ------------------------------------------------------------------------------------------
 class Analyzer(object):
     """Same attribute names and defaults as the reference's Analyzer (analyze.py:560-712) for the
@@ -215,7 +316,12 @@ class Analyzer(object):
     # tools/analyze_bench.py, once its table has been taken on an MI355X host; 0 = no such size.
     POSTPROCESS_DEVICE_MIN_MASKS = 0
 
-    def __init__(self, model, config, dataset=None):
+    # The tester's pixel work (compute_performances, compute_det_mask_pars) runs on the device from this many (true object,
+    # detection) pairs per image on: the smallest G * D at which tools/tester_bench.py measured the device path ahead of the host
+    # statement on an MI355X host.  None = no such run is recorded: the device path stays off by default.
+    EVAL_DEVICE_MIN_PAIRS = 9
+
+    def __init__(self, model, config, dataset=None, gt_data=None, pred_data=None):
         # Off by default: the device path is equal to the host statement value for value (tests/test_analyze_post_gpu.py) but
         # has not been timed against it on an MI355X host yet, and a frame with one to three detections costs the host
         # statement almost nothing.  `postprocess_device = Analyzer.has_gpu(model)` turns it on wherever a GPU is there.
@@ -230,17 +336,29 @@ class Analyzer(object):
         self.model = model
         self.config = config
         self.dataset = dataset
-        self.n_classes = config.NUM_CLASSES
+        self.r = None
+        self.n_classes = dataset.nclasses if dataset else config.NUM_CLASSES          # analyze.py:592-595
         self.class_names = config.CLASS_NAMES
         self.image = None
         self.image_id = -1
         self.image_header = None
+        self.image_uuid = ''
+        self.image_path = self.image_path_base = self.image_path_base_noext = ''
+        self.image_metadata = {}
         self.image_xmin = 0
         self.image_ymin = 0
         self.masks = self.boxes = self.class_ids = self.scores = None
         self.nobjects = 0
         self.masks_final, self.class_ids_final, self.class_names_final, self.scores_final = [], [], [], []
         self.bboxes, self.captions, self.bboxes_gt = [], [], []
+        # processed ground truth (analyze.py:617-624)
+        self.class_names_gt = None
+        self.masks_gt_merged, self.class_ids_gt_merged, self.captions_gt = [], [], []
+        self.split_gtmasks = False
+        self.sidelobes_mixed_or_near_gt_merged = []
+        self.remap_classids = False
+        self.classid_map = {}
+        self.det_obj_pars = []
         self.split_masks = False
         self.merge_overlapped_masks = True
         self.select_best_overlapped_masks = True
@@ -251,6 +369,25 @@ class Analyzer(object):
         self.obj_regions = []
         self.score_thr = 0.7
         self.iou_thr = 0.6
+        # performance results (analyze.py:651-661)
+        self.detobj_scores, self.detobj_ious, self.detobj_gtinfo = [], [], []
+        self.confusion_matrix = np.zeros((self.n_classes, self.n_classes))
+        self.confusion_matrix_norm = np.zeros((self.n_classes, self.n_classes))
+        self.purity = np.zeros((1, self.n_classes))
+        self.nobjs_true = np.zeros((1, self.n_classes))
+        self.nobjs_det = np.zeros((1, self.n_classes))
+        self.nobjs_det_right = np.zeros((1, self.n_classes))
+        self.is_gt_obj_detected = []
+        # data for external metric tools (analyze.py:711-713): lists the caller owns, one entry appended per inspected image
+        self.gt_data = gt_data
+        self.pred_data = pred_data
+        # The tester's device path (compute_performances_device / compute_det_mask_pars_device): on where a GPU is there AND a
+        # break-even has been measured (EVAL_DEVICE_MIN_PAIRS), from that many pairs on; else the host statement.
+        self.eval_device = self.EVAL_DEVICE_MIN_PAIRS is not None and Analyzer.has_gpu(model)
+        self.eval_device_min_pairs = self.EVAL_DEVICE_MIN_PAIRS or 0
+        self.eval_timing = {}
+        self._final_planes = None            # (MaskPlanes of masks_final, that list) when extract_det_masks_device made them
+        self._eval_planes = {}
         self.outfile = self.outfile_json = self.outfile_ds9 = ""
         self.draw = False                    # plotting is out of scope (no matplotlib on the path)
         self.write_to_json = True
@@ -364,6 +501,7 @@ class Analyzer(object):
         t = [clock()]
         self.masks_final, self.class_ids_final, self.class_names_final, self.scores_final = [], [], [], []
         self.bboxes, self.captions = [], []
+        self._final_planes = None
         self.postprocess_timing = {"masks": int(self.masks.shape[-1]), "mask_uploads": 0}
         sel = [i for i in range(self.boxes.shape[0]) if not self.scores[i] < self.score_thr]
         scores_sel = [self.scores[i] for i in sel]
@@ -503,6 +641,12 @@ class Analyzer(object):
             for k, index in enumerate(keep):
                 dtype = np.result_type(*[dtype_det[m] for m in masks_merged[index]])
                 self.masks_final.append(unpacked[k].astype(dtype))
+            if len(keep) != n_final:
+                ids = torch.as_tensor(keep, device=merged.words.device)
+                kept_planes = ops.MaskPlanes(words, merged.count.index_select(0, ids), merged.box.index_select(0, ids), merged.W)
+            else:
+                kept_planes = merged
+            self._final_planes = (kept_planes, self.masks_final)          # the tester's device path works on these
         t.append(clock())
         for name, a, b in zip(("upload_pack", "merge_pairs", "union", "select_pairs", "host_lists", "download_unpack"), t[:-1], t[1:]):
             self.postprocess_timing[name + "_ms"] = round(1e3 * (b - a), 3)
@@ -510,6 +654,7 @@ class Analyzer(object):
     def extract_det_masks_host(self):
         self.masks_final, self.class_ids_final, self.class_names_final, self.scores_final = [], [], [], []
         self.bboxes, self.captions = [], []
+        self._final_planes = None
         masks_sel, class_ids_sel, scores_sel = [], [], []
         for i in range(self.boxes.shape[0]):
             if self.scores[i] < self.score_thr:
@@ -600,6 +745,421 @@ class Analyzer(object):
             self.bboxes.append(bbox[0])
             self.captions.append("{} {:.2f}".format(label, scores_merged[index]))
 
+    # ---- the tester's path (analyze.py:715-828, :907-1157, :1502-1861) ----------------------------------------
+    def set_image_path(self, path):
+        self.image_path = path
+        self.image_path_base = os.path.basename(self.image_path)
+        self.image_path_base_noext = os.path.splitext(self.image_path_base)[0]
+
+    def get_data(self):
+        """analyze.py:724-828: image, detections (class ids remapped on request) and ground truth of self.image_id."""
+        if not self.dataset:
+            logger.error("No dataset present!")
+            return -1
+        self.image = self.dataset.load_image(self.image_id)
+        self.image_path_base = os.path.basename(self.image_path)
+        self.image_path_base_noext = os.path.splitext(self.image_path_base)[0]
+        self.image_uuid = self.dataset.image_uuid(self.image_id)
+        self.image_metadata = self.dataset.image_metadata(self.image_id)
+        r = self.model.detect([self.image], verbose=0)[0]
+        self.class_names = self.dataset.class_names
+        self.masks, self.boxes, self.class_ids, self.scores = r['masks'], r['rois'], r['class_ids'], r['scores']
+        self.nobjects = self.masks.shape[-1]
+        kept = getattr(self.model, "last_masks_device", None)
+        self.masks_device = kept[0] if kept else None
+        self.masks_device_host = self.masks
+        if self.remap_classids and self.classid_map:                                     # :760-776
+            class_ids_remapped = []
+            for class_id in self.class_ids:
+                if class_id in self.classid_map:
+                    class_ids_remapped.append(self.classid_map[class_id])
+                else:
+                    logger.error("Requested to remap class_id=%d but not found in map keys!" % class_id)
+                    return -1
+            self.class_ids = class_ids_remapped
+        self.class_names_gt = self.dataset.class_names
+        self.masks_gt = self.dataset.load_gt_masks(self.image_id, binary=False)
+        self.class_ids_gt = self.dataset.image_info[self.image_id]["class_ids"]
+        self.sidelobes_mixed_or_near_gt = self.dataset.image_info[self.image_id]['sidelobes_mixed_or_near']
+        self.labels_gt, self.captions_gt = [], []
+        for item in self.class_ids_gt:                                                   # (the colours of :805 are for plots only)
+            label = self.class_names_gt[item]
+            self.labels_gt.append(label)
+            self.captions_gt.append(label)
+        self.objs_gt = self.dataset.load_gt_obj_info(self.image_id)
+        if not self.objs_gt:
+            logger.warning("gt object info list is empty (hint: no object in this image or input data not in json format)...")
+        return 0
+
+    def inspect_results(self, image_id, image_path):
+        """analyze.py:907-1034: get_data -> extract_gt_masks -> extract_det_masks -> compute_det_mask_pars ->
+        compute_performances, with the appends to gt_data / pred_data in between; plots stay out of scope."""
+        self.image_id = image_id
+        self.image_path = image_path
+        if self.get_data() < 0:
+            logger.error("Failed to set data from provided dataset!")
+            return -1
+        self.extract_gt_masks()
+        gt_data_for_image = []
+        for i, (bbox_gt, label) in enumerate(zip(self.bboxes_gt, self.captions_gt)):
+            if not self.dataset.consider_sources_near_mixed_sidelobes:
+                if self.sidelobes_mixed_or_near_gt_merged[i] == 1:
+                    continue
+            gt_instance = bbox_gt.tolist()
+            gt_instance.append(label)
+            gt_data_for_image.append(gt_instance)
+        self.gt_data.append(gt_data_for_image)
+        if self.nobjects > 0:
+            self.extract_det_masks()
+        else:
+            logger.warning("No detected object found for image %s ..." % self.image_path_base)
+        if self.nobjects > 0:
+            self.compute_det_mask_pars()
+        pred_data_for_image = []
+        for bbox_pred, label_score in zip(self.bboxes, self.captions):
+            pred_object = bbox_pred.tolist()
+            pred_object.append(label_score.split(' ')[0])
+            pred_object.append(float(label_score.split(' ')[1]))
+            pred_data_for_image.append(pred_object)
+        self.pred_data.append(pred_data_for_image)
+        self.compute_performances()
+        return 0
+
+    def extract_gt_masks(self):
+        """analyze.py:1039-1155: the true masks as they are, or (split_gtmasks) split into connected pieces and the touching
+        pieces of one class merged again; then their boxes and captions."""
+        self.masks_gt_merged, self.class_ids_gt_merged, self.bboxes_gt, self.captions_gt = [], [], [], []
+        self.sidelobes_mixed_or_near_gt_merged = []
+        if self.split_gtmasks:
+            masks_gt_det, class_ids_gt_det, sidelobes_gt_det = [], [], []
+            for k in range(self.masks_gt.shape[-1]):
+                mask_gt, label_gt = self.masks_gt[:, :, k], self.labels_gt[k]
+                if label_gt in NO_SPLIT_CLASSES_GT:                                       # :1065
+                    masks_gt_det.append(mask_gt)
+                    class_ids_gt_det.append(self.class_ids_gt[k])
+                    sidelobes_gt_det.append(self.sidelobes_mixed_or_near_gt[k])
+                    continue
+                component_labels_gt, ncomponents_gt = self.extract_mask_connected_components(mask_gt)
+                for i in range(ncomponents_gt):
+                    # As the reference has it (:1075): component 1 on EVERY iteration, not component i + 1 -- a mask of k
+                    # components yields k copies of its first component (which the merge below joins into one again).
+                    extracted_mask = np.zeros(mask_gt.shape, dtype=mask_gt.dtype)
+                    extracted_mask[np.where(component_labels_gt == 1)] = 1
+                    masks_gt_det.append(extracted_mask)
+                    class_ids_gt_det.append(self.class_ids_gt[k])
+                    sidelobes_gt_det.append(self.sidelobes_mixed_or_near_gt[k])
+            N = len(masks_gt_det)
+            edges = []
+            for i in range(N):
+                for j in range(i + 1, N):
+                    connected = self.are_mask_connected(masks_gt_det[i], masks_gt_det[j])
+                    if connected and class_ids_gt_det[i] == class_ids_gt_det[j]:
+                        edges.append((i, j))
+            for comp in connected_components(N, edges):
+                merged_mask = masks_gt_det[comp[0]]
+                for index in comp[1:]:
+                    merged_mask = self.merge_masks(merged_mask, masks_gt_det[index])
+                self.masks_gt_merged.append(merged_mask)
+                self.class_ids_gt_merged.append(class_ids_gt_det[comp[-1]])               # class and flag of the last member
+                self.sidelobes_mixed_or_near_gt_merged.append(sidelobes_gt_det[comp[-1]])
+        else:
+            for k in range(self.masks_gt.shape[-1]):
+                self.masks_gt_merged.append(self.masks_gt[:, :, k])
+                self.class_ids_gt_merged.append(self.class_ids_gt[k])
+                self.sidelobes_mixed_or_near_gt_merged.append(self.sidelobes_mixed_or_near_gt[k])
+        for i in range(len(self.masks_gt_merged)):
+            mask = self.masks_gt_merged[i]
+            mask_expanded = np.zeros([mask.shape[0], mask.shape[1], 1], dtype=bool)
+            mask_expanded[:, :, 0] = mask
+            self.bboxes_gt.append(utils.extract_bboxes(mask_expanded)[0])
+            self.captions_gt.append(self.class_names_gt[self.class_ids_gt_merged[i]])
+
+    # -- where the pixel work of the two steps below runs
+    def _eval_on_device(self):
+        if not self.eval_device or len(self.masks_gt_merged) * len(self.masks_final) < max(self.eval_device_min_pairs, 1):
+            return False
+        for m in list(self.masks_final) + list(self.masks_gt_merged):
+            m = np.asarray(m)
+            if m.ndim != 2 or m.size == 0 or m.dtype.kind not in "biu":
+                return False
+        return True
+
+    def _eval_fallback(self, what, e):
+        global _eval_fallback_logged
+        if not _eval_fallback_logged:
+            _eval_fallback_logged = True
+            logger.error("%s failed (%s: %s): this and every later call take the host statement, which reads full frames for every "
+                         "pair of masks ..." % (what, type(e).__name__, e))
+
+    def _planes_of(self, key, masks):
+        """MaskPlanes of a list of [H, W] masks: the planes extract_det_masks_device kept for exactly this list, else one upload and
+        one pack; remembered while the list is the same object."""
+        import torch
+        from . import ops
+        have = self._eval_planes.get(key)
+        if have is not None and have[1] is masks:
+            return have[0]
+        if key == "final" and self._final_planes is not None and self._final_planes[1] is masks:
+            planes = self._final_planes[0]
+        else:
+            stack = np.ascontiguousarray(np.stack([np.asarray(m) != 0 for m in masks], axis=-1))
+            planes = ops.mask_planes_pack(torch.from_numpy(stack.view(np.uint8)).to(self._device()))
+            self.eval_timing["mask_uploads"] = self.eval_timing.get("mask_uploads", 0) + 1
+        self._eval_planes[key] = (planes, masks)
+        return planes
+
+    # ---- compute_det_mask_pars (analyze.py:1502-1676) ------------------------------------------------------------
+    def compute_det_mask_pars(self):
+        """Per detected object: pixel count, flux sum and signal-to-noise on the un-stretched image, upright and minimum-area
+        boxes, islands, border flag, sizes in beams.  The per-mask pixel count, box and flux sum come from
+        ``compute_det_mask_pars_device`` (ops.mask_plane_sums on bit planes) when the device path is on, else from full frames;
+        everything after them is the same host code."""
+        from . import fits
+        logger.info("Reading 2D origin image data from file %s ..." % self.image_path)
+        res = fits.read_fits(self.image_path, stretch=False, normalize=False, convertToRGB=False, to_uint8=False,
+                             stretch_biascontrast=False)
+        if res is None:
+            return -1
+        data = res[0]
+        if data.ndim != 2:
+            logger.error("Image size needed for computing morph pars should be =2 and not %d!" % data.ndim)
+            return -1
+        if self._eval_on_device() and data.dtype == np.float32 and len(self.masks_final) > 0 and \
+                tuple(data.shape) == tuple(np.asarray(self.masks_final[0]).shape):
+            from . import _hip
+            try:
+                return self._det_mask_pars_from(data, *self.compute_det_mask_pars_device(data))
+            except (_hip.HipPathError, OSError) as e:
+                self._eval_fallback("compute_det_mask_pars_device", e)
+        npix, boxes, stot = [], [], []
+        for mask in self.masks_final:
+            mask = np.asarray(mask)
+            cond = np.logical_and(np.isfinite(mask), mask != 0)
+            npix.append(int(np.count_nonzero(cond)))
+            # float64 sum of the float32 pixels (the reference's np.nansum accumulates in the image's own float32: DESIGN.md 4.9)
+            stot.append(float(np.nansum(data[cond], dtype=np.float64)))
+            boxes.append(utils.extract_bboxes((mask != 0)[:, :, None])[0])
+        return self._det_mask_pars_from(data, npix, boxes, stot)
+
+    def compute_det_mask_pars_device(self, data):
+        """(npix, boxes, Stot) of masks_final from the bit planes: counts and boxes as _pack / _union left them, the flux sums from
+        one ops.mask_plane_sums launch over the image, uploaded once."""
+        import torch
+        from . import ops
+        t0 = time.perf_counter()
+        planes = self._planes_of("final", self.masks_final)
+        img_t = torch.from_numpy(np.ascontiguousarray(data)).to(planes.words.device)
+        sums = ops.mask_plane_sums(img_t, planes)
+        ints = torch.cat([planes.count, planes.box.reshape(-1)]).cpu().numpy()
+        stot = sums.cpu().numpy()
+        n = planes.n
+        self.eval_timing["det_mask_pars_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+        return ints[:n].tolist(), list(ints[n:].reshape(n, 4)), stot.tolist()
+
+    def _det_mask_pars_from(self, data, npix, boxes, stot):
+        has_metadata = bool(self.image_metadata)
+        if has_metadata:                                                                  # :1510-1524
+            md = self.image_metadata
+            nx, ny, dx, dy = md["nx"], md["ny"], md["dx"], md["dy"]
+            img_bkg, img_rms, bmaj, bmin = md["bkg"], md["rms"], md["bmaj"], md["bmin"]
+            beamArea = np.pi * bmaj * bmin / (4 * np.log(2))
+            pixelArea = np.abs(dx * dy)
+            npixInBeam = beamArea / pixelArea
+            beamWidth = np.sqrt(np.abs(bmaj * bmin))
+            pixScale = np.sqrt(np.abs(dx * dy))
+            beamWidthInPixel = int(math.ceil(beamWidth / pixScale))
+        else:
+            # The reference goes on to read img_bkg, nx and ny, which it never set: a NameError.  Here the frame's own size
+            # stands for nx, ny and the signal-to-noise is the -999 of the branch below.
+            ny, nx = data.shape
+        self.det_obj_pars = []
+        for i in range(len(self.masks_final)):
+            name = 'Sdet' + str(i + 1)
+            class_name = self.class_names[self.class_ids_final[i]]
+            mask = np.asarray(self.masks_final[i])
+            npix_tot, Stot = npix[i], stot[i]
+            if has_metadata:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    Sbkg = img_bkg * npix_tot
+                    S = Stot - Sbkg
+                    Serr_noise = img_rms * np.sqrt(npix_tot)
+                    SNR = np.float64(S) / Serr_noise
+            else:
+                SNR = -999
+            rect = min_area_rect(mask)
+            if rect is None:                                                              # "no contours": :1592-1595
+                logger.warning("No contours found for object no. %d, fill empty dict!" % (i + 1))
+                self.det_obj_pars.append({})
+                continue
+            nislands = count_islands(mask)
+            # cv.boundingRect of the contour points: x, y of the first pixel, w, h up to one past the last -- extract_bboxes
+            y1, x1, y2, x2 = (int(v) for v in boxes[i])
+            bbox_w, bbox_h = x2 - x1, y2 - y1
+            bbox_x, bbox_y = x1 + 0.5 * bbox_w, y1 + 0.5 * bbox_h
+            (bbox_min_x, bbox_min_y), (bbox_min_w, bbox_min_h), bbox_min_angle = rect
+            at_border_x = (bbox_x - 0.5 * bbox_w <= 0) or (bbox_x + 0.5 * bbox_w >= nx)
+            at_border_y = (bbox_y - 0.5 * bbox_h <= 0) or (bbox_y + 0.5 * bbox_h >= ny)
+            at_border = at_border_x or at_border_y
+            if has_metadata:
+                nbeams = float(npix_tot) / float(npixInBeam)
+                minSizeVSBeam = float(min(bbox_min_w, bbox_min_h)) / beamWidthInPixel
+                maxSizeVSBeam = float(max(bbox_min_w, bbox_min_h)) / beamWidthInPixel
+                minSizeVSImg = min(float(bbox_w) / float(nx), float(bbox_h) / float(ny))
+                maxSizeVSImg = max(float(bbox_w) / float(nx), float(bbox_h) / float(ny))
+            else:
+                nbeams = minSizeVSBeam = maxSizeVSBeam = minSizeVSImg = maxSizeVSImg = -999
+            self.det_obj_pars.append({
+                "Stot": float(Stot), "bbox_angle": float(bbox_min_angle), "bbox_h": float(bbox_min_h), "bbox_w": float(bbox_min_w),
+                "bbox_x": float(bbox_min_x), "bbox_y": float(bbox_min_y), "border": int(at_border), "class": class_name,
+                "maxsize_beam": maxSizeVSBeam, "maxsize_img_fract": maxSizeVSImg, "minsize_beam": minSizeVSBeam,
+                "minsize_img_fract": minSizeVSImg, "name": name, "nbeams": nbeams, "nislands": nislands, "npix": npix_tot,
+                "snr": float(SNR)})
+        return 0
+
+    # ---- compute_performances (analyze.py:1682-1860) -----------------------------------------------------------------
+    def compute_performances(self):
+        """Matches true and detected objects by mask IoU and fills the confusion matrix, the purity and the per-object lists.
+        The IoUs come from ``compute_performances_device`` (one ops.mask_cross_stats launch) when the device path is on, else
+        from ``compute_performances_host`` (mask_iou on full frames per pair); the two loops are the same code."""
+        if self._eval_on_device():
+            from . import _hip
+            try:
+                return self.compute_performances_device()
+            except (_hip.HipPathError, OSError) as e:
+                self._eval_fallback("compute_performances_device", e)
+        return self.compute_performances_host()
+
+    def compute_performances_host(self):
+        # jaccard_score(masks_final[j].flatten(), masks_gt_merged[i].flatten().astype(bool), average='binary') [3P] == mask_iou
+        return self._match_objects(lambda i, j: mask_iou(self.masks_final[j], self.masks_gt_merged[i]))
+
+    def compute_performances_device(self):
+        """The intersections of all (true object, detection) pairs from one launch on bit planes; the union is count_gt +
+        count_det - inter.  One download; every decision is taken by the loops of _match_objects."""
+        import torch
+        from . import ops
+        t0 = time.perf_counter()
+        G, D = len(self.masks_gt_merged), len(self.masks_final)
+        gt = self._planes_of("gt", self.masks_gt_merged)
+        det = self._planes_of("final", self.masks_final)
+        inter = ops.mask_cross_stats(gt, det)
+        got = torch.cat([inter.reshape(-1), gt.count, det.count]).cpu().numpy().tolist()
+        count_gt, count_det = got[G * D:G * D + G], got[G * D + G:]
+        self.eval_timing["performances_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+
+        def iou(i, j):
+            n_inter = got[i * D + j]
+            union = count_gt[i] + count_det[j] - n_inter
+            return float(n_inter) / float(union) if union else 0.0
+        return self._match_objects(iou)
+
+    def _match_objects(self, iou_of):
+        """The two loops of compute_performances, rule for rule; ``iou_of(i, j)`` is the mask IoU of true object i and detection j."""
+        self.confusion_matrix = np.zeros((self.n_classes, self.n_classes))
+        self.confusion_matrix_norm = np.zeros((self.n_classes, self.n_classes))
+        self.purity = np.zeros((1, self.n_classes))
+        self.nobjs_true = np.zeros((1, self.n_classes))
+        self.nobjs_det = np.zeros((1, self.n_classes))
+        self.nobjs_det_right = np.zeros((1, self.n_classes))
+        self.detobj_classids, self.detobj_class_names, self.detobj_gtinfo = [], [], []
+        self.is_gt_obj_detected = []
+        self.is_det_obj_matching_to_gt_obj, self.is_det_obj_matching_to_gt_obj_sameclass = [], []
+        self.matchobj_classids, self.matchobj_class_names, self.matchobj_ious = [], [], []
+        # (detobj_scores and detobj_ious are NOT reset, as in the reference: they grow with every call on one Analyzer)
+
+        # true objects -> detections (:1703-1769)
+        for i in range(len(self.bboxes_gt)):
+            if not self.dataset.consider_sources_near_mixed_sidelobes:
+                if self.sidelobes_mixed_or_near_gt_merged[i] == 1:
+                    continue
+            bbox_gt = self.bboxes_gt[i]
+            class_id_gt = self.class_ids_gt_merged[i]
+            self.nobjs_true[0][class_id_gt] += 1
+            obj_info_gt = {}
+            if self.objs_gt and not self.split_gtmasks:
+                obj_info_gt = self.objs_gt[i]
+            index_best, iou_best, score_best = -1, 0, 0
+            for j in range(len(self.bboxes)):
+                score, bbox = self.scores_final[j], self.bboxes[j]
+                if bbox[1] >= bbox[3] or bbox[0] >= bbox[2]:
+                    logger.warning("Invalid det bbox (%d,%d,%d,%d) in image %s when computing IOU among boxes, skip it..." % (
+                        bbox[1], bbox[3], bbox[0], bbox[2], self.image_path))
+                    continue
+                if bbox_gt[1] >= bbox_gt[3] or bbox_gt[0] >= bbox_gt[2]:
+                    logger.warning("Invalid gt bbox (%d,%d,%d,%d) in image %s when computing IOU among boxes, skip it..." % (
+                        bbox_gt[1], bbox_gt[3], bbox_gt[0], bbox_gt[2], self.image_path))
+                    continue
+                mask_iou_ = iou_of(i, j)
+                if mask_iou_ >= self.iou_thr and mask_iou_ >= iou_best:              # `>=`: of equal candidates the LAST wins
+                    index_best, iou_best, score_best = j, mask_iou_, score
+            if obj_info_gt:
+                self.detobj_gtinfo.append(obj_info_gt)
+            if index_best == -1:
+                self.detobj_scores.append(-999)
+                self.detobj_ious.append(-999)
+                self.detobj_classids.append(-999)
+                self.detobj_class_names.append("not-detected")
+                self.is_gt_obj_detected.append(0)
+            else:
+                class_id_det = self.class_ids_final[index_best]
+                self.confusion_matrix[class_id_gt][class_id_det] += 1
+                self.detobj_scores.append(score_best)
+                self.detobj_ious.append(iou_best)
+                self.detobj_classids.append(class_id_det)
+                self.detobj_class_names.append(self.class_names[class_id_det])
+                self.is_gt_obj_detected.append(1)
+
+        for i in range(self.n_classes):                                                  # :1773-1780
+            norm = self.nobjs_true[0][i]
+            if norm <= 0:
+                continue
+            for j in range(self.n_classes):
+                self.confusion_matrix_norm[i][j] = self.confusion_matrix[i][j] / norm
+
+        # detections -> true objects (:1783-1834); no sidelobe skip here
+        for j in range(len(self.bboxes)):
+            bbox = self.bboxes[j]
+            class_id = self.class_ids_final[j]
+            self.nobjs_det[0][class_id] += 1
+            index_best, iou_best = -1, 0
+            for i in range(len(self.bboxes_gt)):
+                bbox_gt = self.bboxes_gt[i]
+                if bbox[1] >= bbox[3] or bbox[0] >= bbox[2]:
+                    continue
+                if bbox_gt[1] >= bbox_gt[3] or bbox_gt[0] >= bbox_gt[2]:
+                    continue
+                mask_iou_ = iou_of(i, j)
+                if mask_iou_ >= self.iou_thr and mask_iou_ >= iou_best:
+                    index_best, iou_best = i, mask_iou_
+            if index_best != -1:
+                class_id_gt = self.class_ids_gt_merged[index_best]
+                self.is_det_obj_matching_to_gt_obj.append(1)
+                self.matchobj_classids.append(class_id_gt)
+                self.matchobj_class_names.append(self.class_names[class_id_gt])
+                self.matchobj_ious.append(iou_best)
+                if class_id == class_id_gt:                                              # only a match of the same class is "right"
+                    self.nobjs_det_right[0][class_id] += 1
+                    self.is_det_obj_matching_to_gt_obj_sameclass.append(1)
+                else:
+                    self.is_det_obj_matching_to_gt_obj_sameclass.append(0)
+            else:
+                self.is_det_obj_matching_to_gt_obj.append(0)
+                self.is_det_obj_matching_to_gt_obj_sameclass.append(0)
+                self.matchobj_classids.append(-999)
+                self.matchobj_class_names.append("not-matched")
+                self.matchobj_ious.append(-999)
+
+        for j in range(self.n_classes):                                                  # :1836-1840
+            if self.nobjs_det[0][j] <= 0:
+                continue
+            self.purity[0][j] = self.nobjs_det_right[0][j] / self.nobjs_det[0][j]
+
+        for title, value in (("NOBJ TRUE", self.nobjs_true), ("NOBJ DET", self.nobjs_det), ("NOBJ DET CORRECTLY", self.nobjs_det_right),
+                             ("CLASSIFICATION MATRIX (not normalized)", self.confusion_matrix),
+                             ("CLASSIFICATION MATRIX (normalized)", self.confusion_matrix_norm), ("PRECISION (or PURITY)", self.purity)):
+            print("== SAMPLE %s ==" % title)
+            print(value)
+
     # ---- JSON (analyze.py:1866-1955) -----------------------------------------------------------------------
     def make_json_results(self):
         self.results = {"image_id": self.image_id, "objs": []}
@@ -659,3 +1219,187 @@ class Analyzer(object):
             fp.write("# Region file format: DS9\nglobal color=green\nimage\n")
             for line in self.obj_regions:
                 fp.write(line + "\n")
+
+
+# ---- the ModelTester (analyze.py:65-406) -----------------------------------------------------------------------
+class ModelTester(object):
+    """``run.py test`` of the reference: every image of a dataset through ``Analyzer.inspect_results``, the confusion matrix,
+    purity, matched scores and IoUs accumulated, and two tables -- one row per true object (completeness.csv) and one per
+    detected object (reliability.csv) -- rewritten after every image.  compute_mAP (:408-575, never switched on by the reference,
+    writes into vendored tool directories) is out of scope."""
+
+    def __init__(self, model, config, dataset):
+        self.dataset, self.model, self.config = dataset, model, config
+        self.n_max_img = -1
+        self.remap_classids = False
+        self.classid_map = {}
+        self.score_thr = 0.7
+        self.iou_thr = 0.6
+        self.n_classes = dataset.nclasses
+        self.classification_matrix = np.zeros((self.n_classes, self.n_classes))
+        self.classification_matrix_norm = np.zeros((self.n_classes, self.n_classes))
+        self.purity = np.zeros((1, self.n_classes))
+        self.nobjs_true = np.zeros((1, self.n_classes))
+        self.nobjs_det = np.zeros((1, self.n_classes))
+        self.nobjs_det_right = np.zeros((1, self.n_classes))
+        self.detobj_scores, self.detobj_ious = [], []
+        self.detobj_scoreMean = self.detobj_scoreStdDev = self.detobj_iouMean = self.detobj_iouStdDev = 0
+        self.detobj_gtinfo = []
+        self.compute_mAP_metrics = False
+        self.mAP = 0
+        self.completeness_dict_list, self.reliability_dict_list = [], []
+        self.outfilename_completeness = "completeness.csv"
+        self.outfilename_reliability = "reliability.csv"
+        self.eval_device = None               # None: every Analyzer keeps its own default; True / False: set on each of them
+
+    def test(self):
+        """:123-185."""
+        nimg = 0
+        logger.info("Processing up to %d images " % self.n_max_img)
+        gt_data, pred_data = [], []
+        for index, image_id in enumerate(self.dataset.image_ids):
+            if self.n_max_img > 0 and nimg >= self.n_max_img:
+                logger.info("Max number of images to inspect reached, stop here.")
+                break
+            nimg += 1
+            image_path = self.dataset.image_info[index]['path']
+            image_path_base = os.path.basename(image_path)
+            analyzer = Analyzer(self.model, self.config, self.dataset, gt_data, pred_data)
+            analyzer.score_thr = self.score_thr
+            analyzer.iou_thr = self.iou_thr
+            analyzer.remap_classids = self.remap_classids
+            analyzer.classid_map = self.classid_map
+            if self.eval_device is not None:
+                analyzer.eval_device = self.eval_device
+            logger.info("Inspecting results for image %s ..." % image_path_base)
+            if analyzer.inspect_results(image_id, image_path) < 0:
+                logger.error("Failed to analyze results for image %s ..." % image_path_base)
+                continue
+            self.update_performances(analyzer)
+        logger.info("Computing final performances ...")
+        self.compute_performances()
+        logger.info("Saving result data to file ...")
+        self.save()
+        return 0
+
+    def update_performances(self, analyzer):
+        """:190-322: sums the image's counters and appends its rows to the two tables, key for key."""
+        self.classification_matrix += analyzer.confusion_matrix
+        self.nobjs_true += analyzer.nobjs_true
+        self.nobjs_det += analyzer.nobjs_det
+        self.nobjs_det_right += analyzer.nobjs_det_right
+        self.detobj_scores += analyzer.detobj_scores
+        self.detobj_ious += analyzer.detobj_ious
+
+        image_path = analyzer.image_path
+        image_tel = analyzer.image_metadata["telescope"]
+        image_rms = analyzer.image_metadata["rms"]
+        image_bkg = analyzer.image_metadata["bkg"]
+        class_ids_gt = analyzer.class_ids_gt_merged
+        objinfo_gt = analyzer.detobj_gtinfo
+        scores_det, ious_det = analyzer.detobj_scores, analyzer.detobj_ious
+        class_ids_det, class_names_det = analyzer.detobj_classids, analyzer.detobj_class_names
+        is_gt_obj_detected = analyzer.is_gt_obj_detected
+        if objinfo_gt:
+            if len(class_ids_gt) != len(objinfo_gt):
+                logger.warning("classids_gt size is different from objinfo_gt size!")
+            rows = []
+            try:
+                for i in range(len(objinfo_gt)):
+                    obj = objinfo_gt[i]
+                    maxBeamSize, minBeamSize = obj['maxsize_beam'], obj['minsize_beam']
+                    aspectRatio = maxBeamSize / minBeamSize
+                    d = collections.OrderedDict()
+                    d["img"] = image_path
+                    d["telescope"] = image_tel
+                    d["img_rms"] = image_rms
+                    d["img_bkg"] = image_bkg
+                    d["sname"] = obj['name']
+                    d["class_id"] = class_ids_gt[i]
+                    d["class_name"] = obj['class']
+                    d["class_id_det"] = class_ids_det[i]
+                    d["class_name_det"] = class_names_det[i]
+                    d["detected"] = int(is_gt_obj_detected[i])
+                    d["score"] = scores_det[i]
+                    d["iou"] = ious_det[i]
+                    d["snr"] = float(obj['snr'])
+                    d["maxBeamSize"] = float(maxBeamSize)
+                    d["aspectRatio"] = float(aspectRatio)
+                    d["border"] = int(obj['border'])
+                    rows.append(d)
+            except IndexError:
+                # With the sidelobe switch off the per-object lists skip the flagged objects while the object info does not: the
+                # reference indexes them with one counter and raises here.  This image's completeness rows are left out.
+                logger.error("Object info and per-object results of image %s have different lengths (sources near or mixed with "
+                             "sidelobes are not considered): its completeness rows are left out ..." % image_path)
+                rows = []
+            self.completeness_dict_list.extend(rows)
+
+        objinfo_det = analyzer.det_obj_pars
+        class_ids_det, scores_det = analyzer.class_ids_final, analyzer.scores_final
+        if objinfo_det:
+            if len(class_ids_det) != len(objinfo_det):
+                logger.warning("class_ids_det size is different from objinfo_det size!")
+            for i in range(len(objinfo_det)):
+                obj_det = objinfo_det[i]
+                maxBeamSize, minBeamSize = obj_det['maxsize_beam'], obj_det['minsize_beam']
+                aspectRatio = -999
+                if minBeamSize > 0:
+                    aspectRatio = float(maxBeamSize) / float(minBeamSize)
+                d = collections.OrderedDict()
+                d["img"] = image_path
+                d["telescope"] = image_tel
+                d["img_rms"] = image_rms
+                d["img_bkg"] = image_bkg
+                d["sname"] = obj_det['name']
+                d["class_id_det"] = class_ids_det[i]
+                d["class_name_det"] = obj_det['class']
+                d["class_id"] = analyzer.matchobj_classids[i]
+                d["class_name"] = analyzer.matchobj_class_names[i]
+                d["matching_gt"] = int(analyzer.is_det_obj_matching_to_gt_obj[i])
+                d["score"] = float(scores_det[i])
+                d["iou"] = float(analyzer.matchobj_ious[i])
+                d["snr"] = float(obj_det['snr'])
+                d["maxBeamSize"] = float(maxBeamSize)
+                d["aspectRatio"] = float(aspectRatio)
+                d["border"] = int(obj_det['border'])
+                self.reliability_dict_list.append(d)
+        self.save()
+        return 0
+
+    def save(self):
+        """:328-351: "# " and then csv.DictWriter's header and rows in its default dialect."""
+        for rows, filename in ((self.completeness_dict_list, self.outfilename_completeness),
+                               (self.reliability_dict_list, self.outfilename_reliability)):
+            if rows:
+                with open(filename, 'w') as fp:
+                    fp.write("# ")
+                    dict_writer = csv.DictWriter(fp, rows[0].keys())
+                    dict_writer.writeheader()
+                    dict_writer.writerows(rows)
+
+    def compute_performances(self):
+        """:356-406."""
+        for i in range(self.n_classes):
+            norm = self.nobjs_true[0][i]
+            if norm <= 0:
+                continue
+            for j in range(self.n_classes):
+                self.classification_matrix_norm[i][j] = self.classification_matrix[i][j] / norm
+        for j in range(self.n_classes):
+            if self.nobjs_det[0][j] <= 0:
+                continue
+            self.purity[0][j] = self.nobjs_det_right[0][j] / self.nobjs_det[0][j]
+        self.detobj_scoreMean = np.mean(self.detobj_scores)
+        self.detobj_scoreStdDev = np.std(self.detobj_scores)
+        self.detobj_iouMean = np.mean(self.detobj_ious)
+        self.detobj_iouStdDev = np.std(self.detobj_ious)
+        for title, value in (("NOBJ TRUE", self.nobjs_true), ("NOBJ DET", self.nobjs_det), ("NOBJ DET CORRECTLY", self.nobjs_det_right),
+                             ("CLASSIFICATION MATRIX", self.classification_matrix),
+                             ("CLASSIFICATION MATRIX (NORM)", self.classification_matrix_norm), ("PRECISION (or PURITY)", self.purity)):
+            print("== %s ==" % title)
+            print(value)
+        print("== DET SCORES ==")
+        print("scoreThr=%f, <score>=%f, sigma(score)=%f" % (self.score_thr, self.detobj_scoreMean, self.detobj_scoreStdDev))
+        print("== DET IOUs ==")
+        print("iouThr=%f, <iou>=%f, sigma(iou)=%f" % (self.iou_thr, self.detobj_iouMean, self.detobj_iouStdDev))

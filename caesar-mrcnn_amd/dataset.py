@@ -74,6 +74,7 @@ class SourceDataset(Dataset):
         self.apply_biascontrast = False
         self.bias = 0.5
         self.contrast = 1.0
+        self.consider_sources_near_mixed_sidelobes = True      # run.py:1022; False: the tester skips true objects flagged so
 
     def set_class_dict(self, class_dict_str):
         """'{"sidelobe":1,"source":2,"galaxy":3}' -> registered classes (run.py:272-318)."""
@@ -207,6 +208,21 @@ class SourceDataset(Dataset):
 
     def image_uuid(self, image_id):
         return self.image_info[image_id]["id"]
+
+    def load_gt_obj_info(self, image_id):
+        """The ``objs`` list of the image's JSON file (run.py:673-684); empty for list input."""
+        info = self.image_info[image_id]
+        if 'objs' not in info:
+            logger.warning("objs key not present in image info (NB: available only in json input data reading), returning empty list!")
+            return []
+        return info["objs"]
+
+    def image_metadata(self, image_id):
+        """telescope, bkg, rms, bmaj, bmin, dx, dy, nx, ny of the image's JSON file (run.py:774-780); empty for list input."""
+        if 'metadata' not in self.image_info[image_id]:
+            logger.warning("No metadata stored in image info (hint: available only in json input data reading), returning empty dict!")
+            return {}
+        return self.image_info[image_id]['metadata']
 
     def compute_class_weights(self):
         tot = float(sum(self.nobjs_per_class[1:])) or 1.0

@@ -962,6 +962,38 @@ def mask_union(planes, comp_offsets, member_ids):
     return MaskPlanes(words, count, box, planes.W)
 
 
+def mask_cross_stats(planes_a, planes_b):
+    """inter [na, nb] int32 device tensor: the pixels plane i of `planes_a` shares with plane j of `planes_b` (two MaskPlanes of one
+    frame; the same object may be given twice), in one launch (include/mrcnn_hip.h: mrcnn_mask_cross_stats).  An empty set gives
+    an empty tensor, without a launch."""
+    _need_cuda(planes_a.words, planes_a.box, planes_b.words, planes_b.box)
+    if (planes_a.H, planes_a.W) != (planes_b.H, planes_b.W):
+        raise _hip.HipPathError("mask_cross_stats: plane sets of different frames %r, %r" % ((planes_a.H, planes_a.W), (planes_b.H, planes_b.W)))
+    inter = torch.empty((planes_a.n, planes_b.n), dtype=torch.int32, device=planes_a.words.device)
+    if planes_a.n > 0 and planes_b.n > 0 and planes_a.H > 0 and planes_a.W > 0:
+        check(_hip.lib().mrcnn_mask_cross_stats(ptr(planes_a.words), ptr(planes_a.box), planes_a.n, ptr(planes_b.words), ptr(planes_b.box),
+                                                planes_b.n, planes_a.H, planes_a.W, ptr(inter), current_stream()), "mrcnn_mask_cross_stats")
+    return inter
+
+
+def mask_plane_sums(img, planes, big_endian=False):
+    """sum [n] float64 device tensor: np.nansum of the image values under every plane (include/mrcnn_hip.h: mrcnn_mask_plane_sums).
+    img: the image plane [H, W] on the device, float32, or the file's big-endian bytes as uint8 [H, W, 4] with big_endian=True
+    (as for source_params)."""
+    _need_cuda(img, planes.words, planes.box)
+    if big_endian:
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 4, "big-endian input: uint8 [H, W, 4]"
+    else:
+        assert img.dtype == torch.float32 and img.dim() == 2, "native input: float32 [H, W]"
+    if (int(img.shape[0]), int(img.shape[1])) != (planes.H, planes.W):
+        raise _hip.HipPathError("mask_plane_sums: image %r, planes %r" % (tuple(img.shape[:2]), (planes.H, planes.W)))
+    out = torch.empty((planes.n,), dtype=torch.float64, device=planes.words.device)
+    if planes.n > 0 and planes.H > 0 and planes.W > 0:
+        check(_hip.lib().mrcnn_mask_plane_sums(ptr(img.contiguous()), 1 if big_endian else 0, ptr(planes.words), ptr(planes.box), planes.n,
+                                               planes.H, planes.W, ptr(out), current_stream()), "mrcnn_mask_plane_sums")
+    return out
+
+
 def fill_zero(t):
     _need_cuda(t)
     check(_hip.lib().mrcnn_fill_zero(ptr(t), t.numel() * t.element_size(), current_stream()), "mrcnn_fill_zero")

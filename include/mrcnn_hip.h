@@ -283,6 +283,23 @@ int mrcnn_mask_pair_stats(const void* planes, const int32_t* box, int n, int H, 
 int mrcnn_mask_union(const void* planes, int n, int H, int W, const int32_t* comp_offsets, const int32_t* member_ids, int C, int M,
                      void* out_planes, int32_t* out_count, int32_t* out_box, void* stream);
 
+/* The pixel work of the tester (Analyzer.compute_performances / compute_det_mask_pars, mrcnn/analyze.py:1502-1861), on the bit
+ * planes and boxes of the mask graph above (boxes as _pack / _union give them; a box larger than the plane's own is allowed, a
+ * smaller one hides pixels).  Nothing is allocated, nothing synchronises, no atomics.  na, nb, n, H or W <= 0: MRCNN_ERR_ARG.
+ *   mrcnn_mask_cross_stats  inter[i * nb + j] = popcount(a_i & b_j) for all na x nb pairs of two plane sets of ONE frame (the sets
+ *                           may be the same buffer), in one launch, one wavefront per cell.  Only the intersection of the two
+ *                           boxes is read; an empty intersection gives 0.  Every cell is written.  The Jaccard index of the
+ *                           reference's jaccard_score(average='binary') [3P] is inter / (count_a + count_b - inter), 0 when the
+ *                           union is 0, on the host.
+ *   mrcnn_mask_plane_sums   sum[p] = float64 sum of the non-NaN values of img at plane p's set pixels (np.nansum: an infinity
+ *                           propagates; 0 for an empty plane).  img [H, W] float32 (big_endian != 0: the file's byte order,
+ *                           swapped on read, as for mrcnn_source_params).  One workgroup per plane; the partial sums are combined
+ *                           in a fixed order, so the result is bitwise the same from run to run.                                 */
+int mrcnn_mask_cross_stats(const void* planes_a, const int32_t* box_a, int na, const void* planes_b, const int32_t* box_b, int nb,
+                           int H, int W, int32_t* inter, void* stream);
+int mrcnn_mask_plane_sums(const void* img, int big_endian, const void* planes, const int32_t* box, int n, int H, int W, double* sum,
+                          void* stream);
+
 /* detect() post-processing (MaskRCNN.unmold_detections, mrcnn/model.py:2607-2619; utils.unmold_mask, mrcnn/utils.py:629-645;
  * utils.resize -> skimage.transform.resize(order=1, mode='constant', cval=0, clip=True), mrcnn/utils.py:957-978): for each of
  * the n detections of ONE image, resize the class channel of its MH x MW mask to its integer pixel box (float64, half-pixel

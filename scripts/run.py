@@ -7,7 +7,8 @@
 
 Same flag names and defaults; the model behind them is caesar_mrcnn_amd.model.MaskRCNN (MI355X).
 Multi-GPU training: ``torchrun --nproc-per-node NGPU scripts/run.py train --ngpu NGPU ...``.
-`test` reports completeness / reliability per class from mask-IoU matching; `detect` runs the Analyzer
+`test` reports completeness / reliability per class from mask-IoU matching, or with `--reference_tester` runs the reference's
+ModelTester (caesar_mrcnn_amd/analyze.py: confusion matrix, purity, completeness.csv and reliability.csv); `detect` runs the Analyzer
 post-processing (caesar_mrcnn_amd/analyze.py: score filter, connected-mask merging, best-of-overlapping
 selection) on every tile and writes the objects as JSON (`out_<image>.json`: image_id, objs[name, x1, x2,
 y1, y2, class_id, class_name, score, pixels, vertexes, edge]) and DS9 regions.  Plots are not produced.
@@ -80,6 +81,15 @@ def parse_args(argv=None):
     p.add_argument('--reference_augmentation', action='store_true', default=False,
                    help="extension: augment with the reference's imgaug pipeline (0-2 of flip lr / flip ud / rotate -90..90 / "
                         "translate +-30%%), warped on the GPU; default: flips + 90-degree rotations")
+    p.add_argument('--reference_tester', action='store_true', default=False,
+                   help="extension: `test` runs the reference's ModelTester (masks merged and selected first, its matching rule, "
+                        "confusion matrix and purity, completeness.csv and reliability.csv); needs a JSON dataloader; default: the "
+                        "per-class completeness / reliability summary")
+    p.add_argument('--remap_classids', action='store_true', default=False)
+    p.add_argument('--classid_remap_dict', type=str, default='', help='Dictionary used to remap detected classid to gt classid')
+    p.add_argument('--consider_sources_near_mixed_sidelobes', dest='consider_sources_near_mixed_sidelobes', action='store_true',
+                   default=True)
+    p.add_argument('--no_consider_sources_near_mixed_sidelobes', dest='consider_sources_near_mixed_sidelobes', action='store_false')
     p.add_argument('--scoreThr', type=float, default=0.7)
     p.add_argument('--iouThr', type=float, default=0.6)
     p.add_argument('--image', type=str, default=None)
@@ -208,7 +218,42 @@ def _mask_iou(a, b):
     return inter / union if union else 0.0
 
 
+def test_reference(args, model, cfg):
+    """--reference_tester: the reference's test() (run.py:1132-1166) -- ModelTester over the dataset, two CSV tables written."""
+    import ast
+    from caesar_mrcnn_amd.analyze import ModelTester
+    if args.dataloader == 'datalist':
+        # The reference's tester reads the telescope, background and noise of every image from its metadata and raises on list
+        # input, which has none.
+        logger.error("--reference_tester needs the image metadata of a JSON dataset: use --dataloader datalist_json or datadir_json")
+        return -1
+    classid_remap_dict = {}
+    if args.remap_classids:
+        if args.classid_remap_dict == "":
+            logger.error("Classid remap dictionary is empty (you need to provide one if you give the option --remap_classids)!")
+            return -1
+        try:
+            classid_remap_dict = ast.literal_eval(args.classid_remap_dict)
+        except Exception:
+            logger.error("Failed to convert classid remap dict string to dict!")
+            return -1
+    ds = make_dataset(args, args.datadir if args.dataloader == 'datadir_json' else args.datalist)
+    if ds is None:
+        return -1
+    ds.consider_sources_near_mixed_sidelobes = args.consider_sources_near_mixed_sidelobes
+    tester = ModelTester(model, cfg, ds)
+    tester.score_thr = args.scoreThr
+    tester.iou_thr = args.iouThr
+    tester.n_max_img = args.maxnimgs
+    tester.remap_classids = args.remap_classids
+    tester.classid_map = classid_remap_dict
+    tester.test()
+    return 0
+
+
 def test(args, model, cfg):
+    if getattr(args, "reference_tester", False):
+        return test_reference(args, model, cfg)
     ds = make_dataset(args, args.datadir if args.dataloader == 'datadir_json' else args.datalist)
     if ds is None:
         return -1
