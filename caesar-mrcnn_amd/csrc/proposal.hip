@@ -201,6 +201,12 @@ __global__ __launch_bounds__(K1_THREADS) void select_sort_decode_kernel(const Pr
     const unsigned* pre = p.pre_ws + (int64_t)b * PRE_WORDS;
     const unsigned ncand = p.pre_groups ? pre[PRE_NCAND] : ~0u;
     const bool preselected = p.pre_groups && ncand == (unsigned)K && pre[PRE_COUNTER] == (unsigned)K;   // workgroup-uniform
+    // no pre-selection ran: nothing reset the health words, and the grow-only workspace holds whatever an earlier call of another
+    // shape left there (mask words, boxes).  mrcnn_proposal_status_offset documents {0, 0, 0} for this case: write it.
+    if (!p.pre_groups && tid == 0) {
+        unsigned* st = p.pre_ws + (int64_t)b * PRE_WORDS;
+        st[PRE_COUNTER] = 0u; st[PRE_NCAND] = 0u; st[PRE_ERR] = 0u;
+    }
 
     // ---- radix select: largest K keys ------------------------------------------------------------
     if (tid == 0) { s_prefix = 0; s_need = (unsigned)K; }

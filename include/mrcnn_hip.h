@@ -390,7 +390,8 @@ int mrcnn_proposal_fwd(const mrcnn_proposal_desc* d, const float* rpn_probs, con
 /* Health words of the multi-workgroup top-k selection (A >= 32 768), for a host that has synchronised anyway: returns
  * the byte offset from `workspace` of image 0's three uint32 {keys collected, keys announced, stores refused by the
  * bounds guard}; *stride_bytes = distance between images.  A healthy call leaves collected == announced == K and
- * refused == 0; anything else makes the sort kernel discard the pre-selection and select by itself (same result).  */
+ * refused == 0; anything else makes the sort kernel discard the pre-selection and select by itself (same result).
+ * A call without a pre-selection (A < 32 768, or A <= pre_nms_limit) writes {0, 0, 0}.  */
 size_t mrcnn_proposal_status_offset(const mrcnn_proposal_desc* d, const void* workspace, size_t* stride_bytes);
 
 /* DetectionTargetLayer (mrcnn/model.py:570-763) for one batch.  rand_keys [B, R] uniform floats
