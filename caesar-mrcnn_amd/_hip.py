@@ -131,6 +131,11 @@ _SIGNATURES = {
                                      C.c_size_t, _P]),
     "mrcnn_fits_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "mrcnn_fits_to_rgb": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
+    # tiles_host is a HOST table (numpy, a 32-byte record per tile: ops.FITS_TILE_DTYPE)
+    "mrcnn_fits_tiles_check": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "mrcnn_fits_tiles_workspace": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
+    "mrcnn_fits_tiles_to_rgb": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_double), _P, C.c_size_t, _P,
+                                          C.c_size_t, _P]),
     "mrcnn_mold_image_u8": (C.c_int, [_P] + [C.c_int] * 9 + [C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
     "mrcnn_add_inplace": (C.c_int, [_P, _P, C.c_int64, _P]),
     "mrcnn_softmax_rows": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
@@ -209,7 +214,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats")
+_NO_RECORD = ("_workspace", "_tiles_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats")
 
 
 class _LibProxy(object):

@@ -340,6 +340,7 @@ class Analyzer(object):
         self.n_classes = dataset.nclasses if dataset else config.NUM_CLASSES          # analyze.py:592-595
         self.class_names = config.CLASS_NAMES
         self.image = None
+        self.image_shape = None              # set by accept_detection: all that is known of an image that stayed on the device
         self.image_id = -1
         self.image_header = None
         self.image_uuid = ''
@@ -414,20 +415,40 @@ class Analyzer(object):
 
     # ---- predict (analyze.py:833-905) ----------------------------------------------------------------------
     def predict(self, image, image_id='', bboxes_gt=[], header=None, xmin=0, ymin=0):
+        if self._set_image(image, image_id, header, xmin, ymin) < 0:
+            return -1
+        r = self.model.detect([self.image], verbose=0)[0]
+        kept = getattr(self.model, "last_masks_device", None)      # MaskRCNN keeps the device tensor of its last un-mold
+        return self._accept(r, kept[0] if kept else None, bboxes_gt)
+
+    def accept_detection(self, image, r, masks_device=None, image_id='', bboxes_gt=[], header=None, xmin=0, ymin=0):
+        """Everything of predict but its model.detect call, for a detection result `r` that is already there (one image of a
+        batched detect: the tiled source finder).  `image` is the image or just its shape (h, w[, c]): nothing here reads the
+        pixels.  `masks_device`: the device tensor behind r['masks'] when the model kept it, else None."""
+        if self._set_image(image, image_id, header, xmin, ymin) < 0:
+            return -1
+        return self._accept(r, masks_device, bboxes_gt)
+
+    def _set_image(self, image, image_id, header, xmin, ymin):
         if image is None:
             logger.error("No input image given!")
             return -1
-        self.image, self.image_xmin, self.image_ymin = image, xmin, ymin
+        if isinstance(image, (tuple, list)):
+            self.image, self.image_shape = None, tuple(int(v) for v in image)
+        else:
+            self.image, self.image_shape = image, tuple(image.shape)
+        self.image_xmin, self.image_ymin = xmin, ymin
         if image_id:
             self.image_id = image_id
         if header:
             self.image_header = header
-        r = self.model.detect([self.image], verbose=0)[0]
+        return 0
+
+    def _accept(self, r, masks_device, bboxes_gt):
         self.class_names = self.config.CLASS_NAMES
         self.masks, self.boxes, self.class_ids, self.scores = r['masks'], r['rois'], r['class_ids'], r['scores']
         self.nobjects = self.masks.shape[-1]
-        kept = getattr(self.model, "last_masks_device", None)      # MaskRCNN keeps the device tensor of its last un-mold
-        self.masks_device = kept[0] if kept else None
+        self.masks_device = masks_device
         self.masks_device_host = self.masks
         self.results, self.obj_regions = {}, []
         if self.nobjects > 0:
@@ -1164,7 +1185,7 @@ class Analyzer(object):
     def make_json_results(self):
         self.results = {"image_id": self.image_id, "objs": []}
         xmin, ymin = self.image_xmin, self.image_ymin
-        ny, nx = self.image.shape[0], self.image.shape[1]
+        ny, nx = (self.image.shape if self.image is not None else self.image_shape)[:2]
         for i in range(len(self.masks_final)):
             class_id = int(self.class_ids_final[i])
             y1, x1, y2, x2 = [int(v) for v in self.bboxes[i]]

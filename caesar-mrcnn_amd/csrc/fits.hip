@@ -11,6 +11,12 @@
 // the host's, type for type (float32 subtraction, float64 division and clip, float32 normalisation, round-half-even), so the
 // uint8 image is identical to fits.read_fits's; the fit uses the closed form of the weighted least-squares line where the host
 // goes through numpy.polyfit's SVD (agreement ~1e-15 relative in the limits: far below half a grey level).
+//
+// mrcnn_fits_tiles_to_rgb runs the same three stages over T tiles of ONE resident plane (the mosaic of the tiled source finder)
+// with the tile as a grid dimension: the statistics pass reads every tile row as a strided segment of the plane (consecutive
+// lanes = consecutive pixels of a row: a wavefront's loads stay in one row segment, two at a row end) and leaves the tile's
+// native-endian values row-major and contiguous in the workspace, so the sampling and the pixel pass address a tile exactly as
+// the single-tile path does -- the bodies below are shared, not copied.
 #include "common.h"
 #include <math.h>
 
@@ -28,19 +34,33 @@ __device__ __forceinline__ float fits_load(const unsigned* raw, long long i, int
     return __uint_as_float(u);
 }
 
-// chunk statistics; vals gets the native-endian copy
-__global__ __launch_bounds__(256) void fits_stats_kernel(const unsigned* __restrict__ raw, float* __restrict__ vals, long long n,
-                                                         int big_endian, FitsChunk* __restrict__ chunks) {
+// where pixel i (row-major within the tile) of a tile sits in `raw`
+struct FitsLinear {                                     // the tile IS the buffer
+    __device__ __forceinline__ long long operator()(long long i) const { return i; }
+};
+struct FitsRect {                                       // w columns from (x0, y0) of a plane of row stride NX
+    long long origin, NX;
+    int w;
+    __device__ __forceinline__ long long operator()(long long i) const {
+        const long long y = i / w;
+        return origin + y * NX + (i - y * w);
+    }
+};
+
+// statistics of chunk `chunk` of a tile of n pixels; vals gets the native-endian copy (row-major within the tile)
+template <class Addr>
+__device__ __forceinline__ void fits_stats_body(const unsigned* __restrict__ raw, const Addr addr, float* __restrict__ vals, long long n,
+                                                int big_endian, int chunk, FitsChunk* __restrict__ chunks) {
     __shared__ float s_mn[256], s_mx[256];
     __shared__ int s_nan[256], s_inf[256];
     const int tid = threadIdx.x;
-    const long long base = (long long)blockIdx.x * FITS_CHUNK;
+    const long long base = (long long)chunk * FITS_CHUNK;
     float mn = INFINITY, mx = -INFINITY;
     int nn = 0, ni = 0;
     for (int k = tid; k < FITS_CHUNK; k += 256) {
         const long long i = base + k;
         if (i >= n) break;
-        const float v = fits_load(raw, i, big_endian);
+        const float v = fits_load(raw, addr(i), big_endian);
         vals[i] = v;
         if (v != v) { ++nn; continue; }
         if (isinf(v)) ++ni;
@@ -58,7 +78,12 @@ __global__ __launch_bounds__(256) void fits_stats_kernel(const unsigned* __restr
         }
         __syncthreads();
     }
-    if (tid == 0) chunks[blockIdx.x] = {s_mn[0], s_mx[0], s_nan[0], s_inf[0]};
+    if (tid == 0) chunks[chunk] = {s_mn[0], s_mx[0], s_nan[0], s_inf[0]};
+}
+
+__global__ __launch_bounds__(256) void fits_stats_kernel(const unsigned* __restrict__ raw, float* __restrict__ vals, long long n,
+                                                         int big_endian, FitsChunk* __restrict__ chunks) {
+    fits_stats_body(raw, FitsLinear(), vals, n, big_endian, (int)blockIdx.x, chunks);
 }
 
 __device__ __forceinline__ double fits_block_sum(double v, double* red, int tid) {
@@ -82,10 +107,10 @@ __device__ __forceinline__ float fits_stretch(float v, const FitsChannel& c) {
     return (float)o;
 }
 
-// sampling, sort, iterative fit and limits: ONE workgroup of 1024 threads
-__global__ __launch_bounds__(1024) void fits_zscale_kernel(const float* __restrict__ vals, long long n, int nchunks,
-                                                           const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
-                                                           FitsParams* __restrict__ params) {
+// sampling, sort, iterative fit and limits of one tile: ONE workgroup of 1024 threads
+__device__ __forceinline__ void fits_zscale_body(const float* __restrict__ vals, long long n, int nchunks,
+                                                 const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
+                                                 FitsParams* __restrict__ params) {
     __shared__ int s_prefix[FITS_MAX_CHUNKS + 1];
     __shared__ float s_samp[1024];
     __shared__ double s_red[1024];
@@ -242,11 +267,15 @@ __global__ __launch_bounds__(1024) void fits_zscale_kernel(const float* __restri
     }
 }
 
-__global__ __launch_bounds__(256) void fits_rgb_kernel(const float* __restrict__ vals, long long n, const FitsParams* __restrict__ params,
-                                                       unsigned char* __restrict__ rgb) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const FitsParams p = *params;
+__global__ __launch_bounds__(1024) void fits_zscale_kernel(const float* __restrict__ vals, long long n, int nchunks,
+                                                           const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
+                                                           FitsParams* __restrict__ params) {
+    fits_zscale_body(vals, n, nchunks, chunks, c0, c1, c2, params);
+}
+
+// pixel i of a tile: its three bytes
+__device__ __forceinline__ void fits_rgb_pixel(const float* __restrict__ vals, long long i, const FitsParams& p,
+                                               unsigned char* __restrict__ rgb) {
     unsigned char o[3] = {0, 0, 0};
     if (!p.all_nan) {
         float v = vals[i];
@@ -259,6 +288,43 @@ __global__ __launch_bounds__(256) void fits_rgb_kernel(const float* __restrict__
         }
     }
     rgb[i * 3 + 0] = o[0]; rgb[i * 3 + 1] = o[1]; rgb[i * 3 + 2] = o[2];
+}
+
+__global__ __launch_bounds__(256) void fits_rgb_kernel(const float* __restrict__ vals, long long n, const FitsParams* __restrict__ params,
+                                                       unsigned char* __restrict__ rgb) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    fits_rgb_pixel(vals, i, *params, rgb);
+}
+
+// ---- T tiles of one plane: the tile is grid dimension y (stats, pixels) or x (zscale) ------------------------------------------
+// mrcnn_fits_tile (include/mrcnn_hip.h): rectangle + where the tile's pixels / chunks start in the pools
+__device__ __forceinline__ long long fits_tile_chunks(long long n) { return (n + FITS_CHUNK - 1) / FITS_CHUNK; }
+
+__global__ __launch_bounds__(256) void fits_tiles_stats_kernel(const unsigned* __restrict__ plane, long long NX, int big_endian,
+                                                               const mrcnn_fits_tile* __restrict__ tiles, float* __restrict__ vals,
+                                                               FitsChunk* __restrict__ chunks) {
+    const mrcnn_fits_tile t = tiles[blockIdx.y];
+    const long long n = (long long)t.w * t.h;
+    if ((long long)blockIdx.x >= fits_tile_chunks(n)) return;            // the grid is sized for the largest tile of the batch
+    const FitsRect addr = {(long long)t.y0 * NX + t.x0, NX, t.w};
+    fits_stats_body(plane, addr, vals + t.pixel_offset, n, big_endian, (int)blockIdx.x, chunks + t.chunk_offset);
+}
+
+__global__ __launch_bounds__(1024) void fits_tiles_zscale_kernel(const mrcnn_fits_tile* __restrict__ tiles, const float* __restrict__ vals,
+                                                                 const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
+                                                                 FitsParams* __restrict__ params) {
+    const mrcnn_fits_tile t = tiles[blockIdx.x];
+    const long long n = (long long)t.w * t.h;
+    fits_zscale_body(vals + t.pixel_offset, n, (int)fits_tile_chunks(n), chunks + t.chunk_offset, c0, c1, c2, params + blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void fits_tiles_rgb_kernel(const mrcnn_fits_tile* __restrict__ tiles, const float* __restrict__ vals,
+                                                             const FitsParams* __restrict__ params, unsigned char* __restrict__ rgb) {
+    const mrcnn_fits_tile t = tiles[blockIdx.y];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)t.w * t.h) return;
+    fits_rgb_pixel(vals + t.pixel_offset, i, params[blockIdx.y], rgb + 3 * t.pixel_offset);
 }
 
 extern "C" size_t mrcnn_fits_workspace(int H, int W) {
@@ -283,5 +349,62 @@ extern "C" int mrcnn_fits_to_rgb(const void* raw, int big_endian, int H, int W, 
     hipLaunchKernelGGL(fits_zscale_kernel, dim3(1), dim3(1024), 0, s, vals, n, (int)chunks, ch, zscale_contrasts[0], zscale_contrasts[1],
                        zscale_contrasts[2], params);
     hipLaunchKernelGGL(fits_rgb_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, vals, n, params, (unsigned char*)rgb);
+    return mrcnn_launch_status();
+}
+
+// Host-side check of a tile table: every rectangle inside the plane and within the chunk limit, the pools laid out back to back
+// in table order.  Fills the totals the launches and the workspace need.
+struct FitsTilesLayout { long long pixels, chunks, max_pixels, max_chunks; };
+
+static int fits_tiles_layout(const mrcnn_fits_tile* tiles, int T, int NY, int NX, FitsTilesLayout* out) {
+    if (!tiles || T <= 0 || NY <= 0 || NX <= 0) return MRCNN_ERR_ARG;
+    FitsTilesLayout l = {0, 0, 0, 0};
+    for (int t = 0; t < T; ++t) {
+        const mrcnn_fits_tile& r = tiles[t];
+        if (r.w <= 0 || r.h <= 0 || r.x0 < 0 || r.y0 < 0 || (long long)r.x0 + r.w > NX || (long long)r.y0 + r.h > NY) return MRCNN_ERR_ARG;
+        if (r.pixel_offset != l.pixels || r.chunk_offset != l.chunks) return MRCNN_ERR_ARG;
+        const long long n = (long long)r.w * r.h;
+        const long long c = (n + FITS_CHUNK - 1) / FITS_CHUNK;
+        if (c > FITS_MAX_CHUNKS) return MRCNN_ERR_UNSUPPORTED;
+        l.pixels += n;
+        l.chunks += c;
+        if (n > l.max_pixels) l.max_pixels = n;
+        if (c > l.max_chunks) l.max_chunks = c;
+    }
+    if (T > 65535) return MRCNN_ERR_UNSUPPORTED;                          // grid dimension y
+    *out = l;
+    return MRCNN_OK;
+}
+
+extern "C" int mrcnn_fits_tiles_check(const mrcnn_fits_tile* tiles, int T, int NY, int NX) {
+    FitsTilesLayout l;
+    return fits_tiles_layout(tiles, T, NY, NX, &l);
+}
+
+extern "C" size_t mrcnn_fits_tiles_workspace(const mrcnn_fits_tile* tiles, int T, int NY, int NX) {
+    FitsTilesLayout l;
+    if (fits_tiles_layout(tiles, T, NY, NX, &l) != MRCNN_OK) return 0;
+    return (size_t)l.pixels * sizeof(float) + (size_t)l.chunks * sizeof(FitsChunk) + (size_t)T * sizeof(FitsParams) + 256;
+}
+
+extern "C" int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY, int NX, const mrcnn_fits_tile* tiles_host,
+                                       const mrcnn_fits_tile* tiles_dev, int T, const double* zscale_contrasts, void* rgb, size_t rgb_bytes,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!plane || !rgb || !zscale_contrasts || !tiles_dev) return MRCNN_ERR_ARG;
+    FitsTilesLayout l;
+    const int rc = fits_tiles_layout(tiles_host, T, NY, NX, &l);
+    if (rc != MRCNN_OK) return rc;
+    if (rgb_bytes < (size_t)l.pixels * 3) return MRCNN_ERR_ARG;
+    if (!workspace || workspace_bytes < mrcnn_fits_tiles_workspace(tiles_host, T, NY, NX)) return MRCNN_ERR_WORKSPACE;
+    float* vals = (float*)workspace;
+    FitsChunk* ch = (FitsChunk*)(vals + l.pixels);
+    FitsParams* params = (FitsParams*)(((uintptr_t)(ch + l.chunks) + 63) & ~(uintptr_t)63);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(fits_tiles_stats_kernel, dim3((unsigned)l.max_chunks, (unsigned)T), dim3(256), 0, s, (const unsigned*)plane,
+                       (long long)NX, big_endian, tiles_dev, vals, ch);
+    hipLaunchKernelGGL(fits_tiles_zscale_kernel, dim3((unsigned)T), dim3(1024), 0, s, tiles_dev, (const float*)vals, (const FitsChunk*)ch,
+                       zscale_contrasts[0], zscale_contrasts[1], zscale_contrasts[2], params);
+    hipLaunchKernelGGL(fits_tiles_rgb_kernel, dim3((unsigned)cdiv64(l.max_pixels, 256), (unsigned)T), dim3(256), 0, s, tiles_dev,
+                       (const float*)vals, (const FitsParams*)params, (unsigned char*)rgb);
     return mrcnn_launch_status();
 }

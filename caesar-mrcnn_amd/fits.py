@@ -15,6 +15,8 @@ import numpy as np
 
 logger = logging.getLogger("mrcnn")
 
+DEVICE_TILE_MAX_PIXELS = 4096 * 1024      # the size limit of the device chain (csrc/fits.hip: 4096 chunks of 1024 pixels)
+
 _BITPIX = {8: ">u1", 16: ">i2", 32: ">i4", 64: ">i8", -32: ">f4", -64: ">f8"}
 
 
@@ -235,7 +237,7 @@ def read_fits(filename, xmin=-1, xmax=-1, ymin=-1, ymax=-1, stretch=True, normal
     else:
         logger.error('ERROR: Invalid/unsupported number of channels found in file %s (nchan=%d)!' % (filename, data.ndim))
         return None
-    if on_device and out.size and out.shape[0] * out.shape[1] <= 4096 * 1024:
+    if on_device and out.size and out.shape[0] * out.shape[1] <= DEVICE_TILE_MAX_PIXELS:
         return _read_fits_device(out, zscale_contrasts, device), header
     out = out.astype(np.float32)
     out[np.isnan(out)] = np.nanmin(out)

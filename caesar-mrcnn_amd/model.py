@@ -352,36 +352,65 @@ class MaskRCNN(object):
 
     def _mold_inputs_device(self, images):
         """mold_inputs for uint8 images with the pixel work on the GPU (ops.mold_image_u8): each image crosses PCIe as its
-        uint8 bytes and is scaled, padded and mean-subtracted there.  Returns the molded batch as a device tensor
-        [B, H, W, C] float32, image_metas and windows as mold_inputs does -- or None when an image is not uint8 HxWxC or the
-        resize mode draws random numbers ("crop"): the caller then takes the host path."""
+        uint8 bytes and is scaled, padded and mean-subtracted there.  An image may also be a uint8 [h, w, C] torch tensor that is
+        already on the engine's device (the tiled source finder's tiles): it is molded where it is.  Returns the molded batch as a
+        device tensor [B, H, W, C] float32, image_metas and windows as mold_inputs does -- or None when a host image is not uint8
+        HxWxC or the resize mode draws random numbers ("crop"): the caller then takes the host path.  A tensor that cannot be
+        molded here (another device, another dtype or shape, a resize mode of the host path) raises ValueError: it never goes to
+        the host path."""
         import torch
         from . import ops
         cfg = self.config
-        if cfg.IMAGE_RESIZE_MODE not in ("square", "pad64", "none"):
+        dev = self.engine.dev
+        on_device = self._check_device_images(images)
+
+        def host_path(why):
+            """Host images go to mold_inputs (None); a batch that holds device images cannot."""
+            if on_device:
+                raise ValueError("detect: " + why)
             return None
+        if cfg.IMAGE_RESIZE_MODE not in ("square", "pad64", "none"):
+            return host_path("device images need IMAGE_RESIZE_MODE square, pad64 or none (got %r)" % cfg.IMAGE_RESIZE_MODE)
         plans = []
         for image in images:
-            if not (isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] <= 4):
-                return None
-            scale, (oh, ow), padding, window = utils.resize_plan(image.shape, cfg.IMAGE_MIN_DIM, cfg.IMAGE_MAX_DIM, cfg.IMAGE_MIN_SCALE,
+            if not torch.is_tensor(image) and not (isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and
+                                                   image.shape[2] <= 4):
+                return host_path("device images cannot share a batch with host images the GPU molding does not take")
+            scale, (oh, ow), padding, window = utils.resize_plan(tuple(image.shape), cfg.IMAGE_MIN_DIM, cfg.IMAGE_MAX_DIM, cfg.IMAGE_MIN_SCALE,
                                                                  cfg.IMAGE_RESIZE_MODE)
             canvas = (oh + padding[0][0] + padding[0][1], ow + padding[1][0] + padding[1][1])
             plans.append((scale, (oh, ow), padding, window, canvas))
         if any(p[4] != plans[0][4] for p in plans) or any(im.shape[2] != images[0].shape[2] for im in images):
-            return None                                              # the host path raises the reference's assertion
+            return host_path("after resizing, all images must have the same size")     # (the host path raises the reference's assertion)
         OH, OW = plans[0][4]
         C_ = images[0].shape[2]
-        dev = self.engine.dev
         batch = torch.empty((len(images), OH, OW, C_), dtype=torch.float32, device=dev)
         metas, windows = [], []
         for i, (image, (scale, out_hw, padding, window, canvas)) in enumerate(zip(images, plans)):
-            src = torch.from_numpy(np.ascontiguousarray(image)).to(dev, non_blocking=True)
+            if torch.is_tensor(image):
+                src = image.contiguous()
+            else:
+                src = torch.from_numpy(np.ascontiguousarray(image)).to(dev, non_blocking=True)
             ops.mold_image_u8(src, out_hw, (padding[0][0], padding[1][0]), canvas, cfg.MEAN_PIXEL, out=batch[i])
-            metas.append(utils.compose_image_meta(0, image.shape, (OH, OW, C_), window, scale,
+            metas.append(utils.compose_image_meta(0, tuple(image.shape), (OH, OW, C_), window, scale,
                                                   np.zeros([cfg.NUM_CLASSES], dtype=np.int32)))
             windows.append(window)
         return batch, np.stack(metas), np.stack(windows)
+
+    def _check_device_images(self, images):
+        """True when `images` holds torch tensors; ValueError for one that is not a uint8 [h, w, C <= 4] tensor on the engine's device."""
+        import torch
+        d = torch.device(self.engine.dev)
+        found = False
+        for image in images:
+            if not torch.is_tensor(image):
+                continue
+            found = True
+            if not image.is_cuda or image.device.index != (torch.cuda.current_device() if d.index is None else d.index):
+                raise ValueError("detect: image tensor on %s, the model runs on %s (host images go in as NumPy arrays)" % (image.device, d))
+            if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] > 4:
+                raise ValueError("detect: device images must be uint8 [h, w, C <= 4] (got %s %r)" % (image.dtype, tuple(image.shape)))
+        return found
 
     def _unmold_boxes(self, detections, original_image_shape, image_shape, window):
         """Host half of unmold_detections (mrcnn/model.py:2578-2605): the rows before the first class id 0, boxes from
@@ -509,7 +538,7 @@ class MaskRCNN(object):
         if verbose:
             log("Processing {} images".format(len(images)))
             for image in images:
-                log("image", image)
+                log("image", image if isinstance(image, np.ndarray) else image.cpu().numpy())      # (a device tensor: logged from a host copy)
         if timing is not None:
             import time
             timing["start"] = time.perf_counter()
@@ -527,7 +556,7 @@ class MaskRCNN(object):
         if timing is not None:
             timing["molded"] = time.perf_counter()
         out = self._run_graph(molded_images, image_metas)
-        results = self._detect_results(out, [im.shape for im in images], [tuple(m.shape) for m in molded_images], windows, timing)
+        results = self._detect_results(out, [tuple(im.shape) for im in images], [tuple(m.shape) for m in molded_images], windows, timing)
         if timing is not None:
             timing["end"] = time.perf_counter()
         return results

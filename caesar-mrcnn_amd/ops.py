@@ -699,6 +699,68 @@ def fits_to_rgb(raw, H, W, zscale_contrasts=(0.25, 0.25, 0.25), big_endian=False
     return out
 
 
+FITS_TILE_DTYPE = [("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("pixel_offset", "<i8"), ("chunk_offset", "<i8")]
+FITS_TILE_CHUNK = 1024                   # pixels per statistics chunk (csrc/fits.hip)
+
+
+class FitsTileUnsupported(_hip.HipPathError):
+    """A tile above the kernel's size limit (2048 x 2048 pixels): the caller takes the single-tile or the host path."""
+
+
+def fits_tile_table(tiles):
+    """mrcnn_fits_tile records (include/mrcnn_hip.h) of rectangles [(x0, y0, w, h), ...]: the pools laid out back to back in
+    table order.  Host array; nothing is checked here -- mrcnn_fits_tiles_to_rgb does that before it launches."""
+    import numpy as np
+    r = np.asarray(tiles, dtype=np.int64).reshape(-1, 4)
+    table = np.zeros(r.shape[0], dtype=FITS_TILE_DTYPE)
+    for k, name in enumerate(("x0", "y0", "w", "h")):
+        if r.shape[0] and (r[:, k].min() < -2 ** 31 or r[:, k].max() >= 2 ** 31):
+            raise ValueError("tile rectangle outside the 32-bit range")
+        table[name] = r[:, k]
+    n = np.maximum(r[:, 2], 0) * np.maximum(r[:, 3], 0)
+    table["pixel_offset"][1:] = np.cumsum(n)[:-1]
+    table["chunk_offset"][1:] = np.cumsum((n + FITS_TILE_CHUNK - 1) // FITS_TILE_CHUNK)[:-1]
+    return table
+
+
+def fits_tiles_to_rgb(plane, tiles, zscale_contrasts=(0.25, 0.25, 0.25), big_endian=False):
+    """fits_to_rgb for T tiles of one plane that is already on the device, every stage one launch over all tiles
+    (mrcnn_fits_tiles_to_rgb).  plane: [NY, NX] float32 device tensor, or with big_endian=True the file's bytes as uint8
+    [NY, NX, 4]; tiles: T rectangles (x0, y0, w, h) in plane pixels -- sizes may differ, rectangles may overlap.  Returns a list
+    of T uint8 [h, w, 3] device tensors, views into one pool, each byte-identical to fits.read_fits of that cut.  Runs on the
+    current stream.  ValueError for a malformed table (no tile, w or h <= 0, a rectangle that leaves the plane),
+    FitsTileUnsupported for a tile above 2048 x 2048 pixels; neither launches or writes anything."""
+    import numpy as np
+    _need_cuda(plane)
+    if plane.dim() < 2 or plane.numel() * plane.element_size() != 4 * plane.shape[0] * plane.shape[1]:
+        raise ValueError("plane must hold NY x NX float32 values (got shape %r, dtype %s)" % (tuple(plane.shape), plane.dtype))
+    NY, NX = int(plane.shape[0]), int(plane.shape[1])
+    table = fits_tile_table(tiles)
+    T = int(table.shape[0])
+    L = _hip.lib()
+    host = table.ctypes.data_as(C.c_void_p)
+    zc = (C.c_double * 3)(*[float(v) for v in zscale_contrasts])
+    stream = current_stream()
+    rc = L.mrcnn_fits_tiles_check(host, T, NY, NX)          # the call's own host-side check: nothing is allocated for a refused table
+    if rc == ERR_UNSUPPORTED:
+        raise FitsTileUnsupported("mrcnn_fits_tiles_to_rgb: a tile above the kernel's size limit (2048 x 2048 pixels)")
+    if rc:
+        raise ValueError("mrcnn_fits_tiles_to_rgb refuses the tiles (status %d): no tile, an empty rectangle or one outside the "
+                         "%d x %d plane" % (rc, NY, NX))
+    nbytes = L.mrcnn_fits_tiles_workspace(host, T, NY, NX)
+    ws = workspace(nbytes, plane.device, "fits_tiles")
+    total = int(table["pixel_offset"][-1]) + int(table["w"][-1]) * int(table["h"][-1])
+    pool = torch.empty(3 * total, dtype=torch.uint8, device=plane.device)
+    table_dev = torch.from_numpy(table.view(np.uint8)).to(plane.device)
+    check(L.mrcnn_fits_tiles_to_rgb(ptr(plane), 1 if big_endian else 0, NY, NX, host, ptr(table_dev), T, zc, ptr(pool), pool.numel(),
+                                    ptr(ws), ws.numel(), stream), "mrcnn_fits_tiles_to_rgb")
+    out = []
+    for r in table:
+        o, h, w = 3 * int(r["pixel_offset"]), int(r["h"]), int(r["w"])
+        out.append(pool[o:o + 3 * h * w].view(h, w, 3))
+    return out
+
+
 def mold_image_u8(src, out_hw, pad_tl, canvas_hw, mean_pixel, out=None):
     """utils.resize_image's pixel work + mold_image on the device (mrcnn/model.py:2519-2556): src [h, w, C] uint8 device ->
     float32 [OH, OW, C]: the image scaled to out_hw (bilinear, float64, clipped to the image's range, truncated to uint8; a copy

@@ -22,6 +22,11 @@ it).  It has two implementations as well, behind ``SFinder.params_device``:
                                    loop in one launch (csrc/srcparams.hip through ops.source_params), every ratio and the dicts
                                    formed by the host code that also finishes the per-source statement.
 
+The front of a tiled run -- read the tile, stretch it, detect -- has a batched form behind ``SFinder.tile_batch`` (default 0:
+the per-tile loop of the reference; run.py --tile_batch N): the mosaic plane is read and uploaded once, the tiles of a group of
+N are cut and stretched on the GPU in one ops.fits_tiles_to_rgb call and go to ONE model.detect call as device tensors
+(``prepare_tile_images`` / ``_detect_images``); every tile's Analyzer then takes its own result (TileTask.accept_detection).
+
 astropy.stats.sigma_clipped_stats and astropy.wcs.WCS are restated in fits.py (sigma_clipped_stats, SimpleWCS), unpinned;
 cv.moments is its defining sums.  Not restated: plots.
 """
@@ -115,6 +120,27 @@ class TileTask(object):
             logger.warning("[PROC %d] Failed to read tile image for task %d!" % (self.procId, self.tid))
             return -1
         self.imgdata, self.imgheader = res
+        analyzer = self._analyzer()
+        if analyzer.predict(self.imgdata, self.image_id, header=self.imgheader, xmin=self.ix_min, ymin=self.iy_min) < 0:
+            logger.error("[PROC %d] Failed to run model prediction on tile image for task %d!" % (self.procId, self.tid))
+            return -1
+        return self._take(analyzer)
+
+    def accept_detection(self, image_shape, header, r, masks_device=None):
+        """find_sources for a tile whose image was made and detected elsewhere (SFinder's batched front end): `r` is the tile's
+        entry of model.detect's result, `masks_device` the device tensor behind r['masks'] (or None).  The image itself is not
+        needed -- only its shape is."""
+        self.bboxes_det = self.scores_det = self.classid_det = self.masks_det = None
+        self.imgdata, self.imgheader = None, header
+        analyzer = self._analyzer()
+        if analyzer.accept_detection(tuple(image_shape), r, masks_device, self.image_id, header=header, xmin=self.ix_min,
+                                     ymin=self.iy_min) < 0:
+            logger.error("[PROC %d] Failed to run model prediction on tile image for task %d!" % (self.procId, self.tid))
+            return -1
+        return self._take(analyzer)
+
+    def _analyzer(self):
+        cfg = self.config
         analyzer = Analyzer(self.model, cfg)
         analyzer.draw = False
         analyzer.iou_thr, analyzer.score_thr = cfg.IOU_THR, cfg.SCORE_THR
@@ -123,9 +149,10 @@ class TileTask(object):
         analyzer.write_to_ds9 = self.save_regions
         analyzer.outfile_ds9 = 'catalog_' + self.image_id + '_tid' + str(self.tid) + '.reg'
         analyzer.obj_name_tag = self.sname_tag
-        if analyzer.predict(self.imgdata, self.image_id, header=self.imgheader, xmin=self.ix_min, ymin=self.iy_min) < 0:
-            logger.error("[PROC %d] Failed to run model prediction on tile image for task %d!" % (self.procId, self.tid))
-            return -1
+        return analyzer
+
+    def _take(self, analyzer):
+        """The Analyzer's results + the tile info (sfinder.py:221-259)."""
         if not analyzer.bboxes:                                   # sfinder.py:221-224: det_sources stays empty
             logger.info("[PROC %d] No object detected in tile image for task %d ..." % (self.procId, self.tid))
             return 0
@@ -232,7 +259,11 @@ class SFinder(object):
         self.params_timing = {}
         self.beamArea = 0
         self.wcs = None
-        self._plane = None                # (image plane as stored, path) while compute_sources_params runs
+        self._plane = None                # (image plane as stored, path, header) while tiles / compute_sources_params need it
+        self._plane_dev = None            # (its device copy, big-endian bytes?, path): uploaded once, shared by both
+        # Tiles per model.detect call of run_parallel.  0: the reference's loop, one file read / host stretch / detect per tile.
+        # N >= 1: the batched, device-resident front end (needs the run.py read_fits flags and a model built for batches of N).
+        self.tile_batch = 0
         self._wcs_warned = False
 
     def _device(self):
@@ -255,7 +286,7 @@ class SFinder(object):
     # ---- image / tile parameters (sfinder.py:336-444) -------------------------------------------------------
     def set_img_size_params(self):
         cfg = self.config
-        self.header = fits.get_fits_header(cfg.IMG_PATH)
+        self.header = self._read_header()
         if self.header is None:
             logger.error("[PROC %d] Header read from image %s is None!" % (self.procId, cfg.IMG_PATH))
             return -1
@@ -298,13 +329,41 @@ class SFinder(object):
             logger.warning("[PROC %d] Beam area not computed (%s: %s)" % (self.procId, type(e).__name__, e))
             self.beamArea = 0
         self.wcs = fits.SimpleWCS.from_header(self.header)                # :442
-        self._plane = None
+        if not self._tiles_batched():
+            self._drop_plane()
         return 0
+
+    def _tiles_batched(self):
+        """True when run_parallel takes the batched front end: tile_batch set and the read_fits flags those of run.py (stretch,
+        normalize, RGB, uint8, no bias / contrast stretch -- what the device chain computes; fits.read_fits(device=) asks the same)."""
+        cfg = self.config
+        return bool(self.tile_batch >= 1 and cfg.ZSCALE_STRETCH and cfg.NORMALIZE_IMG and cfg.IMG_TO_RGB and cfg.IMG_TO_UINT8 and
+                    not cfg.BIAS_CONTRAST_STRETCH)
+
+    def _read_header(self):
+        """The header of the image; on the batched path from the ONE read of the file that also gives the plane."""
+        if self._tiles_batched():
+            self._drop_plane()
+            try:
+                self._image_plane()
+                return self._plane[2]
+            except Exception as e:
+                logger.warning("[PROC %d] Image plane of %s not read (%s: %s)" % (self.procId, self.config.IMG_PATH, type(e).__name__, e))
+                self._drop_plane()
+        return fits.get_fits_header(self.config.IMG_PATH)
+
+    def _drop_plane(self):
+        self._plane = self._plane_dev = None
 
     # ---- single image (sfinder.py:450-523) ------------------------------------------------------------------
     def run(self):
         cfg = self.config
-        if self.set_img_size_params() < 0:
+        batch, self.tile_batch = self.tile_batch, 0           # one image, no tiles: nothing here would use a resident plane
+        try:
+            rc = self.set_img_size_params()
+        finally:
+            self.tile_batch = batch
+        if rc < 0:
             logger.error("Failed to set image size parameters!")
             return -1
         res = fits.read_fits(cfg.IMG_PATH, cfg.IMG_XMIN, cfg.IMG_XMAX, cfg.IMG_YMIN, cfg.IMG_YMAX, stretch=cfg.ZSCALE_STRETCH,
@@ -345,6 +404,12 @@ class SFinder(object):
 
     # ---- tiles (sfinder.py:549-638) ---------------------------------------------------------------------------
     def run_parallel(self):
+        try:
+            return self._run_parallel()
+        finally:
+            self._drop_plane()                  # the whole image, host and device copy: never kept beyond the run
+
+    def _run_parallel(self):
         self.init_mpi()
         t0 = time.time()
         status = 0
@@ -356,21 +421,22 @@ class SFinder(object):
             status = -2
         if status == 0:
             tasks = self.tasks_per_worker[self.procId]
-            for j, task in enumerate(tasks):
-                logger.info("[PROC %d] Start processing of task id %d (%d/%d) ..." % (self.procId, task.tid, j + 1, len(tasks)))
-                try:
-                    rc = task.find_sources()
-                except Exception as e:              # a failing tile must not keep this rank out of the gather below
-                    logger.error("[PROC %d] Task id %d raised %s: %s" % (self.procId, task.tid, type(e).__name__, e))
-                    task.det_sources = {}
-                    rc = -1
-                if rc < 0:                          # sfinder.py:583-586: log, remember, next tile
-                    logger.error("[PROC %d] Failed to find sources in task no. %d, skip to next!" % (self.procId, j))
-                    status = -1
-                    continue
-                self.find_sources_at_edge(j)
+            if self._tiles_batched():
+                status = self._run_tasks_batched(tasks)
+            else:
+                if self.tile_batch >= 1:
+                    logger.info("[PROC %d] tile_batch = %d ignored: the read_fits flags are not the run.py ones (stretch, normalize, RGB, "
+                                "uint8, no bias/contrast stretch); tiles are read and detected one at a time" % (self.procId, self.tile_batch))
+                for j, task in enumerate(tasks):
+                    logger.info("[PROC %d] Start processing of task id %d (%d/%d) ..." % (self.procId, task.tid, j + 1, len(tasks)))
+                    if self._run_task(j, task, task.find_sources) < 0:
+                        status = -1
             if status < 0:
                 logger.warning("[PROC %d] One or more errors occurred in source finding tasks..." % self.procId)
+            if self.procId != self.MASTER_ID or not self.compute_params:
+                self._drop_plane()
+            elif not self.params_device:
+                self._plane_dev = None          # the host statement of the parameters cuts from the host copy
         # every rank arrives here, whatever happened above (the reference returns early on a set-up error and leaves the others
         # in the barrier): a rank whose set-up failed contributes nothing
         if self.gather_task_data_from_workers(skip_local=(status == -2)) < 0:
@@ -386,6 +452,89 @@ class SFinder(object):
             self.save()
             logger.info("[PROC %d] Run completed in %d seconds" % (self.procId, time.time() - t0))
         return 0
+
+    def _run_task(self, j, task, find):
+        """One tile: find() fills task.det_sources (0 / -1), then the edge flags.  -1 when the tile failed."""
+        try:
+            rc = find()
+        except Exception as e:              # a failing tile must not keep this rank out of the gather below
+            logger.error("[PROC %d] Task id %d raised %s: %s" % (self.procId, task.tid, type(e).__name__, e))
+            task.det_sources = {}
+            rc = -1
+        if rc < 0:                          # sfinder.py:583-586: log, remember, next tile
+            logger.error("[PROC %d] Failed to find sources in task no. %d, skip to next!" % (self.procId, j))
+            return -1
+        self.find_sources_at_edge(j)
+        return 0
+
+    # ---- tiles, N per detect call ---------------------------------------------------------------------------------
+    def _run_tasks_batched(self, tasks):
+        """This rank's tiles in task order, in groups of tile_batch: one prepare_tile_images + one _detect_images per group, then
+        per tile the Analyzer and the edge flags as in the loop above.  A tile read_fits would refuse (xmax <= xmin) fails alone;
+        a tile the device chain does not take (above its size limit, a negative corner) and every tile of a group whose prepare or
+        detect raised go through task.find_sources(), so that a bad tile or batch costs what it costs today."""
+        N = int(self.tile_batch)
+        status = 0
+        for g0 in range(0, len(tasks), N):
+            group = list(range(g0, min(g0 + N, len(tasks))))
+            refused = [j for j in group if tasks[j].ix_max <= tasks[j].ix_min or tasks[j].iy_max <= tasks[j].iy_min]
+            batched = [j for j in group if j not in refused and self._tile_batchable(tasks[j])]
+            results = {}
+            if batched:
+                try:
+                    images = self.prepare_tile_images([tasks[j] for j in batched])
+                    results = dict(zip(batched, self._detect_images(images)))
+                except Exception as e:
+                    logger.error("[PROC %d] Tiles %s: batched read / detect raised %s: %s; taking them one at a time" % (
+                        self.procId, [tasks[j].tid for j in batched], type(e).__name__, e))
+                    results = {}
+            for j in group:
+                task = tasks[j]
+                logger.info("[PROC %d] Start processing of task id %d (%d/%d) ..." % (self.procId, task.tid, j + 1, len(tasks)))
+                if j in refused:
+                    logger.error("xmax/ymax must be > xmin/ymin for tile reading!")
+                    logger.warning("[PROC %d] Failed to read tile image for task %d!" % (self.procId, task.tid))
+                    find = lambda: -1
+                elif j in results:
+                    find = lambda task=task, res=results[j]: task.accept_detection(res[0], self.header, res[1], res[2])
+                else:
+                    find = task.find_sources
+                if self._run_task(j, task, find) < 0:
+                    status = -1
+        return status
+
+    def _tile_batchable(self, task):
+        return min(task.ix_min, task.ix_max, task.iy_min, task.iy_max) >= 0 and \
+            (task.ix_max - task.ix_min) * (task.iy_max - task.iy_min) <= fits.DEVICE_TILE_MAX_PIXELS
+
+    def prepare_tile_images(self, tasks):
+        """The network input images of `tasks`' tiles, in order: uint8 [h, w, 3] device tensors, cut from the resident plane (as
+        NumPy slicing cuts: clipped to the plane), NaN-filled, zscaled, normalised and converted in one ops.fits_tiles_to_rgb call --
+        byte for byte what fits.read_fits gives per tile."""
+        from . import ops
+        plane_t, big = self._plane_device()
+        ny, nx = int(plane_t.shape[0]), int(plane_t.shape[1])
+        rects = []
+        for t in tasks:
+            x0, x1, y0, y1 = min(t.ix_min, nx), min(t.ix_max, nx), min(t.iy_min, ny), min(t.iy_max, ny)
+            rects.append((x0, y0, x1 - x0, y1 - y0))
+        return ops.fits_tiles_to_rgb(plane_t, rects, self._zscale_contrasts(), big_endian=big)
+
+    def _zscale_contrasts(self):
+        zc = self.config.ZSCALE_CONTRASTS
+        return zc if len(zc) == 3 else [0.25, 0.25, 0.25]                 # read_fits: any other length is ignored
+
+    def _detect_images(self, images):
+        """One model.detect call on a group of tile images (host arrays or device tensors).  The model takes exactly tile_batch
+        images: a short group is padded by repeating its last image, and what the padding produced is dropped, the device masks
+        the model keeps (last_masks_device) included.  Returns per image (shape, result dict, device masks or None)."""
+        n, N = len(images), int(self.tile_batch)
+        padded = list(images) + [images[-1]] * (N - n)
+        res = self.model.detect(padded, verbose=0)
+        kept = getattr(self.model, "last_masks_device", None)
+        if isinstance(kept, list) and len(kept) > n:
+            del kept[n:]
+        return [(tuple(int(v) for v in images[i].shape), res[i], kept[i] if kept and i < len(kept) else None) for i in range(n)]
 
     # ---- edge flags (sfinder.py:643-706) ----------------------------------------------------------------------
     def find_sources_at_edge(self, tindex):
@@ -646,13 +795,32 @@ class SFinder(object):
         it when it is done."""
         path = self.config.IMG_PATH
         if self._plane is None or self._plane[1] != path:
-            data, _ = fits.read_primary_hdu(path, native=False)
+            data, header = fits.read_primary_hdu(path, native=False)
             if data.ndim == 4:
                 data = data[0, 0]
             elif data.ndim != 2:
                 raise ValueError("Invalid/unsupported number of channels found in file %s (nchan=%d)!" % (path, data.ndim))
-            self._plane = (data, path)
+            self._plane = (data, path, header)
         return self._plane[0]
+
+    def _plane_device(self):
+        """(_image_plane() on the device, big-endian?), uploaded once per run: an unscaled float32 image as the file's big-endian
+        bytes (uint8 [ny, nx, 4]: the kernels swap what they read), anything else as float32 converted on the host once -- value for
+        value what read_fits's per-tile astype(float32) gives."""
+        path = self.config.IMG_PATH
+        if self._plane_dev is None or self._plane_dev[2] != path:
+            plane = self._image_plane()
+            self._plane_dev = (self._upload_plane(plane), plane.dtype == np.dtype(">f4"), path)
+        return self._plane_dev[0], self._plane_dev[1]
+
+    def _upload_plane(self, plane):
+        import torch
+        ny, nx = plane.shape
+        if plane.dtype == np.dtype(">f4"):
+            raw = torch.from_numpy(np.array(plane, order="C", copy=True).view(np.uint8).reshape(ny, nx, 4))     # (the file view is read-only)
+        else:
+            raw = torch.from_numpy(np.ascontiguousarray(plane, dtype=np.float32))
+        return raw.to(self._device())
 
     def _cutout_geometry(self, source, offset=10):
         """:1006-1016: (xmin, xmax, ymin, ymax, dx, dy, img_offset_x, img_offset_y).  dx = x2 - x1 + 1 whether x2 is the inclusive
@@ -760,7 +928,7 @@ class SFinder(object):
                 logger.warning("[PROC %d] Source parameters on the host: %s" % (self.procId, e))
         t1 = clock()
         failed = sum(0 if self._host_params(sources[i]) else 1 for i in host)
-        self._plane = None                                                # the whole image: not kept beyond this step
+        self._drop_plane()                                                # the whole image: not kept beyond this step
         self.params_timing.update({"host_sources": len(host), "device_sources": len(sources) - len(host), "failed_sources": failed,
                                    "device_path_ms": round(1e3 * (t1 - t0), 3), "host_statement_ms": round(1e3 * (clock() - t1), 3)})
         return 0
@@ -796,12 +964,7 @@ class SFinder(object):
         if tuple(plane.shape) != (self.ny, self.nx):
             from ._hip import HipPathError
             raise HipPathError("image plane %r is not the %d x %d the header states" % (plane.shape, self.ny, self.nx))
-        big = plane.dtype == np.dtype(">f4")
-        if big:
-            raw = torch.from_numpy(np.array(plane, order="C", copy=True).view(np.uint8).reshape(self.ny, self.nx, 4))
-        else:
-            raw = torch.from_numpy(np.ascontiguousarray(plane, dtype=np.float32))
-        img_t = raw.to(dev)
+        img_t, big = self._plane_device()                                  # the batched tile front end's upload, when it made one
         t.append(clock())
         pool, desc = pack_sources(pix)
         t.append(clock())

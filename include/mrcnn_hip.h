@@ -326,6 +326,30 @@ size_t mrcnn_fits_workspace(int H, int W);
 int mrcnn_fits_to_rgb(const void* raw, int big_endian, int H, int W, const double* zscale_contrasts, void* rgb, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* The same chain for T tiles of ONE plane that stays on the device (the mosaic of the tiled source finder), each of the three
+ * stages one launch over all tiles:
+ *   plane       [NY, NX] float32, native or (big_endian != 0) in FITS byte order; addressed with 64-bit indices, row stride NX;
+ *   tiles_host  T rectangles (columns x0 .. x0 + w - 1, rows y0 .. y0 + h - 1; sizes may differ, rectangles may overlap) with the
+ *               layout of the pools: pixel_offset[t] = sum of w * h of the tiles before t, chunk_offset[t] = sum of their
+ *               ceil(w * h / 1024); HOST pointer, checked before anything is launched: T <= 0, w or h <= 0, a rectangle that
+ *               leaves the plane or offsets other than these: MRCNN_ERR_ARG; a tile of more than 2048 x 2048 pixels (or
+ *               T > 65535): MRCNN_ERR_UNSUPPORTED -- nothing launched, nothing written;
+ *   tiles_dev   the same table on the device;
+ *   rgb         pool of rgb_bytes >= 3 * sum(w * h) bytes: tile t is the [h, w, 3] uint8 image at byte 3 * pixel_offset[t], each
+ *               byte-identical to mrcnn_fits_to_rgb of that cut (pixels enumerated row-major within the tile).
+ * workspace: mrcnn_fits_tiles_workspace(tiles_host, T, NY, NX) bytes (0 for a table the call would refuse);
+ * mrcnn_fits_tiles_check: the status the call would return for that table (the host-side check alone; launches nothing).     */
+typedef struct mrcnn_fits_tile {
+    int32_t x0, y0, w, h;
+    int64_t pixel_offset;
+    int64_t chunk_offset;
+} mrcnn_fits_tile;
+int mrcnn_fits_tiles_check(const mrcnn_fits_tile* tiles_host, int T, int NY, int NX);
+size_t mrcnn_fits_tiles_workspace(const mrcnn_fits_tile* tiles_host, int T, int NY, int NX);
+int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY, int NX, const mrcnn_fits_tile* tiles_host,
+                            const mrcnn_fits_tile* tiles_dev, int T, const double* zscale_contrasts, void* rgb, size_t rgb_bytes,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* detect() pre-processing (MaskRCNN.mold_inputs, mrcnn/model.py:2519-2556, for uint8 images): utils.resize_image's pixel work
  * (mrcnn/utils.py:456-561: bilinear up-scaling h x w -> oh x ow through skimage.transform.resize(order=1, mode='constant',
  * clip=True, preserve_range=True) [3P], zero padding into the OH x OW canvas at (top, left), cast to uint8) and mold_image

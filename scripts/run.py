@@ -14,7 +14,8 @@ selection) on every tile and writes the objects as JSON (`out_<image>.json`: ima
 y1, y2, class_id, class_name, score, pixels, vertexes, edge]) and DS9 regions.  Plots are not produced.
 `detect --split_img_in_tiles --merge_tile_sources` is the reference's SFinder (caesar_mrcnn_amd/sfinder.py): sources that
 straddle tile borders are merged and one catalogue (objects gain `merged`, names S1..Sn) is written by rank 0; with
-`--compute_source_params` every object also gains the reference's parameters (nPix, S .. flux, X0 .. Y0w_wcs, Xmin .. Ymax_wcs).
+`--compute_source_params` every object also gains the reference's parameters (nPix, S .. flux, X0 .. Y0w_wcs, Xmin .. Ymax_wcs);
+with `--tile_batch N` the mosaic is read and uploaded once and the tiles are cut, stretched and detected N at a time on the GPU.
 """
 import argparse
 import json
@@ -109,7 +110,17 @@ def parse_args(argv=None):
     p.add_argument('--compute_source_params', action='store_true', default=False,
                    help="with --merge_tile_sources: add the reference's source parameters (pixel count, flux statistics, "
                         "centroids, sky positions) to every catalogue entry before it is written")
+    p.add_argument('--tile_batch', type=int, default=0,
+                   help="extension, with --split_img_in_tiles --merge_tile_sources: read and upload the mosaic once, cut and stretch "
+                        "the tiles on the GPU and detect them N at a time (the model is built for batches of N); needs the default "
+                        "stretch flags; default 0: one file read, host stretch and detect call per tile")
     return p.parse_args(argv)
+
+
+def tile_batch_of(args):
+    """--tile_batch N where it means something: `detect --split_img_in_tiles --merge_tile_sources`; else 0."""
+    n = getattr(args, "tile_batch", 0)
+    return n if n >= 1 and args.command == "detect" and args.split_img_in_tiles and args.merge_tile_sources else 0
 
 
 def build_config(args, class_dict_model):
@@ -123,6 +134,8 @@ def build_config(args, class_dict_model):
     inference = args.command in ("test", "detect")
     cfg.GPU_COUNT = 1 if inference else args.ngpu
     cfg.IMAGES_PER_GPU = 1 if inference else args.nimg_per_gpu
+    if tile_batch_of(args):
+        cfg.IMAGES_PER_GPU = tile_batch_of(args)             # SFinder hands the model that many tiles per detect call
     cfg.LOSS_WEIGHTS = {"%s_loss" % n: getattr(args, "%s_loss_weight" % n)
                         for n in ("rpn_class", "rpn_bbox", "mrcnn_class", "mrcnn_bbox", "mrcnn_mask")}
     cfg.USE_LOSSES = {"%s_loss" % n: getattr(args, "%s_loss" % n)
@@ -299,6 +312,7 @@ def detect_merged(args, model, cfg):
     sf.outfile_json = args.detect_outfile_json or ("out_%s.json" % base)
     sf.outfile_ds9 = os.path.splitext(sf.outfile_json)[0] + ".reg"
     sf.compute_params = bool(args.compute_source_params)
+    sf.tile_batch = tile_batch_of(args)
     if sf.run_parallel() < 0:
         logger.error("Failed to run the tiled source finder on image %s!" % args.image)
         return -1
