@@ -132,6 +132,11 @@ _SIGNATURES = {
     "mrcnn_fits_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "mrcnn_fits_to_rgb": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
     # tiles_host is a HOST table (numpy, a 32-byte record per tile: ops.FITS_TILE_DTYPE)
+    "mrcnn_outline_check": (C.c_int, [_P, C.c_int, C.c_int64, _P]),
+    "mrcnn_outline_workspace": (C.c_size_t, [_P, C.c_int, C.c_int64, _P]),
+    "mrcnn_outline_count": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, C.c_size_t, _P, _P, _P]),
+    "mrcnn_outline_emit": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, _P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_int64, _P, C.c_int64,
+                                     _P, _P, C.c_int64, _P]),
     "mrcnn_fits_tiles_check": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "mrcnn_fits_tiles_workspace": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
     "mrcnn_fits_tiles_to_rgb": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_double), _P, C.c_size_t, _P,
@@ -214,7 +219,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_tiles_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats")
+_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats")
 
 
 class _LibProxy(object):

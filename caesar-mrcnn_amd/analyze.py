@@ -51,6 +51,7 @@ NO_SPLIT_CLASSES_GT = ('galaxy_C2', 'galaxy_C3', 'galaxy', 'extended', 'extended
 
 _device_fallback_logged = False
 _eval_fallback_logged = False
+_results_device_failed = False          # make_json_results_device raised once: this process stays on the host statement
 
 
 # ---- restated third-party helpers -----------------------------------------------------------------------
@@ -177,6 +178,68 @@ def find_contours(arr, level=0.5):
             head.append(q)
             ends[q] = (head, head_num)
     return [np.array(c) for _, c in sorted(contours.items())]
+
+
+# Marching-squares edges of a cell: top, left, bottom, right.  Start (p) and end (q) edge of the first segment of every case of the
+# table in find_contours; a saddle's second segment runs left -> bottom (case 6) or bottom -> right (case 9).
+_EDGE_T, _EDGE_L, _EDGE_B, _EDGE_R = 0, 1, 2, 3
+_SEG_P = np.array([0, 0, 3, 3, 1, 0, 3, 3, 2, 0, 2, 2, 1, 0, 1, 0])
+_SEG_Q = np.array([0, 1, 0, 1, 2, 2, 0, 2, 3, 1, 0, 1, 3, 3, 0, 0])
+_EDGE_DX2 = np.array([-1, -2, -1, 0])        # twice the offset of an edge's midpoint from (c, r), mask coordinates
+_EDGE_DY2 = np.array([-2, -1, 0, -1])
+
+
+def outline_statement(mask):
+    """(contours, pixels) of ONE 2-D mask of 0 / 1: what ``make_json_results`` takes from ``find_contours`` on the zero-padded
+    mask and from ``np.argwhere``, stated without the sequential stitching -- the definition of csrc/outline.hip's results.
+    contours: list of float64 [L + 1, 2] arrays of (x, y), pixel centres at integers, in find_contours' order and starting
+    point; pixels: int64 [K, 2] of (y, x) in raster order.
+
+      1. cells (r, c) of the padded mask in raster order, corners mask[r - 1 .. r, c - 1 .. c]; a cell's segments in the order of
+         find_contours' table (a saddle has two): segment k of cell (r, c) has index 2 * (r * cols + c) + k;
+      2. every crossing point lies on one grid edge shared by two cells, so it ends one segment and starts one: succ(s) is the
+         segment that starts where s ends, and on a padded mask every contour is a cycle of succ;
+      3. contours are ordered by the smallest index of their cycle;
+      4. with `last` the largest index of the cycle, the contour is p(succ(last)), p(succ^2(last)), ..., p(last), q(last);
+      5. level 0.5 between 0 and 1 puts every crossing at an edge's midpoint: coordinates are multiples of 0.5, exact.
+    Not a fast path: the cycles are walked in Python."""
+    m = np.asarray(mask)
+    if m.ndim != 2:
+        raise ValueError("outline_statement: one 2-D mask, got shape %r" % (m.shape,))
+    h, w = m.shape
+    pixels = np.argwhere(m == 1)
+    hi = np.zeros((h + 2, w + 2), bool)
+    hi[1:-1, 1:-1] = m > 0.5
+    case = hi[:-1, :-1] * 1 + hi[:-1, 1:] * 2 + hi[1:, :-1] * 4 + hi[1:, 1:] * 8
+    rr, cc = np.nonzero((case != 0) & (case != 15))
+    kk = case[rr, cc]
+    cell = np.repeat(np.arange(rr.size), 1 + ((kk == 6) | (kk == 9)))         # rule 1: raster order, saddles twice
+    second = np.zeros(cell.size, bool)
+    second[1:] = cell[1:] == cell[:-1]
+    r, c, k = rr[cell], cc[cell], kk[cell]
+    pe = np.where(second, np.where(k == 6, _EDGE_L, _EDGE_B), _SEG_P[k])
+    qe = np.where(second, np.where(k == 6, _EDGE_B, _EDGE_R), _SEG_Q[k])
+    px2, py2 = 2 * c + _EDGE_DX2[pe], 2 * r + _EDGE_DY2[pe]                      # rule 5: doubled coordinates are integers
+    qx2, qy2 = 2 * c + _EDGE_DX2[qe], 2 * r + _EDGE_DY2[qe]
+    pkey, qkey = (py2 + 2) * (2 * w + 4) + px2 + 2, (qy2 + 2) * (2 * w + 4) + qx2 + 2
+    by_p = np.argsort(pkey)
+    succ = by_p[np.searchsorted(pkey[by_p], qkey)] if cell.size else by_p      # rule 2
+    contours, seen = [], np.zeros(cell.size, bool)
+    for first in range(cell.size):                                             # rule 3: a cycle is met at its smallest index
+        if seen[first]:
+            continue
+        cycle, s = [first], int(succ[first])
+        while s != first:
+            cycle.append(s)
+            s = int(succ[s])
+        cycle = np.array(cycle)
+        seen[cycle] = True
+        at = int(np.argmax(cycle))                                             # rule 4
+        walk = np.roll(cycle, -(at + 1))                                       # succ(last), ..., last
+        x2 = np.append(px2[walk], qx2[walk[-1]])
+        y2 = np.append(py2[walk], qy2[walk[-1]])
+        contours.append(np.stack([x2, y2], axis=1) / 2.0)
+    return contours, pixels
 
 
 def maximal_cliques(adj):
@@ -321,6 +384,12 @@ class Analyzer(object):
     # statement on an MI355X host.  None = no such run is recorded: the device path stays off by default.
     EVAL_DEVICE_MIN_PAIRS = 9
 
+    # The contours and pixel lists of make_json_results on the device (csrc/outline.hip): off by default.  With the switch on,
+    # frames with fewer final masks than RESULTS_DEVICE_MIN_MASKS stay on the host statement: the smallest count at which
+    # tools/outline_bench.py measured the device form ahead on an MI355X host (profiles/outline_bench.json).
+    RESULTS_DEVICE = False
+    RESULTS_DEVICE_MIN_MASKS = 1
+
     def __init__(self, model, config, dataset=None, gt_data=None, pred_data=None):
         # Off by default: the device path is equal to the host statement value for value (tests/test_analyze_post_gpu.py) but
         # has not been timed against it on an MI355X host yet, and a frame with one to three detections costs the host
@@ -329,6 +398,9 @@ class Analyzer(object):
         self.postprocess_device_min_masks = self.POSTPROCESS_DEVICE_MIN_MASKS
         self.postprocess_sync_timing = False     # synchronise after every device phase, so that postprocess_timing splits them
         self.postprocess_timing = {}
+        self.results_device = self.RESULTS_DEVICE
+        self.results_device_min_masks = self.RESULTS_DEVICE_MIN_MASKS
+        self.results_timing = {}
         # The device tensor behind self.masks, when the model kept it, and the host array it mirrors (both set by predict).
         # The device path uses the tensor only while self.masks IS that array: masks assigned by hand are uploaded.
         self.masks_device = None
@@ -1182,7 +1254,80 @@ class Analyzer(object):
             print(value)
 
     # ---- JSON (analyze.py:1866-1955) -----------------------------------------------------------------------
+    def _results_masks_ok(self):
+        """The device form outlines bit planes: every final mask 2-D, of one shape, bool or integer 0 / 1 (the host statement
+        takes `mask == 1` for the pixels but `> 0.5` for the contours, so any other value stays with it)."""
+        shape = None
+        for m in self.masks_final:
+            m = np.asarray(m)
+            if m.ndim != 2 or m.size == 0 or (shape is not None and m.shape != shape):
+                return False
+            shape = m.shape
+            if m.dtype != np.bool_ and not (m.dtype.kind in "iu" and int(m.min()) >= 0 and int(m.max()) <= 1):
+                return False
+        return shape is not None
+
     def make_json_results(self):
+        """The result dictionary: contours and pixel lists on the GPU (``make_json_results_device``) when ``results_device`` is
+        set (default: off), a GPU is there, there are at least ``results_device_min_masks`` final masks and they are 0 / 1
+        masks of one shape; else by the host statement.  Both give the same dictionary, value for value."""
+        global _results_device_failed
+        self.results_timing = {}
+        if self.results_device and not _results_device_failed and len(self.masks_final) >= max(self.results_device_min_masks, 1) \
+                and Analyzer.has_gpu(self.model) and self._results_masks_ok():
+            from . import _hip
+            try:
+                return self.make_json_results_device()
+            except (_hip.HipPathError, OSError) as e:
+                _results_device_failed = True
+                logger.error("make_json_results_device failed (%s: %s): this and every later call take the host statement "
+                             "(find_contours and np.argwhere on full frames) ..." % (type(e).__name__, e))
+        return self.make_json_results_host()
+
+    def make_json_results_device(self):
+        """make_json_results_host with find_contours and np.argwhere of all final masks replaced by one ops.mask_plane_outlines
+        call on the frame's bit planes -- those extract_det_masks_device left on the device, else one upload and pack of
+        masks_final -- and one download."""
+        import torch
+        from . import ops
+        clock = time.perf_counter
+        t0 = clock()
+        n = len(self.masks_final)
+        timing = {"masks": n, "mask_uploads": 0}
+        if self._final_planes is not None and self._final_planes[1] is self.masks_final:
+            planes = self._final_planes[0]
+        else:
+            stack = np.ascontiguousarray(np.stack([np.asarray(m) != 0 for m in self.masks_final], axis=-1))
+            planes = ops.mask_planes_pack(torch.from_numpy(stack.view(np.uint8)).to(self._device()))
+            timing["mask_uploads"] = 1
+        t1 = clock()
+        got = ops.mask_plane_outlines(planes).host()
+        t2 = clock()
+        sc, co, po = got["source_contours"].tolist(), got["contour_offsets"].tolist(), got["pixel_offsets"].tolist()
+        xmin, ymin = self.image_xmin, self.image_ymin
+        points = got["points"].astype(np.float64) + np.array([xmin, ymin])
+        pixels_all = got["pixels"].astype(np.int64) + np.array([ymin, xmin])
+        ny, nx = (self.image.shape if self.image is not None else self.image_shape)[:2]
+        results = {"image_id": self.image_id, "objs": []}
+        for i in range(n):
+            class_id = int(self.class_ids_final[i])
+            y1, x1, y2, x2 = [int(v) for v in self.bboxes[i]]
+            at_edge = (x1 <= 0 or x1 >= nx - 1 or x2 <= 0 or x2 >= nx - 1 or
+                       y1 <= 0 or y1 >= ny - 1 or y2 <= 0 or y2 >= ny - 1)
+            pixels = pixels_all[po[i]:po[i + 1]].tolist()
+            vertexes = [points[co[k]:co[k + 1]].tolist() for k in range(sc[i], sc[i + 1])]
+            results["objs"].append({
+                "name": 'S' + str(i + 1) + "_" + self.obj_name_tag,
+                "x1": xmin + x1, "x2": xmin + x2, "y1": ymin + y1, "y2": ymin + y2,
+                "class_id": class_id, "class_name": self.class_names[class_id],
+                "score": float(self.scores_final[i]), "pixels": pixels, "vertexes": vertexes, "edge": bool(at_edge)})
+        self.results = results
+        t3 = clock()
+        for name, a, b in (("planes", t0, t1), ("outlines_download", t1, t2), ("host_lists", t2, t3)):
+            timing[name + "_ms"] = round(1e3 * (b - a), 3)
+        self.results_timing = timing
+
+    def make_json_results_host(self):
         self.results = {"image_id": self.image_id, "objs": []}
         xmin, ymin = self.image_xmin, self.image_ymin
         ny, nx = (self.image.shape if self.image is not None else self.image_shape)[:2]

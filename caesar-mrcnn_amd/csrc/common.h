@@ -24,6 +24,9 @@ extern int g_mrcnn_h16_slab;
 extern int g_mrcnn_sk16;
 //   proposal_skip_zero: tests only (fault injection): 1 suppresses the reset of the multi-workgroup top-k's counters.
 extern int g_mrcnn_proposal_skip_zero;
+//   outline_lds_segs: sources of at most this many contour segments are ranked in LDS by mrcnn_outline_emit, larger ones in the
+//   global workspace (default and maximum 1536; 0 sends every source through the global form -- tests reach it at small shapes).
+extern int g_mrcnn_outline_lds_segs;
 
 static inline int mrcnn_launch_status() {
     hipError_t e = hipGetLastError();

@@ -649,6 +649,11 @@ extern "C" int mrcnn_tuning_set(const char* key, long long value) {
         g_mrcnn_proposal_skip_zero = (int)value;
         return MRCNN_OK;
     }
+    if (!strcmp(key, "outline_lds_segs")) {
+        if (value < 0 || value > 1536) return MRCNN_ERR_ARG;
+        g_mrcnn_outline_lds_segs = (int)value;
+        return MRCNN_OK;
+    }
     return MRCNN_ERR_UNSUPPORTED;
 }
 

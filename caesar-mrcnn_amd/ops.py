@@ -1056,6 +1056,129 @@ def mask_plane_sums(img, planes, big_endian=False):
     return out
 
 
+class OutlineUnsupported(_hip.HipPathError):
+    """A table past a cap of mrcnn_outline_* (include/mrcnn_hip.h: a source wider or higher than 8192 pixels, more than 65535
+    sources, more than 2^22 contour segments in one source, int32 totals): the caller takes the host path."""
+
+
+class Outlines(object):
+    """Contours and pixel lists of n bit masks on the device (include/mrcnn_hip.h: mrcnn_outline_emit), coordinates in each
+    source's own frame:
+      points [P, 2] float32 (x, y); contour_offsets [C + 1] int32; source_contours [n + 1] int32 (the contours of source i);
+      pixels [K, 2] int32 (y, x) in raster order; pixel_offsets [n + 1] int32.
+    P and C are known on the device only: `points` and `contour_offsets` read C once (a synchronisation) to cut their buffers
+    to size; `host()` downloads everything in one copy instead."""
+
+    def __init__(self, points_buf, contour_offsets_buf, source_contours, pixels, pixel_offsets, segments):
+        self._points_buf, self._contour_offsets_buf, self._segments, self._C = points_buf, contour_offsets_buf, int(segments), None
+        self.source_contours, self.pixels, self.pixel_offsets = source_contours, pixels, pixel_offsets
+        self.n = int(source_contours.shape[0]) - 1
+
+    def _contours(self):
+        if self._C is None:
+            self._C = int(self.source_contours[-1])
+        return self._C
+
+    @property
+    def points(self):
+        return self._points_buf[:self._segments + self._contours()]
+
+    @property
+    def contour_offsets(self):
+        return self._contour_offsets_buf[:self._contours() + 1]
+
+    def host(self):
+        """One download: dict of NumPy arrays under the five names above."""
+        n, K, cc = self.n, int(self.pixels.shape[0]), int(self._contour_offsets_buf.shape[0])
+        flat = torch.cat([self.source_contours, self.pixel_offsets, self._contour_offsets_buf, self.pixels.reshape(-1),
+                          self._points_buf.view(torch.int32).reshape(-1)]).cpu().numpy()
+        sc, po, co = flat[:n + 1], flat[n + 1:2 * n + 2], flat[2 * n + 2:2 * n + 2 + cc]
+        rest = flat[2 * n + 2 + cc:]
+        self._C = C_ = int(sc[-1])
+        return {"source_contours": sc, "pixel_offsets": po, "contour_offsets": co[:C_ + 1], "pixels": rest[:2 * K].reshape(K, 2),
+                "points": rest[2 * K:].view("<f4").reshape(-1, 2)[:self._segments + C_]}
+
+
+def _outline_refusal(rc, what):
+    if rc == ERR_UNSUPPORTED:
+        raise OutlineUnsupported("%s: the table is past a cap of the kernels (status %d): a source above 8192 x 8192 pixels, more than "
+                                 "65535 sources, more than 2^22 segments in a source, or totals past int32" % (what, rc))
+    if rc:
+        raise ValueError("%s refuses the table (status %d): no source, a negative size or a descriptor that leaves the pool" % (what, rc))
+
+
+def bitmap_outlines(pool, desc, desc_host=None, timing=None):
+    """Contours (find_contours at 0.5 of the zero-padded mask, as (x, y)) and pixel lists (np.argwhere) of n bit masks in one
+    call: pool, desc as for tile_adjacency (pool of 32-bit words, desc [n, 6] int32 = (x0, y0, w, h, word_offset, words_per_row),
+    both on the device; tile_union's out_pool / out_desc as they stand); desc_host = the NumPy descriptors behind `desc` (read
+    back when not given).  Returns an Outlines.  Synchronises once, to read the per-source totals that size the outputs.
+    ValueError for a malformed table, OutlineUnsupported past a cap; neither launches anything.  timing: a dict that receives
+    the device time of the two launch groups (count_kernels_ms, emit_kernels_ms, from events; costs one more synchronisation)."""
+    import numpy as np
+    _need_cuda(pool, desc)
+    assert desc.dtype == torch.int32 and desc.dim() == 2 and desc.shape[1] == 6 and desc.is_contiguous()
+    assert pool.dim() == 1 and pool.element_size() == 4 and pool.is_contiguous()
+    dh = np.ascontiguousarray(desc.cpu().numpy() if desc_host is None else desc_host, dtype=np.int32).reshape(-1, 6)
+    n, dev, words = int(desc.shape[0]), pool.device, int(pool.numel())
+    assert dh.shape[0] == n, "desc_host must be the host copy of desc"
+    L = _hip.lib()
+    host = dh.ctypes.data_as(C.c_void_p)
+    _outline_refusal(L.mrcnn_outline_check(host, n, words, None), "mrcnn_outline_count")
+    stream = current_stream()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing is not None else None
+    cws = workspace(L.mrcnn_outline_workspace(host, n, words, None), dev, "outline_count")
+    totals = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    pixel_offsets = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    if ev:
+        ev[0].record()
+    check(L.mrcnn_outline_count(ptr(pool), words, host, ptr(desc), n, ptr(cws), cws.numel(), ptr(totals), ptr(pixel_offsets), stream),
+          "mrcnn_outline_count")
+    if ev:
+        ev[1].record()
+    th = np.ascontiguousarray(totals.cpu().numpy())                # the one synchronisation: sizes of everything below
+    thost = th.ctypes.data_as(C.c_void_p)
+    _outline_refusal(L.mrcnn_outline_check(host, n, words, thost), "mrcnn_outline_emit")
+    S, K = int(th[:, 0].sum()), int(th[:, 1].sum())
+    ews = workspace(L.mrcnn_outline_workspace(host, n, words, thost), dev, "outline_emit")
+    points = torch.empty((S + S // 4 + 1, 2), dtype=torch.float32, device=dev)        # one spare row each: never an empty buffer
+    contour_offsets = torch.zeros((S // 4 + 1,), dtype=torch.int32, device=dev)
+    source_contours = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    pixels = torch.empty((K + 1, 2), dtype=torch.int32, device=dev)
+    if ev:
+        ev[2].record()
+    check(L.mrcnn_outline_emit(ptr(pool), words, host, ptr(desc), n, thost, ptr(cws), cws.numel(), ptr(ews), ews.numel(), ptr(pixel_offsets),
+                               ptr(points), points.shape[0], ptr(contour_offsets), S // 4, ptr(source_contours), ptr(pixels), K, stream),
+          "mrcnn_outline_emit")
+    if ev:
+        ev[3].record()
+        ev[3].synchronize()
+        timing["count_kernels_ms"] = round(ev[0].elapsed_time(ev[1]), 4)
+        timing["emit_kernels_ms"] = round(ev[2].elapsed_time(ev[3]), 4)
+        timing["segments"], timing["pixels"] = S, K
+    return Outlines(points, contour_offsets, source_contours, pixels[:K], pixel_offsets, S)
+
+
+def mask_plane_table(n, H, wpr, W):
+    """mrcnn_tile_source records [n, 6] int32 of the bit planes of one frame (MaskPlanes.words as one pool)."""
+    import numpy as np
+    table = np.zeros((n, 6), np.int64)
+    table[:, 2], table[:, 3], table[:, 5] = W, H, wpr
+    table[:, 4] = np.arange(n, dtype=np.int64) * H * wpr
+    if n and table[-1, 4] + H * wpr > 2 ** 31 - 1:
+        raise OutlineUnsupported("mask_plane_outlines: %d planes of %d x %d words are past a pool of 2^31 - 1 words" % (n, H, wpr))
+    return table.astype(np.int32)
+
+
+def mask_plane_outlines(planes, timing=None):
+    """bitmap_outlines of every plane of a MaskPlanes (the masks of one frame), full frame each."""
+    _need_cuda(planes.words)
+    table = mask_plane_table(planes.n, planes.H, planes.wpr, planes.W)
+    if planes.n <= 0:
+        raise ValueError("mask_plane_outlines: no plane")
+    desc = torch.from_numpy(table).to(planes.words.device)
+    return bitmap_outlines(planes.words.contiguous().view(-1), desc, table, timing)
+
+
 def fill_zero(t):
     _need_cuda(t)
     check(_hip.lib().mrcnn_fill_zero(ptr(t), t.numel() * t.element_size(), current_stream()), "mrcnn_fill_zero")

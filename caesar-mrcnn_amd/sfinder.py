@@ -43,6 +43,9 @@ from .analyze import Analyzer
 logger = logging.getLogger("mrcnn")
 
 
+_outlines_failed = False             # SFinder._union_outlines raised once: this process stays on find_contours
+
+
 class MergedSourceInfo(object):
     """Helper of merge_edge_sources (sfinder.py:44-49): source index within its tile entry, index of the tile entry."""
 
@@ -75,6 +78,7 @@ class TileTask(object):
         self.bboxes_det = self.scores_det = self.classid_det = self.masks_det = None
         self.save_json = False
         self.save_regions = False
+        self.results_device = False       # handed to the Analyzer (SFinder.results_device)
         self.procId = 0
 
     def set_worker_id(self, wid):
@@ -149,6 +153,7 @@ class TileTask(object):
         analyzer.write_to_ds9 = self.save_regions
         analyzer.outfile_ds9 = 'catalog_' + self.image_id + '_tid' + str(self.tid) + '.reg'
         analyzer.obj_name_tag = self.sname_tag
+        analyzer.results_device = self.results_device
         return analyzer
 
     def _take(self, analyzer):
@@ -252,6 +257,9 @@ class SFinder(object):
         self.merge_device = self._has_gpu()
         self.merge_device_min_sources = self.MERGE_DEVICE_MIN_SOURCES
         self.merge_timing = {}
+        # Contours and pixel lists on the GPU (csrc/outline.hip): in every Analyzer the tiles build (Analyzer.results_device) and
+        # for the merged sources of merge_edge_sources_device.  Off by default.
+        self.results_device = False
         self.compute_params = False       # the reference always computes them (:613-622); here run.py --compute_source_params
         self.params_device = self._has_gpu()
         self.params_device_min_sources = self.PARAMS_DEVICE_MIN_SOURCES
@@ -379,6 +387,7 @@ class SFinder(object):
         analyzer.outfile_json = self.outfile_json or cfg.OUTFILE_JSON
         analyzer.outfile_ds9 = self.outfile_ds9
         analyzer.iou_thr, analyzer.score_thr = cfg.IOU_THR, cfg.SCORE_THR
+        analyzer.results_device = self.results_device
         if analyzer.predict(image_data, self.image_id) < 0:               # sfinder.py:493: no offsets, no header
             logger.error("Failed to run model prediction on image %s!" % cfg.IMG_PATH)
             return -1
@@ -621,21 +630,25 @@ class SFinder(object):
         return 0
 
     @staticmethod
-    def _merged_source(name, last, pixels_merged, mask, xmin, ymin):
-        """:864-924 from the union's pixels: `mask` = the union in its tight box [ymin.., xmin..]."""
+    def _merged_source(name, last, pixels_merged, mask, xmin, ymin, contours=None):
+        """:864-924 from the union's pixels: `mask` = the union in its tight box [ymin.., xmin..].  contours: the mask's contours
+        as float64 (x, y) arrays in the box's own frame (ops.bitmap_outlines), which replace the find_contours call."""
         dy, dx = mask.shape
         xmax, ymax = xmin + dx - 1, ymin + dy - 1                         # :879-882: pixel max, i.e. INCLUSIVE (unmerged: exclusive)
-        offset = 10                                                       # :887
-        padded_mask = np.zeros((dy + 2 * offset, dx + 2 * offset), dtype=np.uint8)
-        padded_mask[offset:offset + dy, offset:offset + dx] = mask
-        vertexes = []
-        for verts in analyze.find_contours(padded_mask, 0.5):
-            verts = np.fliplr(verts)                                      # :902: (y, x) -> (x, y), padding kept ...
-            verts = verts.tolist()
-            for v in verts:                                               # :906-909: ... and removed here
-                v[0] += xmin - offset
-                v[1] += ymin - offset
-            vertexes.append(verts)
+        if contours is not None:
+            vertexes = [(c + np.array([xmin, ymin])).tolist() for c in contours]
+        else:
+            offset = 10                                                       # :887
+            padded_mask = np.zeros((dy + 2 * offset, dx + 2 * offset), dtype=np.uint8)
+            padded_mask[offset:offset + dy, offset:offset + dx] = mask
+            vertexes = []
+            for verts in analyze.find_contours(padded_mask, 0.5):
+                verts = np.fliplr(verts)                                      # :902: (y, x) -> (x, y), padding kept ...
+                verts = verts.tolist()
+                for v in verts:                                               # :906-909: ... and removed here
+                    v[0] += xmin - offset
+                    v[1] += ymin - offset
+                vertexes.append(verts)
         # :865-870: class / score of `sourcesToBeMerged[index]` with index the LAST member visited (index_largest is computed
         # and never used)
         return {"name": name, "x1": int(xmin), "x2": int(xmax), "y1": int(ymin), "y2": int(ymax), "edge": True, "merged": True,
@@ -761,6 +774,7 @@ class SFinder(object):
             out_count = u["out_count"].cpu().numpy()
             out_pool = u["out_pool"].cpu().numpy().view(np.uint32)
             fresh_pool = u["fresh_pool"].cpu().numpy().view(np.uint32)        # .cpu() synchronises with the launches
+            outlines = self._union_outlines(u, out_desc) if self.results_device else None
             t.append(clock())
             for c, k in enumerate(multi):
                 parts = []
@@ -771,7 +785,8 @@ class SFinder(object):
                 pixels = np.concatenate(parts)
                 x0, y0, w, h, off, wpr = (int(v) for v in out_desc[c])
                 assert pixels.shape[0] == int(out_count[c]), "tile_union: fresh bitmaps and union count disagree"
-                result[k] = (pixels.tolist(), unpack_bitmap(out_pool[off:off + h * wpr], h, w, wpr), x0, y0)
+                result[k] = (pixels.tolist(), unpack_bitmap(out_pool[off:off + h * wpr], h, w, wpr), x0, y0,
+                             None if outlines is None else outlines[c])
         else:
             t.append(clock())
         t.append(clock())
@@ -782,10 +797,30 @@ class SFinder(object):
             self.merge_timing[name + "_ms"] = round(1e3 * (b - a), 3)
 
         def merged_of(i, comp):
-            pixels, mask, x0, y0 = result[i]
-            return self._merged_source("S" + str(i + 1) + "_merged", srcs[comp[-1]], pixels, mask.astype(np.uint8), x0, y0)
+            pixels, mask, x0, y0, contours = result[i]
+            return self._merged_source("S" + str(i + 1) + "_merged", srcs[comp[-1]], pixels, mask.astype(np.uint8), x0, y0, contours)
 
         return self._finish_merge(todo, cc, merged_of)
+
+    def _union_outlines(self, u, out_desc):
+        """The contours of all unions of ops.tile_union's result `u`, outlined where they lie (out_pool / out_desc, one call, one
+        download): per component a list of float64 (x, y) arrays in the union's own box.  None when the device path has failed
+        in this process (logged once): the merged sources then take find_contours, as with the switch off.  A table the check
+        calls malformed would be a bug of tile_union: that ValueError is not caught."""
+        global _outlines_failed
+        from . import _hip, ops
+        if _outlines_failed:
+            return None
+        try:
+            got = ops.bitmap_outlines(u["out_pool"], u["out_desc"], out_desc).host()
+        except (_hip.HipPathError, OSError) as e:
+            _outlines_failed = True
+            logger.error("bitmap_outlines failed (%s: %s): the merged sources of this and every later merge take find_contours on "
+                         "the host ..." % (type(e).__name__, e))
+            return None
+        sc, co = got["source_contours"].tolist(), got["contour_offsets"].tolist()
+        points = got["points"].astype(np.float64)
+        return [[points[co[k]:co[k + 1]] for k in range(sc[c], sc[c + 1])] for c in range(len(sc) - 1)]
 
     # ---- source parameters (sfinder.py:994-1211) --------------------------------------------------------------
     def _image_plane(self):
@@ -1004,6 +1039,7 @@ class SFinder(object):
             tileTask.procId = self.procId
             tileTask.save_regions = self.save_tile_regions
             tileTask.save_json = self.save_tile_json
+            tileTask.results_device = self.results_device
             self.tasks_per_worker[workerCounter].append(tileTask)
             workerCounter = 0 if workerCounter >= self.nproc - 1 else workerCounter + 1
         for i in range(len(self.tasks_per_worker)):                       # :1256-1293: neighbour lists, in this insertion order

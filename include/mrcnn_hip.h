@@ -259,6 +259,42 @@ int mrcnn_source_params(const void* img, int big_endian, int H, int W, const voi
                         const mrcnn_tile_source* desc, int n, const int32_t* cutouts, const int64_t* val_offsets, void* values,
                         int64_t values_len, double sigma, int maxiters, mrcnn_source_record* out, void* stream);
 
+/* Contours and pixel lists of bit masks: the pixel work of Analyzer.make_json_results (mrcnn/analyze.py:1902-1927) and of the
+ * merged sources of SFinder.merge_edge_sources (mrcnn/sfinder.py:887-909) for all n sources of one call.  Sources are given as
+ * for mrcnn_tile_adjacency (pool, pool_words, one mrcnn_tile_source each; x0 / y0 are not read: results are in the source's own
+ * frame, pixel centres at integers); desc_host is the host copy of the device table desc.  The bit planes of the mask graph
+ * below are the table word_offset = i * H * wpr, and mrcnn_tile_union's out_pool / out_desc is one as it stands.  Per source:
+ *   contours   skimage.measure.find_contours(level = 0.5) [3P] of the zero-padded 0 / 1 mask, restated as analyze.find_contours
+ *              (marching squares in raster order, 'low' connectivity; parity with skimage itself stays unpinned), padding
+ *              subtracted, as (x, y): the same contours, in the same order, from the same starting vertex, first point repeated
+ *              at the end (analyze.outline_statement states the rule without the sequential stitching); every coordinate is a
+ *              multiple of 0.5 in [-0.5, w - 0.5], exact in float32;
+ *   pixels     np.argwhere: (y, x) of the set bits in raster order.
+ * Sizes are unknown before a first pass, so the work is two calls:
+ *   mrcnn_outline_count  totals[n][2] = (contour segments, set pixels) per source, pixel_offsets[n + 1] = exclusive scan of the
+ *                        pixel counts, and the per-row offsets kept in count_ws for the second call;
+ *   mrcnn_outline_emit   with totals_host = those totals read back (S segments, K pixels in all): points [P][2] float32,
+ *                        contour_offsets [C + 1] (contour k of the call: points contour_offsets[k] .. contour_offsets[k + 1]),
+ *                        source_contours [n + 1] (source i: contours source_contours[i] .. source_contours[i + 1]), pixels
+ *                        [K][2] int32.  P = S + C and C <= S / 4 are not known to the host before the call: points_cap >=
+ *                        S + S / 4 points, contours_cap >= S / 4 (contour_offsets holds contours_cap + 1 ints), pixels_cap >= K,
+ *                        else MRCNN_ERR_ARG; C = source_contours[n].  The pool must not change between the two calls.
+ *   mrcnn_outline_workspace  bytes of count_ws (totals_host == NULL) or of emit_ws (totals_host given); 0 for a refused table.
+ *   mrcnn_outline_check  the status the calls would return for that table (and those totals, when not NULL); launches nothing.
+ * n <= 0, pool_words < 0, a negative total, or a source with w, h > 0 and word_offset < 0, words_per_row < ceil(w / 32) or rows
+ * past pool_words: MRCNN_ERR_ARG.  Caps (past any: MRCNN_ERR_UNSUPPORTED, use the host path): w, h <= 8192; n <= 65535;
+ * pool_words <= 2^31 - 1; at most 2^22 segments per source; S + S / 4 <= 2^31 - 1 points and K <= 2^31 - 1 pixels per call.  A
+ * source with w <= 0 or h <= 0 is no error: it has no contours and no pixels.  A refused call launches and writes nothing.
+ * Nothing is allocated on the device, nothing synchronises, no atomics: the results are bitwise the same from run to run.  */
+int mrcnn_outline_check(const mrcnn_tile_source* desc_host, int n, int64_t pool_words, const int32_t* totals_host);
+size_t mrcnn_outline_workspace(const mrcnn_tile_source* desc_host, int n, int64_t pool_words, const int32_t* totals_host);
+int mrcnn_outline_count(const void* pool, int64_t pool_words, const mrcnn_tile_source* desc_host, const mrcnn_tile_source* desc, int n,
+                        void* count_ws, size_t count_ws_bytes, int32_t* totals, int32_t* pixel_offsets, void* stream);
+int mrcnn_outline_emit(const void* pool, int64_t pool_words, const mrcnn_tile_source* desc_host, const mrcnn_tile_source* desc, int n,
+                       const int32_t* totals_host, const void* count_ws, size_t count_ws_bytes, void* emit_ws, size_t emit_ws_bytes,
+                       const int32_t* pixel_offsets, float* points, int64_t points_cap, int32_t* contour_offsets, int64_t contours_cap,
+                       int32_t* source_contours, int32_t* pixels, int64_t pixels_cap, void* stream);
+
 /* The mask graph of Analyzer.extract_det_masks (mrcnn/analyze.py:1162-1496): which detection masks of a frame overlap or touch,
  * and the unions of those that are merged.  The masks of ONE frame are bit planes, planes[n][H][wpr] 32-bit words, wpr =
  * ceil(W / 32): pixel x of a row is bit x & 31 of word x >> 5, least significant bit first (numpy.packbits(...,
@@ -694,7 +730,9 @@ const char* mrcnn_allreduce_last_error(void);
  * stream find a free slot on every CU); "h16_phase" (0 / 1); "h16_slab" (-1 = MRCNN_H16_SLAB decides, default off; 0 / 1: the slab form of the phased 16-bit kernel off /
  * on -- tests and A/B timing); "sk16" (0 / 1: the 16 x 16-tile single-launch kernel for layers of a few hundred pixels may be
  * picked -- the engine sets it while it issues the inference graph); "proposal_skip_zero" (tests only, fault injection: 1 suppresses
- * the counter reset of mrcnn_proposal_fwd's multi-workgroup selection).  MRCNN_ERR_UNSUPPORTED for an unknown key.   */
+ * the counter reset of mrcnn_proposal_fwd's multi-workgroup selection); "outline_lds_segs" (0..1536, default 1536: mrcnn_outline_emit
+ * ranks the segments of a source in LDS up to this many and in its global workspace above; 0 = always the global form -- tests).
+ * MRCNN_ERR_UNSUPPORTED for an unknown key.                                                                          */
 int mrcnn_tuning_set(const char* key, long long value);
 
 const char* mrcnn_hip_version(void);
