@@ -1218,7 +1218,6 @@ def weights_to_h16(w, dtype=torch.float16, want_dgrad=True, out=None):
 
 
 # ---- Winograd F(2x2, 3x3) / F(4x4, 3x3), float32 (mask-head 3x3 convolutions) ---------------------------------------------
-_WINO_PERSISTENT_GEMM = os.environ.get("MRCNN_WINOGRAD_GEMM", "persistent") != "blds"     # A/B: the one-tile-per-workgroup LDS-DMA kernel
 _WINO_MIN_ROWS = int(os.environ.get("MRCNN_WINOGRAD_MIN_ROWS", "16384"))   # 84 ROIs of 14 x 14: detect's 100 detections take the path (3.48 -> 3.18 ms/image)
 # 4: F(4x4, 3x3) for layers of at least _WINO_TILE4_MIN_ROWS pixels (512 ROIs of 14 x 14: the training step's layers and their
 # halves; detect's 100 ROIs per image stay on F(2x2, 3x3)); headline step 44.5 -> 40.9 ms.  2: F(2x2, 3x3) everywhere
@@ -1302,7 +1301,7 @@ def winograd_weights(w, out=None, tile=2):
     return out
 
 
-def _winograd_run(x, U, finish, keep_v=None, after_input=None, fuse=None):
+def _winograd_run(x, U, finish, keep_v=None, after_input=None):
     """Per tile group: input transform, the group's transform-domain GEMMs, then finish(group, Mt) -- the output transform the caller
     wants.  V of all groups lives in one flat buffer (keep_v: kept for the weight gradient), Mt is a per-stream scratch buffer
     reused group after group (stream order)."""
@@ -1318,7 +1317,6 @@ def _winograd_run(x, U, finish, keep_v=None, after_input=None, fuse=None):
     V = keep_v if keep_v is not None else workspace(nv * 4, x.device, "winograd_v")[:nv * 4].view(torch.float32)
     assert keep_v is None or (keep_v.numel() == nv and keep_v.dtype == torch.float32)
     Mt = workspace(max(nms) * 4, x.device, "winograd_m")
-    gemm = lib.mrcnn_winograd_gemm if _WINO_PERSISTENT_GEMM else lib.mrcnn_gemm_batched_f32
     off = 0
     for gi, (g, u) in enumerate(zip(groups, Us)):
         Vg = V[off:off + nvs[gi]]
@@ -1328,38 +1326,8 @@ def _winograd_run(x, U, finish, keep_v=None, after_input=None, fuse=None):
             after_input()                # e.g. an event: a second chain on another stream starts one transform behind this one
         nb = _wino_nb(g)
         rows = nvs[gi] // (nb * Cin)
-        if fuse is not None and _WINO_FUSE and _WINO_PERSISTENT_GEMM and g.oth == 4 and g.otw == 4 and cout == 256 and \
-                (nb * rows // 128) >= _WINO_FUSE_MIN_TILES:
-            # the group's output transform inside the GEMM launch (mrcnn_winograd_gemm_fused): no second launch, its memory pass runs
-            # beside the other workgroups' MFMAs
-            f = fuse(g)
-            f.counters = ptr(_wino_counters(x.device, rows // 128))
-            rc = lib.mrcnn_winograd_gemm_fused(ptr(Vg), ptr(u), ptr(Mt), nb, rows, Cin, cout, C.byref(f), current_stream())
-            if rc != ERR_UNSUPPORTED:
-                check(rc, "mrcnn_winograd_gemm_fused")
-                continue
-        check(gemm(ptr(Vg), ptr(u), ptr(Mt), nb, rows, Cin, cout, current_stream()), "mrcnn_winograd_gemm")
+        check(lib.mrcnn_winograd_gemm(ptr(Vg), ptr(u), ptr(Mt), nb, rows, Cin, cout, current_stream()), "mrcnn_winograd_gemm")
         finish(g, Mt)
-
-
-# output transform of the 4 x 4 group fused into its GEMM launch (mrcnn_winograd_gemm_fused).  Built, bit-identical to the separate
-# launches (test_winograd_fused_output_equals_unfused) -- and OFF: measured 1.74 -> 5.3 ms per forward layer, 1.88 -> 12 ms per data
-# gradient at 2048 ROIs (tools/wino_fuse_probe.py; 5.15 / 11.1 ms even without the per-tile release fence).  One workgroup
-# transforming a 128-tile row block is a chain of 64 dependent load rounds from the memory side (~0.5 ms), it holds up that
-# workgroup's next tiles and with them the 35 other row blocks they belong to -- DESIGN.md 4.1e
-_WINO_FUSE = os.environ.get("MRCNN_WINOGRAD_FUSE", "0") != "0"
-_WINO_FUSE_MIN_TILES = int(os.environ.get("MRCNN_WINOGRAD_FUSE_MIN_TILES", "1536"))   # GEMM tiles (two rounds of 768 workgroups) from which it pays
-_wino_counter_cache = {}
-
-
-def _wino_counters(device, n):
-    """Row-block counters of mrcnn_winograd_gemm_fused: zero on entry, left zero by the kernel -- one buffer per stream."""
-    key = (str(device), current_stream())
-    t = _wino_counter_cache.get(key)
-    if t is None or t.numel() < n:
-        t = torch.zeros(max(n, 1024), dtype=torch.int32, device=device)
-        _wino_counter_cache[key] = t
-    return t
 
 
 def winograd_v_floats(xshape, tile=None):
@@ -1383,16 +1351,8 @@ def conv2d_winograd(x, U, bias=None, scale=None, shift=None, act=ACT_NONE, out=N
         check(lib.mrcnn_winograd_output_g(ptr(Mt), ptr(out), ptr(z_out), ptr(bias), ptr(scale), ptr(shift), N, H, W, cout, act, C.byref(g),
                                           current_stream()), "mrcnn_winograd_output_g")
 
-    def fuse(g):
-        f = _hip.WinoFuse()
-        f.mode, f.N, f.H, f.W, f.act, f.g = 1, N, H, W, act, g
-        f.out, f.z, f.bias, f.scale, f.shift = ptr(out), ptr(z_out), ptr(bias), ptr(scale), ptr(shift)
-        return f
-    _winograd_run(x, U, finish, keep_v, after_input, fuse if act in (ACT_NONE, ACT_RELU) else None)
+    _winograd_run(x, U, finish, keep_v, after_input)
     return out
-
-
-_WINO_ZMASK = os.environ.get("MRCNN_WINOGRAD_ZMASK", "1") != "0"       # ReLU mask of the layer below from its stored z (its `out` is not read)
 
 
 def conv2d_dgrad_ep_winograd(dz, Ut, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, act, fwd_shift=None):
@@ -1405,7 +1365,7 @@ def conv2d_dgrad_ep_winograd(dz, Ut, below_out, below_z, scale, mean, rstd, dgam
     cout = (Ut[0] if isinstance(Ut, (list, tuple)) else Ut).shape[2]
     out = empty((N, H, W, cout), torch.float32, dz.device)
     lib = _hip.lib()
-    zmask = _WINO_ZMASK and act == ACT_RELU and fwd_shift is not None and below_z is not None and scale is not None
+    zmask = act == ACT_RELU and fwd_shift is not None and below_z is not None and scale is not None
 
     def finish(g, Mt):
         if zmask:
@@ -1417,14 +1377,7 @@ def conv2d_dgrad_ep_winograd(dz, Ut, below_out, below_z, scale, mean, rstd, dgam
                                               ptr(dgamma), ptr(dbeta), ptr(dbias), N, H, W, cout, act, C.byref(g), current_stream()),
               "mrcnn_winograd_output_bwd_g")
 
-    def fuse(g):
-        f = _hip.WinoFuse()
-        f.mode, f.N, f.H, f.W, f.act, f.g = 2, N, H, W, act, g
-        f.out, f.scale, f.shift = ptr(out), ptr(scale), (ptr(fwd_shift) if zmask else None)
-        f.below_out, f.below_z, f.mean, f.rstd = (None if zmask else ptr(below_out)), ptr(below_z), ptr(mean), ptr(rstd)
-        f.dgamma, f.dbeta, f.dbias = ptr(dgamma), ptr(dbeta), ptr(dbias)
-        return f
-    _winograd_run(dz, Ut, finish, fuse=fuse)
+    _winograd_run(dz, Ut, finish)
     return out
 
 

@@ -607,46 +607,35 @@ int mrcnn_sgd_momentum_guarded(float* params, float* momentum_buf, const float* 
                                float clipnorm, float lr, float momentum, const float* gran_coef, int64_t n,
                                unsigned* skipped_steps, void* stream);
 
-/* ---- Winograd F(m x m, 3x3), m = `tile` = 2 or 4, for the stride-1 "same" 3x3 convolutions of the mask head
- * (KL.Conv2D(256, (3, 3), padding="same"), mrcnn/model.py:1058-1082), float32: (m + 2)^2 multiplications per m x m outputs and
- * channel pair instead of 9 m^2 -- 16 per 4 (tile 2) or 36 per 16 (tile 4).  Three launches per layer -- input transform, the
- * (m + 2)^2 transform-domain GEMMs as ONE launch, output transform with the layer's epilogue (or, for a data gradient, the epilogue
- * backward of the layer below) -- and one weight transform per weight update.  C % 4 == 0 (GEMM: K % 16 == 0, Cout % 128 == 0);
- * tile 2 wants H, W even, tile 4 takes any extent (edge tiles hang over the map: their inputs read as zero, their outputs are
- * dropped).  V / Mt hold mrcnn_winograd_buffer_floats floats each: [(m + 2)^2][rows][C], rows = tiles rounded up to whole 128-row
- * tiles.  Tile 2 uses +-1 and 1/2 only: the result differs from the direct kernels by float32 summation order (measured 2e-6 of
- * the output maximum); tile 4 has constants up to 8 and costs about one more decimal digit (measured 1e-5).                       */
-size_t mrcnn_winograd_buffer_floats(int N, int H, int W, int C, int tile);
-int mrcnn_winograd_weights(const float* w_hwio, float* U, int Cin, int Cout, int tile, void* stream);   /* U [(m + 2)^2][Cin][Cout] */
-int mrcnn_winograd_input(const float* x, float* V, int N, int H, int W, int C, int tile, void* stream);
-int mrcnn_gemm_batched_f32(const float* V, const float* U, float* Mt, int nb, int rows, int K, int Cout, void* stream);
-/* the same product by persistent workgroups (next tile's first stage in flight under the current tile's stores): the default */
-int mrcnn_winograd_gemm(const float* V, const float* U, float* Mt, int nb, int rows, int K, int Cout, void* stream);
-int mrcnn_winograd_output(const float* Mt, float* out, float* z_out, const float* bias, const float* scale, const float* shift,
-                          int N, int H, int W, int C, int act, int tile, void* stream);
-/* weight gradient: dM = A dy A^T (adjoint of the output transform) [(m + 2)^2][rows][C]; dU[xi] = V[xi]^T . dM[xi] are 1 x 1 weight
- * gradients (mrcnn_conv2d_wgrad on the first `tiles` rows of each matrix); dW = G^T dU G (accumulate != 0: added to dW).       */
-int mrcnn_winograd_dy(const float* dy, float* dM, int N, int H, int W, int C, int tile, void* stream);
-int mrcnn_winograd_dw(const float* dU, float* dw_hwio, int Cin, int Cout, int accumulate, int tile, void* stream);
-int mrcnn_winograd_output_bwd(const float* Mt, float* dz_below, const float* below_out, const float* below_z, const float* scale,
-                              const float* mean, const float* rstd, float* dgamma, float* dbeta, float* dbias, int N, int H, int W,
-                              int C, int act, int tile, void* stream);
-
-/* The same passes for one GROUP of tiles -- th_n x tw_n tiles per map of oth x otw outputs (2 or 4 each), the first at output
- * (oh0, ow0) -- so that a map whose extent is not a multiple of 4 is covered without overhang: 14 x 14 = 3 x 3 tiles of 4 x 4,
- * 3 x 1 of 4 x 2 (columns 12..13), 1 x 3 of 2 x 4 (rows 12..13), one of 2 x 2: 484 multiplications per map and channel pair instead of
- * 576 (uniform 4 x 4 with overhang) or 784 (uniform 2 x 2).  Every group has its own V / Mt ((oth + 2)(otw + 2) matrices of
- * mrcnn_winograd_group_floats / C rows) and its own weight transform U = G_oth g G_otw^T; the groups of a map write disjoint
- * outputs, their channel sums (output_bwd) and weight gradients (dw with accumulate) add up.  The `tile` entries above are the
- * one-group case.                                                                                                               */
+/* ---- Winograd F(m x n, 3x3), m, n = 2 or 4, for the stride-1 "same" 3x3 convolutions of the mask head
+ * (KL.Conv2D(256, (3, 3), padding="same"), mrcnn/model.py:1058-1082), the FPN smoothing and the shared RPN convolution, float32:
+ * (m + 2)(n + 2) multiplications per m x n outputs and channel pair instead of 9 m n -- 16 per 4 (2 x 2) or 36 per 16 (4 x 4).
+ * A layer is covered by GROUPS of tiles: th_n x tw_n tiles per map of oth x otw outputs each, the first at output (oh0, ow0).  A
+ * uniform tiling is one group at (0, 0) (edge tiles may hang over the map: their inputs read as zero, their outputs are dropped);
+ * a map whose extent is not a multiple of 4 is covered without overhang by several: 14 x 14 = 3 x 3 tiles of 4 x 4, 3 x 1 of
+ * 4 x 2 (columns 12..13), 1 x 3 of 2 x 4 (rows 12..13), one of 2 x 2: 484 multiplications per map and channel pair instead of 576
+ * (uniform 4 x 4 with overhang) or 784 (uniform 2 x 2).  Three launches per group -- input transform, the (oth + 2)(otw + 2)
+ * transform-domain GEMMs as ONE launch, output transform with the layer's epilogue (or, for a data gradient, the epilogue backward
+ * of the layer below) -- and one weight transform U = G_oth g G_otw^T per group shape and weight update.  C % 4 == 0 (GEMM:
+ * K % 16 == 0, Cout % 128 == 0).  Every group has its own V / Mt of mrcnn_winograd_group_floats floats each:
+ * [(oth + 2)(otw + 2)][rows][C], rows = tiles rounded up to whole 128-row tiles.  The groups of a map write disjoint outputs;
+ * their channel sums (output_bwd) and weight gradients (dw with accumulate) add up.  2 x 2 tiles use +-1 and 1/2 only: the result
+ * differs from the direct kernels by float32 summation order (measured 2e-6 of the output maximum); 4 x 4 tiles have constants up
+ * to 8 and cost about one more decimal digit (measured 1e-5).                                                                   */
 typedef struct mrcnn_wino_group {
     int oth, otw;      /* outputs per tile, rows / columns: 2 or 4 */
     int th_n, tw_n;    /* tiles per map */
     int oh0, ow0;      /* output row / column of the first tile */
 } mrcnn_wino_group;
 size_t mrcnn_winograd_group_floats(const mrcnn_wino_group* g, int N, int C);
-int mrcnn_winograd_input_g(const float* x, float* V, int N, int H, int W, int C, const mrcnn_wino_group* g, void* stream);
+/* the uniform tiling of `tile` x `tile` outputs (2: H, W even; 4: any extent) as one group: its floats, its weight transform */
+size_t mrcnn_winograd_buffer_floats(int N, int H, int W, int C, int tile);
+int mrcnn_winograd_weights(const float* w_hwio, float* U, int Cin, int Cout, int tile, void* stream);   /* U [(tile + 2)^2][Cin][Cout] */
 int mrcnn_winograd_weights_g(const float* w_hwio, float* U, int Cin, int Cout, int oth, int otw, void* stream);
+int mrcnn_winograd_input_g(const float* x, float* V, int N, int H, int W, int C, const mrcnn_wino_group* g, void* stream);
+int mrcnn_gemm_batched_f32(const float* V, const float* U, float* Mt, int nb, int rows, int K, int Cout, void* stream);
+/* the same product by persistent workgroups (next tile's first stage in flight under the current tile's stores): what the layers use */
+int mrcnn_winograd_gemm(const float* V, const float* U, float* Mt, int nb, int rows, int K, int Cout, void* stream);
 int mrcnn_winograd_output_g(const float* Mt, float* out, float* z_out, const float* bias, const float* scale, const float* shift,
                             int N, int H, int W, int C, int act, const mrcnn_wino_group* g, void* stream);
 int mrcnn_winograd_output_bwd_g(const float* Mt, float* dz_below, const float* below_out, const float* below_z, const float* scale,
@@ -657,25 +646,8 @@ int mrcnn_winograd_output_bwd_g(const float* Mt, float* dz_below, const float* b
 int mrcnn_winograd_output_bwd_zmask_g(const float* Mt, float* dz_below, const float* below_z, const float* scale, const float* shift,
                                       const float* mean, const float* rstd, float* dgamma, float* dbeta, float* dbias, int N, int H,
                                       int W, int C, const mrcnn_wino_group* g, void* stream);
-
-/* The transform-domain GEMMs of a 4 x 4 tile group WITH the group's output transform in the same launch (round 3): tiles are
- * walked row-block-major, every workgroup counts its finished tile into its row block's counter and the workgroup that completes
- * a row block transforms its 128 tiles on the spot -- no waiting, no second launch; the transform's memory pass runs beside the
- * other workgroups' MFMAs.  mode 1 = mrcnn_winograd_gemm + mrcnn_winograd_output_g, mode 2 = mrcnn_winograd_gemm +
- * mrcnn_winograd_output_bwd_g / _zmask_g (shift != NULL), same results up to the order of the channel-sum atomics.  Cout = 256,
- * a 4 x 4 group (36 matrices); else MRCNN_ERR_UNSUPPORTED.  counters: rows / 128 ints, zero on entry (left zero).           */
-typedef struct mrcnn_wino_fuse {
-    int32_t mode, N, H, W, act;
-    mrcnn_wino_group g;
-    float* out;              /* mode 1: out [N,H,W,256]; mode 2: dz of the layer below */
-    float* z;                /* mode 1: pre-BN output or NULL */
-    const float* bias; const float* scale; const float* shift;
-    const float* below_out; const float* below_z; const float* mean; const float* rstd;
-    float* dgamma; float* dbeta; float* dbias;
-    int32_t* counters;
-} mrcnn_wino_fuse;
-int mrcnn_winograd_gemm_fused(const float* V, const float* U, float* Mt, int nb, int rows, int K, int N, const mrcnn_wino_fuse* f,
-                              void* stream);
+/* weight gradient: dM = A dy A^T (adjoint of the output transform) [(oth + 2)(otw + 2)][rows][C]; dU[xi] = V[xi]^T . dM[xi] are
+ * 1 x 1 weight gradients (mrcnn_conv2d_wgrad on the first `tiles` rows of each matrix); dW = G^T dU G (accumulate != 0: added to dW). */
 int mrcnn_winograd_dy_g(const float* dy, float* dM, int N, int H, int W, int C, const mrcnn_wino_group* g, void* stream);
 int mrcnn_winograd_dw_g(const float* dU, float* dw_hwio, int Cin, int Cout, int accumulate, int oth, int otw, void* stream);
 
