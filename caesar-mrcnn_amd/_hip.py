@@ -79,6 +79,11 @@ class LossDesc(C.Structure):
                                           "mask_loss_dice")] + [("w", C.c_float * 5)]
 
 
+class DrawDesc(C.Structure):
+    """mrcnn_draw_desc (include/mrcnn_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("H", "W", "scale", "n_planes", "n_items", "n_texts", "n_glyphs", "n_colours", "shaded", "pad")]
+
+
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 RES_NONE, RES_SAME, RES_UP2 = 0, 1, 2
 OUT_NHWC, OUT_DECONV2 = 0, 1
@@ -130,6 +135,9 @@ _SIGNATURES = {
     "mrcnn_outline_count": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, C.c_size_t, _P, _P, _P]),
     "mrcnn_outline_emit": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, _P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_int64, _P, C.c_int64,
                                      _P, _P, C.c_int64, _P]),
+    # items_host / texts_host / glyphs_host are HOST tables (numpy: draw.ITEM_DTYPE, draw.TEXT_DTYPE, uint64)
+    "mrcnn_draw_check": (C.c_int, [C.POINTER(DrawDesc), _P, _P, _P]),
+    "mrcnn_draw_overlay": (C.c_int, [C.POINTER(DrawDesc)] + [_P] * 13),
     "mrcnn_fits_tiles_check": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "mrcnn_fits_tiles_workspace": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
     "mrcnn_fits_tiles_to_rgb": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_double), _P, C.c_size_t, _P,
@@ -206,7 +214,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats")
+_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_draw_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats")
 
 
 class _LibProxy(object):

@@ -41,6 +41,7 @@ from collections import deque
 
 import numpy as np
 
+from . import draw as overlay
 from . import utils
 
 logger = logging.getLogger("mrcnn")
@@ -52,6 +53,7 @@ NO_SPLIT_CLASSES_GT = ('galaxy_C2', 'galaxy_C3', 'galaxy', 'extended', 'extended
 _device_fallback_logged = False
 _eval_fallback_logged = False
 _results_device_failed = False          # make_json_results_device raised once: this process stays on the host statement
+_draw_device_failed = False             # the same for draw_results_device
 
 
 # ---- restated third-party helpers -----------------------------------------------------------------------
@@ -390,6 +392,11 @@ class Analyzer(object):
     RESULTS_DEVICE = False
     RESULTS_DEVICE_MIN_MASKS = 1
 
+    # The overlay of draw_results is rendered on the GPU (csrc/draw.hip) wherever one is there; frames with fewer final masks than
+    # this stay on the host statement.  0 = the device takes every frame: tools/draw_bench.py found no mask count at which the
+    # host statement is ahead on an MI355X host (profiles/draw_bench.json).
+    DRAW_DEVICE_MIN_MASKS = 0
+
     def __init__(self, model, config, dataset=None, gt_data=None, pred_data=None):
         # Off by default: the device path is equal to the host statement value for value (tests/test_analyze_post_gpu.py) but
         # has not been timed against it on an MI355X host yet, and a frame with one to three detections costs the host
@@ -462,7 +469,15 @@ class Analyzer(object):
         self._final_planes = None            # (MaskPlanes of masks_final, that list) when extract_det_masks_device made them
         self._eval_planes = {}
         self.outfile = self.outfile_json = self.outfile_ds9 = ""
-        self.draw = False                    # plotting is out of scope (no matplotlib on the path)
+        # The overlay PNG (draw_results).  `draw` is OFF by default -- the reference's is on (analyze.py:667) -- so
+        # that every command writes what it wrote before the overlay existed.
+        self.draw = False
+        self.draw_shaded_masks = False
+        self.draw_class_label_in_caption = False
+        self.draw_scale = None               # canvas pixels per frame pixel, an integer >= 1; None: max(1, 1024 // (max(H, W) + 4))
+        self.draw_device_min_masks = self.DRAW_DEVICE_MIN_MASKS
+        self.draw_timing = {}
+        self.class_color_map = dict(overlay.CLASS_COLOR_MAP)           # analyze.py:683-690 plus the names of class_color_map_ds9
         self.write_to_json = True
         self.write_to_ds9 = True
         self.use_polygon_regions = True
@@ -531,6 +546,8 @@ class Analyzer(object):
             logger.warning("No detected object found for image %s ..." % self.image_id)
             return 0
         self.bboxes_gt = bboxes_gt
+        if self.draw:                                                     # analyze.py:869-876
+            self.draw_results(self.outfile or 'out_' + str(self.image_id) + '.png')
         self.make_json_results()
         if self.write_to_json:
             self.write_json_results(self.outfile_json or 'out_' + str(self.image_id) + '.json')
@@ -916,6 +933,8 @@ class Analyzer(object):
             pred_data_for_image.append(pred_object)
         self.pred_data.append(pred_data_for_image)
         self.compute_performances()
+        if self.draw:                                                     # analyze.py:1018-1023
+            self.draw_results('out_' + self.image_path_base_noext + '_id' + str(self.image_uuid) + '.png')
         return 0
 
     def extract_gt_masks(self):
@@ -1294,12 +1313,7 @@ class Analyzer(object):
         t0 = clock()
         n = len(self.masks_final)
         timing = {"masks": n, "mask_uploads": 0}
-        if self._final_planes is not None and self._final_planes[1] is self.masks_final:
-            planes = self._final_planes[0]
-        else:
-            stack = np.ascontiguousarray(np.stack([np.asarray(m) != 0 for m in self.masks_final], axis=-1))
-            planes = ops.mask_planes_pack(torch.from_numpy(stack.view(np.uint8)).to(self._device()))
-            timing["mask_uploads"] = 1
+        planes, timing["mask_uploads"] = self._final_mask_planes()
         t1 = clock()
         got = ops.mask_plane_outlines(planes).host()
         t2 = clock()
@@ -1326,6 +1340,16 @@ class Analyzer(object):
         for name, a, b in (("planes", t0, t1), ("outlines_download", t1, t2), ("host_lists", t2, t3)):
             timing[name + "_ms"] = round(1e3 * (b - a), 3)
         self.results_timing = timing
+
+    def _final_mask_planes(self):
+        """(MaskPlanes of masks_final, uploads): the planes extract_det_masks_device left on the device for exactly this list (0
+        uploads), else one upload and one pack."""
+        import torch
+        from . import ops
+        if self._final_planes is not None and self._final_planes[1] is self.masks_final:
+            return self._final_planes[0], 0
+        stack = np.ascontiguousarray(np.stack([np.asarray(m) != 0 for m in self.masks_final], axis=-1))
+        return ops.mask_planes_pack(torch.from_numpy(stack.view(np.uint8)).to(self._device())), 1
 
     def make_json_results_host(self):
         self.results = {"image_id": self.image_id, "objs": []}
@@ -1356,6 +1380,122 @@ class Analyzer(object):
             return
         with open(outfile, 'w') as fp:
             json.dump(self.results, fp, indent=2, sort_keys=True)
+
+    # ---- the overlay PNG (analyze.py:2039-2135; the raster of DESIGN.md 4.12) -----------------------------------
+    def _draw_scene(self):
+        """The scene of draw.render_host / draw.device_tables from what predict / inspect_results left, or None (logged) when
+        the frame cannot be drawn."""
+        if self.image is None:
+            logger.error("The image of %s stayed on the device (only its shape is known here): nothing is drawn ..." % self.image_id)
+            return None
+        image = np.asarray(self.image)
+        if image.ndim != 3 or image.shape[2] != 3 or image.shape[0] == 0 or image.shape[1] == 0:
+            logger.error("Cannot draw an image of shape %r (need [H, W, 3]): nothing is drawn ..." % (tuple(image.shape),))
+            return None
+        H, W = image.shape[:2]
+        scale = overlay.default_scale(H, W) if self.draw_scale is None else int(self.draw_scale)
+        if scale < 1:
+            logger.error("Invalid draw_scale %r (need an integer >= 1): nothing is drawn ..." % (self.draw_scale,))
+            return None
+        masks = [np.asarray(m) for m in self.masks_final]
+        if any(m.shape != (H, W) for m in masks):
+            logger.error("The final masks are not of the image's shape %r: nothing is drawn ..." % ((H, W),))
+            return None
+        gt_colours = []
+        for i in range(len(self.bboxes_gt)):                              # analyze.py:2066-2070
+            label = 'bkg'
+            if len(self.class_ids_gt_merged) > 0:
+                label = self.class_names[self.class_ids_gt_merged[i]]
+            gt_colours.append(self.class_color_map.get(label, overlay.UNKNOWN_COLOUR))
+        colours, texts = [], []
+        for i in range(len(masks)):
+            colour = self.class_color_map.get(self.class_names[self.class_ids_final[i]], overlay.UNKNOWN_COLOUR)
+            colours.append(colour)
+            y1, x1, y2, x2 = [int(v) for v in self.bboxes[i]]
+            if self.draw_class_label_in_caption:
+                texts.append((str(self.captions[i]), x1, y1 + 8, overlay.colour8(colour)))
+            else:
+                texts.append(("{:.2f}".format(self.scores_final[i]), x1 + (x2 - x1) // 2 - 4, y1 - 1, overlay.CAPTION_COLOUR))
+        return {"image": image, "scale": scale, "shaded": bool(self.draw_shaded_masks), "masks": masks, "colours": colours,
+                "boxes": [[int(v) for v in b] for b in self.bboxes[:len(masks)]], "gt_boxes": [[int(v) for v in b] for b in self.bboxes_gt],
+                "gt_colours": gt_colours, "texts": texts}
+
+    def _draw_on_device(self, scene):
+        """The device form takes the frame: a GPU is there, it has not failed in this process, the image holds 8-bit values,
+        the masks are 0 / 1 masks (bit planes hold nothing else) and there are at least draw_device_min_masks of them."""
+        if _draw_device_failed or not Analyzer.has_gpu(self.model) or scene["image"].dtype != np.uint8:
+            return False
+        n = len(scene["masks"])
+        return n >= self.draw_device_min_masks and (n == 0 or self._results_masks_ok())
+
+    def _render_device(self, scene):
+        import torch
+        from . import ops
+        clock = time.perf_counter
+        t0 = clock()
+        timing = {"masks": len(scene["masks"]), "mask_uploads": 0}
+        planes = None
+        if scene["masks"]:
+            planes, timing["mask_uploads"] = self._final_mask_planes()
+        t1 = clock()
+        image = torch.from_numpy(np.ascontiguousarray(scene["image"])).to(self._device())
+        canvas = ops.draw_overlay(image, planes, overlay.device_tables(scene), scene["scale"])
+        torch.cuda.synchronize(canvas.device)
+        t2 = clock()
+        out = canvas.cpu().numpy()
+        t3 = clock()
+        for name, a, b in (("planes", t0, t1), ("render", t1, t2), ("download", t2, t3)):
+            timing[name + "_ms"] = round(1e3 * (b - a), 3)
+        self.draw_timing = timing
+        return out
+
+    def render_results(self, device=None):
+        """The overlay of the current frame as a uint8 array [s (H + 4), s (W + 4), 3], without writing a file; None (logged) when
+        the frame cannot be drawn.  device: None -- on the GPU where ``draw_results`` would render there, with its fallback; True
+        -- the device form, errors raised; False -- the host statement."""
+        global _draw_device_failed
+        self.draw_timing = {}
+        scene = self._draw_scene()
+        if scene is None:
+            return None
+        if device is True:
+            return self._render_device(scene)
+        if device is None and self._draw_on_device(scene):
+            from . import _hip
+            from .ops import DrawUnsupported
+            try:
+                return self._render_device(scene)
+            except DrawUnsupported as e:                                  # this scene only (a tiny frame's default scale is above 64)
+                logger.debug("%s: the host statement draws this frame" % e)
+            except (_hip.HipPathError, OSError) as e:
+                _draw_device_failed = True
+                logger.error("draw_results_device failed (%s: %s): this and every later call take the host statement "
+                             "(NumPy passes over the canvas per box, mask and character) ..." % (type(e).__name__, e))
+        return overlay.render_host(scene)
+
+    def _write_overlay(self, outfile, device):
+        canvas = self.render_results(device)
+        if canvas is None:
+            return -1
+        t0 = time.perf_counter()
+        overlay.write_png(outfile, canvas)
+        self.draw_timing["encode_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+        return 0
+
+    def draw_results(self, outfile):
+        """Write the overlay of the current frame -- the frame, the detected masks' contours (shaded with ``draw_shaded_masks``),
+        their boxes and scores, the ground-truth boxes -- as an 8-bit RGB PNG: rendered on the GPU (``draw_results_device``) where
+        one is there, else by the host statement; both give the same bytes.  0, or -1 when nothing could be drawn."""
+        return self._write_overlay(outfile, None)
+
+    def draw_results_device(self, outfile):
+        """draw_results with the canvas composed by ops.draw_overlay in one pass, from the bit planes extract_det_masks_device left
+        on the device (else one upload and pack of masks_final), and one download."""
+        return self._write_overlay(outfile, True)
+
+    def draw_results_host(self, outfile):
+        """draw_results by draw.render_host, the NumPy statement of DESIGN.md 4.12."""
+        return self._write_overlay(outfile, False)
 
     # ---- DS9 regions (analyze.py:1960-2030) ----------------------------------------------------------------
     def make_ds9_regions(self, use_polygon=True):
@@ -1417,6 +1557,7 @@ class ModelTester(object):
         self.outfilename_completeness = "completeness.csv"
         self.outfilename_reliability = "reliability.csv"
         self.eval_device = None               # None: every Analyzer keeps its own default; True / False: set on each of them
+        self.draw = False                     # every Analyzer draws out_<base>_id<uuid>.png (the reference's always do)
 
     def test(self):
         """:123-185."""
@@ -1437,6 +1578,7 @@ class ModelTester(object):
             analyzer.classid_map = self.classid_map
             if self.eval_device is not None:
                 analyzer.eval_device = self.eval_device
+            analyzer.draw = self.draw
             logger.info("Inspecting results for image %s ..." % image_path_base)
             if analyzer.inspect_results(image_id, image_path) < 0:
                 logger.error("Failed to analyze results for image %s ..." % image_path_base)

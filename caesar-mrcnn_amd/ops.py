@@ -1179,6 +1179,95 @@ def mask_plane_outlines(planes, timing=None):
     return bitmap_outlines(planes.words.contiguous().view(-1), desc, table, timing)
 
 
+class DrawUnsupported(_hip.HipPathError):
+    """A scene past a cap of mrcnn_draw_overlay (include/mrcnn_hip.h: a frame side above 16384, a scale above 64, a canvas side
+    above 65536 or a canvas above 2^31 - 1 bytes, more than 4096 items or texts, a text above 256 characters, more than 256
+    colours, coordinates beyond +-2^20): the caller takes the host statement."""
+
+
+def _draw_desc(H, W, n_planes, tables, scale):
+    import numpy as np
+    from . import draw
+    items = np.ascontiguousarray(tables["items"], dtype=draw.ITEM_DTYPE).reshape(-1)
+    texts = np.ascontiguousarray(tables["texts"], dtype=draw.TEXT_DTYPE).reshape(-1)
+    glyphs = np.ascontiguousarray(tables["glyphs"], dtype=np.uint64).reshape(-1)
+    palette = np.ascontiguousarray(tables["palette"], dtype=np.uint8)
+    shade = tables.get("shade")
+    if palette.ndim != 2 or palette.shape[1] != 4:
+        raise ValueError("draw_overlay: palette must be [K, 4] uint8")
+    if shade is not None:
+        shade = np.ascontiguousarray(shade, dtype=np.uint8)
+        if tuple(shade.shape) != (palette.shape[0], 3, 256):
+            raise ValueError("draw_overlay: shade must be [K, 3, 256] uint8 for the K colours of the palette")
+    d = _hip.DrawDesc(int(H), int(W), int(scale), int(n_planes), items.size, texts.size, glyphs.size, int(palette.shape[0]),
+                      0 if shade is None else 1, 0)
+    return d, items, texts, glyphs, palette, shade
+
+
+def _draw_refusal(rc):
+    if rc == ERR_UNSUPPORTED:
+        raise DrawUnsupported("mrcnn_draw_overlay: the scene is past a cap of the kernel (status %d)" % rc)
+    if rc:
+        raise ValueError("mrcnn_draw_overlay refuses the tables (status %d): an unknown kind, a colour, plane or glyph index outside "
+                         "its table, a glyph beyond 35 bits, or an empty frame" % rc)
+
+
+def draw_check(H, W, n_planes, tables, scale):
+    """The status mrcnn_draw_overlay would return for these tables (draw.device_tables); launches nothing."""
+    d, items, texts, glyphs, _, _ = _draw_desc(H, W, n_planes, tables, scale)
+    host = [a.ctypes.data_as(C.c_void_p) if a.size else None for a in (items, texts, glyphs)]
+    return _hip.lib().mrcnn_draw_check(C.byref(d), *host)
+
+
+def draw_overlay(image_u8, planes, tables, scale, timing=None):
+    """The detection overlay (include/mrcnn_hip.h: mrcnn_draw_overlay) -> uint8 [scale (H + 4), scale (W + 4), 3]
+    device tensor, equal to draw.render_host of the same scene byte for byte.  image_u8 [H, W, 3] uint8 on the device; planes: the
+    MaskPlanes of the frame's masks (None when no item names a plane); tables: draw.device_tables(scene) -- NumPy tables, uploaded
+    here in one copy.  ValueError for malformed tables, DrawUnsupported past a cap; neither launches anything.  timing: a dict
+    that receives the kernel's device time (render_kernel_ms, from events; costs a synchronisation)."""
+    import numpy as np
+    _need_cuda(image_u8)
+    assert image_u8.dtype == torch.uint8 and image_u8.dim() == 3 and image_u8.shape[2] == 3 and image_u8.is_contiguous()
+    H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
+    n_planes = 0
+    if planes is not None:
+        _need_cuda(planes.words, planes.box)
+        if (planes.H, planes.W) != (H, W):
+            raise _hip.HipPathError("draw_overlay: image %r, planes %r" % ((H, W), (planes.H, planes.W)))
+        assert planes.words.is_contiguous() and planes.box.is_contiguous() and planes.box.dtype == torch.int32
+        n_planes = planes.n
+    d, items, texts, glyphs, palette, shade = _draw_desc(H, W, n_planes, tables, scale)
+    L = _hip.lib()
+    host = [a.ctypes.data_as(C.c_void_p) if a.size else None for a in (items, texts, glyphs)]
+    _draw_refusal(L.mrcnn_draw_check(C.byref(d), *host))
+    # one upload: every table at an offset that is a multiple of 8
+    parts, offs, at = [], [], 0
+    for a in (glyphs, items, texts, palette, shade):
+        raw = np.zeros(0, np.uint8) if a is None else a.view(np.uint8).reshape(-1)
+        raw = np.concatenate([raw, np.zeros(-raw.size % 8, np.uint8)])
+        offs.append(at)
+        parts.append(raw)
+        at += raw.size
+    blob = torch.from_numpy(np.concatenate(parts + [np.zeros(8, np.uint8)])).to(image_u8.device)
+    base = blob.data_ptr()
+    dev = [base + o if a is not None and a.size else None for o, a in zip(offs, (glyphs, items, texts, palette, shade))]
+    Hc, Wc = int(scale) * (H + 4), int(scale) * (W + 4)
+    canvas = torch.empty((Hc, Wc, 3), dtype=torch.uint8, device=image_u8.device)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing is not None else None
+    if ev:
+        ev[0].record()
+    check(L.mrcnn_draw_overlay(C.byref(d), host[0], host[1], host[2], ptr(image_u8), ptr(planes.words) if n_planes else None,
+                               ptr(planes.box) if n_planes else None, dev[1], dev[2], dev[0], dev[3], dev[4], ptr(canvas),
+                               current_stream()), "mrcnn_draw_overlay")
+    if ev:
+        ev[1].record()
+        ev[1].synchronize()
+        timing["render_kernel_ms"] = round(ev[0].elapsed_time(ev[1]), 4)
+        timing["canvas_bytes"] = 3 * Hc * Wc
+    canvas._keep = blob                      # alive until the caller has synchronised on the result
+    return canvas
+
+
 def fill_zero(t):
     _need_cuda(t)
     check(_hip.lib().mrcnn_fill_zero(ptr(t), t.numel() * t.element_size(), current_stream()), "mrcnn_fill_zero")

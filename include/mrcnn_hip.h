@@ -295,6 +295,50 @@ int mrcnn_outline_emit(const void* pool, int64_t pool_words, const mrcnn_tile_so
                        const int32_t* pixel_offsets, float* points, int64_t points_cap, int32_t* contour_offsets, int64_t contours_cap,
                        int32_t* source_contours, int32_t* pixels, int64_t pixels_cap, void* stream);
 
+/* The detection overlay of Analyzer.draw_results (mrcnn/analyze.py:2039-2135) as the integer raster of DESIGN.md 4.12, composed in
+ * one pass over the canvas (draw.render_host is the NumPy statement; the two give the same bytes).  image [H][W][3] uint8; the
+ * masks are the bit planes of the mask graph below (planes [n_planes][H][wpr], plane_box [n_planes][4] as _pack / _union give
+ * them: the box culls, so a smaller one hides pixels); canvas [scale (H + 4)][scale (W + 4)][3] uint8, every byte written.
+ *   items    in layer order.  MRCNN_DRAW_GT_BOX: the dashed outline of (y1, x1, y2, x2), thickness max(1, scale / 4).
+ *            MRCNN_DRAW_DETECTION: the solid outline of the box, thickness max(1, scale / 2), then the contour of plane `plane`
+ *            (-1: none) in the opaque colour.  Outlines are blended, (179 colour + 76 below + 127) / 255.  An empty or inverted
+ *            box paints nothing.  With `shaded`, the planes of all detections shade the frame first, in item order.
+ *   texts    in order, over the items: `count` glyphs from glyphs[first], the block's bottom-left corner at frame point (xa, ya).
+ *   glyphs   one per character: 35 bits, bit 5 row + column of a 5 x 7 cell, row 0 on top.
+ *   palette  [n_colours][4] uint8 (r, g, b, unused); shade [n_colours][3][256] uint8 (read only when `shaded`): the value a
+ *            channel value takes under a mask of that colour.
+ * items / texts / glyphs are given twice, as the host tables the call validates and as their device copies.  Malformed
+ * (MRCNN_ERR_ARG): H, W, scale or n_colours <= 0, a negative count, a kind other than the two, a colour outside [0, n_colours),
+ * a plane outside [-1, n_planes), a ground-truth box with a plane, a text that leaves glyphs, a glyph with a bit past 35, a
+ * missing pointer.  Caps (past any: MRCNN_ERR_UNSUPPORTED, use the host statement): H, W <= 16384; scale <= 64; canvas sides
+ * <= 65536 and canvas bytes <= 2^31 - 1; 4096 items; 4096 texts of at most 256 glyphs; 256 colours; coordinates within +-2^20.
+ * A refused call launches and writes nothing.  mrcnn_draw_check: the status for those tables; launches nothing.
+ * Nothing is allocated on the device, nothing synchronises, no atomics: the canvas is bitwise the same from run to run.  */
+#define MRCNN_DRAW_GT_BOX 0
+#define MRCNN_DRAW_DETECTION 1
+typedef struct {
+    int32_t kind;
+    int32_t y1, x1, y2, x2;          /* frame pixels, y2 / x2 exclusive */
+    int32_t colour;                  /* palette index */
+    int32_t plane;                   /* bit plane of a detection, or -1 */
+    int32_t pad;
+} mrcnn_draw_item;
+typedef struct {
+    int32_t ya, xa;                  /* anchor, frame pixels */
+    int32_t colour;                  /* palette index */
+    int32_t first, count;            /* glyphs[first .. first + count) */
+    int32_t pad[3];
+} mrcnn_draw_text;
+typedef struct {
+    int32_t H, W, scale, n_planes, n_items, n_texts, n_glyphs, n_colours, shaded, pad;
+} mrcnn_draw_desc;
+int mrcnn_draw_check(const mrcnn_draw_desc* d, const mrcnn_draw_item* items_host, const mrcnn_draw_text* texts_host,
+                     const uint64_t* glyphs_host);
+int mrcnn_draw_overlay(const mrcnn_draw_desc* d, const mrcnn_draw_item* items_host, const mrcnn_draw_text* texts_host,
+                       const uint64_t* glyphs_host, const void* image, const void* planes, const int32_t* plane_box,
+                       const mrcnn_draw_item* items, const mrcnn_draw_text* texts, const uint64_t* glyphs, const void* palette,
+                       const void* shade, void* canvas, void* stream);
+
 /* The mask graph of Analyzer.extract_det_masks (mrcnn/analyze.py:1162-1496): which detection masks of a frame overlap or touch,
  * and the unions of those that are merged.  The masks of ONE frame are bit planes, planes[n][H][wpr] 32-bit words, wpr =
  * ceil(W / 32): pixel x of a row is bit x & 31 of word x >> 5, least significant bit first (numpy.packbits(...,

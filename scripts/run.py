@@ -11,7 +11,9 @@ Multi-GPU training: ``torchrun --nproc-per-node NGPU scripts/run.py train --ngpu
 ModelTester (caesar_mrcnn_amd/analyze.py: confusion matrix, purity, completeness.csv and reliability.csv); `detect` runs the Analyzer
 post-processing (caesar_mrcnn_amd/analyze.py: score filter, connected-mask merging, best-of-overlapping
 selection) on every tile and writes the objects as JSON (`out_<image>.json`: image_id, objs[name, x1, x2,
-y1, y2, class_id, class_name, score, pixels, vertexes, edge]) and DS9 regions.  Plots are not produced.
+y1, y2, class_id, class_name, score, pixels, vertexes, edge]) and DS9 regions.  With `--draw` or `--detect_outfile NAME` it also
+writes the overlay PNG of the frame (`out_<image>.png` or NAME; rendered on the GPU); matplotlib plots are not
+produced.
 `detect --split_img_in_tiles --merge_tile_sources` is the reference's SFinder (caesar_mrcnn_amd/sfinder.py): sources that
 straddle tile borders are merged and one catalogue (objects gain `merged`, names S1..Sn) is written by rank 0; with
 `--compute_source_params` every object also gains the reference's parameters (nPix, S .. flux, X0 .. Y0w_wcs, Xmin .. Ymax_wcs);
@@ -96,7 +98,12 @@ def parse_args(argv=None):
     p.add_argument('--image', type=str, default=None)
     for n in ("xmin", "xmax", "ymin", "ymax"):
         p.add_argument('--' + n, type=int, default=-1)
-    p.add_argument('--detect_outfile', type=str, default="")
+    p.add_argument('--detect_outfile', type=str, default="",
+                   help="`detect`: draw the overlay PNG (the frame, the detected masks' contours, their boxes and scores) to this file")
+    p.add_argument('--draw', action='store_true', default=False,
+                   help="extension: draw the overlay PNGs under the reference's default names -- out_<image>.png in `detect`, "
+                        "out_<base>_id<uuid>.png per image in `test --reference_tester` (the reference always draws; here it is off "
+                        "by default).  A tiled `detect` (--split_img_in_tiles), merged or not, draws nothing")
     p.add_argument('--detect_outfile_json', type=str, default="")
     p.add_argument('--split_img_in_tiles', action='store_true', default=False)
     p.add_argument('--tile_xsize', type=int, default=512)
@@ -121,6 +128,15 @@ def tile_batch_of(args):
     """--tile_batch N where it means something: `detect --split_img_in_tiles --merge_tile_sources`; else 0."""
     n = getattr(args, "tile_batch", 0)
     return n if n >= 1 and args.command == "detect" and args.split_img_in_tiles and args.merge_tile_sources else 0
+
+
+def draw_settings(args, ntiles=1):
+    """(Analyzer.draw, Analyzer.outfile) of `detect`: --detect_outfile NAME draws to NAME, --draw under the default name; tiles are
+    never drawn (they would all carry the image's name; the reference's TileTask does not draw either)."""
+    wanted = bool(getattr(args, "draw", False) or getattr(args, "detect_outfile", ""))
+    if wanted and ntiles > 1:
+        logger.warning("A tiled detect draws nothing: --draw / --detect_outfile ignored")
+    return wanted and ntiles == 1, getattr(args, "detect_outfile", "") or ""
 
 
 def build_config(args, class_dict_model):
@@ -260,6 +276,7 @@ def test_reference(args, model, cfg):
     tester.n_max_img = args.maxnimgs
     tester.remap_classids = args.remap_classids
     tester.classid_map = classid_remap_dict
+    tester.draw = bool(getattr(args, "draw", False))
     tester.test()
     return 0
 
@@ -344,6 +361,7 @@ def detect(args, model, cfg):
     analyzer = Analyzer(model, cfg)
     analyzer.score_thr, analyzer.iou_thr = args.scoreThr, args.iouThr
     analyzer.write_to_json = analyzer.write_to_ds9 = False          # one file for all tiles, written below
+    analyzer.draw, analyzer.outfile = draw_settings(args, len(tiles))
     objs, regions = [], []
     for t, (xmin, xmax, ymin, ymax) in enumerate(tiles):
         if t % world != rank:            # tiles are independent: replicas only (sfinder.py:1235-1251 round-robin)
