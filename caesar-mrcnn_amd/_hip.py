@@ -188,9 +188,10 @@ _SIGNATURES = {
     "mrcnn_winograd_input_g": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),
     "mrcnn_winograd_weights_g": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mrcnn_winograd_output_g": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),
-    "mrcnn_winograd_output_bwd_g": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.POINTER(WinoGroup), _P]),
-    "mrcnn_winograd_output_bwd_zmask_g": (C.c_int, [_P] * 10 + [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),
+    "mrcnn_winograd_output_bwd_rows": (C.c_int, [C.POINTER(WinoGroup), C.c_int, C.c_int]),
+    "mrcnn_winograd_output_bwd_g": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),
+    "mrcnn_winograd_output_bwd_zmask_g": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),
+    "mrcnn_winograd_output_bwd_sums": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mrcnn_winograd_dy_g": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),
     "mrcnn_winograd_dw_g": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mrcnn_deconv2x2_gemm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -214,7 +215,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_draw_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats")
+_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_draw_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
 
 
 class _LibProxy(object):

@@ -242,116 +242,177 @@ __global__ __launch_bounds__(256) void winograd_output_kernel(const float* __res
     wino_output_tile<OTH, OTW, CV>(Mt, out, z, bi, sc, sh, H, W, C, Tp, act, g, t, c);
 }
 
-// The output transform of a DATA gradient together with the epilogue backward of the layer below (what mrcnn_conv2d_dgrad_ep does
-// for the direct kernel): y = A^T m A is d(loss)/d(activated output of the layer below);
-//   g = y * act'(out_below);  dz = g * scale_below -> stored;  dbeta += sum g, dgamma += sum g (z_below - mean) rstd, dbias += sum dz.
-// A workgroup walks a range of tiles: lane = CV-channel group (C / CV of them, a power of two <= 256), 256 / (C / CV) tiles in
-// flight; channel sums stay in registers, meet in LDS and leave as one atomic per channel and workgroup.
-// one tile x CV channels of the data-gradient output transform + epilogue backward; the channel sums go to the caller's registers
-template <int OTH, int OTW, int CV>
-__device__ __forceinline__ void wino_output_bwd_tile(const float* __restrict__ Mt, float* __restrict__ dz_out, const float* __restrict__ below_out,
-                                                     const float* __restrict__ below_z, const typename WinoVec<CV>::type sc,
-                                                     const typename WinoVec<CV>::type mu, const typename WinoVec<CV>::type rs,
-                                                     const typename WinoVec<CV>::type fsh, bool zmask, bool want_dg, int H, int W, int C,
-                                                     long long Tp, int act, const WinoGrp& g, long long t, int c,
-                                                     typename WinoVec<CV>::type& a_db, typename WinoVec<CV>::type& a_dg,
-                                                     typename WinoVec<CV>::type& a_bias) {
-    typedef typename WinoVec<CV>::type vec;
-    constexpr int ITH = OTH + 2, ITW = OTW + 2;
-    const WinoTile q = wino_tile(t, g.th_n, g.tw_n);
-    vec s[OTH][ITW];
-#pragma unroll
-    for (int k = 0; k < ITW; ++k) {
-        vec col[ITH], o[OTH];
-#pragma unroll
-        for (int r = 0; r < ITH; ++r) col[r] = *(const vec*)(Mt + ((long long)(r * ITW + k) * Tp + t) * C + c);
-        wino_at<OTH>(col, o);
-#pragma unroll
-        for (int a = 0; a < OTH; ++a) s[a][k] = o[a];
+// wino_buffer_load: CV floats at base + lane offset + uniform offset (bytes) -- ONE address register per lane for all the
+// (OTH + 2)(OTW + 2) matrices of a tile (as 64-bit addresses they take 72 registers of a 6 x 6 tile's budget)
+template <int CV>
+__device__ __forceinline__ typename WinoVec<CV>::type wino_buffer_load(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
+    typename WinoVec<CV>::type r;
+    if constexpr (CV == 2) {
+        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, (int)soff, 0);
+        r[0] = __uint_as_float(v[0]); r[1] = __uint_as_float(v[1]);
+    } else {
+        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 0);
+        r[0] = __uint_as_float(v[0]); r[1] = __uint_as_float(v[1]); r[2] = __uint_as_float(v[2]); r[3] = __uint_as_float(v[3]);
     }
-#pragma unroll
-    for (int a = 0; a < OTH; ++a) {
-        vec y[OTW];
-        wino_at<OTW>(s[a], y);
-        const int oh = g.oh0 + OTH * q.th + a;
-        if (oh >= H) continue;
-#pragma unroll
-        for (int b = 0; b < OTW; ++b) {
-            const int ow = g.ow0 + OTW * q.tw + b;
-            if (ow >= W) continue;
-            const long long addr = (((long long)q.n * H + oh) * W + ow) * C + c;
-            vec gg = y[b], dz, zz = {};
-            if (want_dg || zmask) zz = *(const vec*)(below_z + addr);
-            if (act == MRCNN_ACT_RELU) {
-                if (zmask) {
-#pragma unroll
-                    for (int e = 0; e < CV; ++e) {
-                        const float v = sc[e] * zz[e] + fsh[e];
-                        gg[e] = v > 0.f ? gg[e] : 0.f;
-                    }
-                } else {
-                    const vec oo = *(const vec*)(below_out + addr);
-#pragma unroll
-                    for (int e = 0; e < CV; ++e) gg[e] = oo[e] > 0.f ? gg[e] : 0.f;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < CV; ++e) dz[e] = gg[e] * sc[e];
-            *(vec*)(dz_out + addr) = dz;
-            if (want_dg) {
-#pragma unroll
-                for (int e = 0; e < CV; ++e) a_dg[e] += gg[e] * (zz[e] - mu[e]) * rs[e];
-            }
-#pragma unroll
-            for (int e = 0; e < CV; ++e) { a_db[e] += gg[e]; a_bias[e] += dz[e]; }
-        }
-    }
+    return r;
 }
 
-template <int OTH, int OTW, int CV>
+// The output transform of a DATA gradient together with the epilogue backward of the layer below (what mrcnn_conv2d_dgrad_ep does
+// for the direct kernel): y = A^T m A is d(loss)/d(activated output of the layer below);
+//   g = y * act'(out_below);  dz = g * scale_below -> stored;  channel sums of g, g (z_below - mean) rstd and dz.
+// A persistent grid (a few workgroups per CU) walks the tiles: lane = CV-channel group (C / CV of them, a power of two <= 256),
+// R = 256 / (C / CV) tiles in flight per workgroup, tiles blockIdx.x * R + rsub, + gridDim.x * R, ...  Everything a tile reads --
+// its (OTH + 2)(OTW + 2) transform-domain values AND the z (or activated output) of the layer below under its outputs -- is
+// requested before the first addition, so a tile costs one memory round trip, like the forward output transform.  Channel sums
+// stay in registers over the walk, meet in LDS in fixed order and leave as ONE row of partials [3][C] per workgroup (plain
+// stores); winograd_bwd_sums_kernel adds the rows of all groups of a layer up, in fixed order, once per layer.
+// MASK: 0 no activation below, 1 ReLU mask recomputed from z (fwd_shift), 2 ReLU mask from the activated output
+template <int OTH, int OTW, int CV, int MASK>
 __global__ __launch_bounds__(256) void winograd_output_bwd_kernel(const float* __restrict__ Mt, float* __restrict__ dz_out,
                                                                   const float* __restrict__ below_out, const float* __restrict__ below_z,
                                                                   const float* __restrict__ scale, const float* __restrict__ mean,
-                                                                  const float* __restrict__ rstd, float* dgamma, float* dbeta, float* dbias,
-                                                                  int N, int H, int W, int C, long long T, long long Tp, int act,
-                                                                  long long tiles_per_block, int lg, const WinoGrp g,
-                                                                  const float* __restrict__ fwd_shift) {
+                                                                  const float* __restrict__ rstd, const float* __restrict__ fwd_shift,
+                                                                  float* __restrict__ partials, int want_dg, int H, int W, int C, unsigned T,
+                                                                  long long Tp, int lg, const WinoGrp g, const FastDiv d_th,
+                                                                  const FastDiv d_tw) {
     typedef typename WinoVec<CV>::type vec;
     constexpr int ITH = OTH + 2, ITW = OTW + 2;
-    __shared__ float sacc[3 * 4 * 256];
+    __shared__ float sacc[3 * 4 * 256];                         // [3][R][C]
     const int L = 1 << lg, R = 256 >> lg;                       // L = C / CV lanes, R tiles in flight
-    for (int c = threadIdx.x; c < 3 * CV * L; c += 256) sacc[c] = 0.f;
-    __syncthreads();
     const int rsub = threadIdx.x >> lg, lane = threadIdx.x & (L - 1);
     const int c = lane * CV;
-    const long long t0 = (long long)blockIdx.x * tiles_per_block;
-    long long t1 = t0 + tiles_per_block;
-    if (t1 > T) t1 = T;
     vec sc, mu = {}, rs = {}, fsh = {};
 #pragma unroll
     for (int e = 0; e < CV; ++e) sc[e] = 1.f;
     if (scale) sc = *(const vec*)(scale + c);
-    if (dgamma) { mu = *(const vec*)(mean + c); rs = *(const vec*)(rstd + c); }
-    // fwd_shift: the ReLU mask is taken from the stored pre-BN value -- out > 0 <=> scale * z + shift > 0, the very expression
-    // (operation for operation, no contraction) the forward epilogue fed to max(., 0) -- so the activated output of the layer
-    // below is not read at all: one of the pass's four tensor streams (0.41 of 2.25 GB per mask-head layer) gone, same bits
-    const bool zmask = fwd_shift != nullptr;
-    if (zmask) fsh = *(const vec*)(fwd_shift + c);
+    if (want_dg) { mu = *(const vec*)(mean + c); rs = *(const vec*)(rstd + c); }
+    // MASK 1: out > 0 <=> scale * z + shift > 0, the very expression (operation for operation, no contraction) the forward
+    // epilogue fed to max(., 0) -- so the activated output of the layer below is not read at all, same bits
+    if (MASK == 1) fsh = *(const vec*)(fwd_shift + c);
+    const bool need_z = MASK == 1 || want_dg;
     vec a_db = {}, a_dg = {}, a_bias = {};
-    for (long long t = t0 + rsub; t < t1; t += R)
-        wino_output_bwd_tile<OTH, OTW, CV>(Mt, dz_out, below_out, below_z, sc, mu, rs, fsh, zmask, dgamma != nullptr, H, W, C, Tp, act, g, t, c,
-                                           a_db, a_dg, a_bias);
+    const unsigned step = gridDim.x * (unsigned)R;
+    const __amdgpu_buffer_rsrc_t rsrc_m = __builtin_amdgcn_make_buffer_rsrc((void*)Mt, 0, 0xFFFFFFF0u, 0x00020000);
+    const unsigned mstride = (unsigned)Tp * (unsigned)C * 4u;   // bytes per transform-domain matrix (the host checks that all fit 4 GiB)
+    for (unsigned t = blockIdx.x * (unsigned)R + rsub; t < T; t += step) {
+        const unsigned q = fast_div(t, d_tw), n = fast_div(q, d_th);
+        const int tw = (int)(t - q * (unsigned)g.tw_n), th = (int)(q - n * (unsigned)g.th_n);
+        const int oh0 = g.oh0 + OTH * th, ow0 = g.ow0 + OTW * tw;
+        // all the tile's loads first: outputs past the map's edge (uniform 4 x 4 tiling) read the last row / column, unused
+        // (addresses = a uniform base + a 32-bit byte offset per lane: one register per stream instead of two per load)
+        vec m[ITH][ITW], zz[OTH][OTW], oo[OTH][OTW];
+        const unsigned moff = (t * (unsigned)C + c) * 4u;
 #pragma unroll
-    for (int k = 0; k < CV; ++k) {
-        if (dbeta || dgamma) atomicAdd(&sacc[lane * CV + k], a_db[k]);
-        if (dgamma) atomicAdd(&sacc[CV * L + lane * CV + k], a_dg[k]);
-        if (dbias) atomicAdd(&sacc[2 * CV * L + lane * CV + k], a_bias[k]);
+        for (int r = 0; r < ITH; ++r)
+#pragma unroll
+            for (int k = 0; k < ITW; ++k)
+                m[r][k] = wino_buffer_load<CV>(rsrc_m, moff, (unsigned)(r * ITW + k) * mstride);
+        // byte offsets of the tile's outputs, clamped to the map
+        const unsigned base = (((n * (unsigned)H + oh0) * W + ow0) * C + c) * 4u;
+        unsigned roff[OTH], coff[OTW];
+#pragma unroll
+        for (int a = 0; a < OTH; ++a) roff[a] = base + (unsigned)(min(a, H - 1 - oh0) * W * C) * 4u;
+#pragma unroll
+        for (int b = 0; b < OTW; ++b) coff[b] = (unsigned)(min(b, W - 1 - ow0) * C) * 4u;
+        if (need_z) {
+#pragma unroll
+            for (int a = 0; a < OTH; ++a)
+#pragma unroll
+                for (int b = 0; b < OTW; ++b) zz[a][b] = *(const vec*)((const char*)below_z + (roff[a] + coff[b]));
+        } else {
+#pragma unroll
+            for (int a = 0; a < OTH; ++a)
+#pragma unroll
+                for (int b = 0; b < OTW; ++b) zz[a][b] = vec{};
+        }
+        if (MASK == 2) {
+#pragma unroll
+            for (int a = 0; a < OTH; ++a)
+#pragma unroll
+                for (int b = 0; b < OTW; ++b) oo[a][b] = *(const vec*)((const char*)below_out + (roff[a] + coff[b]));
+        }
+        vec s[OTH][ITW];
+#pragma unroll
+        for (int k = 0; k < ITW; ++k) {              // A^T down the rows of every column k
+            vec col[ITH], o[OTH];
+#pragma unroll
+            for (int r = 0; r < ITH; ++r) col[r] = m[r][k];
+            wino_at<OTH>(col, o);
+#pragma unroll
+            for (int a = 0; a < OTH; ++a) s[a][k] = o[a];
+        }
+#pragma unroll
+        for (int a = 0; a < OTH; ++a) {
+            vec y[OTW];
+            wino_at<OTW>(s[a], y);
+#pragma unroll
+            for (int b = 0; b < OTW; ++b) {
+                const bool inside = oh0 + a < H && ow0 + b < W;     // past the edge: nothing stored, zeros into the sums
+                vec gg = y[b], dz;
+                if (MASK == 1) {
+#pragma unroll
+                    for (int e = 0; e < CV; ++e) {
+                        const float v = sc[e] * zz[a][b][e] + fsh[e];
+                        gg[e] = v > 0.f ? gg[e] : 0.f;
+                    }
+                } else if (MASK == 2) {
+#pragma unroll
+                    for (int e = 0; e < CV; ++e) gg[e] = oo[a][b][e] > 0.f ? gg[e] : 0.f;
+                }
+#pragma unroll
+                for (int e = 0; e < CV; ++e) {
+                    gg[e] = inside ? gg[e] : 0.f;
+                    dz[e] = gg[e] * sc[e];
+                }
+                if (inside) *(vec*)((char*)dz_out + (roff[a] + coff[b])) = dz;
+                if (want_dg) {
+#pragma unroll
+                    for (int e = 0; e < CV; ++e) a_dg[e] += gg[e] * (zz[a][b][e] - mu[e]) * rs[e];
+                }
+#pragma unroll
+                for (int e = 0; e < CV; ++e) { a_db[e] += gg[e]; a_bias[e] += dz[e]; }
+            }
+        }
+    }
+    if (!partials) return;
+#pragma unroll
+    for (int e = 0; e < CV; ++e) {
+        sacc[(0 * R + rsub) * C + c + e] = a_db[e];
+        sacc[(1 * R + rsub) * C + c + e] = a_dg[e];
+        sacc[(2 * R + rsub) * C + c + e] = a_bias[e];
     }
     __syncthreads();
-    for (int j = threadIdx.x; j < CV * L; j += 256) {
-        if (dbeta) atomicAdd(&dbeta[j], sacc[j]);
-        if (dgamma) atomicAdd(&dgamma[j], sacc[CV * L + j]);
-        if (dbias) atomicAdd(&dbias[j], sacc[2 * CV * L + j]);
+    for (int j = threadIdx.x; j < 3 * C; j += 256) {
+        const int k = j / C, cc = j - k * C;
+        float v = sacc[k * R * C + cc];
+        for (int r = 1; r < R; ++r) v += sacc[(k * R + r) * C + cc];
+        partials[(long long)blockIdx.x * 3 * C + j] = v;
+    }
+}
+
+// sums over the rows of partials [rows][3][C] (the workgroups of every group of a layer), added to dbeta / dgamma / dbias: a
+// workgroup = 16 columns x 64 row slices, slice s takes rows s, s + 64, ...; the slices meet in LDS and are added in order, so
+// the result does not depend on timing.  One atomic per column (the buffers may be accumulated into from elsewhere).
+#define WINO_SUMS_COLS 16
+#define WINO_SUMS_SLICES 64
+__global__ __launch_bounds__(WINO_SUMS_COLS * WINO_SUMS_SLICES) void winograd_bwd_sums_kernel(const float* __restrict__ partials, int rows,
+                                                                                              int C, float* dgamma, float* dbeta,
+                                                                                              float* dbias) {
+    __shared__ float sm[WINO_SUMS_SLICES][WINO_SUMS_COLS];
+    const int col = threadIdx.x % WINO_SUMS_COLS, slice = threadIdx.x / WINO_SUMS_COLS;
+    const int j = blockIdx.x * WINO_SUMS_COLS + col;
+    const int k = j / C;
+    float* dst = k == 0 ? dbeta : k == 1 ? dgamma : k == 2 ? dbias : nullptr;      // k == 3: past the last column
+    float v = 0.f;
+    if (dst) {
+#pragma unroll 8
+        for (int r = slice; r < rows; r += WINO_SUMS_SLICES) v += partials[(long long)r * 3 * C + j];
+    }
+    sm[slice][col] = v;
+    __syncthreads();
+    if (slice == 0 && dst) {
+        for (int s = 1; s < WINO_SUMS_SLICES; ++s) v += sm[s][col];
+        atomicAdd(&dst[j - k * C], v);
     }
 }
 
@@ -648,44 +709,75 @@ extern "C" int mrcnn_winograd_output_g(const float* Mt, float* out, float* z, co
     return mrcnn_launch_status();
 }
 
-static int wino_output_bwd_g(const float* Mt, float* dz_below, const float* below_out, const float* below_z, const float* scale,
-                             const float* mean, const float* rstd, float* dgamma, float* dbeta, float* dbias, int N, int H,
-                             int W, int C, int act, const mrcnn_wino_group* g, void* stream, const float* fwd_shift);
+// ---- data gradient: output transform + epilogue backward of the layer below --------------------------------------------------------
+// workgroups of a group's launch = rows of partials it writes: every R tiles once, at most 4 workgroups per CU (what fits at
+// <= 128 registers), each walking its tiles
+static int wino_bwd_lanes_lg(const mrcnn_wino_group* g, int C) {            // log2(C / CV), or -1
+    const int cn = C / wino_grp_cv(g);
+    if (cn <= 0 || cn > 256 || (cn & (cn - 1)) || cn * wino_grp_cv(g) != C) return -1;
+    int lg = 0;
+    while ((1 << lg) < cn) ++lg;
+    return lg;
+}
+extern "C" int mrcnn_winograd_output_bwd_rows(const mrcnn_wino_group* g, int N, int C) {
+    if (!g || N <= 0 || (g->oth != 2 && g->oth != 4) || (g->otw != 2 && g->otw != 4) || g->th_n <= 0 || g->tw_n <= 0) return 0;
+    const int lg = wino_bwd_lanes_lg(g, C);
+    if (lg < 0) return 0;
+    const long long T = wino_grp_tiles(g, N), R = 256 >> lg, cap = 4LL * mrcnn_num_cus();
+    const long long wgs = cdiv64(T, R);
+    return (int)(wgs < cap ? wgs : cap);
+}
+
+template <int MASK>
+static int wino_output_bwd_launch(const float* Mt, float* dz_below, const float* below_out, const float* below_z, const float* scale,
+                                  const float* mean, const float* rstd, const float* fwd_shift, float* partials, int N, int H, int W,
+                                  int C, const mrcnn_wino_group* g, void* stream) {
+    const int lg = wino_bwd_lanes_lg(g, C);
+    const long long T = wino_grp_tiles(g, N);
+    if (lg < 0) return MRCNN_ERR_UNSUPPORTED;
+    // tile ids (and their fast division) and the byte offsets into a transform-domain matrix and into the maps are 32-bit
+    if ((long long)wino_grp_nb(g) * wino_rows(T) * C * 4 >= (1LL << 32) || (long long)N * H * W * C * 4 >= (1LL << 32)) return MRCNN_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)mrcnn_winograd_output_bwd_rows(g, N, C));
+    const WinoGrp k = {g->th_n, g->tw_n, g->oh0, g->ow0};
+    const int want_dg = partials && mean && rstd && below_z;
+#define WINO_BWD_INST(oth, otw, cv)                                                                                            \
+    hipLaunchKernelGGL((winograd_output_bwd_kernel<oth, otw, cv, MASK>), grid, dim3(256), 0, (hipStream_t)stream, Mt, dz_below, below_out, \
+                       below_z, scale, mean, rstd, fwd_shift, partials, want_dg, H, W, C, (unsigned)T, wino_rows(T), lg, k,    \
+                       make_fastdiv((unsigned)g->th_n), make_fastdiv((unsigned)g->tw_n))
+    if (g->oth == 2 && g->otw == 2) WINO_BWD_INST(2, 2, 4);
+    else if (g->oth == 4 && g->otw == 4) WINO_BWD_INST(4, 4, 2);
+    else if (g->oth == 4) WINO_BWD_INST(4, 2, 2);
+    else WINO_BWD_INST(2, 4, 2);
+#undef WINO_BWD_INST
+    return mrcnn_launch_status();
+}
 
 extern "C" int mrcnn_winograd_output_bwd_g(const float* Mt, float* dz_below, const float* below_out, const float* below_z, const float* scale,
-                                           const float* mean, const float* rstd, float* dgamma, float* dbeta, float* dbias, int N, int H,
-                                           int W, int C, int act, const mrcnn_wino_group* g, void* stream) {
-    return wino_output_bwd_g(Mt, dz_below, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, N, H, W, C, act, g, stream, nullptr);
+                                           const float* mean, const float* rstd, float* partials, int N, int H, int W, int C, int act,
+                                           const mrcnn_wino_group* g, void* stream) {
+    if (!Mt || !dz_below || !wino_grp_ok(g, N, H, W, C) || (!mean != !rstd) || (mean && !below_z)) return MRCNN_ERR_ARG;
+    if (act == MRCNN_ACT_NONE)
+        return wino_output_bwd_launch<0>(Mt, dz_below, nullptr, below_z, scale, mean, rstd, nullptr, partials, N, H, W, C, g, stream);
+    if (act != MRCNN_ACT_RELU || !below_out) return MRCNN_ERR_ARG;
+    return wino_output_bwd_launch<2>(Mt, dz_below, below_out, below_z, scale, mean, rstd, nullptr, partials, N, H, W, C, g, stream);
 }
 
 /* the same for a ReLU layer below whose forward epilogue was out = max(scale * z + shift, 0): the mask comes from z (bit for bit
  * the forward's decision), `out` is never read */
 extern "C" int mrcnn_winograd_output_bwd_zmask_g(const float* Mt, float* dz_below, const float* below_z, const float* scale,
-                                                 const float* shift, const float* mean, const float* rstd, float* dgamma, float* dbeta,
-                                                 float* dbias, int N, int H, int W, int C, const mrcnn_wino_group* g, void* stream) {
-    if (!below_z || !scale || !shift) return MRCNN_ERR_ARG;
-    return wino_output_bwd_g(Mt, dz_below, nullptr, below_z, scale, mean, rstd, dgamma, dbeta, dbias, N, H, W, C, MRCNN_ACT_RELU, g, stream, shift);
+                                                 const float* shift, const float* mean, const float* rstd, float* partials, int N, int H,
+                                                 int W, int C, const mrcnn_wino_group* g, void* stream) {
+    if (!Mt || !dz_below || !wino_grp_ok(g, N, H, W, C) || !below_z || !scale || !shift || (!mean != !rstd)) return MRCNN_ERR_ARG;
+    return wino_output_bwd_launch<1>(Mt, dz_below, nullptr, below_z, scale, mean, rstd, shift, partials, N, H, W, C, g, stream);
 }
 
-static int wino_output_bwd_g(const float* Mt, float* dz_below, const float* below_out, const float* below_z, const float* scale,
-                             const float* mean, const float* rstd, float* dgamma, float* dbeta, float* dbias, int N, int H,
-                             int W, int C, int act, const mrcnn_wino_group* g, void* stream, const float* fwd_shift) {
-    if (!Mt || !dz_below || !wino_grp_ok(g, N, H, W, C)) return MRCNN_ERR_ARG;
-    if ((act != MRCNN_ACT_NONE && act != MRCNN_ACT_RELU) || (act == MRCNN_ACT_RELU && !below_out && !fwd_shift)) return MRCNN_ERR_ARG;
-    if (dgamma && (!below_z || !mean || !rstd)) return MRCNN_ERR_ARG;
-    const int cv = wino_grp_cv(g);
-    const int cn = C / cv;
-    if (cn > 256 || (cn & (cn - 1))) return MRCNN_ERR_UNSUPPORTED;
-    int lg = 0;
-    while ((1 << lg) < cn) ++lg;
-    const long long T = wino_grp_tiles(g, N);
-    const long long R = 256 >> lg;
-    long long per = (T + 2047) / 2048;                          // ~2048 workgroups; every one a whole number of passes
-    per = (per + R - 1) / R * R;
-    const dim3 grid((unsigned)cdiv64(T, per));
-    const WinoGrp k = {g->th_n, g->tw_n, g->oh0, g->ow0};
-    WINO_LAUNCH_G(winograd_output_bwd_kernel, g, grid, grid, Mt, dz_below, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, N, H, W,
-                  C, T, wino_rows(T), act, per, lg, k, fwd_shift);
+extern "C" int mrcnn_winograd_output_bwd_sums(const float* partials, int rows, int C, float* dgamma, float* dbeta, float* dbias,
+                                              void* stream) {
+    if (!partials || rows <= 0 || C <= 0) return MRCNN_ERR_ARG;
+    if (!dgamma && !dbeta && !dbias) return MRCNN_OK;
+    const dim3 grid((unsigned)cdiv64(3LL * C, WINO_SUMS_COLS));
+    hipLaunchKernelGGL(winograd_bwd_sums_kernel, grid, dim3(WINO_SUMS_COLS * WINO_SUMS_SLICES), 0, (hipStream_t)stream, partials, rows, C,
+                       dgamma, dbeta, dbias);
     return mrcnn_launch_status();
 }
 

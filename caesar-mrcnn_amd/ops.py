@@ -1455,18 +1455,34 @@ def conv2d_dgrad_ep_winograd(dz, Ut, below_out, below_z, scale, mean, rstd, dgam
     out = empty((N, H, W, cout), torch.float32, dz.device)
     lib = _hip.lib()
     zmask = act == ACT_RELU and fwd_shift is not None and below_z is not None and scale is not None
+    if dgamma is None:
+        mean = rstd = None
+    # channel sums: every group's workgroups write one row of partials [3][cout] each into one per-stream buffer, group after
+    # group; one launch after the last group adds the rows up (fixed order) onto dgamma / dbeta / dbias
+    want_sums = dgamma is not None or dbeta is not None or dbias is not None
+    rows = [lib.mrcnn_winograd_output_bwd_rows(C.byref(g), N, cout) for g in winograd_groups(H, W, _wino_tile_of(Ut))]
+    assert min(rows) > 0, "channel count does not fit the Winograd data-gradient transform"
+    part = ptr(workspace(sum(rows) * 3 * cout * 4, dz.device, "winograd_bwd_sums")) if want_sums else None
+    done = []
 
     def finish(g, Mt):
+        p = None
+        if want_sums:
+            p = part + sum(done) * 3 * cout * 4
+            done.append(rows[len(done)])
         if zmask:
             check(lib.mrcnn_winograd_output_bwd_zmask_g(ptr(Mt), ptr(out), ptr(below_z), ptr(scale), ptr(fwd_shift), ptr(mean), ptr(rstd),
-                                                        ptr(dgamma), ptr(dbeta), ptr(dbias), N, H, W, cout, C.byref(g), current_stream()),
+                                                        p, N, H, W, cout, C.byref(g), current_stream()),
                   "mrcnn_winograd_output_bwd_zmask_g")
             return
         check(lib.mrcnn_winograd_output_bwd_g(ptr(Mt), ptr(out), ptr(below_out), ptr(below_z), ptr(scale), ptr(mean), ptr(rstd),
-                                              ptr(dgamma), ptr(dbeta), ptr(dbias), N, H, W, cout, act, C.byref(g), current_stream()),
+                                              p, N, H, W, cout, act, C.byref(g), current_stream()),
               "mrcnn_winograd_output_bwd_g")
 
     _winograd_run(dz, Ut, finish)
+    if want_sums:
+        check(lib.mrcnn_winograd_output_bwd_sums(part, sum(done), cout, ptr(dgamma), ptr(dbeta), ptr(dbias), current_stream()),
+              "mrcnn_winograd_output_bwd_sums")
     return out
 
 

@@ -682,14 +682,21 @@ int mrcnn_gemm_batched_f32(const float* V, const float* U, float* Mt, int nb, in
 int mrcnn_winograd_gemm(const float* V, const float* U, float* Mt, int nb, int rows, int K, int Cout, void* stream);
 int mrcnn_winograd_output_g(const float* Mt, float* out, float* z_out, const float* bias, const float* scale, const float* shift,
                             int N, int H, int W, int C, int act, const mrcnn_wino_group* g, void* stream);
+/* Data gradient: output transform of a group + epilogue backward of the layer below: g = y * act'(out_below), dz_below = g * scale.
+ * Channel sums (of g, of g (z_below - mean) rstd when mean / rstd are given, of dz) leave as partials: the launch writes
+ * mrcnn_winograd_output_bwd_rows(g, N, C) rows of [3][C] floats (one per workgroup, plain stores; partials may be NULL: no sums).
+ * The groups of a layer write their rows one after the other into one buffer; mrcnn_winograd_output_bwd_sums then ADDS the
+ * column sums of all `rows` rows to dbeta / dgamma / dbias (each may be NULL), in a fixed order: the same inputs give the same bits. */
+int mrcnn_winograd_output_bwd_rows(const mrcnn_wino_group* g, int N, int C);
 int mrcnn_winograd_output_bwd_g(const float* Mt, float* dz_below, const float* below_out, const float* below_z, const float* scale,
-                                const float* mean, const float* rstd, float* dgamma, float* dbeta, float* dbias, int N, int H, int W,
-                                int C, int act, const mrcnn_wino_group* g, void* stream);
+                                const float* mean, const float* rstd, float* partials, int N, int H, int W, int C, int act,
+                                const mrcnn_wino_group* g, void* stream);
 /* The same when the layer below is a ReLU layer with a frozen-BN affine (forward epilogue out = max(scale * z + shift, 0)): the
  * ReLU mask is recomputed from the stored z with the forward's own expression, so the activated output is not read. */
 int mrcnn_winograd_output_bwd_zmask_g(const float* Mt, float* dz_below, const float* below_z, const float* scale, const float* shift,
-                                      const float* mean, const float* rstd, float* dgamma, float* dbeta, float* dbias, int N, int H,
-                                      int W, int C, const mrcnn_wino_group* g, void* stream);
+                                      const float* mean, const float* rstd, float* partials, int N, int H, int W, int C,
+                                      const mrcnn_wino_group* g, void* stream);
+int mrcnn_winograd_output_bwd_sums(const float* partials, int rows, int C, float* dgamma, float* dbeta, float* dbias, void* stream);
 /* weight gradient: dM = A dy A^T (adjoint of the output transform) [(oth + 2)(otw + 2)][rows][C]; dU[xi] = V[xi]^T . dM[xi] are
  * 1 x 1 weight gradients (mrcnn_conv2d_wgrad on the first `tiles` rows of each matrix); dW = G^T dU G (accumulate != 0: added to dW). */
 int mrcnn_winograd_dy_g(const float* dy, float* dM, int N, int H, int W, int C, const mrcnn_wino_group* g, void* stream);
