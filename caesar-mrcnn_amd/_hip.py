@@ -124,6 +124,7 @@ _SIGNATURES = {
     "mrcnn_mask_union": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mrcnn_mask_cross_stats": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mrcnn_mask_plane_sums": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mrcnn_voc_match": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
     "mrcnn_unmold_masks_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mrcnn_unmold_masks": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
                                      C.c_size_t, _P]),

@@ -1531,8 +1531,10 @@ class Analyzer(object):
 class ModelTester(object):
     """``run.py test`` of the reference: every image of a dataset through ``Analyzer.inspect_results``, the confusion matrix,
     purity, matched scores and IoUs accumulated, and two tables -- one row per true object (completeness.csv) and one per
-    detected object (reliability.csv) -- rewritten after every image.  compute_mAP (:408-575, never switched on by the reference,
-    writes into vendored tool directories) is out of scope."""
+    detected object (reliability.csv) -- rewritten after every image.  With ``compute_mAP_metrics`` set, compute_mAP (:408-575)
+    follows: the per-image mask AP of the reference, the Pascal-VOC box metrics its vendored tool computes from gt_data /
+    pred_data (metrics.py; matched on the GPU) and, when ``metrics_outdir`` names a directory, the input files of the three
+    external tools under it."""
 
     def __init__(self, model, config, dataset):
         self.dataset, self.model, self.config = dataset, model, config
@@ -1553,6 +1555,10 @@ class ModelTester(object):
         self.detobj_gtinfo = []
         self.compute_mAP_metrics = False
         self.mAP = 0
+        self.APs = []                         # compute_mAP: mask AP at iou_thr per inspected image; mAP is their mean
+        self.voc = None                       # compute_mAP: metrics.voc_metrics(gt_data, pred_data, (0.5, iou_thr))
+        self.metrics_outdir = None            # compute_mAP: write the external tools' input files under this directory
+        self.inspected = []                   # (image_id, image_path) of the images test() went through
         self.completeness_dict_list, self.reliability_dict_list = [], []
         self.outfilename_completeness = "completeness.csv"
         self.outfilename_reliability = "reliability.csv"
@@ -1564,6 +1570,7 @@ class ModelTester(object):
         nimg = 0
         logger.info("Processing up to %d images " % self.n_max_img)
         gt_data, pred_data = [], []
+        self.inspected = []
         for index, image_id in enumerate(self.dataset.image_ids):
             if self.n_max_img > 0 and nimg >= self.n_max_img:
                 logger.info("Max number of images to inspect reached, stop here.")
@@ -1583,9 +1590,13 @@ class ModelTester(object):
             if analyzer.inspect_results(image_id, image_path) < 0:
                 logger.error("Failed to analyze results for image %s ..." % image_path_base)
                 continue
+            self.inspected.append((image_id, image_path))
             self.update_performances(analyzer)
         logger.info("Computing final performances ...")
         self.compute_performances()
+        if self.compute_mAP_metrics:
+            logger.info("Computing Mean AveragePrecision (mAP) ...")
+            self.compute_mAP(gt_data=gt_data, pred_data=pred_data)
         logger.info("Saving result data to file ...")
         self.save()
         return 0
@@ -1711,3 +1722,33 @@ class ModelTester(object):
         print("scoreThr=%f, <score>=%f, sigma(score)=%f" % (self.score_thr, self.detobj_scoreMean, self.detobj_scoreStdDev))
         print("== DET IOUs ==")
         print("iouThr=%f, <iou>=%f, sigma(iou)=%f" % (self.iou_thr, self.detobj_iouMean, self.detobj_iouStdDev))
+
+    def compute_mAP(self, gt_data, pred_data):
+        """:408-575.  (a) Mask AP at iou_thr of every inspected image (the reference's loop stops after the first one, marked TODO
+        there: ``APs[0]`` is its value): load_image_gt, detect, utils.compute_ap -- the [P, G] mask overlaps from the device tensor
+        the model kept (metrics.mask_ap) where there is one.  (b) The box metrics of the vendored Pascal-VOC tool at IoU 0.5 and
+        iou_thr.  (c) The printed block.  (d) The external tools' input files, under ``metrics_outdir`` when it is set (the reference
+        writes them into the current directory)."""
+        from . import datagen, metrics
+        self.APs = []
+        for image_id, _ in self.inspected:
+            image, image_meta, gt_class_id, gt_bbox, gt_mask = datagen.load_image_gt(self.dataset, self.config, image_id,
+                                                                                     use_mini_mask=False)
+            r = self.model.detect([image], verbose=0)[0]
+            kept = getattr(self.model, "last_masks_device", None)
+            AP, _, _, _ = metrics.mask_ap(gt_bbox, gt_class_id, gt_mask, r, kept[0] if kept else None, self.iou_thr)
+            self.APs.append(AP)
+        self.mAP = np.mean(self.APs) if self.APs else float("nan")
+        thresholds = tuple(t for t in (0.5, self.iou_thr) if t > 0)
+        self.voc = metrics.voc_metrics(gt_data, pred_data, thresholds)
+        print("== Mean AveragePrecision (mAP) ==")
+        print("mAP=%f" % self.mAP)
+        for res in self.voc["results"]:
+            for label in self.voc["classes"]:
+                c = res["classes"][label]
+                print("VOC IoU>=%.2f class %s: AP=%f (positives=%d, TP=%d, FP=%d)" % (
+                    res["threshold"], label, c["AP"], c["total positives"], c["total TP"], c["total FP"]))
+            print("VOC IoU>=%.2f mAP=%f" % (res["threshold"], res["mAP"]))
+        if self.metrics_outdir:
+            metrics.write_metric_files(gt_data, pred_data, [path for _, path in self.inspected], self.metrics_outdir)
+        return 0

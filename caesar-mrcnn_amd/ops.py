@@ -1056,6 +1056,39 @@ def mask_plane_sums(img, planes, big_endian=False):
     return out
 
 
+def voc_match(det_box, det_cls, det_score, det_off, gt_box, gt_cls, gt_off, thr):
+    """The matching step of the Pascal-VOC box metrics for a whole test set in one launch (include/mrcnn_hip.h: mrcnn_voc_match).
+    Device tensors: det_box [D, 4] / gt_box [G, 4] float64 corner boxes, det_cls [D] / gt_cls [G] int32, det_score [D] float64, thr [T]
+    float64 (all > 0: the caller's contract).  det_off / gt_off: the CSR offsets of the I images, NumPy (checked here) --
+    image i owns rows off[i] .. off[i + 1].  Returns (best_gt [D] int32, best_iou [D] float64, tp [T, D] uint8) on the device.
+    D == 0 or I == 0 gives empty tensors, without a launch."""
+    import numpy as np
+    _need_cuda(det_box, det_cls, det_score, gt_box, gt_cls, thr)
+    D, G, T = int(det_box.shape[0]), int(gt_box.shape[0]), int(thr.shape[0])
+    assert det_box.dtype == gt_box.dtype == det_score.dtype == thr.dtype == torch.float64 and det_cls.dtype == gt_cls.dtype == torch.int32
+    assert tuple(det_box.shape) == (D, 4) and tuple(gt_box.shape) == (G, 4) and tuple(det_cls.shape) == (D,) and tuple(gt_cls.shape) == (G,)
+    assert tuple(det_score.shape) == (D,) and thr.dim() == 1
+    do = np.ascontiguousarray(det_off, dtype=np.int64).reshape(-1)
+    go = np.ascontiguousarray(gt_off, dtype=np.int64).reshape(-1)
+    I = do.size - 1
+    if I < 0 or go.size != I + 1 or do[0] != 0 or go[0] != 0 or do[-1] != D or go[-1] != G or np.any(np.diff(do) < 0) or np.any(np.diff(go) < 0):
+        raise _hip.HipPathError("voc_match: malformed image offsets")
+    if T <= 0 or max(D, G, I) > 0x7FFFFFFF:
+        raise _hip.HipPathError("voc_match: no threshold, or tables past int32 rows")
+    dev = det_box.device
+    best_gt = torch.empty((D,), dtype=torch.int32, device=dev)
+    best_iou = torch.empty((D,), dtype=torch.float64, device=dev)
+    tp = torch.empty((T, D), dtype=torch.uint8, device=dev)
+    if D > 0 and I > 0:
+        off_t = torch.from_numpy(np.concatenate([do, go]).astype(np.int32)).to(dev)
+        tensors = [t.contiguous() for t in (det_box, det_cls, det_score, gt_box, gt_cls, thr)]
+        check(_hip.lib().mrcnn_voc_match(ptr(tensors[0]), ptr(tensors[1]), ptr(tensors[2]), off_t.data_ptr(), D,
+                                         ptr(tensors[3]) if G else None, ptr(tensors[4]) if G else None, off_t.data_ptr() + 4 * (I + 1), G, I,
+                                         ptr(tensors[5]), T, ptr(best_gt), ptr(best_iou), ptr(tp), current_stream()), "mrcnn_voc_match")
+        best_gt._keep = (off_t, tensors)      # alive until the caller has synchronised on the result
+    return best_gt, best_iou, tp
+
+
 class OutlineUnsupported(_hip.HipPathError):
     """A table past a cap of mrcnn_outline_* (include/mrcnn_hip.h: a source wider or higher than 8192 pixels, more than 65535
     sources, more than 2^22 contour segments in one source, int32 totals): the caller takes the host path."""

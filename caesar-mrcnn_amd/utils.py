@@ -300,19 +300,23 @@ def compute_recall(pred_boxes, gt_boxes, iou):
 
 
 def compute_matches(gt_boxes, gt_class_ids, gt_masks, pred_boxes, pred_class_ids, pred_scores, pred_masks,
-                    iou_threshold=0.5, score_threshold=0.0):
+                    iou_threshold=0.5, score_threshold=0.0, overlaps=None):
     """Greedy one-to-one matching of predictions (best score first) to ground truth by MASK IoU
     (mrcnn/utils.py:725-785).  A prediction takes the unmatched GT instance of highest IoU -- candidates are walked
     in descending IoU, the walk ends at the first IoU below the threshold -- provided the class ids agree; on a class
     mismatch the walk goes on to the next ground-truth instance (as the reference does).  Returns (gt_match [G], pred_match [N] as float arrays of indices or -1
-    in score order, overlaps [N, G])."""
+    in score order, overlaps [N, G]).  `overlaps`: that [N, G] matrix, rows in descending-score order, when the caller has it already
+    (metrics.mask_overlaps_device); the product over full frames is then skipped."""
     keep_g = np.any(gt_boxes != 0, axis=1)
     n_gt = int(keep_g.sum())
     gt_masks = gt_masks[..., :n_gt]
     n_pred = int(np.any(pred_boxes != 0, axis=1).sum())
     order = np.argsort(pred_scores[:n_pred])[::-1]
     pred_class_ids = pred_class_ids[order]
-    overlaps = compute_overlaps_masks(pred_masks[..., order], gt_masks)
+    if overlaps is None:
+        overlaps = compute_overlaps_masks(pred_masks[..., order], gt_masks)
+    else:
+        assert overlaps.shape == (n_pred, n_gt), (overlaps.shape, n_pred, n_gt)
     gt_match = np.full(n_gt, -1.0)
     pred_match = np.full(n_pred, -1.0)
     for i in range(n_pred):
@@ -331,11 +335,12 @@ def compute_matches(gt_boxes, gt_class_ids, gt_masks, pred_boxes, pred_class_ids
     return gt_match, pred_match, overlaps
 
 
-def compute_ap(gt_boxes, gt_class_ids, gt_masks, pred_boxes, pred_class_ids, pred_scores, pred_masks, iou_threshold=0.5):
+def compute_ap(gt_boxes, gt_class_ids, gt_masks, pred_boxes, pred_class_ids, pred_scores, pred_masks, iou_threshold=0.5, overlaps=None):
     """VOC-style average precision at one IoU threshold (mrcnn/utils.py:788-828): precision / recall after every
-    prediction in score order, precision made non-increasing from the right, area under the stepped curve."""
+    prediction in score order, precision made non-increasing from the right, area under the stepped curve.  `overlaps`: as for
+    compute_matches."""
     gt_match, pred_match, overlaps = compute_matches(gt_boxes, gt_class_ids, gt_masks, pred_boxes, pred_class_ids,
-                                                     pred_scores, pred_masks, iou_threshold)
+                                                     pred_scores, pred_masks, iou_threshold, overlaps=overlaps)
     hits = np.cumsum(pred_match > -1)
     precisions = np.concatenate([[0], hits / (np.arange(len(pred_match)) + 1), [0]])
     recalls = np.concatenate([[0], hits.astype(np.float32) / len(gt_match), [1]])
@@ -343,3 +348,22 @@ def compute_ap(gt_boxes, gt_class_ids, gt_masks, pred_boxes, pred_class_ids, pre
     steps = np.flatnonzero(recalls[:-1] != recalls[1:]) + 1
     mAP = np.sum((recalls[steps] - recalls[steps - 1]) * precisions[steps])
     return mAP, precisions, recalls, overlaps
+
+
+def compute_ap_range(gt_box, gt_class_id, gt_mask, pred_box, pred_class_id, pred_score, pred_mask, iou_thresholds=None, verbose=1,
+                     overlaps=None):
+    """Mean of compute_ap over IoU thresholds, 0.5 to 0.95 in steps of 0.05 by default (mrcnn/utils.py:823-845), with the
+    reference's printed lines.  `overlaps`: as for compute_matches; the matrix does not depend on the threshold."""
+    if iou_thresholds is None:
+        iou_thresholds = np.arange(0.5, 1.0, 0.05)
+    aps = []
+    for iou_threshold in iou_thresholds:
+        ap, _, _, overlaps_t = compute_ap(gt_box, gt_class_id, gt_mask, pred_box, pred_class_id, pred_score, pred_mask,
+                                          iou_threshold=iou_threshold, overlaps=overlaps)
+        if verbose:
+            print("AP @{:.2f}:\t {:.3f}".format(iou_threshold, ap))
+        aps.append(ap)
+    mean = np.array(aps).mean()
+    if verbose:
+        print("AP @{:.2f}-{:.2f}:\t {:.3f}".format(iou_thresholds[0], iou_thresholds[-1], mean))
+    return mean

@@ -380,6 +380,25 @@ int mrcnn_mask_cross_stats(const void* planes_a, const int32_t* box_a, int na, c
 int mrcnn_mask_plane_sums(const void* img, int big_endian, const void* planes, const int32_t* box, int n, int H, int W, double* sum,
                           void* stream);
 
+/* The matching step of the Pascal-VOC box metrics of the reference's vendored tool (Object-Detection-Metrics,
+ * lib/Evaluator.py:99-122: best ground truth per detection and the "seen" flag; :382-426: the IoU), for the detections and ground
+ * truths of a whole test set, flat, in one launch.  Rows of one image are contiguous: image i owns detections det_off[i] ..
+ * det_off[i + 1] and ground truths gt_off[i] .. gt_off[i + 1] (CSR, I + 1 entries each, 0 = off[0] <= ... <= off[I] = D resp. G --
+ * the caller's contract; rows outside the tables are never touched).  Boxes [., 4] float64 in corner form (c0, c1, c2, c3), classes
+ * int32, scores float64, thr [T] float64, all > 0.  float64 in the tool's order of operations:
+ *   IoU       0 when a0 > b2, b0 > a2, a3 < b1 or a1 > b3; else inter = (min(a2, b2) - max(a0, b0) + 1) (min(a3, b3) - max(a1, b1) + 1),
+ *             area = (c2 - c0 + 1) (c3 - c1 + 1), iou = inter / (areaA + areaB - inter);
+ *   best_gt   [D] the global ground-truth row of the detection's image and class with the greatest IoU, the first one in row order
+ *             on a tie; -1 (and best_iou 0) when every IoU is 0 (the tool starts from sys.float_info.min);  best_iou [D] that IoU;
+ *   tp        [T, D] uint8: 1 iff best_iou[d] >= thr[t] and no detection d' of the image with the same best_gt and
+ *             best_iou[d'] >= thr[t] precedes d -- a higher score, or the same score and an earlier row (the tool's stable sort by
+ *             descending confidence and its "seen" flag).
+ * One workgroup (one wavefront) per image; the image's ground truths are staged in LDS up to 256 of them and read from global
+ * memory above that.  No atomics, nothing allocated, bitwise the same from run to run.  D, I or T <= 0, G < 0: MRCNN_ERR_ARG.   */
+int mrcnn_voc_match(const double* det_box, const int32_t* det_cls, const double* det_score, const int32_t* det_off, int D,
+                    const double* gt_box, const int32_t* gt_cls, const int32_t* gt_off, int G, int I, const double* thr, int T,
+                    int32_t* best_gt, double* best_iou, uint8_t* tp, void* stream);
+
 /* detect() post-processing (MaskRCNN.unmold_detections, mrcnn/model.py:2607-2619; utils.unmold_mask, mrcnn/utils.py:629-645;
  * utils.resize -> skimage.transform.resize(order=1, mode='constant', cval=0, clip=True), mrcnn/utils.py:957-978): for each of
  * the n detections of ONE image, resize the class channel of its MH x MW mask to its integer pixel box (float64, half-pixel

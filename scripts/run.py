@@ -8,7 +8,8 @@
 Same flag names and defaults; the model behind them is caesar_mrcnn_amd.model.MaskRCNN (MI355X).
 Multi-GPU training: ``torchrun --nproc-per-node NGPU scripts/run.py train --ngpu NGPU ...``.
 `test` reports completeness / reliability per class from mask-IoU matching, or with `--reference_tester` runs the reference's
-ModelTester (caesar_mrcnn_amd/analyze.py: confusion matrix, purity, completeness.csv and reliability.csv); `detect` runs the Analyzer
+ModelTester (caesar_mrcnn_amd/analyze.py: confusion matrix, purity, completeness.csv and reliability.csv; with `--compute_map` also
+its compute_mAP: mask AP per image and the Pascal-VOC box AP / mAP, caesar_mrcnn_amd/metrics.py); `detect` runs the Analyzer
 post-processing (caesar_mrcnn_amd/analyze.py: score filter, connected-mask merging, best-of-overlapping
 selection) on every tile and writes the objects as JSON (`out_<image>.json`: image_id, objs[name, x1, x2,
 y1, y2, class_id, class_name, score, pixels, vertexes, edge]) and DS9 regions.  With `--draw` or `--detect_outfile NAME` it also
@@ -88,6 +89,11 @@ def parse_args(argv=None):
                    help="extension: `test` runs the reference's ModelTester (masks merged and selected first, its matching rule, "
                         "confusion matrix and purity, completeness.csv and reliability.csv); needs a JSON dataloader; default: the "
                         "per-class completeness / reliability summary")
+    p.add_argument('--compute_map', action='store_true', default=False,
+                   help="with `test --reference_tester`: after the tables, the reference's compute_mAP -- per-image mask AP, the "
+                        "Pascal-VOC box AP per class and mAP at IoU 0.5 and --iouThr (matched on the GPU)")
+    p.add_argument('--map_outdir', type=str, default="",
+                   help="with --compute_map: write the input files of the three external metric tools under this directory")
     p.add_argument('--remap_classids', action='store_true', default=False)
     p.add_argument('--classid_remap_dict', type=str, default='', help='Dictionary used to remap detected classid to gt classid')
     p.add_argument('--consider_sources_near_mixed_sidelobes', dest='consider_sources_near_mixed_sidelobes', action='store_true',
@@ -121,7 +127,12 @@ def parse_args(argv=None):
                    help="extension, with --split_img_in_tiles --merge_tile_sources: read and upload the mosaic once, cut and stretch "
                         "the tiles on the GPU and detect them N at a time (the model is built for batches of N); needs the default "
                         "stretch flags; default 0: one file read, host stretch and detect call per tile")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if (args.compute_map or args.map_outdir) and not (args.command == "test" and args.reference_tester):
+        p.error("--compute_map / --map_outdir belong to `test --reference_tester`")
+    if args.map_outdir and not args.compute_map:
+        p.error("--map_outdir needs --compute_map")
+    return args
 
 
 def tile_batch_of(args):
@@ -277,6 +288,8 @@ def test_reference(args, model, cfg):
     tester.remap_classids = args.remap_classids
     tester.classid_map = classid_remap_dict
     tester.draw = bool(getattr(args, "draw", False))
+    tester.compute_mAP_metrics = bool(getattr(args, "compute_map", False))
+    tester.metrics_outdir = getattr(args, "map_outdir", "") or None
     tester.test()
     return 0
 
