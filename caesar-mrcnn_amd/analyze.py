@@ -3,15 +3,18 @@ table): score filter, optional splitting of non-connected masks, merging of conn
 selection of the best mask among overlapping ones, JSON and DS9-region output.  Restates
 ``Analyzer.predict / extract_det_masks / make_json_results / make_ds9_regions`` of mrcnn/analyze.py
 (:833-905, :1162-1496, :1866-2030) and mrcnn/graph.py.  Host-side NumPy, except the mask graph of
-``extract_det_masks`` -- which masks overlap or touch, and the unions of the merged ones -- which has two
+``extract_det_masks`` -- which masks overlap or touch, and the unions of the merged ones.  Its decisions are written
+once (``Analyzer._extract_det_masks``: score filter, graph searches, clique walk, captions) against a mask set with two
 implementations behind ``Analyzer.postprocess_device``:
 
-  * ``extract_det_masks_host``    the literal statement: ``mask_iou`` and ``are_mask_connected`` (three labellings)
-                                  on full frames for every pair of masks, twice -- the CPU-testable statement and
-                                  the yardstick of the kernels;
-  * ``extract_det_masks_device``  the same decisions, in the same order, from three launches on bit planes
-                                  (csrc/maskgraph.hip: ops.mask_planes_pack / mask_pair_stats / mask_union); the
-                                  score filter, the graph searches, the clique walk and the captions stay host code.
+  * ``extract_det_masks_host``    ``_FrameMasks``, the literal statement: ``mask_iou`` and ``are_mask_connected`` (three
+                                  labellings) on full frames, pair by pair as the decisions ask for them -- the
+                                  CPU-testable statement and the yardstick of the kernels;
+  * ``extract_det_masks_device``  ``_PlaneMasks``: the same answers from three launches on bit planes (csrc/maskgraph.hip:
+                                  ops.mask_planes_pack / mask_pair_stats / mask_union).
+
+Every device form here and in sfinder.py runs under one policy (``device_or_host``: a form that raised is logged once and
+stays off for the process) on one device resolution (``model_device`` / ``model_has_gpu``).
 
 The tester -- ``ModelTester`` and ``Analyzer.inspect_results`` (``get_data``, ``extract_gt_masks``, ``compute_det_mask_pars``,
 ``compute_performances``; analyze.py:65-406, :715-828, :907-1157, :1502-1861) -- is restated rule for rule as well: true and
@@ -32,6 +35,7 @@ them; the semantics are the published ones):
 """
 import collections
 import csv
+import functools
 import json
 import logging
 import math
@@ -50,10 +54,64 @@ NO_SPLIT_CLASSES = ('galaxy_C2', 'galaxy_C3', 'galaxy', 'extended-multisland')  
 
 NO_SPLIT_CLASSES_GT = ('galaxy_C2', 'galaxy_C3', 'galaxy', 'extended', 'extended-multisland')      # analyze.py:1065
 
-_device_fallback_logged = False
-_eval_fallback_logged = False
-_results_device_failed = False          # make_json_results_device raised once: this process stays on the host statement
-_draw_device_failed = False             # the same for draw_results_device
+
+# ---- where the pixel work runs: one device resolution, one failure policy, one plane eligibility --------------------
+def model_device(model):
+    """The device the model's engine runs on, else torch's current CUDA device (a stand-in model has no engine)."""
+    dev = getattr(getattr(model, "engine", None), "dev", None)
+    if dev is not None:
+        return dev
+    import torch
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def model_has_gpu(model):
+    dev = getattr(getattr(model, "engine", None), "dev", None)
+    if dev is not None:
+        return getattr(dev, "type", "") == "cuda"
+    try:
+        import torch
+        return bool(torch.cuda.is_available())
+    except Exception:
+        return False
+
+
+device_forms_failed = set()             # names of the device forms that raised once: this process stays on their host statements
+
+
+def device_or_host(name, device_form, host_form, refusal=None):
+    """``device_form()``, or ``host_form()`` once the form called `name` has failed in this process.  A _hip.HipPathError or an
+    OSError (no library) is such a failure: logged once, at ERROR, and remembered in ``device_forms_failed``.  An exception of the
+    type `refusal` is no failure: the device form declines this call only, and the next call tries it again.  Whether a call is
+    for the device at all (switch, size, a GPU, masks that fit planes) is the caller's business."""
+    if name in device_forms_failed:
+        return host_form()
+    from . import _hip
+    try:
+        return device_form()
+    except (_hip.HipPathError, OSError) as e:
+        if refusal is not None and isinstance(e, refusal):
+            logger.debug("%s: the host statement takes this call" % e)
+        else:
+            device_forms_failed.add(name)
+            logger.error("%s failed (%s: %s): this and every later call take the host statement ..." % (name, type(e).__name__, e))
+    return host_form()
+
+
+def masks_fit_planes(masks, binary):
+    """Can these [H, W] masks become the bit planes of one frame: 2-D, not empty, of one shape, bool or integer.  Planes are made
+    with `!= 0`, as mask_iou reads a mask, so the tester's steps (binary=False) take any values.  Whatever hands the masks or their
+    values on (binary=True) needs 0 / 1: a lone mask keeps its own values, and make_json_results takes `== 1` for the pixels but
+    `> 0.5` for the contours."""
+    shape = None
+    for m in masks:
+        m = np.asarray(m)
+        if m.ndim != 2 or m.size == 0 or m.dtype.kind not in "biu" or (shape is not None and m.shape != shape):
+            return False
+        shape = m.shape
+        if binary and m.dtype != np.bool_ and not (int(m.min()) >= 0 and int(m.max()) <= 1):
+            return False
+    return shape is not None
 
 
 # ---- restated third-party helpers -----------------------------------------------------------------------
@@ -372,6 +430,107 @@ def count_islands(bmap):
         return n
 
 
+# ---- the two mask sets of Analyzer._extract_det_masks -----------------------------------------------------------
+# What the decision body asks of either: pair_stats(ii, jj) -> (iou, connected), indexable by the pair's position; union(comps)
+# -> the set of the merged masks; box(k) -> (y1, x1, y2, x2) as utils.extract_bboxes; final(keep) -> the arrays of masks_final;
+# sync() at a phase's end.  box and final are asked of a union.
+@functools.lru_cache(maxsize=256)
+def _pairs_below(n):
+    """All (i, j), i < j < n, in the order of the reference's double loop, as two index arrays (shared: not to be written)."""
+    return np.triu_indices(n, 1)
+
+
+class _OnDemand(object):
+    def __init__(self, answer):
+        self.answer = answer
+
+    def __getitem__(self, k):
+        return self.answer(k)
+
+
+class _FrameMasks(object):
+    """Full-frame arrays, the reference's statement.  Nothing is computed before it is asked for, so the body's short-circuits
+    decide how many mask_iou and are_mask_connected calls (three labellings each) a frame costs."""
+
+    def __init__(self, an, masks):
+        self.an, self.masks = an, masks
+
+    def sync(self):
+        pass
+
+    def pair_stats(self, ii, jj):
+        m, ii, jj = self.masks, ii.tolist(), jj.tolist()
+        return (_OnDemand(lambda k: mask_iou(m[ii[k]], m[jj[k]])), _OnDemand(lambda k: self.an.are_mask_connected(m[ii[k]], m[jj[k]])))
+
+    def union(self, comps):
+        out = []
+        for comp in comps:
+            merged = self.masks[comp[0]]                          # a lone mask stays the array it came as
+            for index in comp[1:]:
+                merged = self.an.merge_masks(merged, self.masks[index])
+            out.append(merged)
+        return _FrameMasks(self.an, out)
+
+    def box(self, k):
+        return utils.extract_bboxes(np.asarray(self.masks[k]).astype(bool)[:, :, None])[0]
+
+    def final(self, keep):
+        return [self.masks[k] for k in keep]
+
+
+class _PlaneMasks(object):
+    """Bit planes on the device (ops.MaskPlanes): mask k is plane index[k]; dtypes[k] lists the dtypes of the host statement's
+    arrays that went into it.  A whole pair list is answered by one ops.mask_pair_stats launch and one download (which brings
+    the planes' counts and boxes along), a union is one ops.mask_union launch, and only the kept planes are downloaded."""
+
+    def __init__(self, an, planes, index, dtypes):
+        self.an, self.planes, self.index, self.dtypes = an, planes, np.asarray(index, dtype=np.int32), dtypes
+        self.boxes = None
+
+    def sync(self):
+        if self.an.postprocess_sync_timing:
+            import torch
+            torch.cuda.synchronize()
+
+    def pair_stats(self, ii, jj):
+        import torch
+        from . import ops
+        pi, pj = self.index[ii], self.index[jj]
+        inter, touch = ops.mask_pair_stats(self.planes, np.stack([pi, pj], axis=1))
+        got = torch.cat([inter, touch, self.planes.count, self.planes.box.reshape(-1)]).cpu().numpy().astype(np.int64)
+        P, n = ii.size, self.planes.n
+        n_inter, count, self.boxes = got[:P], got[2 * P:2 * P + n], got[2 * P + n:].reshape(n, 4)
+        union = count[pi] + count[pj] - n_inter
+        iou = n_inter / np.maximum(union, 1)                     # mask_iou: float(inter) / float(union), 0.0 for two empty masks
+        return iou.tolist(), got[P:2 * P].tolist()
+
+    def union(self, comps):
+        from . import ops
+        comp_offsets = np.concatenate([[0], np.cumsum([len(comp) for comp in comps])])
+        merged = ops.mask_union(self.planes, comp_offsets, self.index[[k for comp in comps for k in comp]])
+        return _PlaneMasks(self.an, merged, range(len(comps)), [[d for k in comp for d in self.dtypes[k]] for comp in comps])
+
+    def box(self, k):
+        if self.boxes is None:
+            self.boxes = self.planes.box.cpu().numpy()
+        return self.boxes[k].astype(np.int32)
+
+    def final(self, keep):
+        import torch
+        from . import ops
+        if not keep:
+            return []
+        p = self.planes
+        if len(keep) != p.n:
+            ids = torch.as_tensor(keep, device=p.words.device)
+            p = ops.MaskPlanes(p.words.index_select(0, ids), p.count.index_select(0, ids), p.box.index_select(0, ids), p.W)
+        unpacked = unpack_mask_planes(p.words.cpu().numpy(), p.W)
+        # a lone mask keeps its dtype, a merged one has the NumPy result type of mask1 + mask2 over its members
+        arrays = [unpacked[k].astype(np.result_type(*self.dtypes[index])) for k, index in enumerate(keep)]
+        self.an._final_planes = (p, arrays)                       # make_json_results, draw_results and the tester work on these
+        return arrays
+
+
 # ---- the Analyzer ------------------------------------------------------------------------------------------
 class Analyzer(object):
     """Same attribute names and defaults as the reference's Analyzer (analyze.py:560-712) for the
@@ -559,157 +718,129 @@ class Analyzer(object):
     # ---- extract_det_masks (analyze.py:1162-1496) ----------------------------------------------------------
     @staticmethod
     def has_gpu(model):
-        dev = getattr(getattr(model, "engine", None), "dev", None)
-        if dev is not None:
-            return getattr(dev, "type", "") == "cuda"
-        try:
-            import torch
-            return bool(torch.cuda.is_available())
-        except Exception:
-            return False
+        return model_has_gpu(model)
 
     def _device(self):
-        dev = getattr(getattr(self.model, "engine", None), "dev", None)
-        if dev is not None:
-            return dev
-        import torch
-        return torch.device("cuda", torch.cuda.current_device())
-
-    def _device_masks_ok(self):
-        """The bit planes hold set / not set: masks that are not bool must hold 0 / 1 only, or the values the host path
-        hands on (a lone mask keeps its own) could not be rebuilt."""
-        m = np.asarray(self.masks)
-        if m.ndim != 3 or m.shape[0] == 0 or m.shape[1] == 0:
-            return False
-        return m.dtype == np.bool_ or (m.dtype.kind in "iu" and bool(((m == 0) | (m == 1)).all()))
+        return model_device(self.model)
 
     def extract_det_masks(self):
         """Score filter, mask splitting, merging and selection: on the GPU's bit planes when ``postprocess_device`` is set
-        (default: off, see __init__) and there are at least ``postprocess_device_min_masks`` detections, else by the host
-        statement.  Both give the same lists, value for value."""
-        global _device_fallback_logged
-        if self.postprocess_device and self.masks.shape[-1] >= self.postprocess_device_min_masks and self._device_masks_ok():
-            from . import _hip
-            try:
-                return self.extract_det_masks_device()
-            except (_hip.HipPathError, OSError) as e:
-                if not _device_fallback_logged:
-                    _device_fallback_logged = True
-                    logger.error("extract_det_masks_device failed (%s: %s): this and every later call take the host path "
-                                 "of extract_det_masks, which is slower by orders of magnitude ..." % (type(e).__name__, e))
+        (default: off, see __init__), there are at least ``postprocess_device_min_masks`` detections and the masks are 0 / 1
+        masks (a lone mask is handed on with its own values); else by the host statement.  Both give the same lists."""
+        m = np.asarray(self.masks)
+        if self.postprocess_device and m.shape[-1] >= self.postprocess_device_min_masks and m.ndim == 3 and \
+                masks_fit_planes(np.moveaxis(m, -1, 0), binary=True):
+            return device_or_host("extract_det_masks_device", self.extract_det_masks_device, self.extract_det_masks_host)
         return self.extract_det_masks_host()
 
+    def extract_det_masks_host(self):
+        """The literal statement: mask_iou and are_mask_connected (three labellings) on full frames, asked pair by pair."""
+        self._extract_det_masks(lambda dets: _FrameMasks(self, [self.masks[:, :, i] if piece is None else np.where(piece, [1], [0])
+                                                               for i, piece in dets]))
+
     def extract_det_masks_device(self):
-        """extract_det_masks_host with the all-pairs mask_iou / are_mask_connected of the merge phase, the merge_masks chains
-        and the all-pairs are_mask_connected (+ IoU) of the selection phase replaced by one launch each on bit planes; every
-        decision is taken on the host from exact integer counts, in the order of the host statement.  Only the planes that
-        end up in masks_final are downloaded."""
+        """The same decisions from three launches on bit planes (_PlaneMasks), every one taken on the host from exact integer
+        counts; only the planes that end up in masks_final are downloaded, and they stay on the device as _final_planes."""
+        self.postprocess_timing = {"masks": int(self.masks.shape[-1]), "mask_uploads": 0}
+        t = self._extract_det_masks(self._plane_masks)
+        for name, a, b in zip(("upload_pack", "merge_pairs", "union", "select_pairs", "host_lists", "download_unpack"), t[:-1], t[1:]):
+            self.postprocess_timing[name + "_ms"] = round(1e3 * (b - a), 3)
+
+    def _plane_masks(self, dets):
+        """The _PlaneMasks of `dets` (see _extract_det_masks): packed from the model's own device tensor, else from one upload --
+        of self.masks, or with split_masks of the split masks."""
         import torch
         from . import ops
+        split_dtype = np.where(np.zeros(1, bool), [1], [0]).dtype
+        dtypes = [[self.masks.dtype if piece is None else split_dtype] for _, piece in dets]     # of the host statement's arrays
+        kept = self.masks_device
+        if self.split_masks:
+            index = range(len(dets))
+            masks_t = np.stack([self.masks[:, :, i] != 0 if piece is None else piece for i, piece in dets], axis=-1).view(np.uint8)
+        else:
+            index = [i for i, _ in dets]
+            if kept is not None and self.masks_device_host is self.masks and torch.is_tensor(kept) and kept.is_cuda and \
+                    tuple(kept.shape) == tuple(self.masks.shape):
+                masks_t = kept
+            else:
+                m = self.masks if self.masks.dtype == np.bool_ else self.masks != 0
+                masks_t = np.ascontiguousarray(m).view(np.uint8)
+        if not torch.is_tensor(masks_t):
+            masks_t = torch.from_numpy(masks_t).to(self._device())
+            self.postprocess_timing["mask_uploads"] += 1
+        return _PlaneMasks(self, ops.mask_planes_pack(masks_t.contiguous()), index, dtypes)
+
+    def _extract_det_masks(self, mask_set):
+        """extract_det_masks, rule for rule in the order of the reference, on a mask set (_FrameMasks or _PlaneMasks) that answers
+        the pixel questions.  ``mask_set(dets)`` builds it from dets = [(detection, None: its whole mask, or the bool frame of one
+        of its components)].  Returns the times at the borders of the device form's phases."""
         clock = time.perf_counter
-        sync = torch.cuda.synchronize if self.postprocess_sync_timing else (lambda *a: None)
         t = [clock()]
         self.masks_final, self.class_ids_final, self.class_names_final, self.scores_final = [], [], [], []
         self.bboxes, self.captions = [], []
         self._final_planes = None
-        self.postprocess_timing = {"masks": int(self.masks.shape[-1]), "mask_uploads": 0}
         sel = [i for i in range(self.boxes.shape[0]) if not self.scores[i] < self.score_thr]
-        scores_sel = [self.scores[i] for i in sel]
-        order = np.argsort(scores_sel)[::-1]
+        order = np.argsort([self.scores[i] for i in sel])[::-1]
 
-        # masks_det as (plane index, class id, score, dtype of the host path's array)
-        split_dtype = np.where(np.zeros(1, bool), [1], [0]).dtype
-        plane_det, class_ids_det, scores_det, dtype_det, split_out = [], [], [], [], []
+        dets, class_ids_det, scores_det = [], [], []
         for index in order:
             i = sel[index]
             class_id, score = self.class_ids[i], self.scores[i]
             if not self.split_masks or self.class_names[class_id] in NO_SPLIT_CLASSES:
-                if self.split_masks:
-                    split_out.append(self.masks[:, :, i] != 0)
-                plane_det.append(len(split_out) - 1 if self.split_masks else i)
-                class_ids_det.append(class_id); scores_det.append(score); dtype_det.append(self.masks.dtype)
-                continue
-            labels, ncomp = label_components(self.masks[:, :, i])
-            for k in range(ncomp):
-                split_out.append(labels == k + 1)
-                plane_det.append(len(split_out) - 1)
-                class_ids_det.append(class_id); scores_det.append(score); dtype_det.append(split_dtype)
-        N = len(plane_det)
+                pieces = [None]
+            else:
+                labels, ncomp = label_components(self.masks[:, :, i])
+                pieces = [labels == k + 1 for k in range(ncomp)]
+            for piece in pieces:
+                dets.append((i, piece)); class_ids_det.append(class_id); scores_det.append(score)
+        N = len(dets)
         if N == 0:
-            return
-
-        # the planes: the model's own device tensor, else an upload (with split_masks: of the split masks)
-        kept = self.masks_device
-        if self.split_masks:
-            masks_t = np.stack(split_out, axis=-1).view(np.uint8)
-        elif kept is not None and self.masks_device_host is self.masks and torch.is_tensor(kept) and kept.is_cuda and \
-                tuple(kept.shape) == tuple(self.masks.shape):
-            masks_t = kept
-        else:
-            m = self.masks if self.masks.dtype == np.bool_ else self.masks != 0
-            masks_t = np.ascontiguousarray(m).view(np.uint8)
-        if not torch.is_tensor(masks_t):
-            masks_t = torch.from_numpy(masks_t).to(self._device())
-            self.postprocess_timing["mask_uploads"] += 1
-        planes = ops.mask_planes_pack(masks_t.contiguous())
-        sync()
+            return t
+        masks_det = mask_set(dets)
+        masks_det.sync()
         t.append(clock())
 
-        masks_merged, class_ids_merged, scores_merged = [], [], []       # masks_merged: member lists
-        if self.merge_overlapped_masks:
+        thr = self.merge_overlap_iou_thr
+        if self.merge_overlapped_masks:                                 # class equality, then IoU, then contact
+            ii, jj = _pairs_below(N)
             cls = np.asarray(class_ids_det)
-            ii, jj = np.triu_indices(N, 1)                              # (i, j), i < j, in the order of the double loop
             same = cls[ii] == cls[jj]
             ii, jj = ii[same], jj[same]
-            pd = np.asarray(plane_det, dtype=np.int32)
-            inter, touch = ops.mask_pair_stats(planes, np.stack([pd[ii], pd[jj]], axis=1))
-            got = torch.cat([inter, touch, planes.count]).cpu().numpy()
-            P = ii.size
-            count = got[2 * P:].tolist()
+            iou, connected = masks_det.pair_stats(ii, jj)
             edges = []
-            for i, j, n_inter, connected in zip(ii.tolist(), jj.tolist(), got[:P].tolist(), got[P:2 * P].tolist()):
-                union = count[plane_det[i]] + count[plane_det[j]] - n_inter
-                iou = float(n_inter) / float(union) if union else 0.0    # mask_iou
-                if iou < self.merge_overlap_iou_thr:
+            for k, (i, j) in enumerate(zip(ii.tolist(), jj.tolist())):
+                if iou[k] < thr:
                     continue
-                if connected:
+                if connected[k]:
                     edges.append((i, j))
-            for comp in connected_components(N, edges):
-                masks_merged.append(comp)
+            comps, class_ids_merged, scores_merged = connected_components(N, edges), [], []
+            for comp in comps:
                 class_ids_merged.append(class_ids_det[comp[-1]])
                 score_avg = 0
                 for index in comp:
                     score_avg += scores_det[index]
                 scores_merged.append(score_avg * (1. / len(comp)))
         else:
-            masks_merged, class_ids_merged, scores_merged = [[k] for k in range(N)], list(class_ids_det), list(scores_det)
-        sync()
+            comps, class_ids_merged, scores_merged = [[k] for k in range(N)], list(class_ids_det), list(scores_det)
+        masks_det.sync()
         t.append(clock())
-        n_final = len(masks_merged)
-        comp_offsets = np.concatenate([[0], np.cumsum([len(comp) for comp in masks_merged])])
-        merged = ops.mask_union(planes, comp_offsets, [plane_det[k] for comp in masks_merged for k in comp])
-        sync()
+        masks_merged = masks_det.union(comps)
+        masks_det.sync()
         t.append(clock())
 
+        n_final = len(comps)
         is_selected = [True] * n_final
-        if self.select_best_overlapped_masks:
-            ii, jj = np.triu_indices(n_final, 1)
-            inter, touch = ops.mask_pair_stats(merged, np.stack([ii, jj], axis=1))
-            got = torch.cat([inter, touch, merged.count, merged.box.reshape(-1)]).cpu().numpy()
-            P = ii.size
-            count = got[2 * P:2 * P + n_final].tolist()
-            boxes = got[2 * P + n_final:].reshape(n_final, 4)
+        if self.select_best_overlapped_masks:                           # contact, then IoU only for source / sidelobe pairs
+            ii, jj = _pairs_below(n_final)
+            iou, connected = masks_merged.pair_stats(ii, jj)
             adj = {}
-            for i, j, n_inter, connected in zip(ii.tolist(), jj.tolist(), got[:P].tolist(), got[P:2 * P].tolist()):
-                if not connected:
+            for k, (i, j) in enumerate(zip(ii.tolist(), jj.tolist())):
+                if not connected[k]:
                     continue
                 label_i, label_j = self.class_names[class_ids_merged[i]], self.class_names[class_ids_merged[j]]
                 sidelobe_other = (label_i == 'spurious') != (label_j == 'spurious')
-                if self.split_source_sidelobe and sidelobe_other:
-                    union = count[i] + count[j] - n_inter
-                    iou = float(n_inter) / float(union) if union else 0.0
-                    if iou < self.merge_overlap_iou_thr:
-                        continue
+                if self.split_source_sidelobe and sidelobe_other and iou[k] < thr:
+                    continue
                 adj.setdefault(i, set()).add(j)
                 adj.setdefault(j, set()).add(i)
             cliques = maximal_cliques(adj)
@@ -724,16 +855,14 @@ class Analyzer(object):
                 for index in cliques[k]:
                     if index != best[k][1] and is_selected[index]:
                         is_selected[index] = False
-        else:
-            boxes = merged.box.cpu().numpy()
-        sync()
+        masks_det.sync()
         t.append(clock())
 
         keep = []
         for index in range(n_final):
             if not is_selected[index]:
                 continue
-            bbox = boxes[index].astype(np.int32)
+            bbox = masks_merged.box(index)
             if bbox[1] >= bbox[3] or bbox[0] >= bbox[2]:
                 logger.warning("Invalid det bbox(%d,%d,%d,%d), skip it ..." % (bbox[1], bbox[3], bbox[0], bbox[2]))
                 continue
@@ -745,115 +874,9 @@ class Analyzer(object):
             self.bboxes.append(bbox)
             self.captions.append("{} {:.2f}".format(label, scores_merged[index]))
         t.append(clock())
-        if keep:
-            words = merged.words if len(keep) == n_final else merged.words.index_select(0, torch.as_tensor(keep, device=merged.words.device))
-            unpacked = unpack_mask_planes(words.cpu().numpy(), merged.W)
-            for k, index in enumerate(keep):
-                dtype = np.result_type(*[dtype_det[m] for m in masks_merged[index]])
-                self.masks_final.append(unpacked[k].astype(dtype))
-            if len(keep) != n_final:
-                ids = torch.as_tensor(keep, device=merged.words.device)
-                kept_planes = ops.MaskPlanes(words, merged.count.index_select(0, ids), merged.box.index_select(0, ids), merged.W)
-            else:
-                kept_planes = merged
-            self._final_planes = (kept_planes, self.masks_final)          # the tester's device path works on these
+        self.masks_final = masks_merged.final(keep)
         t.append(clock())
-        for name, a, b in zip(("upload_pack", "merge_pairs", "union", "select_pairs", "host_lists", "download_unpack"), t[:-1], t[1:]):
-            self.postprocess_timing[name + "_ms"] = round(1e3 * (b - a), 3)
-
-    def extract_det_masks_host(self):
-        self.masks_final, self.class_ids_final, self.class_names_final, self.scores_final = [], [], [], []
-        self.bboxes, self.captions = [], []
-        self._final_planes = None
-        masks_sel, class_ids_sel, scores_sel = [], [], []
-        for i in range(self.boxes.shape[0]):
-            if self.scores[i] < self.score_thr:
-                continue
-            masks_sel.append(self.masks[:, :, i])
-            class_ids_sel.append(self.class_ids[i])
-            scores_sel.append(self.scores[i])
-        order = np.argsort(scores_sel)[::-1]
-
-        masks_det, class_ids_det, scores_det = [], [], []
-        for index in order:
-            mask, class_id, score = masks_sel[index], class_ids_sel[index], scores_sel[index]
-            if not self.split_masks or self.class_names[class_id] in NO_SPLIT_CLASSES:
-                masks_det.append(mask); class_ids_det.append(class_id); scores_det.append(score)
-                continue
-            labels, ncomp = label_components(mask)
-            for k in range(ncomp):
-                masks_det.append(np.where(labels == k + 1, [1], [0]))
-                class_ids_det.append(class_id); scores_det.append(score)
-
-        masks_merged, class_ids_merged, scores_merged = [], [], []
-        if self.merge_overlapped_masks:
-            N = len(masks_det)
-            edges = []
-            for i in range(N):
-                for j in range(i + 1, N):
-                    if class_ids_det[i] != class_ids_det[j]:
-                        continue
-                    if mask_iou(masks_det[i], masks_det[j]) < self.merge_overlap_iou_thr:
-                        continue
-                    if self.are_mask_connected(masks_det[i], masks_det[j]):
-                        edges.append((i, j))
-            for comp in connected_components(N, edges):
-                merged = masks_det[comp[0]]
-                for index in comp[1:]:
-                    merged = self.merge_masks(merged, masks_det[index])
-                masks_merged.append(merged)
-                class_ids_merged.append(class_ids_det[comp[-1]])
-                score_avg = 0
-                for index in comp:
-                    score_avg += scores_det[index]
-                scores_merged.append(score_avg * (1. / len(comp)))
-        else:
-            masks_merged, class_ids_merged, scores_merged = list(masks_det), list(class_ids_det), list(scores_det)
-
-        is_selected = [True] * len(masks_merged)
-        if self.select_best_overlapped_masks:
-            adj = {}
-            n_final = len(masks_merged)
-            for i in range(n_final):
-                label_i = self.class_names[class_ids_merged[i]]
-                for j in range(i + 1, n_final):
-                    label_j = self.class_names[class_ids_merged[j]]
-                    if not self.are_mask_connected(masks_merged[i], masks_merged[j]):
-                        continue
-                    sidelobe_other = (label_i == 'spurious') != (label_j == 'spurious')
-                    if self.split_source_sidelobe and sidelobe_other and \
-                            mask_iou(masks_merged[i], masks_merged[j]) < self.merge_overlap_iou_thr:
-                        continue
-                    adj.setdefault(i, set()).add(j)
-                    adj.setdefault(j, set()).add(i)
-            cliques = maximal_cliques(adj)
-            best = []
-            for clique in cliques:
-                max_score, max_index = -1, -1
-                for index in clique:
-                    if scores_merged[index] > max_score:
-                        max_score, max_index = scores_merged[index], index
-                best.append((max_score, max_index))
-            for k in sorted(range(len(cliques)), key=lambda k: best[k][0], reverse=True):
-                for index in cliques[k]:
-                    if index != best[k][1] and is_selected[index]:
-                        is_selected[index] = False
-
-        for index in range(len(masks_merged)):
-            if not is_selected[index]:
-                continue
-            m = masks_merged[index]
-            bbox = utils.extract_bboxes(np.asarray(m).astype(bool)[:, :, None])
-            if bbox[0][1] >= bbox[0][3] or bbox[0][0] >= bbox[0][2]:
-                logger.warning("Invalid det bbox(%d,%d,%d,%d), skip it ..." % (bbox[0][1], bbox[0][3], bbox[0][0], bbox[0][2]))
-                continue
-            label = self.class_names[class_ids_merged[index]]
-            self.masks_final.append(m)
-            self.class_ids_final.append(class_ids_merged[index])
-            self.class_names_final.append(label)
-            self.scores_final.append(scores_merged[index])
-            self.bboxes.append(bbox[0])
-            self.captions.append("{} {:.2f}".format(label, scores_merged[index]))
+        return t
 
     # ---- the tester's path (analyze.py:715-828, :907-1157, :1502-1861) ----------------------------------------
     def set_image_path(self, path):
@@ -990,34 +1013,30 @@ class Analyzer(object):
     def _eval_on_device(self):
         if not self.eval_device or len(self.masks_gt_merged) * len(self.masks_final) < max(self.eval_device_min_pairs, 1):
             return False
-        for m in list(self.masks_final) + list(self.masks_gt_merged):
-            m = np.asarray(m)
-            if m.ndim != 2 or m.size == 0 or m.dtype.kind not in "biu":
-                return False
-        return True
+        return masks_fit_planes(list(self.masks_final) + list(self.masks_gt_merged), binary=False)
 
-    def _eval_fallback(self, what, e):
-        global _eval_fallback_logged
-        if not _eval_fallback_logged:
-            _eval_fallback_logged = True
-            logger.error("%s failed (%s: %s): this and every later call take the host statement, which reads full frames for every "
-                         "pair of masks ..." % (what, type(e).__name__, e))
-
-    def _planes_of(self, key, masks):
-        """MaskPlanes of a list of [H, W] masks: the planes extract_det_masks_device kept for exactly this list, else one upload and
-        one pack; remembered while the list is the same object."""
-        import torch
-        from . import ops
+    def _planes_of(self, masks, key=None):
+        """(MaskPlanes, uploads) of a list of [H, W] masks: the planes extract_det_masks_device left on the device when `masks` is
+        the very list they were made for (0 uploads), else one stack, upload and pack.  Under a key (the tester's "gt" and
+        "final") the planes are remembered while the list is the same object."""
         have = self._eval_planes.get(key)
         if have is not None and have[1] is masks:
-            return have[0]
-        if key == "final" and self._final_planes is not None and self._final_planes[1] is masks:
-            planes = self._final_planes[0]
+            return have[0], 0
+        if self._final_planes is not None and self._final_planes[1] is masks:
+            planes, uploads = self._final_planes[0], 0
         else:
+            import torch
+            from . import ops
             stack = np.ascontiguousarray(np.stack([np.asarray(m) != 0 for m in masks], axis=-1))
-            planes = ops.mask_planes_pack(torch.from_numpy(stack.view(np.uint8)).to(self._device()))
-            self.eval_timing["mask_uploads"] = self.eval_timing.get("mask_uploads", 0) + 1
-        self._eval_planes[key] = (planes, masks)
+            planes, uploads = ops.mask_planes_pack(torch.from_numpy(stack.view(np.uint8)).to(self._device())), 1
+        if key is not None:
+            self._eval_planes[key] = (planes, masks)
+        return planes, uploads
+
+    def _eval_planes_of(self, key, masks):
+        planes, uploads = self._planes_of(masks, key)
+        if uploads:
+            self.eval_timing["mask_uploads"] = self.eval_timing.get("mask_uploads", 0) + uploads
         return planes
 
     # ---- compute_det_mask_pars (analyze.py:1502-1676) ------------------------------------------------------------
@@ -1038,11 +1057,14 @@ class Analyzer(object):
             return -1
         if self._eval_on_device() and data.dtype == np.float32 and len(self.masks_final) > 0 and \
                 tuple(data.shape) == tuple(np.asarray(self.masks_final[0]).shape):
-            from . import _hip
-            try:
-                return self._det_mask_pars_from(data, *self.compute_det_mask_pars_device(data))
-            except (_hip.HipPathError, OSError) as e:
-                self._eval_fallback("compute_det_mask_pars_device", e)
+            pixel_sums = device_or_host("compute_det_mask_pars_device", lambda: self.compute_det_mask_pars_device(data),
+                                        lambda: self.compute_det_mask_pars_host(data))
+        else:
+            pixel_sums = self.compute_det_mask_pars_host(data)
+        return self._det_mask_pars_from(data, *pixel_sums)
+
+    def compute_det_mask_pars_host(self, data):
+        """(npix, boxes, Stot) of masks_final from full frames."""
         npix, boxes, stot = [], [], []
         for mask in self.masks_final:
             mask = np.asarray(mask)
@@ -1051,7 +1073,7 @@ class Analyzer(object):
             # float64 sum of the float32 pixels (the reference's np.nansum accumulates in the image's own float32: DESIGN.md 4.9)
             stot.append(float(np.nansum(data[cond], dtype=np.float64)))
             boxes.append(utils.extract_bboxes((mask != 0)[:, :, None])[0])
-        return self._det_mask_pars_from(data, npix, boxes, stot)
+        return npix, boxes, stot
 
     def compute_det_mask_pars_device(self, data):
         """(npix, boxes, Stot) of masks_final from the bit planes: counts and boxes as _pack / _union left them, the flux sums from
@@ -1059,8 +1081,8 @@ class Analyzer(object):
         import torch
         from . import ops
         t0 = time.perf_counter()
-        planes = self._planes_of("final", self.masks_final)
-        img_t = torch.from_numpy(np.ascontiguousarray(data)).to(planes.words.device)
+        planes = self._eval_planes_of("final", self.masks_final)
+        img_t =torch.from_numpy(np.ascontiguousarray(data)).to(planes.words.device)
         sums = ops.mask_plane_sums(img_t, planes)
         ints = torch.cat([planes.count, planes.box.reshape(-1)]).cpu().numpy()
         stot = sums.cpu().numpy()
@@ -1134,11 +1156,7 @@ class Analyzer(object):
         The IoUs come from ``compute_performances_device`` (one ops.mask_cross_stats launch) when the device path is on, else
         from ``compute_performances_host`` (mask_iou on full frames per pair); the two loops are the same code."""
         if self._eval_on_device():
-            from . import _hip
-            try:
-                return self.compute_performances_device()
-            except (_hip.HipPathError, OSError) as e:
-                self._eval_fallback("compute_performances_device", e)
+            return device_or_host("compute_performances_device", self.compute_performances_device, self.compute_performances_host)
         return self.compute_performances_host()
 
     def compute_performances_host(self):
@@ -1152,8 +1170,8 @@ class Analyzer(object):
         from . import ops
         t0 = time.perf_counter()
         G, D = len(self.masks_gt_merged), len(self.masks_final)
-        gt = self._planes_of("gt", self.masks_gt_merged)
-        det = self._planes_of("final", self.masks_final)
+        gt = self._eval_planes_of("gt", self.masks_gt_merged)
+        det = self._eval_planes_of("final", self.masks_final)
         inter = ops.mask_cross_stats(gt, det)
         got = torch.cat([inter.reshape(-1), gt.count, det.count]).cpu().numpy().tolist()
         count_gt, count_det = got[G * D:G * D + G], got[G * D + G:]
@@ -1274,92 +1292,64 @@ class Analyzer(object):
 
     # ---- JSON (analyze.py:1866-1955) -----------------------------------------------------------------------
     def _results_masks_ok(self):
-        """The device form outlines bit planes: every final mask 2-D, of one shape, bool or integer 0 / 1 (the host statement
-        takes `mask == 1` for the pixels but `> 0.5` for the contours, so any other value stays with it)."""
-        shape = None
-        for m in self.masks_final:
-            m = np.asarray(m)
-            if m.ndim != 2 or m.size == 0 or (shape is not None and m.shape != shape):
-                return False
-            shape = m.shape
-            if m.dtype != np.bool_ and not (m.dtype.kind in "iu" and int(m.min()) >= 0 and int(m.max()) <= 1):
-                return False
-        return shape is not None
+        """The device forms of make_json_results and draw_results work on bit planes: 0 / 1 masks of one shape."""
+        return masks_fit_planes(self.masks_final, binary=True)
 
     def make_json_results(self):
         """The result dictionary: contours and pixel lists on the GPU (``make_json_results_device``) when ``results_device`` is
         set (default: off), a GPU is there, there are at least ``results_device_min_masks`` final masks and they are 0 / 1
         masks of one shape; else by the host statement.  Both give the same dictionary, value for value."""
-        global _results_device_failed
         self.results_timing = {}
-        if self.results_device and not _results_device_failed and len(self.masks_final) >= max(self.results_device_min_masks, 1) \
-                and Analyzer.has_gpu(self.model) and self._results_masks_ok():
-            from . import _hip
-            try:
-                return self.make_json_results_device()
-            except (_hip.HipPathError, OSError) as e:
-                _results_device_failed = True
-                logger.error("make_json_results_device failed (%s: %s): this and every later call take the host statement "
-                             "(find_contours and np.argwhere on full frames) ..." % (type(e).__name__, e))
+        if self.results_device and len(self.masks_final) >= max(self.results_device_min_masks, 1) and Analyzer.has_gpu(self.model) \
+                and self._results_masks_ok():
+            return device_or_host("make_json_results_device", self.make_json_results_device, self.make_json_results_host)
         return self.make_json_results_host()
 
-    def make_json_results_device(self):
-        """make_json_results_host with find_contours and np.argwhere of all final masks replaced by one ops.mask_plane_outlines
-        call on the frame's bit planes -- those extract_det_masks_device left on the device, else one upload and pack of
-        masks_final -- and one download."""
-        import torch
-        from . import ops
-        clock = time.perf_counter
-        t0 = clock()
-        n = len(self.masks_final)
-        timing = {"masks": n, "mask_uploads": 0}
-        planes, timing["mask_uploads"] = self._final_mask_planes()
-        t1 = clock()
-        got = ops.mask_plane_outlines(planes).host()
-        t2 = clock()
-        sc, co, po = got["source_contours"].tolist(), got["contour_offsets"].tolist(), got["pixel_offsets"].tolist()
+    def _results_from(self, outline_of):
+        """The result dictionary; ``outline_of(i)`` gives the pixels [(y, x)] and the vertexes [[(x, y)]] of final mask i, as
+        lists in mosaic coordinates."""
         xmin, ymin = self.image_xmin, self.image_ymin
-        points = got["points"].astype(np.float64) + np.array([xmin, ymin])
-        pixels_all = got["pixels"].astype(np.int64) + np.array([ymin, xmin])
         ny, nx = (self.image.shape if self.image is not None else self.image_shape)[:2]
         results = {"image_id": self.image_id, "objs": []}
-        for i in range(n):
+        for i in range(len(self.masks_final)):
             class_id = int(self.class_ids_final[i])
             y1, x1, y2, x2 = [int(v) for v in self.bboxes[i]]
             at_edge = (x1 <= 0 or x1 >= nx - 1 or x2 <= 0 or x2 >= nx - 1 or
                        y1 <= 0 or y1 >= ny - 1 or y2 <= 0 or y2 >= ny - 1)
-            pixels = pixels_all[po[i]:po[i + 1]].tolist()
-            vertexes = [points[co[k]:co[k + 1]].tolist() for k in range(sc[i], sc[i + 1])]
+            pixels, vertexes = outline_of(i)
             results["objs"].append({
                 "name": 'S' + str(i + 1) + "_" + self.obj_name_tag,
                 "x1": xmin + x1, "x2": xmin + x2, "y1": ymin + y1, "y2": ymin + y2,
                 "class_id": class_id, "class_name": self.class_names[class_id],
                 "score": float(self.scores_final[i]), "pixels": pixels, "vertexes": vertexes, "edge": bool(at_edge)})
         self.results = results
+
+    def make_json_results_device(self):
+        """make_json_results_host with find_contours and np.argwhere of all final masks replaced by one ops.mask_plane_outlines
+        call on the frame's bit planes -- those extract_det_masks_device left on the device, else one upload and pack of
+        masks_final -- and one download."""
+        from . import ops
+        clock = time.perf_counter
+        t0 = clock()
+        timing = {"masks": len(self.masks_final), "mask_uploads": 0}
+        planes, timing["mask_uploads"] = self._planes_of(self.masks_final)
+        t1 = clock()
+        got = ops.mask_plane_outlines(planes).host()
+        t2 = clock()
+        sc, co, po = got["source_contours"].tolist(), got["contour_offsets"].tolist(), got["pixel_offsets"].tolist()
+        points = got["points"].astype(np.float64) + np.array([self.image_xmin, self.image_ymin])
+        pixels_all = got["pixels"].astype(np.int64) + np.array([self.image_ymin, self.image_xmin])
+        self._results_from(lambda i: (pixels_all[po[i]:po[i + 1]].tolist(),
+                                      [points[co[k]:co[k + 1]].tolist() for k in range(sc[i], sc[i + 1])]))
         t3 = clock()
         for name, a, b in (("planes", t0, t1), ("outlines_download", t1, t2), ("host_lists", t2, t3)):
             timing[name + "_ms"] = round(1e3 * (b - a), 3)
         self.results_timing = timing
 
-    def _final_mask_planes(self):
-        """(MaskPlanes of masks_final, uploads): the planes extract_det_masks_device left on the device for exactly this list (0
-        uploads), else one upload and one pack."""
-        import torch
-        from . import ops
-        if self._final_planes is not None and self._final_planes[1] is self.masks_final:
-            return self._final_planes[0], 0
-        stack = np.ascontiguousarray(np.stack([np.asarray(m) != 0 for m in self.masks_final], axis=-1))
-        return ops.mask_planes_pack(torch.from_numpy(stack.view(np.uint8)).to(self._device())), 1
-
     def make_json_results_host(self):
-        self.results = {"image_id": self.image_id, "objs": []}
         xmin, ymin = self.image_xmin, self.image_ymin
-        ny, nx = (self.image.shape if self.image is not None else self.image_shape)[:2]
-        for i in range(len(self.masks_final)):
-            class_id = int(self.class_ids_final[i])
-            y1, x1, y2, x2 = [int(v) for v in self.bboxes[i]]
-            at_edge = (x1 <= 0 or x1 >= nx - 1 or x2 <= 0 or x2 >= nx - 1 or
-                       y1 <= 0 or y1 >= ny - 1 or y2 <= 0 or y2 >= ny - 1)
+
+        def outline_of(i):
             mask = np.asarray(self.masks_final[i])
             pixels = (np.argwhere(mask == 1) + np.array([ymin, xmin])).tolist()
             padded = np.zeros((mask.shape[0] + 2, mask.shape[1] + 2), dtype=np.uint8)
@@ -1368,11 +1358,8 @@ class Analyzer(object):
             for verts in find_contours(padded, 0.5):
                 verts = np.fliplr(verts) - 1                      # drop the padding, (y, x) -> (x, y)
                 vertexes.append((verts + np.array([xmin, ymin])).tolist())
-            self.results["objs"].append({
-                "name": 'S' + str(i + 1) + "_" + self.obj_name_tag,
-                "x1": xmin + x1, "x2": xmin + x2, "y1": ymin + y1, "y2": ymin + y2,
-                "class_id": class_id, "class_name": self.class_names[class_id],
-                "score": float(self.scores_final[i]), "pixels": pixels, "vertexes": vertexes, "edge": bool(at_edge)})
+            return pixels, vertexes
+        self._results_from(outline_of)
 
     def write_json_results(self, outfile):
         if not self.results:
@@ -1421,9 +1408,9 @@ class Analyzer(object):
                 "gt_colours": gt_colours, "texts": texts}
 
     def _draw_on_device(self, scene):
-        """The device form takes the frame: a GPU is there, it has not failed in this process, the image holds 8-bit values,
-        the masks are 0 / 1 masks (bit planes hold nothing else) and there are at least draw_device_min_masks of them."""
-        if _draw_device_failed or not Analyzer.has_gpu(self.model) or scene["image"].dtype != np.uint8:
+        """The device form takes the frame: a GPU is there, the image holds 8-bit values, the masks are 0 / 1 masks (bit planes
+        hold nothing else) and there are at least draw_device_min_masks of them."""
+        if not Analyzer.has_gpu(self.model) or scene["image"].dtype != np.uint8:
             return False
         n = len(scene["masks"])
         return n >= self.draw_device_min_masks and (n == 0 or self._results_masks_ok())
@@ -1436,9 +1423,9 @@ class Analyzer(object):
         timing = {"masks": len(scene["masks"]), "mask_uploads": 0}
         planes = None
         if scene["masks"]:
-            planes, timing["mask_uploads"] = self._final_mask_planes()
+            planes, timing["mask_uploads"] = self._planes_of(self.masks_final)
         t1 = clock()
-        image = torch.from_numpy(np.ascontiguousarray(scene["image"])).to(self._device())
+        image =torch.from_numpy(np.ascontiguousarray(scene["image"])).to(self._device())
         canvas = ops.draw_overlay(image, planes, overlay.device_tables(scene), scene["scale"])
         torch.cuda.synchronize(canvas.device)
         t2 = clock()
@@ -1453,7 +1440,6 @@ class Analyzer(object):
         """The overlay of the current frame as a uint8 array [s (H + 4), s (W + 4), 3], without writing a file; None (logged) when
         the frame cannot be drawn.  device: None -- on the GPU where ``draw_results`` would render there, with its fallback; True
         -- the device form, errors raised; False -- the host statement."""
-        global _draw_device_failed
         self.draw_timing = {}
         scene = self._draw_scene()
         if scene is None:
@@ -1461,16 +1447,9 @@ class Analyzer(object):
         if device is True:
             return self._render_device(scene)
         if device is None and self._draw_on_device(scene):
-            from . import _hip
-            from .ops import DrawUnsupported
-            try:
-                return self._render_device(scene)
-            except DrawUnsupported as e:                                  # this scene only (a tiny frame's default scale is above 64)
-                logger.debug("%s: the host statement draws this frame" % e)
-            except (_hip.HipPathError, OSError) as e:
-                _draw_device_failed = True
-                logger.error("draw_results_device failed (%s: %s): this and every later call take the host statement "
-                             "(NumPy passes over the canvas per box, mask and character) ..." % (type(e).__name__, e))
+            from .ops import DrawUnsupported                              # this scene only (a tiny frame's default scale is above 64)
+            return device_or_host("draw_results_device", lambda: self._render_device(scene), lambda: overlay.render_host(scene),
+                                  refusal=DrawUnsupported)
         return overlay.render_host(scene)
 
     def _write_overlay(self, outfile, device):

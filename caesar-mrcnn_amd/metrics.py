@@ -26,6 +26,7 @@ import sys
 import numpy as np
 
 from . import utils
+from .analyze import model_device, model_has_gpu
 
 # voc_metrics takes the device form from this many detections on: the measured break-even (tools/map_bench.py,
 # profiles/map_bench.json `break_even_detections`: the smallest measured test set from which on the device form was ahead; below
@@ -171,7 +172,7 @@ def voc_metrics_device(gt_data, pred_data, iou_thresholds=(0.5,), device=None):
     from . import ops
     flat = Flat(gt_data, pred_data)
     thr = _thresholds(iou_thresholds)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    dev = model_device(None) if device is None else device
     if flat.D == 0 or flat.I == 0:
         empty = np.zeros((thr.size, 0), np.int64)
         return _curves(flat, thr, _groups(flat.det_cls, len(flat.classes)), empty.astype(np.uint8), empty)
@@ -192,10 +193,8 @@ def voc_metrics_device(gt_data, pred_data, iou_thresholds=(0.5,), device=None):
 def voc_metrics(gt_data, pred_data, iou_thresholds=(0.5,)):
     """The device form from DEVICE_MIN_DETECTIONS detections on, where a GPU is present; else the host form.  Same numbers."""
     n_det = sum(len(img) for img in pred_data)
-    if n_det >= DEVICE_MIN_DETECTIONS:
-        import torch
-        if torch.cuda.is_available():
-            return voc_metrics_device(gt_data, pred_data, iou_thresholds)
+    if n_det >= DEVICE_MIN_DETECTIONS and model_has_gpu(None):
+        return voc_metrics_device(gt_data, pred_data, iou_thresholds)
     return voc_metrics_host(gt_data, pred_data, iou_thresholds)
 
 

@@ -43,9 +43,6 @@ from .analyze import Analyzer
 logger = logging.getLogger("mrcnn")
 
 
-_outlines_failed = False             # SFinder._union_outlines raised once: this process stays on find_contours
-
-
 class MergedSourceInfo(object):
     """Helper of merge_edge_sources (sfinder.py:44-49): source index within its tile entry, index of the tile entry."""
 
@@ -275,21 +272,10 @@ class SFinder(object):
         self._wcs_warned = False
 
     def _device(self):
-        dev = getattr(getattr(self.model, "engine", None), "device", None)
-        if dev is not None:
-            return dev
-        import torch
-        return torch.device("cuda", torch.cuda.current_device())
+        return analyze.model_device(self.model)
 
     def _has_gpu(self):
-        dev = getattr(getattr(self.model, "engine", None), "device", None)
-        if dev is not None:
-            return getattr(dev, "type", "") == "cuda"
-        try:
-            import torch
-            return bool(torch.cuda.is_available())
-        except Exception:
-            return False
+        return analyze.model_has_gpu(self.model)
 
     # ---- image / tile parameters (sfinder.py:336-444) -------------------------------------------------------
     def set_img_size_params(self):
@@ -804,23 +790,16 @@ class SFinder(object):
 
     def _union_outlines(self, u, out_desc):
         """The contours of all unions of ops.tile_union's result `u`, outlined where they lie (out_pool / out_desc, one call, one
-        download): per component a list of float64 (x, y) arrays in the union's own box.  None when the device path has failed
-        in this process (logged once): the merged sources then take find_contours, as with the switch off.  A table the check
-        calls malformed would be a bug of tile_union: that ValueError is not caught."""
-        global _outlines_failed
-        from . import _hip, ops
-        if _outlines_failed:
-            return None
-        try:
+        download): per component a list of float64 (x, y) arrays in the union's own box.  None when the device form has failed
+        in this process (analyze.device_or_host): the merged sources then take find_contours, as with the switch off.  A table
+        the check calls malformed would be a bug of tile_union: that ValueError is not caught."""
+        def outlines():
+            from . import ops
             got = ops.bitmap_outlines(u["out_pool"], u["out_desc"], out_desc).host()
-        except (_hip.HipPathError, OSError) as e:
-            _outlines_failed = True
-            logger.error("bitmap_outlines failed (%s: %s): the merged sources of this and every later merge take find_contours on "
-                         "the host ..." % (type(e).__name__, e))
-            return None
-        sc, co = got["source_contours"].tolist(), got["contour_offsets"].tolist()
-        points = got["points"].astype(np.float64)
-        return [[points[co[k]:co[k + 1]] for k in range(sc[c], sc[c + 1])] for c in range(len(sc) - 1)]
+            sc, co = got["source_contours"].tolist(), got["contour_offsets"].tolist()
+            points = got["points"].astype(np.float64)
+            return [[points[co[k]:co[k + 1]] for k in range(sc[c], sc[c + 1])] for c in range(len(sc) - 1)]
+        return analyze.device_or_host("bitmap_outlines", outlines, lambda: None)
 
     # ---- source parameters (sfinder.py:994-1211) --------------------------------------------------------------
     def _image_plane(self):

@@ -109,6 +109,69 @@ def scenarios():
     return out
 
 
+# What extract_det_masks costs per scenario, recorded from the code before its two forms shared one decision body: the calls of
+# mask_iou and are_mask_connected the host statement makes (its short-circuits decide them), and the calls of ops.mask_planes_pack,
+# mask_pair_stats and mask_union the device form makes (pair_stats is called for an empty pair list too, without a launch).
+PIXEL_WORK = {
+    "chain_of_three":                    (6, 3, 1, 2, 1),
+    "same_class_below_iou_thr":          (1, 1, 1, 2, 1),
+    "other_classes_touch_and_diagonal":  (2, 6, 1, 2, 1),
+    "clique_of_four":                    (2, 6, 1, 2, 1),
+    "two_cliques_sharing_a_member":      (1, 3, 1, 2, 1),
+    "spurious_below_and_above_thr":      (4, 6, 1, 2, 1),
+    "spurious_rule_off":                 (2, 6, 1, 2, 1),
+    "iou_thr_zero":                      (7, 12, 1, 2, 1),
+    "split_two_islands":                 (3, 4, 1, 2, 1),
+    "merge_off":                         (2, 28, 1, 1, 1),
+    "select_off":                        (11, 2, 1, 1, 1),
+    "merge_and_select_off":              (0, 0, 1, 0, 1),
+    "one_row_and_empty":                 (1, 3, 1, 2, 1),
+    "nothing_above_score_thr":           (0, 0, 0, 0, 0),
+    "one_detection":                     (0, 0, 1, 2, 1),
+    "one_pixel_frame":                   (0, 1, 1, 2, 1),
+    "discs_24":                          (94, 276, 1, 2, 1),
+    "discs_24_split":                    (89, 254, 1, 2, 1),
+}
+
+
+def counted(monkeypatch, owner, name, calls):
+    """Count the calls of owner.name in calls[name]; the function itself still runs."""
+    real = getattr(owner, name)
+    calls[name] = 0
+
+    def wrapped(*a, **k):
+        calls[name] += 1
+        return real(*a, **k)
+    monkeypatch.setattr(owner, name, wrapped)
+
+
+def planted_failure(entered):
+    def broken(*a, **k):
+        from caesar_mrcnn_amd import _hip
+        entered.append(1)
+        raise _hip.HipPathError("planted")
+    return broken
+
+
+def check_failure_policy(monkeypatch, caplog, name, break_device_form, call, want, same=lambda a, b: a == b):
+    """The policy of analyze.device_or_host as one of its users shows it.  break_device_form(entered) makes the device form
+    called `name` append 1 to `entered` and raise _hip.HipPathError("planted"); call() goes through the dispatcher, eligible for
+    the device, and returns what same(got, want) compares; `want` is the host statement's result."""
+    from caesar_mrcnn_amd import analyze
+    monkeypatch.setattr(analyze, "device_forms_failed", set())
+    entered = []
+    break_device_form(entered)
+    with caplog.at_level("ERROR", logger="mrcnn"):
+        caplog.clear()
+        assert same(call(), want) and entered == [1]               # the device form raised: the host statement's result
+        assert same(call(), want) and entered == [1]               # not entered again
+        said = [r.getMessage() for r in caplog.records if r.levelname == "ERROR"]
+    assert len(said) == 1 and said[0].startswith(name + " failed (HipPathError: planted): this and every later call take the host statement")
+    assert analyze.device_forms_failed == {name}
+    analyze.device_forms_failed.clear()
+    assert same(call(), want) and entered == [1, 1]                 # forgotten: entered again
+
+
 def analyzer(objs, shape, settings, device, model=None):
     from caesar_mrcnn_amd import analyze
     an = analyze.Analyzer(model or StubModel(result(shape, objs)), cfg())

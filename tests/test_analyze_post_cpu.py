@@ -167,6 +167,68 @@ def test_device_path_host_half_with_numpy_kernels(case, monkeypatch):
     cases.assert_same(got, ref, name)
 
 
+@pytest.mark.parametrize("case", cases.scenarios(), ids=lambda c: c[0])
+def test_both_forms_do_the_pixel_work_they_did(case, monkeypatch):
+    """One decision body serves both forms; neither may pay for it.  The host statement makes exactly the mask_iou and
+    are_mask_connected calls it made before (it asks pair by pair, under its short-circuits), the device form exactly the
+    pack / pair_stats / union calls (one per phase): cases.PIXEL_WORK."""
+    import torch
+    from caesar_mrcnn_amd import ops
+    name, shape, objs, settings = case
+    calls = {}
+    cases.counted(monkeypatch, analyze, "mask_iou", calls)
+    cases.counted(monkeypatch, analyze.Analyzer, "are_mask_connected", calls)
+    an = cases.analyzer(objs, shape, settings, device=False)
+    an.masks, an.boxes, an.class_ids, an.scores = (an.model.result[k] for k in ("masks", "rois", "class_ids", "scores"))
+    an.extract_det_masks_host()
+    assert (calls["mask_iou"], calls["are_mask_connected"]) == cases.PIXEL_WORK[name][:2]
+    _numpy_ops(monkeypatch)
+    for k in ("mask_planes_pack", "mask_pair_stats", "mask_union"):
+        cases.counted(monkeypatch, ops, k, calls)
+    an._device = lambda: torch.device("cpu")
+    an.extract_det_masks_device()
+    assert (calls["mask_planes_pack"], calls["mask_pair_stats"], calls["mask_union"]) == cases.PIXEL_WORK[name][2:]
+    assert (calls["mask_iou"], calls["are_mask_connected"]) == cases.PIXEL_WORK[name][:2]          # none of the host's
+
+
+def test_failed_device_form_is_left_for_the_process(monkeypatch, caplog):
+    name, shape, objs, settings = cases.scenarios()[0]
+    ref = cases.run(cases.analyzer(objs, shape, settings, device=False), shape)
+    an = cases.analyzer(objs, shape, settings, device=True)
+
+    def same(got, want):
+        cases.assert_same(got, want, name)
+        return True
+    cases.check_failure_policy(monkeypatch, caplog, "extract_det_masks_device",
+                               lambda entered: monkeypatch.setattr(analyze.Analyzer, "extract_det_masks_device", cases.planted_failure(entered)),
+                               lambda: cases.run(an, shape), ref, same)
+
+
+def test_one_device_resolution(monkeypatch):
+    """Analyzer and SFinder ask the same two functions, which read the engine's `dev`; without a model, torch's current device."""
+    import torch
+    from caesar_mrcnn_amd import sfinder
+
+    class Engine(object):
+        dev = torch.device("cpu")
+
+    class Model(object):
+        engine = Engine()
+    cfg = cases.cfg()
+    cfg.IMG_PATH = "none.fits"
+    an, sf = analyze.Analyzer(Model(), cfg), sfinder.SFinder(Model(), cfg)
+    assert an._device() is Engine.dev and sf._device() is Engine.dev and analyze.model_device(Model()) is Engine.dev
+    assert analyze.Analyzer.has_gpu(an.model) is False and sf._has_gpu() is False and analyze.model_has_gpu(Model()) is False
+    assert sf.merge_device is False and sf.params_device is False and an.eval_device is False
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 3)
+    for there in (True, False):
+        monkeypatch.setattr(torch.cuda, "is_available", lambda: there)
+        an, sf = analyze.Analyzer(None, cfg), sfinder.SFinder(None, cfg)
+        assert an._device() == sf._device() == analyze.model_device(None) == torch.device("cuda", 3)
+        assert analyze.Analyzer.has_gpu(None) is sf._has_gpu() is analyze.model_has_gpu(None) is there
+        assert sf.merge_device is there and sf.params_device is there and an.eval_device is there
+
+
 def test_values_other_than_0_1_take_the_host_path():
     """A lone mask is handed on as it came, so masks that are not bool and hold other values than 0 / 1 cannot go through
     bit planes."""

@@ -453,3 +453,27 @@ def test_device_tables_of_every_frame_case_pass_the_check():
         sc = cases.frame_case(name)
         H, W = sc["image"].shape[:2]
         assert draw.check_tables(H, W, sc["scale"], len(sc["masks"]), draw.device_tables(sc)) == 0, name
+
+
+def test_failed_device_form_is_left_for_the_process_and_a_refusal_is_not(monkeypatch, caplog):
+    from caesar_mrcnn_amd import ops
+    an, shape = _planted()
+    want = an.render_results(device=False)
+    monkeypatch.setattr(analyze.Analyzer, "has_gpu", staticmethod(lambda model: True))
+    post.check_failure_policy(monkeypatch, caplog, "draw_results_device",
+                              lambda entered: monkeypatch.setattr(analyze.Analyzer, "_render_device", post.planted_failure(entered)),
+                              an.render_results, want, np.array_equal)
+    refused = []
+
+    def refuse(self, scene):
+        refused.append(1)
+        raise ops.DrawUnsupported("scale 204 is above 64")
+    monkeypatch.setattr(analyze, "device_forms_failed", set())
+    monkeypatch.setattr(analyze.Analyzer, "_render_device", refuse)
+    with caplog.at_level("DEBUG", logger="mrcnn"):
+        caplog.clear()
+        for k in (1, 2):                                           # this frame only: the next one tries the device again
+            assert np.array_equal(an.render_results(), want) and refused == [1] * k and analyze.device_forms_failed == set()
+        assert [r.levelname for r in caplog.records] == ["DEBUG", "DEBUG"]
+    with pytest.raises(ops.DrawUnsupported):
+        an.render_results(device=True)                             # asked for by name: raised, not taken to the host

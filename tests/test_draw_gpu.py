@@ -145,7 +145,7 @@ def test_planes_left_on_the_device_give_the_same_picture(dev, case):
             with pytest.raises(ops.DrawUnsupported):
                 an.render_results(device=True)
             assert np.array_equal(an.render_results(), an.render_results(device=False)) and an.draw_timing == {}      # this frame only
-            assert analyze._draw_device_failed is False
+            assert "draw_results_device" not in analyze.device_forms_failed
             an.draw_scale = draw.MAX_SCALE
         for labels in (False, True):
             an.draw_class_label_in_caption = labels

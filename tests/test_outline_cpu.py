@@ -65,7 +65,6 @@ class _Cpu(object):
 
 class _CpuEngine(object):
     dev = _Cpu()
-    device = _Cpu()
 
 
 def _analyzer(objs, shape, results_device, tmp_path, tag):
@@ -131,9 +130,33 @@ def test_other_values_and_failures_stay_on_the_host(tmp_path, monkeypatch):
     def broken(self):
         calls.append(2)
         raise _hip.HipPathError("no library")
-    monkeypatch.setattr(analyze, "_results_device_failed", False)
+    monkeypatch.setattr(analyze, "device_forms_failed", set())
     monkeypatch.setattr(analyze.Analyzer, "make_json_results_device", broken)
     an.make_json_results()
     an.make_json_results()
-    assert calls == [1, 2] and an.results == ref and analyze._results_device_failed is True
-    monkeypatch.setattr(analyze, "_results_device_failed", False)
+    assert calls == [1, 2] and an.results == ref and analyze.device_forms_failed == {"make_json_results_device"}
+
+
+def test_failed_device_forms_are_left_for_the_process(tmp_path, monkeypatch, caplog):
+    """make_json_results_device, and the outlines of SFinder's merged sources (whose host answer is None: find_contours later)."""
+    from caesar_mrcnn_amd import ops, sfinder
+    from caesar_mrcnn_amd.config import run_py_config
+    name, shape, objs, _ = post.scenarios()[0]
+    an = post.run(_analyzer(objs, shape, False, tmp_path, "a"), shape)
+    want = an.results
+    monkeypatch.setattr(analyze.Analyzer, "has_gpu", staticmethod(lambda model: True))
+    an.results_device = True
+
+    def results():
+        an.results = {}
+        an.make_json_results()
+        return an.results
+    post.check_failure_policy(monkeypatch, caplog, "make_json_results_device",
+                              lambda entered: monkeypatch.setattr(analyze.Analyzer, "make_json_results_device", post.planted_failure(entered)),
+                              results, want)
+    cfg = run_py_config(num_classes=4, imgsize=64, mode="inference")
+    cfg.IMG_PATH = "none.fits"
+    sf = sfinder.SFinder(None, cfg)
+    post.check_failure_policy(monkeypatch, caplog, "bitmap_outlines",
+                              lambda entered: monkeypatch.setattr(ops, "bitmap_outlines", post.planted_failure(entered)),
+                              lambda: sf._union_outlines({"out_pool": None, "out_desc": None}, None), None)

@@ -186,13 +186,29 @@ def test_device_failure_falls_back_to_host_and_says_so(monkeypatch, standins, ca
     def broken(a, b):
         raise _hip.HipPathError("no kernel")
     monkeypatch.setattr(ops, "mask_cross_stats", broken)
-    monkeypatch.setattr(analyze, "_eval_fallback_logged", False)
+    monkeypatch.setattr(analyze, "device_forms_failed", set())
     sc = cases.scenario("unmatched")
     with caplog.at_level("ERROR", logger="mrcnn"):
         dev = _drive(sc, True)
     host = _drive(sc, False)
     assert dev.detobj_ious == host.detobj_ious and dev.matchobj_ious == host.matchobj_ious
     assert sum("compute_performances_device failed (HipPathError: no kernel)" in r.getMessage() for r in caplog.records) == 1
+
+
+@pytest.mark.parametrize("form", ["compute_performances_device", "compute_det_mask_pars_device"])
+def test_failed_device_form_is_left_for_the_process(form, monkeypatch, standins, caplog, tmp_path):
+    import analyze_post_cases as post
+    sc = cases.scenario("unmatched")
+    path = str(tmp_path / "img.fits")
+    _image(sc["shape"], path)
+
+    def same(a, b):
+        ra, rb = cases.analyzer_record(a, sc["shape"]), cases.analyzer_record(b, sc["shape"])
+        return sorted(ra) == sorted(rb) and all(ra[k].shape == rb[k].shape and bool(np.all(ra[k] == rb[k])) for k in ra) and \
+            a.det_obj_pars == b.det_obj_pars and len(a.det_obj_pars) > 0
+    post.check_failure_policy(monkeypatch, caplog, form,
+                              lambda entered: monkeypatch.setattr(analyze.Analyzer, form, post.planted_failure(entered)),
+                              lambda: _det_pars(sc, True, path), _det_pars(sc, False, path), same)
 
 
 def test_det_mask_pars_values(tmp_path):
