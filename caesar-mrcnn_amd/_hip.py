@@ -124,6 +124,12 @@ _SIGNATURES = {
     "mrcnn_mask_union": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mrcnn_mask_cross_stats": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mrcnn_mask_plane_sums": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    # box_host / piece_offsets_host are HOST tables (numpy int32)
+    "mrcnn_mask_components_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t]),
+    "mrcnn_mask_components_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, _P]),
+    "mrcnn_mask_components_count": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P]),
+    "mrcnn_mask_components_emit": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "mrcnn_mask_row_extents": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "mrcnn_voc_match": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
     "mrcnn_unmold_masks_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mrcnn_unmold_masks": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
@@ -216,7 +222,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_draw_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
+_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
 
 
 class _LibProxy(object):

@@ -23,6 +23,11 @@ work, the mask IoU of every (true object, detection) pair and the flux sum under
 behind ``Analyzer.eval_device``: ``mask_iou`` / ``np.nansum`` on full frames, or one launch each on bit planes
 (csrc/maskeval.hip: ops.mask_cross_stats / mask_plane_sums); the matching loops are the same code for both.
 
+Connected components -- the pieces of ``split_masks``, the true masks of ``split_gtmasks``, the islands and hull points of
+``compute_det_mask_pars`` -- come from the same planes behind ``Analyzer.components_device`` (csrc/components.hip:
+ops.mask_components / mask_components_split / mask_row_extents), else from ``label_components`` / ``count_islands`` /
+``row_extreme_points`` on full frames.
+
 Third-party pieces the reference imports and this file restates (absent here, so parity is UNPINNED for
 them; the semantics are the published ones):
   * skimage.measure.label(connectivity=1)      -> ``label_components`` (4-connected, raster-order numbering)
@@ -53,6 +58,8 @@ logger = logging.getLogger("mrcnn")
 NO_SPLIT_CLASSES = ('galaxy_C2', 'galaxy_C3', 'galaxy', 'extended-multisland')      # analyze.py:1221
 
 NO_SPLIT_CLASSES_GT = ('galaxy_C2', 'galaxy_C3', 'galaxy', 'extended', 'extended-multisland')      # analyze.py:1065
+
+SPLIT_DTYPE = np.where(np.zeros(1, bool), [1], [0]).dtype      # of a piece of split_masks as the host statement makes it
 
 
 # ---- where the pixel work runs: one device resolution, one failure policy, one plane eligibility --------------------
@@ -363,22 +370,45 @@ def convex_hull(points):
     return np.array(lower[:-1] + upper[:-1], dtype=np.float64).reshape(-1, 2)
 
 
+def row_extreme_points(mask):
+    """[2 R, 2] integer points (x, y): the leftmost set pixel of each of the R rows that have one, then the rightmost of each; None
+    for an empty mask.  They suffice for the hull of the mask's pixels.  ops.mask_row_extents gives the same columns from bit
+    planes (``row_extents_points``)."""
+    m = np.asarray(mask) != 0
+    ys, xs = np.nonzero(m)
+    if ys.size == 0:
+        return None
+    starts = np.flatnonzero(np.r_[True, ys[1:] != ys[:-1]])         # np.nonzero lists the pixels row by row
+    ends = np.r_[starts[1:], ys.size] - 1
+    return np.concatenate([np.stack([xs[starts], ys[starts]], 1), np.stack([xs[ends], ys[ends]], 1)])
+
+
+def row_extents_points(extents, y1):
+    """row_extreme_points from the [rows, 2] (leftmost, rightmost) table of ops.mask_row_extents for a box that starts at row y1."""
+    extents = np.asarray(extents).reshape(-1, 2)
+    rows = np.flatnonzero(extents[:, 0] >= 0)
+    if rows.size == 0:
+        return None
+    ys = rows + int(y1)
+    return np.concatenate([np.stack([extents[rows, 0], ys], 1), np.stack([extents[rows, 1], ys], 1)]).astype(np.int64)
+
+
 def min_area_rect(mask):
-    """((cx, cy), (w, h), angle) of the minimum-area enclosing rectangle of a mask's set pixels, in coordinate measure (a single
-    pixel is 0 x 0, an a x b block is (a - 1) x (b - 1)); None for an empty mask.  Stands for cv.findContours(RETR_EXTERNAL,
+    """``min_area_rect_of_points`` of the mask's ``row_extreme_points``; None for an empty mask."""
+    points = row_extreme_points(mask)
+    return None if points is None else min_area_rect_of_points(points)
+
+
+def min_area_rect_of_points(points):
+    """((cx, cy), (w, h), angle) of the minimum-area enclosing rectangle of a mask's set pixels, given as integer points (x, y)
+    that hold the hull's vertices (``row_extreme_points``), in coordinate measure (a single
+    pixel is 0 x 0, an a x b block is (a - 1) x (b - 1)).  Stands for cv.findContours(RETR_EXTERNAL,
     CHAIN_APPROX_SIMPLE) followed by cv.minAreaRect on the merged contours (analyze.py:1562-1617), UNPINNED: that is the rectangle
     of the convex hull of the pixels' integer coordinates -- the outer contours hold every hull vertex, holes and collinear
     points never reach the hull.  Rotating calipers in float64: a minimum-area rectangle has a side along a hull edge, so for
     every edge the hull's extent along and across it is taken and the first smallest area kept.  The angle follows OpenCV >= 4.5.1:
     in (0, 90], the rotation of the side reported as the width from the x axis; nothing reads it."""
-    m = np.asarray(mask) != 0
-    ys, xs = np.nonzero(m)
-    if ys.size == 0:
-        return None
-    # the leftmost and rightmost set pixel of every row suffice for the hull (np.nonzero lists the pixels row by row)
-    starts = np.flatnonzero(np.r_[True, ys[1:] != ys[:-1]])
-    ends = np.r_[starts[1:], ys.size] - 1
-    hull = convex_hull(np.concatenate([np.stack([xs[starts], ys[starts]], 1), np.stack([xs[ends], ys[ends]], 1)]))
+    hull = convex_hull(points)
     if len(hull) == 1:
         return (float(hull[0, 0]), float(hull[0, 1])), (0.0, 0.0), 90.0
     best = None
@@ -556,6 +586,11 @@ class Analyzer(object):
     # host statement is ahead on an MI355X host (profiles/draw_bench.json).
     DRAW_DEVICE_MIN_MASKS = 0
 
+    # Connected components on the GPU (csrc/components.hip): the pieces of split_masks (with postprocess_device), the true masks of
+    # split_gtmasks, and the island count and hull points of compute_det_mask_pars (where its device path runs anyway).  Off by
+    # default; tools/components_bench.py times it against the host statement (profiles/components_bench.json).
+    COMPONENTS_DEVICE = False
+
     def __init__(self, model, config, dataset=None, gt_data=None, pred_data=None):
         # Off by default: the device path is equal to the host statement value for value (tests/test_analyze_post_gpu.py) but
         # has not been timed against it on an MI355X host yet, and a frame with one to three detections costs the host
@@ -567,6 +602,8 @@ class Analyzer(object):
         self.results_device = self.RESULTS_DEVICE
         self.results_device_min_masks = self.RESULTS_DEVICE_MIN_MASKS
         self.results_timing = {}
+        self.components_device = self.COMPONENTS_DEVICE
+        self.components_timing = {}
         # The device tensor behind self.masks, when the model kept it, and the host array it mirrors (both set by predict).
         # The device path uses the tensor only while self.masks IS that array: masks assigned by hand are uploaded.
         self.masks_device = None
@@ -735,8 +772,26 @@ class Analyzer(object):
 
     def extract_det_masks_host(self):
         """The literal statement: mask_iou and are_mask_connected (three labellings) on full frames, asked pair by pair."""
-        self._extract_det_masks(lambda dets: _FrameMasks(self, [self.masks[:, :, i] if piece is None else np.where(piece, [1], [0])
-                                                               for i, piece in dets]))
+        self._extract_det_masks(self._frame_masks)
+
+    def _host_pieces(self, wanted):
+        """The host statement of "the pieces of these detections": for wanted = [(detection, split it?)] the list [(detection,
+        None: its whole mask, or the bool frame of one of its 4-connected components, in label order)] and the number of entries
+        each detection gave."""
+        dets, pieces = [], []
+        for i, split in wanted:
+            if not split:
+                dets.append((i, None))
+                pieces.append(1)
+                continue
+            labels, ncomp = label_components(self.masks[:, :, i])
+            dets.extend((i, labels == k + 1) for k in range(ncomp))
+            pieces.append(ncomp)
+        return dets, pieces
+
+    def _frame_masks(self, wanted):
+        dets, pieces = self._host_pieces(wanted)
+        return _FrameMasks(self, [self.masks[:, :, i] if piece is None else np.where(piece, [1], [0]) for i, piece in dets]), pieces
 
     def extract_det_masks_device(self):
         """The same decisions from three launches on bit planes (_PlaneMasks), every one taken on the host from exact integer
@@ -746,34 +801,81 @@ class Analyzer(object):
         for name, a, b in zip(("upload_pack", "merge_pairs", "union", "select_pairs", "host_lists", "download_unpack"), t[:-1], t[1:]):
             self.postprocess_timing[name + "_ms"] = round(1e3 * (b - a), 3)
 
-    def _plane_masks(self, dets):
-        """The _PlaneMasks of `dets` (see _extract_det_masks): packed from the model's own device tensor, else from one upload --
-        of self.masks, or with split_masks of the split masks."""
+    def _plane_masks(self, wanted):
+        """The _PlaneMasks of `wanted` (see _extract_det_masks) and the pieces per detection.  With split_masks the pieces are cut
+        on the device (ops.mask_components_split) when ``components_device`` is set, else on the host and uploaded."""
+        if self.split_masks and self.components_device:
+            from . import ops
+            return device_or_host("split_masks_device", lambda: self._plane_pieces_device(wanted),
+                                  lambda: self._plane_pieces_host(wanted), refusal=ops.ComponentsUnsupported)
+        return self._plane_pieces_host(wanted)
+
+    def _masks_tensor(self):
+        """(self.masks as a device tensor of bytes, uploads): the model's own tensor when it is theirs, else one upload."""
+        import torch
+        kept = self.masks_device
+        if kept is not None and self.masks_device_host is self.masks and torch.is_tensor(kept) and kept.is_cuda and \
+                tuple(kept.shape) == tuple(self.masks.shape):
+            return kept, 0
+        m = self.masks if self.masks.dtype == np.bool_ else self.masks != 0
+        return torch.from_numpy(np.ascontiguousarray(m).view(np.uint8)).to(self._device()), 1
+
+    def _plane_pieces_host(self, wanted):
+        """Packed from the model's own device tensor, else from one upload -- of self.masks, or with split_masks of the masks the
+        host statement split."""
         import torch
         from . import ops
-        split_dtype = np.where(np.zeros(1, bool), [1], [0]).dtype
-        dtypes = [[self.masks.dtype if piece is None else split_dtype] for _, piece in dets]     # of the host statement's arrays
-        kept = self.masks_device
+        dets, pieces = self._host_pieces(wanted)
+        if not dets:
+            return None, pieces
+        dtypes = [[self.masks.dtype if piece is None else SPLIT_DTYPE] for _, piece in dets]     # of the host statement's arrays
         if self.split_masks:
             index = range(len(dets))
-            masks_t = np.stack([self.masks[:, :, i] != 0 if piece is None else piece for i, piece in dets], axis=-1).view(np.uint8)
+            stack = np.stack([self.masks[:, :, i] != 0 if piece is None else piece for i, piece in dets], axis=-1).view(np.uint8)
+            masks_t, uploads = torch.from_numpy(stack).to(self._device()), 1
         else:
             index = [i for i, _ in dets]
-            if kept is not None and self.masks_device_host is self.masks and torch.is_tensor(kept) and kept.is_cuda and \
-                    tuple(kept.shape) == tuple(self.masks.shape):
-                masks_t = kept
+            masks_t, uploads = self._masks_tensor()
+        self.postprocess_timing["mask_uploads"] = uploads
+        return _PlaneMasks(self, ops.mask_planes_pack(masks_t.contiguous()), index, dtypes), pieces
+
+    def _plane_pieces_device(self, wanted):
+        """The planes of the wanted detections, packed from the tensor the model kept (else one upload of self.masks), followed by
+        the planes of their components (ops.mask_components, 4-connected, and mask_components_split): a detection that is not
+        split is its own plane, one that is becomes its pieces in label order.  No mask is labelled or uploaded piece by piece."""
+        import torch
+        from . import ops
+        t0 = time.perf_counter()
+        masks_t, uploads = self._masks_tensor()
+        self.postprocess_timing["mask_uploads"] = uploads
+        planes = ops.mask_planes_pack(masks_t.contiguous())
+        ids = torch.as_tensor([i for i, _ in wanted], device=planes.words.device)
+        whole = ops.MaskPlanes(planes.words.index_select(0, ids), planes.count.index_select(0, ids), planes.box.index_select(0, ids), planes.W)
+        parts, offs = ops.mask_components_split(ops.mask_components(whole, 4))
+        index, dtypes, pieces = [], [], []
+        for k, (_, split) in enumerate(wanted):
+            if split:
+                first, last = whole.n + int(offs[k]), whole.n + int(offs[k + 1])
+                index.extend(range(first, last))
+                dtypes.extend([[SPLIT_DTYPE]] * (last - first))
+                pieces.append(last - first)
             else:
-                m = self.masks if self.masks.dtype == np.bool_ else self.masks != 0
-                masks_t = np.ascontiguousarray(m).view(np.uint8)
-        if not torch.is_tensor(masks_t):
-            masks_t = torch.from_numpy(masks_t).to(self._device())
-            self.postprocess_timing["mask_uploads"] += 1
-        return _PlaneMasks(self, ops.mask_planes_pack(masks_t.contiguous()), index, dtypes)
+                index.append(k)
+                dtypes.append([self.masks.dtype])
+                pieces.append(1)
+        self.components_timing["split_masks_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+        self.components_timing["split_pieces"] = int(offs[-1])
+        if not index:
+            return None, pieces
+        both = ops.MaskPlanes(torch.cat([whole.words, parts.words]), torch.cat([whole.count, parts.count]),
+                              torch.cat([whole.box, parts.box]), whole.W)
+        return _PlaneMasks(self, both, index, dtypes), pieces
 
     def _extract_det_masks(self, mask_set):
         """extract_det_masks, rule for rule in the order of the reference, on a mask set (_FrameMasks or _PlaneMasks) that answers
-        the pixel questions.  ``mask_set(dets)`` builds it from dets = [(detection, None: its whole mask, or the bool frame of one
-        of its components)].  Returns the times at the borders of the device form's phases."""
+        the pixel questions.  ``mask_set(wanted)`` builds it from wanted = [(detection, is it to be split into its connected
+        pieces)] and says how many masks each detection became (a whole mask: 1; a split one: its components in label order).
+        Returns the times at the borders of the device form's phases."""
         clock = time.perf_counter
         t = [clock()]
         self.masks_final, self.class_ids_final, self.class_names_final, self.scores_final = [], [], [], []
@@ -782,21 +884,18 @@ class Analyzer(object):
         sel = [i for i in range(self.boxes.shape[0]) if not self.scores[i] < self.score_thr]
         order = np.argsort([self.scores[i] for i in sel])[::-1]
 
-        dets, class_ids_det, scores_det = [], [], []
-        for index in order:
-            i = sel[index]
-            class_id, score = self.class_ids[i], self.scores[i]
-            if not self.split_masks or self.class_names[class_id] in NO_SPLIT_CLASSES:
-                pieces = [None]
-            else:
-                labels, ncomp = label_components(self.masks[:, :, i])
-                pieces = [labels == k + 1 for k in range(ncomp)]
-            for piece in pieces:
-                dets.append((i, piece)); class_ids_det.append(class_id); scores_det.append(score)
-        N = len(dets)
+        wanted = [(sel[index], bool(self.split_masks and self.class_names[self.class_ids[sel[index]]] not in NO_SPLIT_CLASSES))
+                  for index in order]
+        if not wanted:
+            return t
+        masks_det, pieces = mask_set(wanted)
+        class_ids_det, scores_det = [], []
+        for (i, _), count in zip(wanted, pieces):
+            class_ids_det.extend([self.class_ids[i]] * count)
+            scores_det.extend([self.scores[i]] * count)
+        N = len(class_ids_det)
         if N == 0:
             return t
-        masks_det = mask_set(dets)
         masks_det.sync()
         t.append(clock())
 
@@ -962,7 +1061,79 @@ class Analyzer(object):
 
     def extract_gt_masks(self):
         """analyze.py:1039-1155: the true masks as they are, or (split_gtmasks) split into connected pieces and the touching
-        pieces of one class merged again; then their boxes and captions."""
+        pieces of one class merged again; then their boxes and captions.  With ``split_gtmasks`` and ``components_device`` the
+        pieces, the contact tests and the unions are done on bit planes (``extract_gt_masks_device``) where a GPU is there and the
+        true masks are 0 / 1 frames; else, and for every other setting, by the host statement."""
+        m = np.asarray(self.masks_gt)
+        if self.split_gtmasks and self.components_device and m.ndim == 3 and m.shape[-1] > 0 and Analyzer.has_gpu(self.model) and \
+                masks_fit_planes(np.moveaxis(m, -1, 0), binary=True):
+            from . import ops
+            return device_or_host("extract_gt_masks_device", self.extract_gt_masks_device, self.extract_gt_masks_host,
+                                  refusal=ops.ComponentsUnsupported)
+        return self.extract_gt_masks_host()
+
+    def extract_gt_masks_device(self):
+        """extract_gt_masks_host with split_gtmasks, on bit planes: the true masks are packed once; component 1 of every mask that
+        is split comes from ops.mask_components_split(first_only) and stands ncomp times in the list, as the reference has it;
+        same-class pairs are tested with mask_pair_stats' touch (== are_mask_connected); the groups are merged by mask_union,
+        whose boxes are bboxes_gt.  A true mask that ends up alone and whole is handed on as the array it came as."""
+        import torch
+        from . import ops
+        t0 = time.perf_counter()
+        masks_gt, dtype = self.masks_gt, self.masks_gt.dtype
+        K = masks_gt.shape[-1]
+        planes, _ = self._planes_of([masks_gt[:, :, k] for k in range(K)])
+        handle = ops.mask_components(planes, 4)
+        parts, offs = ops.mask_components_split(handle, first_only=True)
+        ncomp = handle.ncomp_host
+        index, source, class_ids_gt_det, sidelobes_gt_det = [], [], [], []     # per list entry: its plane, the whole mask it is (or None)
+        for k in range(K):
+            whole = self.labels_gt[k] in NO_SPLIT_CLASSES_GT
+            copies = 1 if whole else int(ncomp[k])
+            index.extend([k if whole else K + int(offs[k])] * copies)
+            source.extend([k if whole else None] * copies)
+            class_ids_gt_det.extend([self.class_ids_gt[k]] * copies)
+            sidelobes_gt_det.extend([self.sidelobes_mixed_or_near_gt[k]] * copies)
+        N = len(index)
+        self.masks_gt_merged, self.class_ids_gt_merged, self.bboxes_gt, self.captions_gt = [], [], [], []
+        self.sidelobes_mixed_or_near_gt_merged = []
+        self.components_timing["gt_entries"] = N
+        if N == 0:
+            return
+        both = ops.MaskPlanes(torch.cat([planes.words, parts.words]), torch.cat([planes.count, parts.count]),
+                              torch.cat([planes.box, parts.box]), planes.W)
+        index = np.asarray(index, dtype=np.int32)
+        ii, jj = _pairs_below(N)
+        cls = np.asarray([int(c) for c in class_ids_gt_det])
+        same = cls[ii] == cls[jj]
+        ii, jj = ii[same], jj[same]
+        edges = []
+        if ii.size:
+            _, touch = ops.mask_pair_stats(both, np.stack([index[ii], index[jj]], axis=1))
+            hit = touch.cpu().numpy() != 0
+            edges = list(zip(ii[hit].tolist(), jj[hit].tolist()))
+        comps = connected_components(N, edges)
+        comp_offsets = np.concatenate([[0], np.cumsum([len(comp) for comp in comps])])
+        merged = ops.mask_union(both, comp_offsets, index[[k for comp in comps for k in comp]])
+        boxes = merged.box.cpu().numpy()
+        alone = [source[comp[0]] if len(comp) == 1 else None for comp in comps]
+        need = [c for c in range(len(comps)) if alone[c] is None]
+        unpacked = {}
+        if need:
+            ids = torch.as_tensor(need, device=merged.words.device)
+            frames = unpack_mask_planes(merged.words.index_select(0, ids).cpu().numpy(), merged.W)
+            unpacked = {c: frames[q].astype(dtype) for q, c in enumerate(need)}
+        for c, comp in enumerate(comps):
+            self.masks_gt_merged.append(masks_gt[:, :, alone[c]] if alone[c] is not None else unpacked[c])
+            self.class_ids_gt_merged.append(class_ids_gt_det[comp[-1]])               # class and flag of the last member
+            self.sidelobes_mixed_or_near_gt_merged.append(sidelobes_gt_det[comp[-1]])
+            self.bboxes_gt.append(boxes[c].astype(np.int32))
+            self.captions_gt.append(self.class_names_gt[self.class_ids_gt_merged[c]])
+        self._eval_planes["gt"] = (merged, self.masks_gt_merged)          # compute_performances_device works on these
+        self.components_timing["gt_masks_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+
+    def extract_gt_masks_host(self):
+        """The literal statement: every true mask labelled, are_mask_connected (three labellings) for all pairs of pieces."""
         self.masks_gt_merged, self.class_ids_gt_merged, self.bboxes_gt, self.captions_gt = [], [], [], []
         self.sidelobes_mixed_or_near_gt_merged = []
         if self.split_gtmasks:
@@ -1044,7 +1215,8 @@ class Analyzer(object):
         """Per detected object: pixel count, flux sum and signal-to-noise on the un-stretched image, upright and minimum-area
         boxes, islands, border flag, sizes in beams.  The per-mask pixel count, box and flux sum come from
         ``compute_det_mask_pars_device`` (ops.mask_plane_sums on bit planes) when the device path is on, else from full frames;
-        everything after them is the same host code."""
+        with ``components_device`` that path also brings the island counts (ops.mask_components, 8-connected) and the hull points
+        of the minimum-area box (ops.mask_row_extents); everything after them is the same host code."""
         from . import fits
         logger.info("Reading 2D origin image data from file %s ..." % self.image_path)
         res = fits.read_fits(self.image_path, stretch=False, normalize=False, convertToRGB=False, to_uint8=False,
@@ -1084,13 +1256,46 @@ class Analyzer(object):
         planes = self._eval_planes_of("final", self.masks_final)
         img_t =torch.from_numpy(np.ascontiguousarray(data)).to(planes.words.device)
         sums = ops.mask_plane_sums(img_t, planes)
+        n = planes.n
+        if self.components_device:
+            shape = device_or_host("det_mask_shape_device", lambda: self._det_mask_shape_device(planes), lambda: None,
+                                   refusal=ops.ComponentsUnsupported)
+            if shape is not None:
+                ints, islands, points = shape
+                stot = sums.cpu().numpy()
+                self.eval_timing["det_mask_pars_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+                return ints[:n].tolist(), list(ints[n:5 * n].reshape(n, 4)), stot.tolist(), islands, points
         ints = torch.cat([planes.count, planes.box.reshape(-1)]).cpu().numpy()
         stot = sums.cpu().numpy()
-        n = planes.n
         self.eval_timing["det_mask_pars_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
         return ints[:n].tolist(), list(ints[n:].reshape(n, 4)), stot.tolist()
 
-    def _det_mask_pars_from(self, data, npix, boxes, stot):
+    def _det_mask_shape_device(self, planes):
+        """(ints, islands, points) of the final planes: the counts and boxes compute_det_mask_pars_device reads anyway, the
+        8-connected component count of every plane (count_islands) and the row_extreme_points of every plane (None for an empty
+        one), all from ONE download.  The workspace is sized from self.bboxes, the boxes extract_det_masks left for these very
+        masks; the download brings the planes' own boxes along, and only if the two differ is the work done again from those."""
+        import torch
+        from . import ops
+        n = planes.n
+        host = np.asarray(self.bboxes, dtype=np.int32).reshape(-1, 4) if len(self.bboxes) == n else planes.box.cpu().numpy()
+        for attempt in range(2):
+            handle = ops.mask_components(planes, 8, boxes_host=host)
+            extents, row_offsets = ops.mask_row_extents(planes, boxes_host=host)
+            ints = torch.cat([planes.count, planes.box.reshape(-1), handle.ncomp, extents.reshape(-1)]).cpu().numpy()
+            boxes = ints[n:5 * n].reshape(n, 4)
+            if np.array_equal(boxes, host):
+                break
+            host = np.ascontiguousarray(boxes, dtype=np.int32)
+        else:
+            raise ops.ComponentsUnsupported("the planes' boxes changed between two downloads")
+        islands = ints[5 * n:6 * n].tolist()
+        ext = ints[6 * n:].reshape(-1, 2)
+        points = [row_extents_points(ext[row_offsets[k]:row_offsets[k + 1]], boxes[k, 0]) for k in range(n)]
+        self.components_timing["det_mask_shape_downloads"] = attempt + 1
+        return ints, islands, points
+
+    def _det_mask_pars_from(self, data, npix, boxes, stot, islands=None, points=None):
         has_metadata = bool(self.image_metadata)
         if has_metadata:                                                                  # :1510-1524
             md = self.image_metadata
@@ -1120,12 +1325,15 @@ class Analyzer(object):
                     SNR = np.float64(S) / Serr_noise
             else:
                 SNR = -999
-            rect = min_area_rect(mask)
+            if points is None:
+                rect = min_area_rect(mask)
+            else:
+                rect = None if points[i] is None else min_area_rect_of_points(points[i])
             if rect is None:                                                              # "no contours": :1592-1595
                 logger.warning("No contours found for object no. %d, fill empty dict!" % (i + 1))
                 self.det_obj_pars.append({})
                 continue
-            nislands = count_islands(mask)
+            nislands = count_islands(mask) if islands is None else islands[i]
             # cv.boundingRect of the contour points: x, y of the first pixel, w, h up to one past the last -- extract_bboxes
             y1, x1, y2, x2 = (int(v) for v in boxes[i])
             bbox_w, bbox_h = x2 - x1, y2 - y1
@@ -1542,6 +1750,7 @@ class ModelTester(object):
         self.outfilename_completeness = "completeness.csv"
         self.outfilename_reliability = "reliability.csv"
         self.eval_device = None               # None: every Analyzer keeps its own default; True / False: set on each of them
+        self.components_device = None         # likewise (Analyzer.components_device)
         self.draw = False                     # every Analyzer draws out_<base>_id<uuid>.png (the reference's always do)
 
     def test(self):
@@ -1564,6 +1773,8 @@ class ModelTester(object):
             analyzer.classid_map = self.classid_map
             if self.eval_device is not None:
                 analyzer.eval_device = self.eval_device
+            if self.components_device is not None:
+                analyzer.components_device = self.components_device
             analyzer.draw = self.draw
             logger.info("Inspecting results for image %s ..." % image_path_base)
             if analyzer.inspect_results(image_id, image_path) < 0:

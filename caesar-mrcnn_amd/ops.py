@@ -1056,6 +1056,120 @@ def mask_plane_sums(img, planes, big_endian=False):
     return out
 
 
+class ComponentsUnsupported(_hip.HipPathError):
+    """A frame or box table past a cap of mrcnn_mask_components_* (include/mrcnn_hip.h: a frame side above 8192, more than 4096
+    planes, a box whose run capacity rows * ceil(columns / 2) is above 2^22, a workspace past 2^31 - 1 words, more than 2^24
+    pieces): the caller takes the host statement."""
+
+
+COMPONENTS_ALL, COMPONENTS_FIRST = 0, 1
+
+
+class MaskComponents(object):
+    """What mask_components leaves on the device for mask_components_split: ncomp [n] int32 (components per plane) and the
+    workspace with the run table and its labels, for the planes and the host copy of their boxes they were made from."""
+
+    def __init__(self, planes, connectivity, boxes_host, ncomp, ws):
+        self.planes, self.connectivity, self.boxes_host, self.ncomp, self.ws = planes, int(connectivity), boxes_host, ncomp, ws
+        self.ncomp_host = None               # set by mask_components_split, the one reader
+
+
+def _components_refusal(rc, what):
+    if rc == ERR_UNSUPPORTED:
+        raise ComponentsUnsupported("%s: the frame or its box table is past a cap of the kernels (status %d): a side above 8192, more "
+                                    "than 4096 planes, a box of more than 2^22 possible runs, or a workspace past int32 words" % (what, rc))
+    if rc:
+        raise ValueError("%s refuses the request (status %d): no plane, an empty frame or a connectivity other than 4 or 8" % (what, rc))
+
+
+def _plane_boxes_host(planes, boxes_host):
+    """The host copy of planes.box as contiguous int32 [n, 4]: the caller's, or one download (a synchronisation)."""
+    import numpy as np
+    b = planes.box.cpu().numpy() if boxes_host is None else boxes_host
+    b = np.ascontiguousarray(b, dtype=np.int32).reshape(-1, 4)
+    if b.shape[0] != planes.n:
+        raise ValueError("boxes_host must be the host copy of the planes' boxes")
+    return b
+
+
+def mask_components(planes, connectivity=4, boxes_host=None):
+    """Labels the 4- or 8-connected components of every plane of a MaskPlanes inside its box (include/mrcnn_hip.h:
+    mrcnn_mask_components_count), numbered as analyze.label_components numbers them.  Returns a MaskComponents: ncomp stays on the
+    device, nothing is read back here when `boxes_host` -- the NumPy copy of planes.box, which sizes the workspace -- is given;
+    without it the boxes are downloaded first.  ValueError for a malformed request, ComponentsUnsupported past a cap; neither
+    launches anything."""
+    _need_cuda(planes.words, planes.box)
+    if planes.n <= 0:
+        raise ValueError("mask_components: no plane")
+    bh = _plane_boxes_host(planes, boxes_host)
+    L = _hip.lib()
+    host = bh.ctypes.data_as(C.c_void_p)
+    nbytes = int(L.mrcnn_mask_components_workspace(planes.n, planes.H, planes.W, host))
+    _components_refusal(L.mrcnn_mask_components_check(planes.n, planes.H, planes.W, int(connectivity), host, nbytes), "mrcnn_mask_components_count")
+    dev = planes.words.device
+    ws = torch.empty((max(nbytes // 4, 1),), dtype=torch.int32, device=dev)
+    ncomp = torch.empty((planes.n,), dtype=torch.int32, device=dev)
+    check(L.mrcnn_mask_components_count(ptr(planes.words.contiguous()), host, ptr(planes.box.contiguous()), planes.n, planes.H, planes.W,
+                                        int(connectivity), ptr(ws), nbytes, ptr(ncomp), current_stream()), "mrcnn_mask_components_count")
+    return MaskComponents(planes, connectivity, bh, ncomp, ws)
+
+
+def mask_components_split(handle, first_only=False):
+    """The components of a MaskComponents as planes: (MaskPlanes of the P pieces, piece_offsets [n + 1] NumPy) -- plane p's pieces are
+    piece_offsets[p] .. piece_offsets[p + 1], in component order; with `first_only` component 1 of every plane that has one.  The
+    pieces have the layout of mask_union's result.  Reads ncomp back (kept as handle.ncomp_host): the one synchronisation."""
+    import numpy as np
+    planes = handle.planes
+    nc = handle.ncomp.cpu().numpy().astype(np.int64)
+    handle.ncomp_host = nc
+    per = np.minimum(nc, 1) if first_only else nc
+    if int(per.sum()) > 2 ** 24:
+        raise ComponentsUnsupported("mask_components_split: %d pieces are past the 2^24 of mrcnn_mask_components_emit" % int(per.sum()))
+    offs = np.concatenate([[0], np.cumsum(per)]).astype(np.int32)
+    P, dev = int(offs[-1]), planes.words.device
+    words = torch.empty((P, planes.H, planes.wpr), dtype=torch.int32, device=dev)
+    count = torch.empty((P,), dtype=torch.int32, device=dev)
+    box = torch.empty((P, 4), dtype=torch.int32, device=dev)
+    if P:
+        offs_t = torch.from_numpy(offs).to(dev)
+        rc = _hip.lib().mrcnn_mask_components_emit(
+            handle.boxes_host.ctypes.data_as(C.c_void_p), ptr(planes.box.contiguous()), planes.n, planes.H, planes.W, ptr(handle.ws),
+            4 * handle.ws.numel(), ptr(handle.ncomp), offs.ctypes.data_as(C.c_void_p), ptr(offs_t),
+            COMPONENTS_FIRST if first_only else COMPONENTS_ALL, ptr(words), ptr(count), ptr(box), current_stream())
+        _components_refusal(rc if rc == ERR_UNSUPPORTED else 0, "mrcnn_mask_components_emit")
+        check(rc, "mrcnn_mask_components_emit")
+        words._keep = offs_t                 # alive until the caller has synchronised on the result
+    return MaskPlanes(words, count, box, planes.W), offs
+
+
+def mask_row_extents(planes, boxes_host=None):
+    """(extents [R, 2] int32 device tensor, row_offsets [n + 1] NumPy): for every row of every plane's box the x of its leftmost and
+    rightmost set pixel, (-1, -1) for a row without one; plane p's rows are extents[row_offsets[p] : row_offsets[p + 1]], top to
+    bottom from its box's y1 (include/mrcnn_hip.h: mrcnn_mask_row_extents).  boxes_host as for mask_components."""
+    import numpy as np
+    _need_cuda(planes.words, planes.box)
+    if planes.n <= 0:
+        raise ValueError("mask_row_extents: no plane")
+    bh = _plane_boxes_host(planes, boxes_host)
+    b = bh.astype(np.int64)
+    hgt = np.minimum(b[:, 2], planes.H) - np.maximum(b[:, 0], 0)
+    wid = np.minimum(b[:, 3], planes.W) - np.maximum(b[:, 1], 0)
+    hgt = np.where((hgt > 0) & (wid > 0), hgt, 0)
+    if int(hgt.sum()) > 2 ** 31 - 1:
+        raise ComponentsUnsupported("mask_row_extents: %d rows are past int32" % int(hgt.sum()))
+    offs = np.concatenate([[0], np.cumsum(hgt)]).astype(np.int32)
+    R, dev = int(offs[-1]), planes.words.device
+    extents = torch.empty((R, 2), dtype=torch.int32, device=dev)
+    if R:
+        offs_t = torch.from_numpy(offs).to(dev)
+        rc = _hip.lib().mrcnn_mask_row_extents(ptr(planes.words.contiguous()), bh.ctypes.data_as(C.c_void_p), ptr(planes.box.contiguous()),
+                                               planes.n, planes.H, planes.W, ptr(offs_t), R, ptr(extents), current_stream())
+        _components_refusal(rc if rc == ERR_UNSUPPORTED else 0, "mrcnn_mask_row_extents")
+        check(rc, "mrcnn_mask_row_extents")
+        extents._keep = offs_t
+    return extents, offs
+
+
 def voc_match(det_box, det_cls, det_score, det_off, gt_box, gt_cls, gt_off, thr):
     """The matching step of the Pascal-VOC box metrics for a whole test set in one launch (include/mrcnn_hip.h: mrcnn_voc_match).
     Device tensors: det_box [D, 4] / gt_box [G, 4] float64 corner boxes, det_cls [D] / gt_cls [G] int32, det_score [D] float64, thr [T]

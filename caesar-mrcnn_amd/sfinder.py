@@ -76,6 +76,7 @@ class TileTask(object):
         self.save_json = False
         self.save_regions = False
         self.results_device = False       # handed to the Analyzer (SFinder.results_device)
+        self.components_device = False    # likewise (SFinder.components_device)
         self.procId = 0
 
     def set_worker_id(self, wid):
@@ -151,6 +152,7 @@ class TileTask(object):
         analyzer.outfile_ds9 = 'catalog_' + self.image_id + '_tid' + str(self.tid) + '.reg'
         analyzer.obj_name_tag = self.sname_tag
         analyzer.results_device = self.results_device
+        analyzer.components_device = self.components_device
         return analyzer
 
     def _take(self, analyzer):
@@ -257,6 +259,9 @@ class SFinder(object):
         # Contours and pixel lists on the GPU (csrc/outline.hip): in every Analyzer the tiles build (Analyzer.results_device) and
         # for the merged sources of merge_edge_sources_device.  Off by default.
         self.results_device = False
+        # Connected components on the GPU (csrc/components.hip) in every Analyzer the tiles build (Analyzer.components_device): the
+        # pieces of split_masks.  Off by default.
+        self.components_device = False
         self.compute_params = False       # the reference always computes them (:613-622); here run.py --compute_source_params
         self.params_device = self._has_gpu()
         self.params_device_min_sources = self.PARAMS_DEVICE_MIN_SOURCES
@@ -374,6 +379,7 @@ class SFinder(object):
         analyzer.outfile_ds9 = self.outfile_ds9
         analyzer.iou_thr, analyzer.score_thr = cfg.IOU_THR, cfg.SCORE_THR
         analyzer.results_device = self.results_device
+        analyzer.components_device = self.components_device
         if analyzer.predict(image_data, self.image_id) < 0:               # sfinder.py:493: no offsets, no header
             logger.error("Failed to run model prediction on image %s!" % cfg.IMG_PATH)
             return -1
@@ -1019,6 +1025,7 @@ class SFinder(object):
             tileTask.save_regions = self.save_tile_regions
             tileTask.save_json = self.save_tile_json
             tileTask.results_device = self.results_device
+            tileTask.components_device = self.components_device
             self.tasks_per_worker[workerCounter].append(tileTask)
             workerCounter = 0 if workerCounter >= self.nproc - 1 else workerCounter + 1
         for i in range(len(self.tasks_per_worker)):                       # :1256-1293: neighbour lists, in this insertion order

@@ -380,6 +380,52 @@ int mrcnn_mask_cross_stats(const void* planes_a, const int32_t* box_a, int na, c
 int mrcnn_mask_plane_sums(const void* img, int big_endian, const void* planes, const int32_t* box, int n, int H, int W, double* sum,
                           void* stream);
 
+/* Connected components of the bit planes of the mask graph above (csrc/components.hip): the labelling behind
+ * Analyzer.split_masks, extract_gt_masks(split_gtmasks) and the island count of compute_det_mask_pars, and the per-row extents
+ * the hull of analyze.min_area_rect starts from.  Planes, boxes and conventions are those of the mask graph: integer arithmetic
+ * throughout, nothing is allocated on the device, no call synchronises.  A plane is labelled INSIDE its box cut to the frame (the
+ * box of _pack / _union covers the plane; a smaller one hides pixels, an empty one gives no component).  box_host is the host
+ * copy of the device table box: it sizes the workspace and is what the caps are checked on; the kernels place their tables from
+ * the device copy by the same rule and touch nothing when that would leave the workspace.
+ *   numbering   components are numbered 1..k in raster order of their first pixel, which is what analyze.label_components
+ *               (scipy.ndimage.label, or its breadth-first fallback) gives.  connectivity 4: up, down, left, right; 8: the
+ *               diagonals too (analyze.count_islands).  The labelling is a union-find over row runs whose root is the smallest
+ *               run id, ranked by a prefix sum: the atomics it uses (integer min, on LDS up to 12288 runs in a box, else on the
+ *               workspace) cannot change the result, so two calls on the same input give the same bytes.
+ *   mrcnn_mask_components_check      the status the calls below return for this frame, connectivity, host box table and workspace
+ *                                    size; launches nothing.  n, H or W <= 0, a connectivity other than 4 or 8, no table:
+ *                                    MRCNN_ERR_ARG.  Caps (past any: MRCNN_ERR_UNSUPPORTED, use the host statement): H, W <= 8192;
+ *                                    n <= 4096; rows * ceil(columns / 2) of one box <= 2^22 (its run capacity); workspace <= 2^31
+ *                                    - 1 words.  A workspace below mrcnn_mask_components_workspace: MRCNN_ERR_WORKSPACE.
+ *   mrcnn_mask_components_workspace  bytes of workspace for that table; 0 for a refused one.  Per box, in 32-bit words:
+ *                                    rows + 1 + 2 * capacity, and one capacity more when the capacity is above 12288.
+ *   mrcnn_mask_components_count      ncomp[n] = components per plane; the run table and its labels stay in the workspace.
+ *   mrcnn_mask_components_emit       the components as planes out_planes[P][H][wpr] with out_count[P] and out_box[P, 4], laid out
+ *                                    as mrcnn_mask_union's outputs (every word written).  piece_offsets[n + 1], given as the host
+ *                                    prefix and its device copy, places them: plane p owns pieces piece_offsets[p] ..
+ *                                    piece_offsets[p + 1], P = piece_offsets[n], the j-th of them being component j + 1.  mode
+ *                                    MRCNN_COMPONENTS_ALL: the caller gives every plane ncomp[p] pieces; MRCNN_COMPONENTS_FIRST: at
+ *                                    most one, component 1.  A piece past ncomp[p] is a zero plane; a plane with no set pixel has
+ *                                    no component and no piece.  workspace, box tables and ncomp: those of the count call,
+ *                                    unchanged.  A prefix that is not 0-based and monotone (or grows by more than 1 in FIRST
+ *                                    mode), another mode: MRCNN_ERR_ARG; P > 2^24: MRCNN_ERR_UNSUPPORTED.  P == 0 launches nothing.
+ *   mrcnn_mask_row_extents           extents[R][2] = (x of the leftmost, x of the rightmost set pixel), (-1, -1) for a row without
+ *                                    one, for every row of every plane's box: plane p's rows at row_offsets[p] (device, [n + 1],
+ *                                    the prefix of the box heights), R = the sum of the heights of box_host, else MRCNN_ERR_ARG.
+ *                                    Bit scans of the words; no labelling, no workspace.
+ * A refused call launches and writes nothing.                                                                                   */
+#define MRCNN_COMPONENTS_ALL 0
+#define MRCNN_COMPONENTS_FIRST 1
+int mrcnn_mask_components_check(int n, int H, int W, int connectivity, const int32_t* box_host, size_t ws_bytes);
+size_t mrcnn_mask_components_workspace(int n, int H, int W, const int32_t* box_host);
+int mrcnn_mask_components_count(const void* planes, const int32_t* box_host, const int32_t* box, int n, int H, int W, int connectivity,
+                                void* ws, size_t ws_bytes, int32_t* ncomp, void* stream);
+int mrcnn_mask_components_emit(const int32_t* box_host, const int32_t* box, int n, int H, int W, const void* ws, size_t ws_bytes,
+                               const int32_t* ncomp, const int32_t* piece_offsets_host, const int32_t* piece_offsets, int mode,
+                               void* out_planes, int32_t* out_count, int32_t* out_box, void* stream);
+int mrcnn_mask_row_extents(const void* planes, const int32_t* box_host, const int32_t* box, int n, int H, int W,
+                           const int32_t* row_offsets, int R, int32_t* extents, void* stream);
+
 /* The matching step of the Pascal-VOC box metrics of the reference's vendored tool (Object-Detection-Metrics,
  * lib/Evaluator.py:99-122: best ground truth per detection and the "seen" flag; :382-426: the IoU), for the detections and ground
  * truths of a whole test set, flat, in one launch.  Rows of one image are contiguous: image i owns detections det_off[i] ..
