@@ -27,6 +27,9 @@ extern int g_mrcnn_proposal_skip_zero;
 //   outline_lds_segs: sources of at most this many contour segments are ranked in LDS by mrcnn_outline_emit, larger ones in the
 //   global workspace (default and maximum 1536; 0 sends every source through the global form -- tests reach it at small shapes).
 extern int g_mrcnn_outline_lds_segs;
+//   catalog_max_sources: the longest catalogue mrcnn_catalog_count / _fill take (default and maximum 2^18; tests lower it to reach
+//   the refusal where the host statement is cheap).
+extern int g_mrcnn_catalog_max_sources;
 
 static inline int mrcnn_launch_status() {
     hipError_t e = hipGetLastError();

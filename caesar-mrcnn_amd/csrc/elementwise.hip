@@ -654,6 +654,11 @@ extern "C" int mrcnn_tuning_set(const char* key, long long value) {
         g_mrcnn_outline_lds_segs = (int)value;
         return MRCNN_OK;
     }
+    if (!strcmp(key, "catalog_max_sources")) {
+        if (value < 1 || value > MRCNN_CATALOG_MAX_SOURCES) return MRCNN_ERR_ARG;
+        g_mrcnn_catalog_max_sources = (int)value;
+        return MRCNN_OK;
+    }
     return MRCNN_ERR_UNSUPPORTED;
 }
 

@@ -291,6 +291,34 @@ def _read_fits_device(tile, zscale_contrasts, device):
     return host.numpy().copy()
 
 
+def read_table(filename):
+    """Rows of a whitespace-separated ascii table (utils.py:984-987 hands the file to astropy.io.ascii, which cannot run here): a
+    list of lists, one per line that is neither empty nor starts with '#'.  A column whose every value parses as a float becomes
+    float, any other stays str.  Every row must have the first row's number of columns.  None when the file cannot be read or
+    rows differ in length."""
+    try:
+        with open(filename) as f:
+            rows = [line.split() for line in f if line.strip() and not line.lstrip().startswith("#")]
+    except (OSError, UnicodeDecodeError):
+        logger.error('ERROR: Cannot read table file: ' + str(filename))
+        return None
+    if any(len(r) != len(rows[0]) for r in rows):
+        logger.error('ERROR: Rows of table %s differ in their number of columns' % filename)
+        return None
+
+    def number(v):
+        try:
+            return float(v)
+        except ValueError:
+            return None
+    for c in range(len(rows[0]) if rows else 0):
+        vals = [number(r[c]) for r in rows]
+        if all(v is not None for v in vals):
+            for r, v in zip(rows, vals):
+                r[c] = v
+    return rows
+
+
 def get_fits_header(filename):
     try:
         return read_primary_hdu(filename)[1]

@@ -761,6 +761,105 @@ def fits_tiles_to_rgb(plane, tiles, zscale_contrasts=(0.25, 0.25, 0.25), big_end
     return out
 
 
+# ---- source catalogue (csrc/catalog.hip) ------------------------------------------------------------------------------------
+CATALOG_MAX_SOURCES = 1 << 18            # MRCNN_CATALOG_MAX_SOURCES (include/mrcnn_hip.h)
+CATALOG_FILL_WALK, CATALOG_FILL_LAUNCHES = 0, 1
+
+
+class CatalogUnsupported(_hip.HipPathError):
+    """A catalogue mrcnn_catalog_count / _fill do not take: more sources than the cap (2^18), member lists of more than 2^31 - 1
+    entries, or a window coordinate outside the supported range (not finite, or of magnitude 2^31 or more).  Nothing was launched:
+    the caller takes the host statement."""
+
+
+def catalog_members(table, dx, dy, device):
+    """Windows and member lists of a whole catalogue (mrcnn_catalog_count, a scan, mrcnn_catalog_fill).  table: host float64
+    [S, 6], columns x0, y0, xmin, xmax, ymin, ymax; dx, dy: the cut-out size.  Returns host arrays: windows int32 [S, 4] (xmin,
+    xmax, ymin, ymax = int(x0 -/+ dx / 2), int(y0 -/+ dy / 2)), offsets int64 [S + 1], members int32 and cut uint8 [offsets[S]]:
+    row i = the sources j != i, ascending, whose centre lies strictly inside window i, and whether j's box touches or crosses it.
+    CatalogUnsupported -- before any launch -- for a catalogue past the caps above."""
+    import numpy as np
+    t = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1, 6).T)        # six columns, each contiguous
+    S = int(t.shape[1])
+    dx, dy = float(dx), float(dy)
+    if S == 0 or not (0 < dx < 2 ** 31 and 0 < dy < 2 ** 31):
+        raise ValueError("catalog_members needs at least one source and a positive cut-out size")
+    L = _hip.lib()
+    rc = L.mrcnn_catalog_check(S)
+    if rc == ERR_UNSUPPORTED:
+        raise CatalogUnsupported("mrcnn_catalog_count: %d sources are above the kernel's cap" % S)
+    check(rc, "mrcnn_catalog_check")
+    with np.errstate(all="ignore"):
+        edges = np.stack([t[0] - dx / 2, t[0] + dx / 2, t[1] - dy / 2, t[1] + dy / 2])
+        if not (np.isfinite(edges).all() and (np.abs(edges) < 2.0 ** 31).all()):
+            raise CatalogUnsupported("mrcnn_catalog_count: a window coordinate is not finite or outside the 32-bit range")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _hip.HipPathError("catalog_members needs a GPU device")
+    cols = torch.from_numpy(t).to(device)
+    windows = torch.empty((S, 4), dtype=torch.int32, device=device)
+    counts = torch.empty(S, dtype=torch.int32, device=device)
+    stream = current_stream()
+    check(L.mrcnn_catalog_count(ptr(cols[0]), ptr(cols[1]), S, dx, dy, ptr(windows), ptr(counts), stream), "mrcnn_catalog_count")
+    offsets = torch.zeros(S + 1, dtype=torch.int64, device=device)
+    offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)
+    total = int(offsets[-1].item())
+    if total > 2 ** 31 - 1:
+        raise CatalogUnsupported("mrcnn_catalog_fill: %d member entries are above 2^31 - 1" % total)
+    members = torch.empty(total, dtype=torch.int32, device=device)
+    cut = torch.empty(total, dtype=torch.uint8, device=device)
+    check(L.mrcnn_catalog_fill(ptr(cols[0]), ptr(cols[1]), ptr(cols[2]), ptr(cols[3]), ptr(cols[4]), ptr(cols[5]), S, dx, dy,
+                               ptr(offsets), total, ptr(members) if total else None, ptr(cut) if total else None, stream),
+          "mrcnn_catalog_fill")
+    return windows.cpu().numpy(), offsets.cpu().numpy(), members.cpu().numpy(), cut.cpu().numpy()
+
+
+def _catalog_plane(plane):
+    _need_cuda(plane)
+    if plane.dim() != 2 or plane.dtype != torch.float32:
+        raise ValueError("plane must be a [NY, NX] float32 device tensor (got shape %r, dtype %s)" % (tuple(plane.shape), plane.dtype))
+    return int(plane.shape[0]), int(plane.shape[1])
+
+
+def _catalog_windows(windows, device):
+    import numpy as np
+    w = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 4))
+    if w.size and (w.min() < -2 ** 31 or w.max() >= 2 ** 31):
+        raise ValueError("window outside the 32-bit range")
+    return torch.from_numpy(w.astype(np.int32)).to(device)
+
+
+def catalog_window_flags(plane, windows):
+    """Finite and NaN pixel counts of T windows (xmin, xmax, ymin, ymax) of a resident float32 plane, clipped to the plane at the
+    far edges as NumPy slicing clips (mrcnn_catalog_window_flags, one launch).  Returns a host int32 [T, 2]; a window with a
+    negative corner or without a pixel gets (0, 0)."""
+    import numpy as np
+    NY, NX = _catalog_plane(plane)
+    w = _catalog_windows(windows, plane.device)
+    T = int(w.shape[0])
+    if T == 0:
+        return np.zeros((0, 2), np.int32)
+    flags = torch.empty((T, 2), dtype=torch.int32, device=plane.device)
+    check(_hip.lib().mrcnn_catalog_window_flags(ptr(plane), NY, NX, ptr(w), T, ptr(flags), current_stream()), "mrcnn_catalog_window_flags")
+    return flags.cpu().numpy()
+
+
+def catalog_nan_fill(plane, windows, form=CATALOG_FILL_WALK):
+    """crop_img's in-place NaN fill for K windows of the resident plane, in the order given (mrcnn_catalog_nan_fill): window k's
+    NaN pixels get the non-NaN minimum of window k of the plane as it is after the turns before it; a window without a finite
+    pixel at its turn is left alone.  Writes `plane`.  Returns a host bool [K]: the window had a finite pixel at its turn.
+    form: CATALOG_FILL_WALK (one workgroup walks the table) or CATALOG_FILL_LAUNCHES (one launch per window); same plane."""
+    import numpy as np
+    NY, NX = _catalog_plane(plane)
+    w = _catalog_windows(windows, plane.device)
+    K = int(w.shape[0])
+    if K == 0:
+        return np.zeros(0, bool)
+    alive = torch.zeros(K, dtype=torch.int32, device=plane.device)
+    check(_hip.lib().mrcnn_catalog_nan_fill(ptr(plane), NY, NX, ptr(w), K, int(form), ptr(alive), current_stream()), "mrcnn_catalog_nan_fill")
+    return alive.cpu().numpy().astype(bool)
+
+
 def mold_image_u8(src, out_hw, pad_tl, canvas_hw, mean_pixel, out=None):
     """utils.resize_image's pixel work + mold_image on the device (mrcnn/model.py:2519-2556): src [h, w, C] uint8 device ->
     float32 [OH, OW, C]: the image scaled to out_hw (bilinear, float64, clipped to the image's range, truncated to uint8; a copy

@@ -68,6 +68,21 @@ def extract_bboxes(mask):
     return boxes
 
 
+def get_iou(bb1, bb2):
+    """IoU of two boxes (y1, x1, y2, x2), no +1 pixel convention (mrcnn/utils.py:100-144).  A box with x1 >= x2 or y1 >= y2 --
+    where the reference asserts and takes the run down -- has IoU 0 with everything."""
+    if not (bb1[1] < bb1[3] and bb1[0] < bb1[2] and bb2[1] < bb2[3] and bb2[0] < bb2[2]):
+        return 0.0
+    x_left, y_top = max(bb1[1], bb2[1]), max(bb1[0], bb2[0])
+    x_right, y_bottom = min(bb1[3], bb2[3]), min(bb1[2], bb2[2])
+    if x_right < x_left or y_bottom < y_top:
+        return 0.0
+    intersection_area = (x_right - x_left) * (y_bottom - y_top)
+    bb1_area = (bb1[3] - bb1[1]) * (bb1[2] - bb1[0])
+    bb2_area = (bb2[3] - bb2[1]) * (bb2[2] - bb2[0])
+    return intersection_area / float(bb1_area + bb2_area - intersection_area)
+
+
 def compute_iou(box, boxes, box_area, boxes_area):
     y1 = np.maximum(box[0], boxes[:, 0])
     y2 = np.minimum(box[2], boxes[:, 2])

@@ -813,14 +813,50 @@ int mrcnn_allreduce_direct_simulate(float* const* grads, float* const* scratch, 
 int mrcnn_allreduce_destroy(void* comm);
 const char* mrcnn_allreduce_last_error(void);
 
+/* ---- source catalogue: cut-out windows, member lists, window flags, ordered NaN fill (csrc/catalog.hip) ----------------------
+ * The geometry and the pixel bookkeeping of the source classifier (mrcnn/classifier.py:167-260, utils.crop_img :1211-1227) for a
+ * whole catalogue at once.  All pointers are device pointers; nothing is allocated, nothing synchronises, no atomic
+ * read-modify-write: every result is bitwise the same from run to run.
+ *
+ * S sources as six float64 columns x0, y0, xmin, xmax, ymin, ymax (centre and box), a cut-out of dx x dy pixels:
+ *   window of i    (xmin, xmax, ymin, ymax)_i = (int)(x0 - dx / 2), (int)(x0 + dx / 2), (int)(y0 - dy / 2), (int)(y0 + dy / 2): float64
+ *                  arithmetic, truncation toward zero.  Supported coordinates: every x0 -/+ dx / 2 and y0 -/+ dy / 2 finite and of
+ *                  magnitude below 2^31 (the CALLER checks this: the conversion is undefined outside it).
+ *   members of i   every j != i, ascending, with x0_j > xmin_i && x0_j < xmax_i && y0_j > ymin_i && y0_j < ymax_i;
+ *   cut flag       xmin_j <= xmin_i || xmax_j >= xmax_i || ymin_j <= ymin_i || ymax_j >= ymax_i.
+ * mrcnn_catalog_count writes windows [S][4] int32 and counts [S] int32; the caller scans the counts into offsets [S + 1] int64
+ * (exclusive, offsets[S] = total) and mrcnn_catalog_fill writes members [total] int32 and cut [total] uint8, row i at offsets[i].
+ * A row is written in ascending j by ballot + prefix popcount of the wavefront that owns it.  S <= 0, dx or dy <= 0 or not
+ * finite, a missing pointer: MRCNN_ERR_ARG.  S above the cap (2^18, "catalog_max_sources" of mrcnn_tuning_set) or total above
+ * 2^31 - 1: MRCNN_ERR_UNSUPPORTED -- nothing launched (use the host statement).  mrcnn_catalog_check: the status
+ * mrcnn_catalog_count would return for S (launches nothing).                                                                      */
+#define MRCNN_CATALOG_MAX_SOURCES (1 << 18)
+int mrcnn_catalog_check(int S);
+int mrcnn_catalog_count(const double* x0, const double* y0, int S, double dx, double dy, int* windows, int* counts, void* stream);
+int mrcnn_catalog_fill(const double* x0, const double* y0, const double* xmin, const double* xmax, const double* ymin,
+                       const double* ymax, int S, double dx, double dy, const long long* offsets, long long total, int* members,
+                       unsigned char* cut, void* stream);
+/* T windows (xmin, xmax, ymin, ymax) of a resident float32 plane [NY][NX], clipped to the plane at the far edges as NumPy slicing
+ * clips: flags [T][2] int32 = (pixels that are finite, pixels that are NaN).  A window with a negative corner or without a pixel
+ * gets (0, 0).  One launch, one workgroup per window.  T <= 0, NY or NX <= 0: MRCNN_ERR_ARG.                                     */
+int mrcnn_catalog_window_flags(const float* plane, int NY, int NX, const int* windows, int T, int* flags, void* stream);
+/* crop_img's in-place NaN fill for K windows IN TABLE ORDER: for k = 0 .. K - 1 the non-NaN minimum of window k of the plane AS
+ * IT IS THEN (earlier fills included) goes into the window's NaN pixels; a window without a finite pixel at its turn (or with a
+ * negative corner, or empty) is left as it is.  alive [K] int32 = 1 where the window had a finite pixel at its turn, else 0.
+ * form 0: one launch of one workgroup that walks the table with a workgroup barrier between windows; form 1: one launch of one
+ * workgroup per window, in stream order.  Both write the same plane.  K == 0 launches nothing; K < 0, NY or NX <= 0, another
+ * form: MRCNN_ERR_ARG.                                                                                                          */
+int mrcnn_catalog_nan_fill(float* plane, int NY, int NX, const int* windows, int K, int form, int* alive, void* stream);
+
 /* Process-wide tuning values, read by the host side of later launches.  Keys: "wgrad_lds_pad" (0..32768 bytes of extra
  * LDS per workgroup of the large weight-gradient kernel: 8192 caps it at four workgroups per CU so that kernels of another
  * stream find a free slot on every CU); "h16_phase" (0 / 1); "h16_slab" (-1 = MRCNN_H16_SLAB decides, default off; 0 / 1: the slab form of the phased 16-bit kernel off /
  * on -- tests and A/B timing); "sk16" (0 / 1: the 16 x 16-tile single-launch kernel for layers of a few hundred pixels may be
  * picked -- the engine sets it while it issues the inference graph); "proposal_skip_zero" (tests only, fault injection: 1 suppresses
  * the counter reset of mrcnn_proposal_fwd's multi-workgroup selection); "outline_lds_segs" (0..1536, default 1536: mrcnn_outline_emit
- * ranks the segments of a source in LDS up to this many and in its global workspace above; 0 = always the global form -- tests).
- * MRCNN_ERR_UNSUPPORTED for an unknown key.                                                                          */
+ * ranks the segments of a source in LDS up to this many and in its global workspace above; 0 = always the global form -- tests);
+ * "catalog_max_sources" (1..2^18, default 2^18: mrcnn_catalog_count / _fill refuse a longer catalogue -- tests reach the refusal
+ * at a size whose host statement is cheap).  MRCNN_ERR_UNSUPPORTED for an unknown key.                                                                          */
 int mrcnn_tuning_set(const char* key, long long value);
 
 const char* mrcnn_hip_version(void);
