@@ -1736,7 +1736,10 @@ __global__ void cast_from_h16_kernel(const T* __restrict__ src, float* dst, long
         *(f32x4*)(dst + i + 4) = hi;
         return;
     }
-    for (long long j = t * 8; j < t * 8 + 8 && j < n; ++j) dst[j] = (ACC ? dst[j] : 0.f) + (float)src[j] * mul;
+    for (long long j = t * 8; j < t * 8 + 8 && j < n; ++j) {        // no `0.f +` in the plain cast: it would turn -0 into +0
+        const float v = (float)src[j] * mul;
+        dst[j] = ACC ? dst[j] + v : v;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
