@@ -131,6 +131,9 @@ _SIGNATURES = {
     "mrcnn_mask_components_emit": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "mrcnn_mask_row_extents": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "mrcnn_voc_match": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    # caps is a HOST table (4 x int32)
+    "mrcnn_ap_sweep_caps": (C.c_int, [_P]),
+    "mrcnn_ap_sweep": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     "mrcnn_unmold_masks_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mrcnn_unmold_masks": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
                                      C.c_size_t, _P]),

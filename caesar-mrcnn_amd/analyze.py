@@ -1745,6 +1745,8 @@ class ModelTester(object):
         self.APs = []                         # compute_mAP: mask AP at iou_thr per inspected image; mAP is their mean
         self.voc = None                       # compute_mAP: metrics.voc_metrics(gt_data, pred_data, (0.5, iou_thr))
         self.metrics_outdir = None            # compute_mAP: write the external tools' input files under this directory
+        self.sweep_map = False                # compute_mAP: also the second vendored tool's numbers (metrics.sweep_metrics)
+        self.sweep = None                     # compute_mAP with sweep_map: the precision / recall sweep and the mAP over IoU 0.50 ... 0.95
         self.inspected = []                   # (image_id, image_path) of the images test() went through
         self.completeness_dict_list, self.reliability_dict_list = [], []
         self.outfilename_completeness = "completeness.csv"
@@ -1917,8 +1919,10 @@ class ModelTester(object):
         """:408-575.  (a) Mask AP at iou_thr of every inspected image (the reference's loop stops after the first one, marked TODO
         there: ``APs[0]`` is its value): load_image_gt, detect, utils.compute_ap -- the [P, G] mask overlaps from the device tensor
         the model kept (metrics.mask_ap) where there is one.  (b) The box metrics of the vendored Pascal-VOC tool at IoU 0.5 and
-        iou_thr.  (c) The printed block.  (d) The external tools' input files, under ``metrics_outdir`` when it is set (the reference
-        writes them into the current directory)."""
+        iou_thr.  (c) The printed block.  (d) With ``sweep_map``, what the second vendored tool (tarlen5-calculate-mean-ap) computes
+        from the same rows -- the curve over every score threshold, the mAP over IoU 0.50 ... 0.95, the per-class APs -- and the
+        lines it prints (metrics.sweep_metrics, format_sweep).  (e) The external tools' input files, under ``metrics_outdir`` when
+        it is set (the reference writes them into the current directory)."""
         from . import datagen, metrics
         self.APs = []
         for image_id, _ in self.inspected:
@@ -1939,6 +1943,10 @@ class ModelTester(object):
                 print("VOC IoU>=%.2f class %s: AP=%f (positives=%d, TP=%d, FP=%d)" % (
                     res["threshold"], label, c["AP"], c["total positives"], c["total TP"], c["total FP"]))
             print("VOC IoU>=%.2f mAP=%f" % (res["threshold"], res["mAP"]))
+        if self.sweep_map:
+            self.sweep = metrics.sweep_metrics(gt_data, pred_data)
+            for line in metrics.format_sweep(self.sweep):
+                print(line)
         if self.metrics_outdir:
             metrics.write_metric_files(gt_data, pred_data, [path for _, path in self.inspected], self.metrics_outdir)
         return 0

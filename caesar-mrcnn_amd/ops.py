@@ -1302,6 +1302,66 @@ def voc_match(det_box, det_cls, det_score, det_off, gt_box, gt_cls, gt_off, thr)
     return best_gt, best_iou, tp
 
 
+class ApSweepUnsupported(_hip.HipPathError):
+    """A request past a cap of mrcnn_ap_sweep (include/mrcnn_hip.h: more than AP_SWEEP_CAPS["det"] detections or
+    AP_SWEEP_CAPS["gt"] ground truths in one problem, more than AP_SWEEP_CAPS["thr"] thresholds): the caller keeps such problems
+    for the host statement, or splits the thresholds."""
+
+
+AP_SWEEP_OK, AP_SWEEP_OVER_CANDIDATES, AP_SWEEP_OVER_ROWS = 0, 1, 2
+_ap_sweep_caps = None
+
+
+def ap_sweep_caps():
+    """{"det", "gt", "thr", "cand"}: the compile-time caps of csrc/apsweep.hip, read from the library once."""
+    global _ap_sweep_caps
+    if _ap_sweep_caps is None:
+        caps = (C.c_int32 * 4)()
+        check(_hip.lib().mrcnn_ap_sweep_caps(C.cast(caps, C.c_void_p)), "mrcnn_ap_sweep_caps")
+        _ap_sweep_caps = dict(zip(("det", "gt", "thr", "cand"), (int(v) for v in caps)))
+    return dict(_ap_sweep_caps)
+
+
+def ap_sweep(det_box, det_off, gt_box, gt_off, thr):
+    """The suffix tables of the sweep mAP for the N problems of a test set in one launch (include/mrcnn_hip.h: mrcnn_ap_sweep).
+    Device tensors: det_box [D, 4] / gt_box [G, 4] float64 corner boxes, each problem's detections in ascending-score order, thr [T]
+    float64 (all > 0, boxes well formed: the caller's contract).  det_off / gt_off: the CSR offsets of the N problems, NumPy
+    (checked here) -- problem p owns rows off[p] .. off[p + 1].  Returns (tp [T * (D + N)] int32, status [N] int32) on the device:
+    problem p's T x (P + 1) table starts at tp[T * (det_off[p] + p)]; a problem whose status is AP_SWEEP_OVER_CANDIDATES is the
+    caller's to compute (its rows are zeros).  A problem past the row caps, or T past the threshold cap: ApSweepUnsupported, nothing
+    launched.  No problem: a HipPathError."""
+    import numpy as np
+    _need_cuda(det_box, gt_box, thr)
+    D, G, T = int(det_box.shape[0]), int(gt_box.shape[0]), int(thr.shape[0])
+    assert det_box.dtype == gt_box.dtype == thr.dtype == torch.float64
+    assert tuple(det_box.shape) == (D, 4) and tuple(gt_box.shape) == (G, 4) and thr.dim() == 1
+    do = np.ascontiguousarray(det_off, dtype=np.int64).reshape(-1)
+    go = np.ascontiguousarray(gt_off, dtype=np.int64).reshape(-1)
+    N = do.size - 1
+    if N < 1 or go.size != N + 1:
+        raise _hip.HipPathError("ap_sweep: empty problem table")
+    if do[0] != 0 or go[0] != 0 or do[-1] != D or go[-1] != G or np.any(np.diff(do) < 0) or np.any(np.diff(go) < 0):
+        raise _hip.HipPathError("ap_sweep: malformed problem offsets")
+    if T <= 0 or max(G, N) > 0x7FFFFFFF or T * (D + N) > 0x7FFFFFFF:
+        raise _hip.HipPathError("ap_sweep: no threshold, or tables past int32 entries")
+    caps = ap_sweep_caps()
+    if T > caps["thr"]:
+        raise ApSweepUnsupported("ap_sweep: %d thresholds are past the %d of mrcnn_ap_sweep" % (T, caps["thr"]))
+    if int(np.diff(do).max()) > caps["det"] or int(np.diff(go).max()) > caps["gt"]:
+        raise ApSweepUnsupported("ap_sweep: a problem of %d detections x %d ground truths is past the %d x %d of mrcnn_ap_sweep" % (
+            int(np.diff(do).max()), int(np.diff(go).max()), caps["det"], caps["gt"]))
+    dev = thr.device
+    tp = torch.empty((T * (D + N),), dtype=torch.int32, device=dev)
+    status = torch.empty((N,), dtype=torch.int32, device=dev)
+    off_t = torch.from_numpy(np.concatenate([do, go]).astype(np.int32)).to(dev)
+    tensors = [t.contiguous() for t in (det_box, gt_box, thr)]
+    check(_hip.lib().mrcnn_ap_sweep(ptr(tensors[0]) if D else None, off_t.data_ptr(), D, ptr(tensors[1]) if G else None,
+                                    off_t.data_ptr() + 4 * (N + 1), G, N, ptr(tensors[2]), T, ptr(tp), ptr(status), current_stream()),
+          "mrcnn_ap_sweep")
+    tp._keep = (off_t, tensors)               # alive until the caller has synchronised on the result
+    return tp, status
+
+
 class OutlineUnsupported(_hip.HipPathError):
     """A table past a cap of mrcnn_outline_* (include/mrcnn_hip.h: a source wider or higher than 8192 pixels, more than 65535
     sources, more than 2^22 contour segments in one source, int32 totals): the caller takes the host path."""

@@ -445,6 +445,42 @@ int mrcnn_voc_match(const double* det_box, const int32_t* det_cls, const double*
                     const double* gt_box, const int32_t* gt_cls, const int32_t* gt_off, int G, int I, const double* thr, int T,
                     int32_t* best_gt, double* best_iou, uint8_t* tp, void* stream);
 
+/* The matching step of the sweep mAP of the reference's second vendored tool (tarlen5-calculate-mean-ap/calculate.py:
+ * calc_iou_individual :40-77, get_single_image_results :80-139), for the N problems of a test set, flat, in one launch.  A problem is
+ * the detections of one image -- all of them or those of one class, ALREADY in ascending-score order -- against its ground truths:
+ * problem p owns detection rows det_off[p] .. det_off[p + 1] and ground-truth rows gt_off[p] .. gt_off[p + 1] (CSR, N + 1 entries
+ * each, 0 = off[0] <= ... <= off[N] = D resp. G -- the caller's contract; rows outside the tables are never touched).  Boxes
+ * [., 4] float64 corner boxes (c0, c1, c2, c3) with c0 <= c2 and c1 <= c3 (the tool raises on others; the caller checks), thr [T]
+ * float64, all > 0.  float64 in the tool's order of operations:
+ *   IoU     0 when t2 < p0, p2 < t0, t3 < p1 or p3 < t1 (p the detection, t the ground truth); else
+ *           inter = (min(t2, p2) - max(t0, p0) + 1) (min(t3, p3) - max(t1, p1) + 1), area = (c2 - c0 + 1) (c3 - c1 + 1),
+ *           iou = inter / (area_t + area_p - inter);
+ *   tp      int32, problem p at tp[T * (det_off[p] + p)], T rows of P + 1 entries (P = the problem's detections; T * (D + N) entries in
+ *           all): tp[t][k] = the matches of the tool's walk when detections k .. P - 1 are kept (a score threshold keeps a suffix
+ *           of the ascending order), tp[t][P] = 0.  The walk: the pairs (d >= k, g) with iou > thr[t], strictly, in descending IoU
+ *           -- among bit-equal IoUs the pair enumerated later (detection-major, ground-truth-minor) first, which is
+ *           np.argsort(ious, kind="stable")[::-1] where the tool leaves the order of equal keys to NumPy's unstable sort; a pair is
+ *           a match when neither its detection nor its ground truth is matched yet;
+ *   status  [N] int32: MRCNN_AP_SWEEP_OK; MRCNN_AP_SWEEP_OVER_CANDIDATES when more than MRCNN_AP_SWEEP_MAX_CAND pairs of the problem
+ *           lie above the smallest threshold (found on the device: the list is kept in LDS); MRCNN_AP_SWEEP_OVER_ROWS for a problem
+ *           of more than MRCNN_AP_SWEEP_MAX_DET detections or MRCNN_AP_SWEEP_MAX_GT ground truths.  The tp rows of a problem whose
+ *           status is not OK are zeros: the caller computes that problem, and only that, with the host statement.
+ * One workgroup of 256 lanes per problem, 62 KiB of LDS (two per CU): the pairs above the smallest threshold are collected, sorted
+ * by the unique key (IoU descending, pair descending) and walked once per (t, k) by a lane with its own bit sets.  No atomics on
+ * global memory, nothing allocated, bitwise the same from run to run.  N or T <= 0, D or G < 0: MRCNN_ERR_ARG;
+ * T > MRCNN_AP_SWEEP_MAX_THR: MRCNN_ERR_UNSUPPORTED, nothing launched.  mrcnn_ap_sweep_caps writes the four caps (detections,
+ * ground truths, thresholds, candidates) to caps[0 .. 3] (HOST pointer).                                                         */
+#define MRCNN_AP_SWEEP_MAX_DET 128      /* >= DETECTION_MAX_INSTANCES = 100 of the reference configuration */
+#define MRCNN_AP_SWEEP_MAX_GT 320       /* >= MAX_GT_INSTANCES = 300 */
+#define MRCNN_AP_SWEEP_MAX_THR 16
+#define MRCNN_AP_SWEEP_MAX_CAND 4096
+#define MRCNN_AP_SWEEP_OK 0
+#define MRCNN_AP_SWEEP_OVER_CANDIDATES 1
+#define MRCNN_AP_SWEEP_OVER_ROWS 2
+int mrcnn_ap_sweep_caps(int32_t* caps);
+int mrcnn_ap_sweep(const double* det_box, const int32_t* det_off, int D, const double* gt_box, const int32_t* gt_off, int G, int N,
+                   const double* thr, int T, int32_t* tp, int32_t* status, void* stream);
+
 /* detect() post-processing (MaskRCNN.unmold_detections, mrcnn/model.py:2607-2619; utils.unmold_mask, mrcnn/utils.py:629-645;
  * utils.resize -> skimage.transform.resize(order=1, mode='constant', cval=0, clip=True), mrcnn/utils.py:957-978): for each of
  * the n detections of ONE image, resize the class channel of its MH x MW mask to its integer pixel box (float64, half-pixel

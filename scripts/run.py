@@ -9,7 +9,8 @@ Same flag names and defaults; the model behind them is caesar_mrcnn_amd.model.Ma
 Multi-GPU training: ``torchrun --nproc-per-node NGPU scripts/run.py train --ngpu NGPU ...``.
 `test` reports completeness / reliability per class from mask-IoU matching, or with `--reference_tester` runs the reference's
 ModelTester (caesar_mrcnn_amd/analyze.py: confusion matrix, purity, completeness.csv and reliability.csv; with `--compute_map` also
-its compute_mAP: mask AP per image and the Pascal-VOC box AP / mAP, caesar_mrcnn_amd/metrics.py); `detect` runs the Analyzer
+its compute_mAP: mask AP per image and the Pascal-VOC box AP / mAP, and with `--sweep_map` the sweep over every score threshold
+and the mAP over IoU 0.50 ... 0.95 of its second metric tool, caesar_mrcnn_amd/metrics.py); `detect` runs the Analyzer
 post-processing (caesar_mrcnn_amd/analyze.py: score filter, connected-mask merging, best-of-overlapping
 selection) on every tile and writes the objects as JSON (`out_<image>.json`: image_id, objs[name, x1, x2,
 y1, y2, class_id, class_name, score, pixels, vertexes, edge]) and DS9 regions.  With `--draw` or `--detect_outfile NAME` it also
@@ -94,6 +95,10 @@ def parse_args(argv=None):
                         "Pascal-VOC box AP per class and mAP at IoU 0.5 and --iouThr (matched on the GPU)")
     p.add_argument('--map_outdir', type=str, default="",
                    help="with --compute_map: write the input files of the three external metric tools under this directory")
+    p.add_argument('--sweep_map', action='store_true', default=False,
+                   help="with --compute_map: also what the reference's second vendored tool (tarlen5-calculate-mean-ap) computes "
+                        "from the boxes -- average precision over every score threshold at IoU 0.50 ... 0.95, their mAP and the "
+                        "per-class APs at 0.5 and 0.6 -- printed as the tool prints them (matched on the GPU)")
     p.add_argument('--remap_classids', action='store_true', default=False)
     p.add_argument('--classid_remap_dict', type=str, default='', help='Dictionary used to remap detected classid to gt classid')
     p.add_argument('--consider_sources_near_mixed_sidelobes', dest='consider_sources_near_mixed_sidelobes', action='store_true',
@@ -132,6 +137,8 @@ def parse_args(argv=None):
         p.error("--compute_map / --map_outdir belong to `test --reference_tester`")
     if args.map_outdir and not args.compute_map:
         p.error("--map_outdir needs --compute_map")
+    if args.sweep_map and not args.compute_map:
+        p.error("--sweep_map needs --compute_map")
     return args
 
 
@@ -290,6 +297,7 @@ def test_reference(args, model, cfg):
     tester.draw = bool(getattr(args, "draw", False))
     tester.compute_mAP_metrics = bool(getattr(args, "compute_map", False))
     tester.metrics_outdir = getattr(args, "map_outdir", "") or None
+    tester.sweep_map = bool(getattr(args, "sweep_map", False))
     tester.test()
     return 0
 
