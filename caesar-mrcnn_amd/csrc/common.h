@@ -22,6 +22,9 @@ extern int g_mrcnn_wgrad_lds_pad;
 extern int g_mrcnn_h16_phase;
 extern int g_mrcnn_h16_slab;
 extern int g_mrcnn_sk16;
+//   sk64: the single-launch kernel for short-K 1 x 1 layers (conv_fwd_sk64_kernel): -1 (default) its measured window, 0 off (the
+//   two-launch split-K plan), 1 every shape its rules allow (tests, A/B).
+extern int g_mrcnn_sk64;
 //   proposal_skip_zero: tests only (fault injection): 1 suppresses the reset of the multi-workgroup top-k's counters.
 extern int g_mrcnn_proposal_skip_zero;
 //   outline_lds_segs: sources of at most this many contour segments are ranked in LDS by mrcnn_outline_emit, larger ones in the

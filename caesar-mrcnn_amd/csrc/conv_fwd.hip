@@ -1159,6 +1159,204 @@ __global__ __launch_bounds__(256, 4) void conv_fwd_sk16_kernel(const ConvArgs p,
     p.out[addr] = y;
 }
 
+// ---- short-K 1 x 1 layers: 64 x 64 tiles, four waves of 32 x 32 over the WHOLE K, the K slices kept as accumulators ------------------
+// res4 2c (M = 1 024, Cout = 1 024, K = 256) and the data gradient of res4 2a have 8 K-steps: nothing for conv_fwd_sk_kernel's four
+// waves to share, so the planner cut K into TWO slices over 256 workgroups and a second launch summed two slabs (13 + 7 us forward,
+// 30 + 32 us beside the weight-gradient stream).  Here one workgroup owns a 64 x 64 output tile, wave (wm, wn) its 32 x 32 quarter
+// over every K-step, streaming its own operands global -> LDS exactly as conv_fwd_sk_kernel does (two private 8 KiB stages, counted
+// vmcnt, no barrier in the K loop; 64 KiB per workgroup).  The wave keeps ONE ACCUMULATOR PER SLICE of the plan it replaces
+// (K-steps [0, ksteps) and [ksteps, nk)), issues the sixteen MFMAs of a K-step in conv_fwd_body's order (lanes 0-31 k = j, lanes
+// 32-63 k = 16 + j), and the tile is (0 + slice 0) + slice 1 as mrcnn_slab_sum adds the slabs: bit for bit the two-launch result,
+// without the slabs.  The partial tiles meet in LDS; every thread finishes four adjacent columns of four rows (one row of the tile
+// is 16 threads = 256 contiguous bytes) with the forward epilogue of conv_splitk_epilogue_vec_body or the backward epilogue of
+// conv_splitk_epilogue_bwd_kernel.  1 x 1, stride 1, no padding, Cin % 32 == 0, Cout % 64 == 0, dense NHWC.
+#define SK64_STAGE_BYTES 8192
+__global__ __launch_bounds__(256, 2) void conv_fwd_sk64_kernel(const ConvArgs p, const unsigned x_records) {
+    __shared__ __attribute__((aligned(16))) char lds[4 * 2 * SK64_STAGE_BYTES];     // 64 KiB: 4 waves x 2 stages x (A 4 KiB + B 4 KiB)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ntiles = p.Cout >> 6;
+    const int mtile = blockIdx.x / ntiles, ntile = blockIdx.x - mtile * ntiles;
+    const int m0 = mtile * 64, n0 = ntile * 64;
+    const int mw = m0 + (wave >> 1) * 32, nw = n0 + (wave & 1) * 32;             // this wave's quarter
+    char* my = lds + wave * (2 * SK64_STAGE_BYTES);
+
+    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_records, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_b =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + nw), 0, (unsigned)(((long long)p.Ktot * p.Cout - nw) * 4), 0x00020000);
+
+    // A: 4 pieces of 8 rows x 128 B; lane -> row 8 j + (lane >> 3), physical chunk lane & 7.  Rows past M read zeros.
+    unsigned a_voff[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int r = j * 8 + (lane >> 3);
+        const int cl = (lane & 7) ^ ((r >> 1) & 7);
+        const int m = mw + r;
+        a_voff[j] = m < p.M ? (unsigned)(((long long)m * p.Cin + cl * 4) * 4) : CONV_OOB_OFFSET;
+    }
+    // B: 4 pieces of 8 k-rows x 128 B (32 columns): lane -> k-row 8 j + (lane >> 3), chunk lane & 7 (no swizzle: b32 reads)
+    const unsigned b_voff = (unsigned)(((lane >> 3) * p.Cout + (lane & 7) * 4) * 4);
+    auto stage = [&](char* buf, int ks) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (conv_lds_ptr)(buf + j * 1024), 16, a_voff[j], (unsigned)(ks * 128), 0, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (conv_lds_ptr)(buf + 4096 + j * 1024), 16, b_voff,
+                                                     (unsigned)(((ks * 32 + j * 8) * p.Cout) * 4), 0, 0);
+    };
+
+    // Everything the epilogue reads besides the accumulators does not depend on them: those loads go out FIRST, ahead of the
+    // operand stream (loads return in order, so the counted vmcnt below covers them), and cost the epilogue no round trip.
+    // This thread finishes columns [n, n + 4) of rows m0 + (tid >> 4) + 16 i; rows past M are clamped here and skipped there.
+    // Forward: c_a / c_b / c_c = bias / scale / shift;  data gradient: scale / mean / rstd of the layer below.
+    const int c4 = (tid & 15) * 4, n = n0 + c4;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f}, one4 = {1.f, 1.f, 1.f, 1.f};
+    f32x4 e_res[4], e_out[4], e_z[4], c_a, c_b, c_c;
+    if (p.fb_act < 0) {
+        c_a = p.bias ? *(const f32x4*)(p.bias + n) : zero4;
+        c_b = p.scale ? *(const f32x4*)(p.scale + n) : one4;
+        c_c = p.scale ? *(const f32x4*)(p.shift + n) : zero4;
+    } else {
+        c_a = p.fb_scale ? *(const f32x4*)(p.fb_scale + n) : one4;
+        c_b = p.fb_dgamma ? *(const f32x4*)(p.fb_mean + n) : zero4;
+        c_c = p.fb_dgamma ? *(const f32x4*)(p.fb_rstd + n) : zero4;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int m = m0 + (tid >> 4) + 16 * i;
+        if (m > p.M - 1) m = p.M - 1;
+        const long long addr = (long long)m * p.Cout + n;
+        e_res[i] = p.res_mode != MRCNN_RES_NONE ? *(const f32x4*)(p.res + addr) : zero4;
+        e_out[i] = p.fb_act == MRCNN_ACT_RELU ? *(const f32x4*)(p.fb_out + addr) : zero4;
+        e_z[i] = (p.fb_act >= 0 && p.fb_dgamma) ? *(const f32x4*)(p.fb_z + addr) : zero4;
+    }
+
+    f32x16 acc0, acc1;                                           // slice 0: K-steps [0, ksteps); slice 1: [ksteps, nk)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+    const int li = lane & 31, lh = lane >> 5;
+    int a_rd[4];
+#pragma unroll
+    for (int t4 = 0; t4 < 4; ++t4) a_rd[t4] = li * 128 + (((lh * 4 + t4) ^ ((li >> 1) & 7)) << 4);
+    const int b_rd = 4096 + lh * 16 * 128 + li * 4;
+    auto compute = [&](const char* buf, f32x16& acc) {
+#pragma unroll
+        for (int t4 = 0; t4 < 4; ++t4) {
+            const f32x4 av = *(const f32x4*)(buf + a_rd[t4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float bv = *(const float*)(buf + b_rd + (t4 * 4 + e) * 128);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bv, acc, 0, 0, 0);
+            }
+        }
+    };
+    const int nk = p.nk;
+    stage(my, 0);
+    int slot = 0;
+    for (int i = 0; i < nk; ++i) {
+        if (i + 1 < nk) {
+            stage(my + (slot ^ 1) * SK64_STAGE_BYTES, i + 1);     // its previous content (step i - 1) has been consumed
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // 8 DMA instructions per stage: step i + 1 stays in flight
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        if (i < p.ksteps) compute(my + slot * SK64_STAGE_BYTES, acc0);
+        else compute(my + slot * SK64_STAGE_BYTES, acc1);
+        slot ^= 1;
+    }
+
+    // ---- the partial tiles meet in LDS: [wave][slice][row 32][col 32] ------------------------------------------------------------
+    __syncthreads();                                             // every wave is done with its stages
+    float* part = (float*)lds;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int e = (4 * lh + (r & 3) + 8 * (r >> 2)) * 32 + li;
+        part[wave * 2048 + e] = acc0[r];
+        part[wave * 2048 + 1024 + e] = acc1[r];
+    }
+    float* sums = part + 4 * 2048;                               // [3][64] column sums of this workgroup (behind the partial tiles)
+    if (p.fb_act >= 0 && tid < 192) sums[tid] = 0.f;
+    __syncthreads();
+    const int pw = (c4 >> 5) * 2048 + (c4 & 31);                 // column part of the address in `part`
+    f32x4 v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = (tid >> 4) + 16 * i;
+        const float* q = part + (row >> 5) * 4096 + (row & 31) * 32 + pw;
+        const f32x4 s0 = *(const f32x4*)q, s1 = *(const f32x4*)(q + 1024);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[i][e] = (0.f + s0[e]) + s1[e];   // mrcnn_slab_sum's order
+    }
+    if (p.fb_act < 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = m0 + (tid >> 4) + 16 * i;
+            if (m >= p.M) continue;
+            const long long addr = (long long)m * p.Cout + n;
+            f32x4 zv, y;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) zv[e] = v[i][e] + c_a[e];
+            if (p.z) *(f32x4*)(p.z + addr) = zv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) y[e] = c_b[e] * zv[e] + c_c[e];
+            if (p.res_mode != MRCNN_RES_NONE) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[e] += e_res[i][e];
+            }
+            if (p.act == MRCNN_ACT_RELU) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[e] = fmaxf(y[e], 0.f);
+            } else if (p.act == MRCNN_ACT_SIGMOID) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[e] = 1.f / (1.f + expf(-y[e]));
+            }
+            *(f32x4*)(p.out + addr) = y;
+        }
+        return;
+    }
+    // ---- data gradient: y = v (+ res) is d(loss)/d(out_below); apply that layer's epilogue backward ---------------------------------
+    f32x4 a_db = zero4, a_dg = zero4, a_bias = zero4;            // this thread's four rows, then LDS, then one atomic per channel
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int m = m0 + (tid >> 4) + 16 * i;
+        if (m >= p.M) continue;
+        const long long addr = (long long)m * p.Cout + n;
+        f32x4 g = v[i];
+        if (p.res_mode != MRCNN_RES_NONE) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) g[e] += e_res[i][e];
+        }
+        if (p.fb_act == MRCNN_ACT_RELU) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) g[e] = e_out[i][e] > 0.f ? g[e] : 0.f;
+        }
+        f32x4 dz;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dz[e] = g[e] * c_a[e];
+        *(f32x4*)(p.out + addr) = dz;
+        if (p.fb_dy) *(f32x4*)(p.fb_dy + addr) = g;
+        if (p.fb_dgamma) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a_dg[e] += g[e] * (e_z[i][e] - c_b[e]) * c_c[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { a_db[e] += g[e]; a_bias[e] += dz[e]; }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (p.fb_dbeta || p.fb_dgamma) atomicAdd(&sums[c4 + e], a_db[e]);
+        if (p.fb_dgamma) atomicAdd(&sums[64 + c4 + e], a_dg[e]);
+        if (p.fb_dbias) atomicAdd(&sums[128 + c4 + e], a_bias[e]);
+    }
+    __syncthreads();
+    if (tid < 64) {
+        if (p.fb_dbeta) atomicAdd(p.fb_dbeta + n0 + tid, sums[tid]);
+        if (p.fb_dgamma) atomicAdd(p.fb_dgamma + n0 + tid, sums[64 + tid]);
+        if (p.fb_dbias) atomicAdd(p.fb_dbias + n0 + tid, sums[128 + tid]);
+    }
+}
+
 static long long sk_max_tiles() { static const long long v = getenv("MRCNN_SK_MAX_TILES") ? atoll(getenv("MRCNN_SK_MAX_TILES")) : 512; return v; }
 // applicability window, measured (ResNet-101, layer loops and whole steps): 192 .. 512 tiles of 32 x 32 and >= 16 K-steps.
 // Fewer tiles (batch-1 detect: 64) leave three quarters of the SIMDs without a wave -- the old split over 16 K slices
@@ -1170,15 +1368,40 @@ static int sk_min_steps() { static const int v = getenv("MRCNN_SK_MIN_STEPS") ? 
 // Shapes the single-launch kernel takes: a "fast" layer (Cin % 32 == 0), Cout % 32 == 0, dense NHWC output and residual,
 // 16-byte aligned operands, at most 64 taps, buffer-addressable tensors -- and small enough that the large-tile kernels
 // would not fill the chip (the caller decides that part).
-static bool conv_sk_ok(const mrcnn_conv_desc* d, const ConvArgs& a) {
-    static const bool on = !(getenv("MRCNN_SK_KERNEL") && getenv("MRCNN_SK_KERNEL")[0] == '0');
+static bool conv_sk_shape_ok(const mrcnn_conv_desc* d, const ConvArgs& a) {
     auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (!on || !a.fastA || !a.dense || d->Cout % 32 || d->out_mode != MRCNN_OUT_NHWC || d->res_mode == MRCNN_RES_UP2) return false;
+    if (!a.fastA || !a.dense || d->Cout % 32 || d->out_mode != MRCNN_OUT_NHWC || d->res_mode == MRCNN_RES_UP2) return false;
     if (d->KH * d->KW > 64) return false;
     const long long xb = (long long)d->N * d->H * d->W * d->Cin * 4 + ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
     if (xb >= 0x7FFFFFF0LL || (long long)a.Ktot * d->Cout * 4 >= 0x7FFFFFF0LL) return false;
     return al(a.w) && al(a.out) && al(a.z) && al(a.res) && al(a.bias) && al(a.scale) && al(a.shift) && al(a.fb_out) && al(a.fb_z) &&
            al(a.fb_scale) && al(a.fb_mean) && al(a.fb_rstd) && al(a.fb_dy);
+}
+
+static bool conv_sk_ok(const mrcnn_conv_desc* d, const ConvArgs& a) {
+    static const bool on = !(getenv("MRCNN_SK_KERNEL") && getenv("MRCNN_SK_KERNEL")[0] == '0');
+    return on && conv_sk_shape_ok(d, a);
+}
+
+// Window of conv_fwd_sk64_kernel in workgroups (64 x 64 tiles): 64 .. 512, the range measured with tools/trunk_layer_bench.py
+// --shortk (Cout = 1024, K = 256; pair -> one launch, forward / data gradient with the backward epilogue, alone):
+//   M =  256 ( 64 workgroups) 10.9 ->  9.6 us / 17.7 -> 13.9 us      M = 1024 (256) 17.8 -> 10.4 us / 24.8 -> 14.9 us
+//   M =  512 (128)            12.0 ->  9.8 us / 18.8 -> 14.2 us      M = 2048 (512) 26.0 -> 16.2 us / 36.3 -> 26.1 us
+// Smaller and larger grids are not measured and stay on the pair.  mrcnn_tuning_set("sk64", 1) lifts the window, 0 and
+// MRCNN_SK64_KERNEL=0 (read once) restore the two-launch plan.
+static long long sk64_min_wgs() { static const long long v = getenv("MRCNN_SK64_MIN_WGS") ? atoll(getenv("MRCNN_SK64_MIN_WGS")) : 64; return v; }
+static long long sk64_max_wgs() { static const long long v = getenv("MRCNN_SK64_MAX_WGS") ? atoll(getenv("MRCNN_SK64_MAX_WGS")) : 512; return v; }
+
+// Shapes conv_fwd_sk64_kernel takes in place of a TWO-slice split-K plan: 1 x 1, stride 1, no padding, Cout % 64 == 0, a K too
+// short for conv_fwd_sk_kernel (fewer K-steps than its four waves need), and everything conv_sk_shape_ok asks.
+static bool conv_sk64_ok(const mrcnn_conv_desc* d, const ConvArgs& a, int plan_ksplit, bool plan_dma_split) {
+    static const bool on = !(getenv("MRCNN_SK64_KERNEL") && getenv("MRCNN_SK64_KERNEL")[0] == '0');
+    if (!on || g_mrcnn_sk64 == 0 || plan_ksplit != 2 || plan_dma_split) return false;
+    if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad_t || d->pad_l || d->OH != d->H || d->OW != d->W) return false;
+    if (!a.vecB || d->Cout % 64 || d->cmod != d->Cout || a.nk >= sk_min_steps() || !conv_sk_shape_ok(d, a)) return false;
+    if (g_mrcnn_sk64 == 1) return true;
+    const long long wgs = (long long)((a.M + 63) / 64) * (d->Cout / 64);
+    return wgs >= sk64_min_wgs() && wgs <= sk64_max_wgs();
 }
 
 static void launch_splitk_reduction(const ConvArgs& a, hipStream_t s);
@@ -1423,6 +1646,14 @@ static int conv_fwd_impl(const mrcnn_conv_desc* d, const float* x, const float* 
             hipLaunchKernelGGL(conv_fwd_sk16_kernel, dim3((unsigned)t16), dim3(256), 0, s, a, (unsigned)shift, (unsigned)(xbytes + shift));
             return mrcnn_launch_status();
         }
+    }
+    // short-K 1 x 1 layer on a two-slice plan (res4 2c, the data gradient of res4 2a): one launch, the two slices as accumulators;
+    // a.ksteps stays the plan's slice boundary.  With a backward epilogue this point is reached only where split_ok held.
+    if (conv_sk64_ok(d, a, pl.ksplit, pl.dma_split)) {
+        a.slab = nullptr;
+        hipLaunchKernelGGL(conv_fwd_sk64_kernel, dim3((unsigned)(((a.M + 63) / 64) * (d->Cout / 64))), dim3(256), 0, s, a,
+                           (unsigned)((long long)a.M * d->Cin * 4));
+        return mrcnn_launch_status();
     }
     if (pl.ksplit > 1 && !pl.dma_split && conv_sk_ok(d, a) && (long long)((a.M + 31) / 32) * (d->Cout / 32) <= sk_max_tiles() &&
         (long long)((a.M + 31) / 32) * (d->Cout / 32) >= sk_min_tiles() && a.nk >= sk_min_steps()) {

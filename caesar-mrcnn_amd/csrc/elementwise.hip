@@ -622,6 +622,8 @@ int g_mrcnn_h16_slab = -1;               // -1: MRCNN_H16_SLAB decides (default 
 int g_mrcnn_proposal_skip_zero = 0;
 int g_mrcnn_sk16 = 0;                    // 1 while the inference graph is issued (engine.infer): the 16 x 16-tile small-layer kernel may be picked
 
+int g_mrcnn_sk64 = -1;                   // -1: default window of conv_fwd_sk64_kernel; 0: off; 1: every shape it can take (tests, A/B)
+
 extern "C" int mrcnn_tuning_set(const char* key, long long value) {
     if (!key) return MRCNN_ERR_ARG;
     if (!strcmp(key, "wgrad_lds_pad")) {
@@ -642,6 +644,11 @@ extern "C" int mrcnn_tuning_set(const char* key, long long value) {
     if (!strcmp(key, "sk16")) {
         if (value < 0 || value > 1) return MRCNN_ERR_ARG;
         g_mrcnn_sk16 = (int)value;
+        return MRCNN_OK;
+    }
+    if (!strcmp(key, "sk64")) {
+        if (value < -1 || value > 1) return MRCNN_ERR_ARG;
+        g_mrcnn_sk64 = (int)value;
         return MRCNN_OK;
     }
     if (!strcmp(key, "proposal_skip_zero")) {

@@ -3,11 +3,15 @@
 // K.binary_crossentropy semantics are [3P] Keras 2.2.4 + TF 1.13).
 //
 //   phase 1 (reduce): per-image RPN pass (ordered rank of positive anchors == batch_pack_graph order)
-//                     and per-ROI head pass; block sums -> float atomics on 16 scalars.
+//                     and per-ROI head pass; every workgroup stores its block sums, and one workgroup adds them
+//                     into the 16 scalars in a fixed order (loss_finalize_kernel): the same inputs give the same
+//                     five losses bit for bit, run after run (float atomics on the scalars did not).
 //   phase 2 (grads):  elementwise passes that read the scalars (means) and write dense gradients.
 #include "common.h"
 
 enum { S_RC_SUM = 0, S_RC_CNT, S_RB_SUM, S_RB_CNT, S_C_SUM, S_C_PA, S_B_SUM, S_POS, S_M_SUM, S_D_Y, S_D_P, S_NUM = 16 };
+
+enum { PART_RPN = 4, PART_HEADS = 7 };
 
 struct LossArgs {
     const int32_t* rpn_match; const float* rpn_bbox_t; const float* rpn_logits; const float* rpn_bbox;
@@ -15,6 +19,8 @@ struct LossArgs {
     const float* cls_logits; const float* mbbox; const float* mmask;
     float* losses; float* d_rpn_logits; float* d_rpn_bbox; float* d_cls_logits; float* d_mbbox; float* d_mmask;
     float* scal; int32_t* rank;
+    float* part_rpn;                   // [B][PART_RPN] block sums of rpn_loss_reduce_kernel
+    float* part_heads;                 // [B * T][PART_HEADS] block sums of heads_loss_reduce_kernel
     int B, A, T, C, mh, mw, max_rpn_pos, dice;
     float w0, w1, w2, w3, w4;
 };
@@ -118,8 +124,8 @@ __global__ __launch_bounds__(1024) void rpn_loss_reduce_kernel(const LossArgs p)
     csum = block_sum(csum, sbuf); ccnt = block_sum(ccnt, sbuf);
     bsum = block_sum(bsum, sbuf); bcnt = block_sum(bcnt, sbuf);
     if (tid == 0) {
-        atomicAdd(&p.scal[S_RC_SUM], csum); atomicAdd(&p.scal[S_RC_CNT], ccnt);
-        atomicAdd(&p.scal[S_RB_SUM], bsum); atomicAdd(&p.scal[S_RB_CNT], bcnt);
+        float* o = p.part_rpn + b * PART_RPN;                    // S_RC_SUM, S_RC_CNT, S_RB_SUM, S_RB_CNT
+        o[0] = csum; o[1] = ccnt; o[2] = bsum; o[3] = bcnt;
     }
 }
 
@@ -129,6 +135,7 @@ __global__ __launch_bounds__(256) void heads_loss_reduce_kernel(const LossArgs p
     const int64_t row = blockIdx.x;
     const int tid = threadIdx.x, C = p.C;
     const int cls = p.tcls[row];
+    float* o = p.part_heads + row * PART_HEADS;          // S_C_SUM, S_C_PA, S_B_SUM, S_POS, S_M_SUM, S_D_Y, S_D_P of this row
     if (tid == 0) {
         const float* l = p.cls_logits + row * C;
         float mx = l[0];
@@ -138,13 +145,14 @@ __global__ __launch_bounds__(256) void heads_loss_reduce_kernel(const LossArgs p
         for (int c = 0; c < C; ++c) s += expf(l[c] - mx);
         const float ce = (mx + logf(s)) - l[cls];
         const float pa = (float)p.active[am];            // active_class_ids[0] (model.py:1182)
-        atomicAdd(&p.scal[S_C_SUM], ce * pa);
-        atomicAdd(&p.scal[S_C_PA], pa);
+        o[0] = ce * pa;
+        o[1] = pa;
+        o[2] = 0.f; o[3] = 0.f; o[4] = 0.f; o[5] = 0.f; o[6] = 0.f;
         if (cls > 0) {
             const float* t = p.tbbox + row * 4;
             const float* q = p.mbbox + (row * C + cls) * 4;
-            atomicAdd(&p.scal[S_B_SUM], smooth_l1(t[0], q[0]) + smooth_l1(t[1], q[1]) + smooth_l1(t[2], q[2]) + smooth_l1(t[3], q[3]));
-            atomicAdd(&p.scal[S_POS], 1.f);
+            o[2] = smooth_l1(t[0], q[0]) + smooth_l1(t[1], q[1]) + smooth_l1(t[2], q[2]) + smooth_l1(t[3], q[3]);
+            o[3] = 1.f;
         }
     }
     if (cls <= 0) return;
@@ -164,9 +172,38 @@ __global__ __launch_bounds__(256) void heads_loss_reduce_kernel(const LossArgs p
     }
     ms = block_sum(ms, sbuf);
     if (p.dice) { sy = block_sum(sy, sbuf); sp = block_sum(sp, sbuf); }
+    if (tid == 0) {                                      // the same thread wrote the zeros above
+        o[4] = ms;
+        if (p.dice) { o[5] = sy; o[6] = sp; }
+    }
+}
+
+// ---- phase 1c: the block sums into the 16 scalars, in a fixed order ---------------------------------------------------
+// One workgroup: thread t adds rows t, t + 256, ... in ascending order, then the fixed tree of block_sum.  Sets every scalar
+// (no zeroing launch before the reduce kernels).
+__global__ __launch_bounds__(256) void loss_finalize_kernel(const LossArgs p) {
+    __shared__ float sbuf[4];
+    const int tid = threadIdx.x;
+    float r[PART_RPN], h[PART_HEADS];
+#pragma unroll
+    for (int j = 0; j < PART_RPN; ++j) r[j] = 0.f;
+#pragma unroll
+    for (int j = 0; j < PART_HEADS; ++j) h[j] = 0.f;
+    for (int b = tid; b < p.B; b += 256)
+#pragma unroll
+        for (int j = 0; j < PART_RPN; ++j) r[j] += p.part_rpn[b * PART_RPN + j];
+    const int64_t rows = (int64_t)p.B * p.T;
+    for (int64_t row = tid; row < rows; row += 256)
+#pragma unroll
+        for (int j = 0; j < PART_HEADS; ++j) h[j] += p.part_heads[row * PART_HEADS + j];
+#pragma unroll
+    for (int j = 0; j < PART_RPN; ++j) r[j] = block_sum(r[j], sbuf);
+#pragma unroll
+    for (int j = 0; j < PART_HEADS; ++j) h[j] = block_sum(h[j], sbuf);
     if (tid == 0) {
-        atomicAdd(&p.scal[S_M_SUM], ms);
-        if (p.dice) { atomicAdd(&p.scal[S_D_Y], sy); atomicAdd(&p.scal[S_D_P], sp); }
+        p.scal[S_RC_SUM] = r[0]; p.scal[S_RC_CNT] = r[1]; p.scal[S_RB_SUM] = r[2]; p.scal[S_RB_CNT] = r[3];
+        p.scal[S_C_SUM] = h[0]; p.scal[S_C_PA] = h[1]; p.scal[S_B_SUM] = h[2]; p.scal[S_POS] = h[3];
+        p.scal[S_M_SUM] = h[4]; p.scal[S_D_Y] = h[5]; p.scal[S_D_P] = h[6];
     }
 }
 
@@ -264,13 +301,10 @@ __global__ __launch_bounds__(256) void heads_loss_grad_kernel(const LossArgs p) 
     }
 }
 
-__global__ void loss_zero_kernel(float* p, int n) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0.f;
-}
-
 extern "C" size_t mrcnn_losses_workspace(const mrcnn_loss_desc* d) {
     if (!d || d->B <= 0 || d->A <= 0) return 0;
-    return 256 + S_NUM * sizeof(float) + (size_t)d->B * d->A * sizeof(int32_t);
+    const size_t parts = (size_t)d->B * PART_RPN + (size_t)d->B * (d->T > 0 ? d->T : 0) * PART_HEADS;
+    return 256 + S_NUM * sizeof(float) + (size_t)d->B * d->A * sizeof(int32_t) + parts * sizeof(float);
 }
 
 extern "C" int mrcnn_losses_fwd_bwd(const mrcnn_loss_desc* d, const int32_t* rpn_match, const float* rpn_bbox_t,
@@ -297,15 +331,15 @@ extern "C" int mrcnn_losses_fwd_bwd(const mrcnn_loss_desc* d, const int32_t* rpn
     uintptr_t base = (reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255;
     a.scal = reinterpret_cast<float*>(base);
     a.rank = reinterpret_cast<int32_t*>(base + S_NUM * sizeof(float));
+    a.part_rpn = reinterpret_cast<float*>(a.rank + (size_t)d->B * d->A);
+    a.part_heads = a.part_rpn + (size_t)d->B * PART_RPN;
     a.B = d->B; a.A = d->A; a.T = d->T; a.C = d->C; a.mh = d->mask_h; a.mw = d->mask_w;
     a.max_rpn_pos = d->max_rpn_pos; a.dice = d->mask_loss_dice;
     a.w0 = d->w[0]; a.w1 = d->w[1]; a.w2 = d->w[2]; a.w3 = d->w[3]; a.w4 = d->w[4];
     hipStream_t s = (hipStream_t)stream;
-    // a kernel, not hipMemsetAsync: this call sits inside captured training steps, and a captured memset node writes a
-    // garbage value from the second replay on (ROCm 7.2; tools/graph_memset_probe.py)
-    hipLaunchKernelGGL(loss_zero_kernel, dim3(1), dim3(64), 0, s, a.scal, S_NUM);
     hipLaunchKernelGGL(rpn_loss_reduce_kernel, dim3(d->B), dim3(1024), 0, s, a);
     hipLaunchKernelGGL(heads_loss_reduce_kernel, dim3((unsigned)(d->B * d->T)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, a);
     const int64_t na = (int64_t)d->B * d->A;
     hipLaunchKernelGGL(rpn_loss_grad_kernel, dim3((unsigned)cdiv64(na, 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(heads_loss_grad_kernel, dim3((unsigned)(d->B * d->T)), dim3(256), 0, s, a);
