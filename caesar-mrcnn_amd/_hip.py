@@ -152,6 +152,11 @@ _SIGNATURES = {
     "mrcnn_fits_tiles_workspace": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
     "mrcnn_fits_tiles_to_rgb": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_double), _P, C.c_size_t, _P,
                                           C.c_size_t, _P]),
+    "mrcnn_mosaic_overview_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double]),
+    "mrcnn_mosaic_overview_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "mrcnn_mosaic_overview": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "mrcnn_sources_to_planes_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mrcnn_sources_to_planes": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mrcnn_catalog_check": (C.c_int, [C.c_int]),
     "mrcnn_catalog_count": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, _P, _P, _P]),
     "mrcnn_catalog_fill": (C.c_int, [_P] * 6 + [C.c_int, C.c_double, C.c_double, _P, C.c_longlong, _P, _P, _P]),
@@ -230,7 +235,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
+_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_overview_check", "_planes_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
 
 
 class _LibProxy(object):

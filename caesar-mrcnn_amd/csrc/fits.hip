@@ -17,6 +17,10 @@
 // lanes = consecutive pixels of a row: a wavefront's loads stay in one row segment, two at a row end) and leaves the tile's
 // native-endian values row-major and contiguous in the workspace, so the sampling and the pixel pass address a tile exactly as
 // the single-tile path does -- the bodies below are shared, not copied.
+//
+// mrcnn_mosaic_overview (at the end of this file) stretches a WHOLE plane of any size up to 2^31 - 1 pixels and shrinks it by
+// block maxima: the same statistics per 1024-pixel chunk, a two-level scan of the chunks' finite counts instead of the one LDS
+// table, the sampling from the plane where it lies (no native-endian copy), then fits_zscale_fit and fits_byte as above.
 #include "common.h"
 #include <math.h>
 
@@ -107,79 +111,14 @@ __device__ __forceinline__ float fits_stretch(float v, const FitsChannel& c) {
     return (float)o;
 }
 
-// sampling, sort, iterative fit and limits of one tile: ONE workgroup of 1024 threads
-__device__ __forceinline__ void fits_zscale_body(const float* __restrict__ vals, long long n, int nchunks,
-                                                 const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
-                                                 FitsParams* __restrict__ params) {
-    __shared__ int s_prefix[FITS_MAX_CHUNKS + 1];
-    __shared__ float s_samp[1024];
-    __shared__ double s_red[1024];
+// Sort, iterative fit and limits of the npix samples in s_samp[0 .. npix) (+inf in s_samp[npix .. 1024)): the part of
+// ZScaleInterval.get_limits after the sampling, for ONE workgroup of 1024 threads; every thread passes the same npix, fill and
+// dmax (the plane's maximum).  s_samp and s_red are the caller's LDS arrays of 1024 entries; the caller has synchronised after
+// writing s_samp.  Shared by the tile chain and the mosaic overview.
+__device__ __forceinline__ void fits_zscale_fit(float* s_samp, double* s_red, int npix, float fill, float dmax, double c0, double c1,
+                                                double c2, FitsParams* __restrict__ params) {
     __shared__ unsigned char s_bad[1024], s_bad2[1024];
     const int tid = threadIdx.x;
-    // ---- global min / max / counts ------------------------------------------------------------------------------------
-    float mn = INFINITY, mx = -INFINITY;
-    int nn = 0;
-    for (int k = tid; k < nchunks; k += 1024) {
-        const FitsChunk c = chunks[k];
-        mn = fminf(mn, c.mn); mx = fmaxf(mx, c.mx); nn += c.n_nan;
-    }
-    s_samp[tid] = mn;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) { if (tid < s) s_samp[tid] = fminf(s_samp[tid], s_samp[tid + s]); __syncthreads(); }
-    const float fill = s_samp[0];                       // np.nanmin(out): +inf only when every pixel is NaN
-    __syncthreads();
-    s_samp[tid] = mx;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) { if (tid < s) s_samp[tid] = fmaxf(s_samp[tid], s_samp[tid + s]); __syncthreads(); }
-    const float dmax = s_samp[0];
-    __syncthreads();
-    const long long total_nan = (long long)fits_block_sum((double)nn, s_red, tid);
-    if (total_nan == n) {                               // nothing to scale: the host gets NaN everywhere (uint8 of NaN: 0)
-        if (tid == 0) { params->all_nan = 1; params->fill = fill; }
-        return;
-    }
-    const bool fill_finite = !isinf(fill);
-    // ---- finite pixels per chunk, exclusive prefix ------------------------------------------------------------------------
-    for (int k = tid; k < nchunks; k += 1024) {
-        const long long left = n - (long long)k * FITS_CHUNK;
-        const int size = left < FITS_CHUNK ? (int)left : FITS_CHUNK;
-        s_prefix[k + 1] = size - chunks[k].n_inf - (fill_finite ? 0 : chunks[k].n_nan);
-    }
-    if (tid == 0) s_prefix[0] = 0;
-    __syncthreads();
-    if (tid == 0) for (int k = 0; k < nchunks; ++k) s_prefix[k + 1] += s_prefix[k];     // <= 4096 adds: microseconds
-    __syncthreads();
-    const long long nfinite = s_prefix[nchunks];
-    int npix = 0, stride = 1;
-    if (nfinite > 0) {
-        stride = (int)fmax(1.0, (double)nfinite / (double)FITS_NSAMPLES);
-        const long long avail = (nfinite + stride - 1) / stride;
-        npix = avail < FITS_NSAMPLES ? (int)avail : FITS_NSAMPLES;
-    }
-    // ---- values[isfinite][::stride][:nsamples] ---------------------------------------------------------------------------
-    float sv = INFINITY;
-    if (tid < npix) {
-        const long long rank = (long long)tid * stride;
-        int lo = 0, hi = nchunks;                       // last chunk with prefix <= rank
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_prefix[mid] <= rank) lo = mid; else hi = mid; }
-        int need = (int)(rank - s_prefix[lo]);
-        const long long base = (long long)lo * FITS_CHUNK;
-        const long long left = n - base;
-        const int size = left < FITS_CHUNK ? (int)left : FITS_CHUNK;
-        if (s_prefix[lo + 1] - s_prefix[lo] == size) {
-            float v = vals[base + need];
-            sv = v != v ? fill : v;
-        } else {
-            for (int k = 0; k < size; ++k) {
-                float v = vals[base + k];
-                if (v != v) v = fill;
-                if (isinf(v)) continue;
-                if (need-- == 0) { sv = v; break; }
-            }
-        }
-    }
-    s_samp[tid] = sv;
-    __syncthreads();
     // ---- bitonic sort, ascending; the +inf padding ends up behind the npix samples ----------------------------------------
     for (int k = 2; k <= 1024; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -267,10 +206,92 @@ __device__ __forceinline__ void fits_zscale_body(const float* __restrict__ vals,
     }
 }
 
+// sampling, sort, iterative fit and limits of one tile: ONE workgroup of 1024 threads
+__device__ __forceinline__ void fits_zscale_body(const float* __restrict__ vals, long long n, int nchunks,
+                                                 const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
+                                                 FitsParams* __restrict__ params) {
+    __shared__ int s_prefix[FITS_MAX_CHUNKS + 1];
+    __shared__ float s_samp[1024];
+    __shared__ double s_red[1024];
+    const int tid = threadIdx.x;
+    // ---- global min / max / counts ------------------------------------------------------------------------------------
+    float mn = INFINITY, mx = -INFINITY;
+    int nn = 0;
+    for (int k = tid; k < nchunks; k += 1024) {
+        const FitsChunk c = chunks[k];
+        mn = fminf(mn, c.mn); mx = fmaxf(mx, c.mx); nn += c.n_nan;
+    }
+    s_samp[tid] = mn;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) { if (tid < s) s_samp[tid] = fminf(s_samp[tid], s_samp[tid + s]); __syncthreads(); }
+    const float fill = s_samp[0];                       // np.nanmin(out): +inf only when every pixel is NaN
+    __syncthreads();
+    s_samp[tid] = mx;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) { if (tid < s) s_samp[tid] = fmaxf(s_samp[tid], s_samp[tid + s]); __syncthreads(); }
+    const float dmax = s_samp[0];
+    __syncthreads();
+    const long long total_nan = (long long)fits_block_sum((double)nn, s_red, tid);
+    if (total_nan == n) {                               // nothing to scale: the host gets NaN everywhere (uint8 of NaN: 0)
+        if (tid == 0) { params->all_nan = 1; params->fill = fill; }
+        return;
+    }
+    const bool fill_finite = !isinf(fill);
+    // ---- finite pixels per chunk, exclusive prefix ------------------------------------------------------------------------
+    for (int k = tid; k < nchunks; k += 1024) {
+        const long long left = n - (long long)k * FITS_CHUNK;
+        const int size = left < FITS_CHUNK ? (int)left : FITS_CHUNK;
+        s_prefix[k + 1] = size - chunks[k].n_inf - (fill_finite ? 0 : chunks[k].n_nan);
+    }
+    if (tid == 0) s_prefix[0] = 0;
+    __syncthreads();
+    if (tid == 0) for (int k = 0; k < nchunks; ++k) s_prefix[k + 1] += s_prefix[k];     // <= 4096 adds: microseconds
+    __syncthreads();
+    const long long nfinite = s_prefix[nchunks];
+    int npix = 0, stride = 1;
+    if (nfinite > 0) {
+        stride = (int)fmax(1.0, (double)nfinite / (double)FITS_NSAMPLES);
+        const long long avail = (nfinite + stride - 1) / stride;
+        npix = avail < FITS_NSAMPLES ? (int)avail : FITS_NSAMPLES;
+    }
+    // ---- values[isfinite][::stride][:nsamples] ---------------------------------------------------------------------------
+    float sv = INFINITY;
+    if (tid < npix) {
+        const long long rank = (long long)tid * stride;
+        int lo = 0, hi = nchunks;                       // last chunk with prefix <= rank
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_prefix[mid] <= rank) lo = mid; else hi = mid; }
+        int need = (int)(rank - s_prefix[lo]);
+        const long long base = (long long)lo * FITS_CHUNK;
+        const long long left = n - base;
+        const int size = left < FITS_CHUNK ? (int)left : FITS_CHUNK;
+        if (s_prefix[lo + 1] - s_prefix[lo] == size) {
+            float v = vals[base + need];
+            sv = v != v ? fill : v;
+        } else {
+            for (int k = 0; k < size; ++k) {
+                float v = vals[base + k];
+                if (v != v) v = fill;
+                if (isinf(v)) continue;
+                if (need-- == 0) { sv = v; break; }
+            }
+        }
+    }
+    s_samp[tid] = sv;
+    __syncthreads();
+    fits_zscale_fit(s_samp, s_red, npix, fill, dmax, c0, c1, c2, params);
+}
+
 __global__ __launch_bounds__(1024) void fits_zscale_kernel(const float* __restrict__ vals, long long n, int nchunks,
                                                            const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
                                                            FitsParams* __restrict__ params) {
     fits_zscale_body(vals, n, nchunks, chunks, c0, c1, c2, params);
+}
+
+// one channel's byte of a (NaN-filled) pixel value
+__device__ __forceinline__ unsigned char fits_byte(float v, const FitsChannel& c) {
+    const float s = fits_stretch(v, c);
+    const float q = rintf((s / c.cmax) * 255.f);                         // normalize_img (float32), gray2rgb: (c * 255).round()
+    return (q >= 0.f && q <= 255.f) ? (unsigned char)q : (unsigned char)0;             // 0 / 0 (constant tile): NaN -> 0
 }
 
 // pixel i of a tile: its three bytes
@@ -281,11 +302,7 @@ __device__ __forceinline__ void fits_rgb_pixel(const float* __restrict__ vals, l
         float v = vals[i];
         if (v != v) v = p.fill;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float s = fits_stretch(v, p.ch[c]);
-            const float q = rintf((s / p.ch[c].cmax) * 255.f);           // normalize_img (float32), gray2rgb: (c * 255).round()
-            o[c] = (q >= 0.f && q <= 255.f) ? (unsigned char)q : (unsigned char)0;     // 0 / 0 (constant tile): NaN -> 0
-        }
+        for (int c = 0; c < 3; ++c) o[c] = fits_byte(v, p.ch[c]);
     }
     rgb[i * 3 + 0] = o[0]; rgb[i * 3 + 1] = o[1]; rgb[i * 3 + 2] = o[2];
 }
@@ -406,5 +423,306 @@ extern "C" int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY
                        zscale_contrasts[0], zscale_contrasts[1], zscale_contrasts[2], params);
     hipLaunchKernelGGL(fits_tiles_rgb_kernel, dim3((unsigned)cdiv64(l.max_pixels, 256), (unsigned)T), dim3(256), 0, s, tiles_dev,
                        (const float*)vals, (const FitsParams*)params, (unsigned char*)rgb);
+    return mrcnn_launch_status();
+}
+
+// ---- the overview of a whole mosaic (include/mrcnn_hip.h: mrcnn_mosaic_overview) -----------------------------------------------
+// G = one channel of the chain above on the WHOLE plane [ny, nx] with one contrast; O[Y, X] = max of G over the k x k block
+// (partial at the right and lower edge); out = O in three channels.  Four launches, the plane read twice where it lies:
+//   mosaic_stats_kernel    one wavefront per 1024-pixel chunk (16-byte loads, shuffles, no LDS): FitsChunk per chunk;
+//   mosaic_scan_kernel     one workgroup per super-chunk of 1024 chunks: exclusive prefixes of the NaN and the infinity counts
+//                          within the super-chunk (which of the two count as "not finite" depends on the plane's minimum, known
+//                          only one level up) and the super-chunk's own FitsChunk;
+//   mosaic_zscale_kernel   ONE workgroup: minimum / maximum / counts over <= 2048 super-chunks, their prefix in LDS, per sample a
+//                          binary search of the super-chunk (LDS) and of the chunk inside it (10 loads), the sample read from the
+//                          plane -- a chunk with pixels that are not finite is walked by a whole wavefront, 16 ballots -- then
+//                          fits_zscale_fit;
+//   mosaic_pixels_kernel   one workgroup per output row Y and run of output pixels: a thread owns one plane column of the block
+//                          row (consecutive lanes = consecutive pixels of a plane row, whatever k), keeps the maximum of the
+//                          NaN-filled VALUE down its k rows, LDS folds k columns, and one fits_byte per output pixel: the byte map
+//                          is non-decreasing in the value, so the byte of the maximum is the maximum of the bytes.
+// Integer sums and min / max only: bitwise the same from run to run.
+#define MOSAIC_SUPER 1024                // chunks per super-chunk
+#define MOSAIC_MAX_SUPERS 2048           // 2^31 - 1 pixels: 2097152 chunks
+#define MOSAIC_MAX_PIXELS 0x7FFFFFFFll
+
+__device__ __forceinline__ void mosaic_take(unsigned u, int big_endian, float& mn, float& mx, int& nn, int& ni) {
+    if (big_endian) u = __builtin_bswap32(u);
+    const float v = __uint_as_float(u);
+    if (v != v) { ++nn; return; }
+    if (isinf(v)) ++ni;
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+}
+
+__global__ __launch_bounds__(256) void mosaic_stats_kernel(const unsigned* __restrict__ raw, long long n, long long nchunks, int big_endian,
+                                                           int vec, FitsChunk* __restrict__ chunks) {
+    const int lane = threadIdx.x & 63;
+    const long long nwaves = (long long)gridDim.x * 4;
+    for (long long c = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); c < nchunks; c += nwaves) {       // wave-uniform
+        const long long base = c * FITS_CHUNK;
+        float mn = INFINITY, mx = -INFINITY;
+        int nn = 0, ni = 0;
+        if (vec && base + FITS_CHUNK <= n) {
+            const uint4* p = (const uint4*)(raw + base);
+            uint4 q[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) q[j] = p[j * 64 + lane];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                mosaic_take(q[j].x, big_endian, mn, mx, nn, ni); mosaic_take(q[j].y, big_endian, mn, mx, nn, ni);
+                mosaic_take(q[j].z, big_endian, mn, mx, nn, ni); mosaic_take(q[j].w, big_endian, mn, mx, nn, ni);
+            }
+        } else {
+            for (int k = lane; k < FITS_CHUNK && base + k < n; k += 64) mosaic_take(raw[base + k], big_endian, mn, mx, nn, ni);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+            nn += __shfl_xor(nn, o, 64); ni += __shfl_xor(ni, o, 64);
+        }
+        if (lane == 0) chunks[c] = {mn, mx, nn, ni};
+    }
+}
+
+__global__ __launch_bounds__(1024) void mosaic_scan_kernel(const FitsChunk* __restrict__ chunks, long long nchunks, int2* __restrict__ pre,
+                                                           FitsChunk* __restrict__ supers) {
+    __shared__ int s_nan[16], s_inf[16];
+    __shared__ float s_mn[16], s_mx[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long long c = (long long)blockIdx.x * MOSAIC_SUPER + tid;
+    FitsChunk ch = {INFINITY, -INFINITY, 0, 0};
+    if (c < nchunks) ch = chunks[c];
+    int in = ch.n_nan, ii = ch.n_inf;                    // inclusive scan within the wavefront
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int a = __shfl_up(in, o, 64), b = __shfl_up(ii, o, 64);
+        if (lane >= o) { in += a; ii += b; }
+    }
+    float mn = ch.mn, mx = ch.mx;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
+    if (lane == 63) { s_nan[wv] = in; s_inf[wv] = ii; }
+    if (lane == 0) { s_mn[wv] = mn; s_mx[wv] = mx; }
+    __syncthreads();
+    int bn = 0, bi = 0;
+    for (int w = 0; w < wv; ++w) { bn += s_nan[w]; bi += s_inf[w]; }
+    if (c < nchunks) pre[c] = make_int2(bn + in - ch.n_nan, bi + ii - ch.n_inf);
+    if (tid == 0) {
+        FitsChunk t = {INFINITY, -INFINITY, 0, 0};
+        for (int w = 0; w < 16; ++w) { t.mn = fminf(t.mn, s_mn[w]); t.mx = fmaxf(t.mx, s_mx[w]); t.n_nan += s_nan[w]; t.n_inf += s_inf[w]; }
+        supers[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(1024) void mosaic_zscale_kernel(const unsigned* __restrict__ raw, long long n, long long nchunks, int nsupers,
+                                                             int big_endian, const FitsChunk* __restrict__ chunks,
+                                                             const int2* __restrict__ pre, const FitsChunk* __restrict__ supers,
+                                                             double contrast, FitsParams* __restrict__ params) {
+    __shared__ long long s_sprefix[MOSAIC_MAX_SUPERS + 1];
+    __shared__ float s_samp[1024];
+    __shared__ double s_red[1024];
+    __shared__ int s_walk_chunk[1024], s_walk_need[1024];
+    const int tid = threadIdx.x;
+    // ---- global min / max / counts ------------------------------------------------------------------------------------
+    float mn = INFINITY, mx = -INFINITY;
+    long long nn = 0;
+    for (int k = tid; k < nsupers; k += 1024) {
+        const FitsChunk c = supers[k];
+        mn = fminf(mn, c.mn); mx = fmaxf(mx, c.mx); nn += c.n_nan;
+    }
+    s_samp[tid] = mn;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) { if (tid < s) s_samp[tid] = fminf(s_samp[tid], s_samp[tid + s]); __syncthreads(); }
+    const float fill = s_samp[0];
+    __syncthreads();
+    s_samp[tid] = mx;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) { if (tid < s) s_samp[tid] = fmaxf(s_samp[tid], s_samp[tid + s]); __syncthreads(); }
+    const float dmax = s_samp[0];
+    __syncthreads();
+    const long long total_nan = (long long)fits_block_sum((double)nn, s_red, tid);     // < 2^31: exact
+    if (total_nan == n) {
+        if (tid == 0) { params->all_nan = 1; params->fill = fill; }
+        return;
+    }
+    const bool fill_finite = !isinf(fill);
+    // ---- finite pixels per super-chunk, exclusive prefix --------------------------------------------------------------------
+    const long long super_pixels = (long long)MOSAIC_SUPER * FITS_CHUNK;
+    for (int k = tid; k < nsupers; k += 1024) {
+        const long long left = n - (long long)k * super_pixels;
+        const long long size = left < super_pixels ? left : super_pixels;
+        s_sprefix[k + 1] = size - supers[k].n_inf - (fill_finite ? 0 : supers[k].n_nan);
+    }
+    if (tid == 0) s_sprefix[0] = 0;
+    __syncthreads();
+    if (tid == 0) for (int k = 0; k < nsupers; ++k) s_sprefix[k + 1] += s_sprefix[k];   // <= 2048 adds
+    __syncthreads();
+    const long long nfinite = s_sprefix[nsupers];
+    int npix = 0, stride = 1;
+    if (nfinite > 0) {
+        stride = (int)fmax(1.0, (double)nfinite / (double)FITS_NSAMPLES);
+        const long long avail = (nfinite + stride - 1) / stride;
+        npix = avail < FITS_NSAMPLES ? (int)avail : FITS_NSAMPLES;
+    }
+    // ---- values[isfinite][::stride][:nsamples]: the chunk of every sample's rank; the sample itself where the chunk is all finite
+    float sv = INFINITY;
+    int wc = -1, wn = 0;
+    if (tid < npix) {
+        const long long rank = (long long)tid * stride;
+        int lo = 0, hi = nsupers;                       // last super-chunk with prefix <= rank
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_sprefix[mid] <= rank) lo = mid; else hi = mid; }
+        const long long r2 = rank - s_sprefix[lo];
+        const long long c0 = (long long)lo * MOSAIC_SUPER;
+        const int nc = nchunks - c0 < MOSAIC_SUPER ? (int)(nchunks - c0) : MOSAIC_SUPER;
+        // finite pixels before chunk j of the super-chunk: every chunk before another one is full
+        int a = 0, b = nc;                              // last chunk with that count <= r2
+        while (b - a > 1) {
+            const int mid = (a + b) >> 1;
+            const int2 p = pre[c0 + mid];
+            if ((long long)mid * FITS_CHUNK - p.y - (fill_finite ? 0 : p.x) <= r2) a = mid; else b = mid;
+        }
+        const int2 p = pre[c0 + a];
+        const int need = (int)(r2 - ((long long)a * FITS_CHUNK - p.y - (fill_finite ? 0 : p.x)));
+        const long long c = c0 + a, base = c * FITS_CHUNK;
+        const int size = n - base < FITS_CHUNK ? (int)(n - base) : FITS_CHUNK;
+        const FitsChunk ch = chunks[c];
+        if (size - ch.n_inf - (fill_finite ? 0 : ch.n_nan) == size) {
+            if (need >= 0 && need < size) {
+                const float v = fits_load(raw, base + need, big_endian);
+                sv = v != v ? fill : v;
+            }
+        } else {
+            wc = (int)c;
+            wn = need;
+        }
+    }
+    s_samp[tid] = sv;
+    s_walk_chunk[tid] = wc;
+    s_walk_need[tid] = wn;
+    __syncthreads();
+    // ---- a chunk with pixels that are not finite: one wavefront walks it, 64 pixels per ballot ------------------------------
+    const int lane = tid & 63;
+    for (int s = tid >> 6; s < npix; s += 16) {           // wave-uniform
+        const int c = s_walk_chunk[s];
+        if (c < 0) continue;
+        int need = s_walk_need[s];
+        const long long base = (long long)c * FITS_CHUNK;
+        float v[16];
+#pragma unroll
+        for (int it = 0; it < 16; ++it) {
+            const long long i = base + it * 64 + lane;
+            float x = INFINITY;                           // past the plane: skipped like an infinity
+            if (i < n) x = fits_load(raw, i, big_endian);
+            v[it] = x != x ? fill : x;
+        }
+        bool found = false;
+#pragma unroll
+        for (int it = 0; it < 16; ++it) {
+            const bool ok = !isinf(v[it]);
+            const unsigned long long m = __ballot(ok);
+            const int cnt = __popcll(m);
+            if (!found) {
+                if (need < cnt) {
+                    if (ok && __popcll(m & ((1ull << lane) - 1ull)) == need) s_samp[s] = v[it];
+                    found = true;
+                } else {
+                    need -= cnt;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    fits_zscale_fit(s_samp, s_red, npix, fill, dmax, contrast, contrast, contrast, params);
+}
+
+__global__ __launch_bounds__(256) void mosaic_pixels_kernel(const unsigned* __restrict__ raw, int ny, int nx, int big_endian, int k, int w,
+                                                            int nout, int nbx, const FitsParams* __restrict__ params,
+                                                            unsigned char* __restrict__ out) {
+    __shared__ float s_col[256];
+    __shared__ unsigned char s_byte[256];
+    const int tid = threadIdx.x;
+    const int Y = blockIdx.x / nbx, X0 = (blockIdx.x % nbx) * nout;
+    const int nq = min(nout, w - X0);                                     // output pixels of this workgroup
+    unsigned char* o = out + ((long long)Y * w + X0) * 3;
+    if (params->all_nan) {                                                 // (the same for every thread)
+        for (int t = tid; t < 3 * nq; t += 256) o[t] = 0;
+        return;
+    }
+    const float fill = params->fill;
+    const long long y0 = (long long)Y * k, y1 = y0 + k < ny ? y0 + k : ny;
+    const long long xs = (long long)X0 * k;
+    const long long span = (long long)nout * k < nx - xs ? (long long)nout * k : nx - xs;
+    float m = -INFINITY;
+    for (long long cx = tid; cx < span; cx += 256) {                       // one trip unless k > 256 (then nout == 1)
+        long long i = y0 * nx + xs + cx;
+#pragma unroll 4
+        for (long long y = y0; y < y1; ++y, i += nx) {
+            float v = fits_load(raw, i, big_endian);
+            if (v != v) v = fill;
+            m = fmaxf(m, v);
+        }
+    }
+    s_col[tid] = m;
+    __syncthreads();
+    if (tid < nq) {
+        const int lo = nout == 1 ? 0 : tid * k, hi = nout == 1 ? 256 : lo + k;
+        float r = -INFINITY;
+        for (int j = lo; j < hi; ++j) r = fmaxf(r, s_col[j]);
+        s_byte[tid] = fits_byte(r, params->ch[0]);
+    }
+    __syncthreads();
+    for (int t = tid; t < 3 * nq; t += 256) o[t] = s_byte[t / 3];
+}
+
+struct MosaicLayout { long long n, chunks, supers; int h, w, nout, nbx; };
+
+static int mosaic_layout(int ny, int nx, int shrink, double contrast, MosaicLayout* out) {
+    if (ny <= 0 || nx <= 0 || shrink <= 0 || !(contrast == contrast) || isinf(contrast)) return MRCNN_ERR_ARG;
+    MosaicLayout l;
+    l.n = (long long)ny * nx;
+    if (l.n > MOSAIC_MAX_PIXELS) return MRCNN_ERR_UNSUPPORTED;
+    l.chunks = (l.n + FITS_CHUNK - 1) / FITS_CHUNK;
+    l.supers = (l.chunks + MOSAIC_SUPER - 1) / MOSAIC_SUPER;
+    l.h = (int)(((long long)ny + shrink - 1) / shrink);
+    l.w = (int)(((long long)nx + shrink - 1) / shrink);
+    l.nout = shrink <= 256 ? 256 / shrink : 1;
+    l.nbx = (l.w + l.nout - 1) / l.nout;
+    *out = l;
+    return MRCNN_OK;
+}
+
+extern "C" int mrcnn_mosaic_overview_check(int ny, int nx, int shrink, double contrast) {
+    MosaicLayout l;
+    return mosaic_layout(ny, nx, shrink, contrast, &l);
+}
+
+extern "C" size_t mrcnn_mosaic_overview_workspace(int ny, int nx) {
+    MosaicLayout l;
+    if (mosaic_layout(ny, nx, 1, 0.25, &l) != MRCNN_OK) return 0;
+    return (size_t)l.chunks * (sizeof(FitsChunk) + sizeof(int2)) + (size_t)l.supers * sizeof(FitsChunk) + sizeof(FitsParams) + 256;
+}
+
+extern "C" int mrcnn_mosaic_overview(const void* plane, int big_endian, int ny, int nx, int shrink, double contrast, void* out,
+                                     size_t out_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    MosaicLayout l;
+    const int rc = mosaic_layout(ny, nx, shrink, contrast, &l);
+    if (rc != MRCNN_OK) return rc;
+    if (!plane || !out || ((uintptr_t)plane & 3) || out_bytes < (size_t)l.h * l.w * 3) return MRCNN_ERR_ARG;
+    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < mrcnn_mosaic_overview_workspace(ny, nx)) return MRCNN_ERR_WORKSPACE;
+    FitsChunk* ch = (FitsChunk*)workspace;
+    FitsChunk* sup = ch + l.chunks;
+    int2* pre = (int2*)(sup + l.supers);
+    FitsParams* params = (FitsParams*)(((uintptr_t)(pre + l.chunks) + 63) & ~(uintptr_t)63);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned* raw = (const unsigned*)plane;
+    const long long stat_blocks = (l.chunks + 3) / 4;
+    hipLaunchKernelGGL(mosaic_stats_kernel, dim3((unsigned)(stat_blocks < 4096 ? stat_blocks : 4096)), dim3(256), 0, s, raw, l.n, l.chunks,
+                       big_endian, ((uintptr_t)plane & 15) == 0 ? 1 : 0, ch);
+    hipLaunchKernelGGL(mosaic_scan_kernel, dim3((unsigned)l.supers), dim3(1024), 0, s, (const FitsChunk*)ch, l.chunks, pre, sup);
+    hipLaunchKernelGGL(mosaic_zscale_kernel, dim3(1), dim3(1024), 0, s, raw, l.n, l.chunks, (int)l.supers, big_endian, (const FitsChunk*)ch,
+                       (const int2*)pre, (const FitsChunk*)sup, contrast, params);
+    hipLaunchKernelGGL(mosaic_pixels_kernel, dim3((unsigned)((long long)l.h * l.nbx)), dim3(256), 0, s, raw, ny, nx, big_endian, shrink, l.w,
+                       l.nout, l.nbx, (const FitsParams*)params, (unsigned char*)out);
     return mrcnn_launch_status();
 }

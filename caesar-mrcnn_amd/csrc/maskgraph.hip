@@ -8,10 +8,13 @@
 //                                          count_b - inter on the host -- and the 4-neighbour predicate analyze.masks_touch4,
 //                                          which equals Analyzer.are_mask_connected (the component count of a | b drops below
 //                                          n_a + n_b iff some pixel of a equals or is a 4-neighbour of some pixel of b);
-//   mask_union_kernel                      OR of the members of each component (merge_masks chains), with count and box.
+//   mask_union_kernel                      OR of the members of each component (merge_masks chains), with count and box;
+//   source_planes_kernel + mask_stats_kernel   the bit-mask sources of a mosaic (mrcnn_tile_source) -> planes of a frame shrunk by
+//                                          k: a bit is set when the source has a pixel in its k x k block.
 // Integer kernels, latency-bound: no MFMA; LDS only to turn the (x, d)-contiguous bytes into per-detection ballots and for the
 // per-plane reductions.
 #include "common.h"
+#include "tile_source.h"
 #include <climits>
 
 #define MG_DC 64        // detections per staging pass of the pack kernel
@@ -222,5 +225,61 @@ extern "C" int mrcnn_mask_union(const void* planes, int n, int H, int W, const i
     if ((int64_t)H * wpr > 0x7FFFFFFFll) return MRCNN_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(mask_union_kernel, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, (const unsigned*)planes, n, H, wpr,
                        (const int*)comp_offsets, (const int*)member_ids, M, (unsigned*)out_planes, (int*)out_count, (int*)out_box);
+    return mrcnn_launch_status();
+}
+
+// One thread per output word (i, Y, Kw): it covers the plane pixels [k Y, k (Y + 1)) x [32 k Kw, 32 k (Kw + 1)), clipped to the
+// frame's w columns and to source i's box.  The thread ORs the source's words over those rows and moves every set bit to the
+// output column (x0 + local column) / k: a gather, no atomics; words outside the box and the bits past w come out zero.
+__global__ __launch_bounds__(256) void source_planes_kernel(const unsigned* __restrict__ pool, long long pool_words,
+                                                            const TmSrc* __restrict__ desc, int n, int k, int h, int w, int wpr,
+                                                            unsigned* __restrict__ planes) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)n * h * wpr) return;
+    const int Kw = (int)(idx % wpr);
+    const long long t = idx / wpr;
+    const int Y = (int)(t % h), i = (int)(t / h);
+    const TmSrc d = desc[i];
+    unsigned out = 0u;
+    if (tm_valid(d)) {
+        const int nbits = min(32, w - 32 * Kw);
+        const long long ry0 = max((long long)Y * k - d.y0, 0ll), ry1 = min(((long long)Y + 1) * k - d.y0, (long long)d.h);
+        const long long cx0 = max(32ll * Kw * k - d.x0, 0ll), cx1 = min((32ll * Kw + nbits) * k - d.x0, (long long)d.w);
+        if (ry0 < ry1 && cx0 < cx1) {
+            for (long long p = cx0 & ~31ll; p < cx1; p += 32) {           // the words of the source's rows under this output word
+                unsigned acc = 0u;
+                for (long long r = ry0; r < ry1; ++r) acc |= tm_word(pool, pool_words, d, (int)r, (int)(p >> 5));
+                if (p < cx0) acc &= 0xFFFFFFFFu << (int)(cx0 - p);
+                if (cx1 - p < 32) acc &= 0xFFFFFFFFu >> (int)(32 - (cx1 - p));
+                while (acc) {
+                    const int j = __ffs((int)acc) - 1;
+                    acc &= acc - 1u;
+                    out |= 1u << (int)(((long long)d.x0 + p + j) / k - 32ll * Kw);
+                }
+            }
+        }
+    }
+    planes[idx] = out;
+}
+
+extern "C" int mrcnn_sources_to_planes_check(int n, int shrink, int h, int w) {
+    if (n <= 0 || shrink <= 0 || h <= 0 || w <= 0) return MRCNN_ERR_ARG;
+    const int64_t wpr = ((int64_t)w + 31) >> 5;
+    if ((int64_t)n * h * wpr > 0x7FFFFFFFll || (int64_t)shrink * h > 0x7FFFFFFFll || (int64_t)shrink * wpr * 32 > 0x7FFFFFFFll)
+        return MRCNN_ERR_UNSUPPORTED;
+    return MRCNN_OK;
+}
+
+extern "C" int mrcnn_sources_to_planes(const void* pool, int64_t pool_words, const mrcnn_tile_source* desc, int n, int shrink, int h, int w,
+                                       void* planes, int32_t* count, int32_t* box, void* stream) {
+    const int rc = mrcnn_sources_to_planes_check(n, shrink, h, w);
+    if (rc != MRCNN_OK) return rc;
+    if (!pool || pool_words < 0 || !desc || !planes || !count || !box) return MRCNN_ERR_ARG;
+    const int wpr = (w + 31) >> 5;
+    const int64_t words = (int64_t)n * h * wpr;
+    hipLaunchKernelGGL(source_planes_kernel, dim3((unsigned)cdiv64(words, 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned*)pool,
+                       (long long)pool_words, desc, n, shrink, h, w, wpr, (unsigned*)planes);
+    hipLaunchKernelGGL(mask_stats_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, (const unsigned*)planes, h, wpr, (int*)count,
+                       (int*)box);
     return mrcnn_launch_status();
 }

@@ -267,6 +267,37 @@ def read_fits(filename, xmin=-1, xmax=-1, ymin=-1, ymax=-1, stretch=True, normal
     return np.copy(chans[0]) if chans[0] is out else chans[0], header
 
 
+def mosaic_overview_host(plane, shrink, contrast=0.25):
+    """The overview frame of a whole mosaic, the statement ops.mosaic_overview is held to.  plane [ny, nx] (what
+    SFinder._image_plane() returns); shrink: an integer k >= 1; contrast: a zscale contrast.
+      G [ny, nx] uint8 = one channel of read_fits on the whole plane with the run.py flags and that contrast -- the same
+        functions, type for type: astype(float32), NaN -> nanmin, stretch_img, normalize_img, round(255 x);
+      O [ceil(ny / k), ceil(nx / k)]: O[Y, X] = max of G[k Y : k (Y + 1), k X : k (X + 1)] (partial blocks at the lower and
+        right edge).  The maximum, not the mean: a compact source of a few pixels survives the shrink.
+    Returns O in all three channels, uint8 [h, w, 3].  A plane without a single finite pixel gives zeros (read_fits raises
+    there)."""
+    k = int(shrink)
+    if k != shrink or k < 1:
+        raise ValueError("shrink must be an integer >= 1 (got %r)" % (shrink,))
+    plane = np.asarray(plane)
+    if plane.ndim != 2 or plane.size == 0:
+        raise ValueError("plane must be a non-empty 2-D array (got shape %r)" % (plane.shape,))
+    ny, nx = plane.shape
+    h, w = -(-ny // k), -(-nx // k)
+    out = plane.astype(np.float32)
+    if not np.isfinite(out).any():
+        return np.zeros((h, w, 3), np.uint8)
+    out[np.isnan(out)] = np.nanmin(out)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        c = stretch_img(out, contrast).astype(np.float32)
+        c = normalize_img(c).astype(np.float32)
+        G = np.array((c * 255).round(), dtype=np.uint8)
+    padded = np.zeros((h * k, w * k), np.uint8)
+    padded[:ny, :nx] = G
+    O = padded.reshape(h, k, w, k).max(axis=(1, 3))
+    return np.repeat(O[:, :, None], 3, axis=2)
+
+
 def _read_fits_device(tile, zscale_contrasts, device):
     """The cut tile (still in the file's dtype / byte order) -> uint8 [H, W, 3] through ops.fits_to_rgb; returns a host array.
     Called from loader threads while the main thread issues training steps: the three launches go to ONE side stream shared

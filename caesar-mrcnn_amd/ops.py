@@ -761,6 +761,86 @@ def fits_tiles_to_rgb(plane, tiles, zscale_contrasts=(0.25, 0.25, 0.25), big_end
     return out
 
 
+# ---- the overview picture of a mosaic (csrc/fits.hip: mrcnn_mosaic_overview; csrc/maskgraph.hip: mrcnn_sources_to_planes) --------
+class MosaicUnsupported(_hip.HipPathError):
+    """A mosaic past a cap of mrcnn_mosaic_overview (more than 2^31 - 1 pixels) or of mrcnn_sources_to_planes (planes of more
+    than 2^31 - 1 words, shrink * h or shrink * w beyond 2^31 - 1): nothing was launched, the caller takes the host statement."""
+
+
+def _mosaic_refusal(rc, what):
+    if rc == ERR_UNSUPPORTED:
+        raise MosaicUnsupported("%s: past a cap of the kernel (status %d)" % (what, rc))
+    if rc:
+        raise ValueError("%s refuses the call (status %d): an empty plane or frame, a shrink below 1 or a contrast that is not "
+                         "finite" % (what, rc))
+
+
+def mosaic_overview(plane, shrink, contrast=0.25, big_endian=False, timing=None):
+    """The overview frame of a whole mosaic (fits.mosaic_overview_host is the statement): plane [ny, nx] float32 on the device,
+    or with big_endian=True the file's bytes as uint8 [ny, nx, 4] (what SFinder._plane_device holds) -> uint8 [ceil(ny / shrink),
+    ceil(nx / shrink), 3] device tensor: read_fits's chain on the whole plane with that zscale contrast, then the maximum of every
+    shrink x shrink block.  The plane is read where it lies, twice; the workspace holds 24 bytes per 1024 pixels.  ValueError for
+    a malformed call, MosaicUnsupported past 2^31 - 1 pixels; neither launches anything.  timing: a dict that receives the device
+    time of the four launches (overview_kernels_ms, from events; costs a synchronisation)."""
+    _need_cuda(plane)
+    if plane.dim() < 2 or not plane.is_contiguous() or plane.numel() * plane.element_size() != 4 * plane.shape[0] * plane.shape[1]:
+        raise ValueError("plane must hold ny x nx float32 values, contiguous (got shape %r, dtype %s)" % (tuple(plane.shape), plane.dtype))
+    if big_endian and plane.dtype != torch.uint8:
+        raise ValueError("big-endian input: the file's bytes as uint8 [ny, nx, 4]")
+    if not big_endian and plane.dtype != torch.float32:
+        raise ValueError("native input: float32 [ny, nx]")
+    if int(shrink) != shrink:
+        raise ValueError("shrink must be an integer (got %r)" % (shrink,))
+    ny, nx, k = int(plane.shape[0]), int(plane.shape[1]), int(shrink)
+    if ny >= 2 ** 31 or nx >= 2 ** 31 or not -2 ** 31 <= k < 2 ** 31:
+        raise ValueError("plane side or shrink outside the 32-bit range")
+    L = _hip.lib()
+    _mosaic_refusal(L.mrcnn_mosaic_overview_check(ny, nx, k, float(contrast)), "mrcnn_mosaic_overview")
+    h, w = -(-ny // k), -(-nx // k)
+    ws = workspace(L.mrcnn_mosaic_overview_workspace(ny, nx), plane.device, "mosaic")
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=plane.device)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing is not None else None
+    if ev:
+        ev[0].record()
+    check(L.mrcnn_mosaic_overview(ptr(plane), 1 if big_endian else 0, ny, nx, k, float(contrast), ptr(out), out.numel(), ptr(ws),
+                                  ws.numel(), current_stream()), "mrcnn_mosaic_overview")
+    if ev:
+        ev[1].record()
+        ev[1].synchronize()
+        timing["overview_kernels_ms"] = round(ev[0].elapsed_time(ev[1]), 4)
+        timing["plane_bytes"] = 4 * ny * nx
+    return out
+
+
+def sources_to_planes(pool, desc, shrink, h, w, timing=None):
+    """The sources of a mosaic as the MaskPlanes of its overview frame (sfinder.source_planes_host is the statement): pool, desc
+    from tile_upload (x0 / y0 in mosaic pixels); bit (Y, X) of plane i is set iff source i has a pixel (y, x) with y // shrink == Y
+    and x // shrink == X, pixels outside [0, shrink h) x [0, shrink w) are dropped; count and box as mask_planes_pack fills them.
+    ValueError for a malformed call, MosaicUnsupported past a cap; neither launches anything."""
+    _need_cuda(pool, desc)
+    assert pool.dtype == torch.int32 and desc.dtype == torch.int32 and desc.dim() == 2 and desc.shape[1] == 6 and desc.is_contiguous()
+    for name, v in (("shrink", shrink), ("h", h), ("w", w)):
+        if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+            raise ValueError("sources_to_planes: %s must be a 32-bit integer (got %r)" % (name, v))
+    n, k, h, w = int(desc.shape[0]), int(shrink), int(h), int(w)
+    L = _hip.lib()
+    _mosaic_refusal(L.mrcnn_sources_to_planes_check(n, k, h, w), "mrcnn_sources_to_planes")
+    dev = pool.device
+    words = torch.empty((n, h, (w + 31) // 32), dtype=torch.int32, device=dev)
+    count = torch.empty((n,), dtype=torch.int32, device=dev)
+    box = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing is not None else None
+    if ev:
+        ev[0].record()
+    check(L.mrcnn_sources_to_planes(ptr(pool), pool.numel(), ptr(desc), n, k, h, w, ptr(words), ptr(count), ptr(box), current_stream()),
+          "mrcnn_sources_to_planes")
+    if ev:
+        ev[1].record()
+        ev[1].synchronize()
+        timing["planes_kernels_ms"] = round(ev[0].elapsed_time(ev[1]), 4)
+    return MaskPlanes(words, count, box, w)
+
+
 # ---- source catalogue (csrc/catalog.hip) ------------------------------------------------------------------------------------
 CATALOG_MAX_SOURCES = 1 << 18            # MRCNN_CATALOG_MAX_SOURCES (include/mrcnn_hip.h)
 CATALOG_FILL_WALK, CATALOG_FILL_LAUNCHES = 0, 1

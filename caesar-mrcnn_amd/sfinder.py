@@ -210,6 +210,34 @@ def unpack_bitmap(words, h, w, wpr):
     return b[:, :w].astype(bool)
 
 
+def source_planes_host(pool, desc, shrink, h, w):
+    """pack_sources' sources as planes of a frame shrunk by k = shrink, the statement ops.sources_to_planes is held to: bool
+    [n, h, w]; plane i has bit (Y, X) set exactly when source i has a pixel (y, x) with y // k == Y and x // k == X.  Pixels
+    outside [0, k h) x [0, k w) are dropped; a source without pixels gives a zero plane."""
+    k, h, w = int(shrink), int(h), int(w)
+    pool = np.asarray(pool).reshape(-1).view(np.uint32)
+    desc = np.asarray(desc, dtype=np.int64).reshape(-1, 6)
+    planes = np.zeros((desc.shape[0], h, w), bool)
+    for i, (x0, y0, sw, sh, off, wpr) in enumerate(desc):
+        if sw <= 0 or sh <= 0:
+            continue
+        ys, xs = np.nonzero(unpack_bitmap(pool[off:off + sh * wpr], sh, sw, wpr))
+        ys, xs = ys + y0, xs + x0
+        keep = (ys >= 0) & (ys < k * h) & (xs >= 0) & (xs < k * w)
+        planes[i, ys[keep] // k, xs[keep] // k] = True
+    return planes
+
+
+def plane_boxes_host(planes):
+    """(y1, x1, y2, x2) per plane as utils.extract_bboxes: upper corner exclusive, zeros for an empty plane.  int32 [n, 4]."""
+    boxes = np.zeros((len(planes), 4), np.int32)
+    for i, m in enumerate(planes):
+        ys, xs = np.nonzero(m)
+        if ys.size:
+            boxes[i] = (ys.min(), xs.min(), ys.max() + 1, xs.max() + 1)
+    return boxes
+
+
 # ===============================
 #        SFinder
 # ===============================
@@ -224,6 +252,7 @@ class SFinder(object):
     # 4.8): on a 1024 x 1024 image the device path is behind at 1 and 4 sources (0.78 against 0.42 ms, 1.16 against 1.05 ms) and
     # ahead at 116 (30.5 against 41.2 ms); 116 is the smallest count at which it was measured ahead on every mosaic.
     PARAMS_DEVICE_MIN_SOURCES = 116
+    MOSAIC_CAPTIONS = ("name", "score", "none")
     PARAM_KEYS = ("nPix", "X0", "Y0", "X0w", "Y0w", "X0_wcs", "Y0_wcs", "X0w_wcs", "Y0w_wcs", "Xmin", "Xmax", "Ymin", "Ymax",
                   "Xmin_wcs", "Xmax_wcs", "Ymin_wcs", "Ymax_wcs", "S", "Smin", "Smax", "Smean", "Smedian", "Sstddev", "flux")
 
@@ -275,6 +304,15 @@ class SFinder(object):
         # N >= 1: the batched, device-resident front end (needs the run.py read_fits flags and a model built for batches of N).
         self.tile_batch = 0
         self._wcs_warned = False
+        # The overview picture of the mosaic with the merged catalogue on it: off by default.
+        self.draw_mosaic = False
+        self.mosaic_outfile = ""          # "": mosaic_<image_id>.png
+        self.mosaic_shrink = None         # None: max(1, ceil(max(ny, nx) / 1024))
+        self.mosaic_scale = None          # None: draw.default_scale(h, w)
+        self.mosaic_captions = "name"     # "name", "score" or "none"
+        self.mosaic_shaded = False
+        self.mosaic_device = self._has_gpu()
+        self.mosaic_timing = {}
 
     def _device(self):
         return analyze.model_device(self.model)
@@ -434,10 +472,10 @@ class SFinder(object):
                         status = -1
             if status < 0:
                 logger.warning("[PROC %d] One or more errors occurred in source finding tasks..." % self.procId)
-            if self.procId != self.MASTER_ID or not self.compute_params:
+            if self.procId != self.MASTER_ID or not (self.compute_params or self.draw_mosaic):
                 self._drop_plane()
-            elif not self.params_device:
-                self._plane_dev = None          # the host statement of the parameters cuts from the host copy
+            elif not ((self.compute_params and self.params_device) or (self.draw_mosaic and self.mosaic_device)):
+                self._plane_dev = None          # the host statements (parameters, overview) cut from the host copy
         # every rank arrives here, whatever happened above (the reference returns early on a set-up error and leaves the others
         # in the barrier): a rank whose set-up failed contributes nothing
         if self.gather_task_data_from_workers(skip_local=(status == -2)) < 0:
@@ -451,6 +489,8 @@ class SFinder(object):
                 logger.info("[PROC %d] Computing source parameters ..." % self.procId)
                 self.compute_sources_params()
             self.save()
+            if self.draw_mosaic:
+                self.draw_mosaic_results()
             logger.info("[PROC %d] Run completed in %d seconds" % (self.procId, time.time() - t0))
         return 0
 
@@ -948,7 +988,8 @@ class SFinder(object):
                 logger.warning("[PROC %d] Source parameters on the host: %s" % (self.procId, e))
         t1 = clock()
         failed = sum(0 if self._host_params(sources[i]) else 1 for i in host)
-        self._drop_plane()                                                # the whole image: not kept beyond this step
+        if not self.draw_mosaic:
+            self._drop_plane()                                            # the whole image: not kept beyond this step
         self.params_timing.update({"host_sources": len(host), "device_sources": len(sources) - len(host), "failed_sources": failed,
                                    "device_path_ms": round(1e3 * (t1 - t0), 3), "host_statement_ms": round(1e3 * (clock() - t1), 3)})
         return 0
@@ -1008,6 +1049,147 @@ class SFinder(object):
         for name, a, b in zip(("select", "read_upload", "pack", "launch_download", "dicts"), t[:-1], t[1:]):
             self.params_timing[name + "_ms"] = round(1e3 * (b - a), 3)
         return sorted(host)
+
+    # ---- the overview picture of the mosaic (no counterpart in the reference) -----------------------------
+    def _mosaic_geometry(self):
+        """(ny, nx, k, h, w, scale) of the overview frame, or None (logged) for settings that cannot be drawn."""
+        from . import draw as overlay
+        ny, nx = (int(v) for v in self._image_plane().shape)
+        k = max(1, -(-max(ny, nx) // 1024)) if self.mosaic_shrink is None else self.mosaic_shrink
+        if int(k) != k or k < 1:
+            logger.error("Invalid mosaic_shrink %r (need an integer >= 1): nothing is drawn ..." % (self.mosaic_shrink,))
+            return None
+        k = int(k)
+        h, w = -(-ny // k), -(-nx // k)
+        scale = overlay.default_scale(h, w) if self.mosaic_scale is None else self.mosaic_scale
+        if int(scale) != scale or scale < 1:
+            logger.error("Invalid mosaic_scale %r (need an integer >= 1): nothing is drawn ..." % (self.mosaic_scale,))
+            return None
+        if self.mosaic_captions not in self.MOSAIC_CAPTIONS:
+            logger.error("Invalid mosaic_captions %r (need one of %r): nothing is drawn ..." % (self.mosaic_captions, self.MOSAIC_CAPTIONS))
+            return None
+        return ny, nx, k, h, w, int(scale)
+
+    def _mosaic_contrast(self):
+        return float(self.config.ZSCALE_CONTRASTS[0])
+
+    def _mosaic_pixel_lists(self):
+        return [np.asarray(s["pixels"], dtype=np.int64).reshape(-1, 2) for s in self.sources["sources"]]
+
+    def _mosaic_scene_of(self, image, masks, boxes, scale):
+        """The scene dict of draw.py from the overview frame, the sources' planes (None: the device form keeps them) and the
+        planes' boxes: colours by class_name from the map the Analyzer draws with, no ground truth, the captions at the upper
+        left corner of the planes' boxes."""
+        from . import draw as overlay
+        sources = self.sources["sources"]
+        colours = [overlay.CLASS_COLOR_MAP.get(s.get("class_name"), overlay.UNKNOWN_COLOUR) for s in sources]
+        texts = []
+        for s, (y1, x1, y2, x2) in zip(sources, boxes):
+            if self.mosaic_captions == "name":
+                texts.append((str(s.get("name", "")), int(x1), int(y1) - 1, overlay.CAPTION_COLOUR))
+            elif self.mosaic_captions == "score":
+                texts.append(("%.2f" % s["score"], int(x1), int(y1) - 1, overlay.CAPTION_COLOUR))
+        return {"image": image, "scale": scale, "shaded": bool(self.mosaic_shaded), "masks": masks, "colours": colours,
+                "boxes": [[int(v) for v in b] for b in boxes], "gt_boxes": [], "gt_colours": [], "texts": texts}
+
+    def mosaic_scene(self):
+        """The scene of draw.render_host for the mosaic and its catalogue: fits.mosaic_overview_host of the image plane with
+        the contrast ZSCALE_CONTRASTS[0], source_planes_host of the catalogue's pixel lists, the planes' boxes (extract_bboxes
+        convention -- not the catalogue's x1 .. y2, whose upper corner is inclusive for merged sources and exclusive for the
+        others).  None (logged) for settings that cannot be drawn."""
+        geo = self._mosaic_geometry()
+        if geo is None:
+            return None
+        ny, nx, k, h, w, scale = geo
+        image = fits.mosaic_overview_host(self._image_plane(), k, self._mosaic_contrast())
+        pool, desc = pack_sources(self._mosaic_pixel_lists())
+        planes = source_planes_host(pool, desc, k, h, w)
+        return self._mosaic_scene_of(image, [m.astype(np.uint8) for m in planes], plane_boxes_host(planes), scale)
+
+    def _render_mosaic_device(self):
+        import torch
+        from . import draw as overlay
+        from . import ops
+        clock = time.perf_counter
+        timing = {"sources": len(self.sources["sources"])}
+        geo = self._mosaic_geometry()
+        if geo is None:
+            return None
+        ny, nx, k, h, w, scale = geo
+        t0 = clock()
+        plane_t, big = self._plane_device()                              # resident after a tile_batch / params_device run
+        torch.cuda.synchronize(plane_t.device)
+        t1 = clock()
+        frame = ops.mosaic_overview(plane_t, k, self._mosaic_contrast(), big_endian=big)
+        torch.cuda.synchronize(plane_t.device)
+        t2 = clock()
+        planes, boxes = None, np.zeros((0, 4), np.int32)
+        if self.sources["sources"]:
+            pool, desc = pack_sources(self._mosaic_pixel_lists())
+            pool_t, desc_t = ops.tile_upload(pool, desc, plane_t.device)
+            planes = ops.sources_to_planes(pool_t, desc_t, k, h, w)
+            boxes = planes.box.cpu().numpy()
+        t3 = clock()
+        scene = self._mosaic_scene_of(None, None, boxes, scale)
+        canvas = ops.draw_overlay(frame, planes, overlay.device_tables(scene), scale)
+        torch.cuda.synchronize(canvas.device)
+        t4 = clock()
+        out = canvas.cpu().numpy()
+        t5 = clock()
+        for name, a, b in (("plane", t0, t1), ("overview", t1, t2), ("planes", t2, t3), ("render", t3, t4), ("download", t4, t5)):
+            timing[name + "_ms"] = round(1e3 * (b - a), 3)
+        self.mosaic_timing = timing
+        return out
+
+    def _render_mosaic_host(self):
+        from . import draw as overlay
+        clock = time.perf_counter
+        t0 = clock()
+        scene = self.mosaic_scene()
+        if scene is None:
+            return None
+        t1 = clock()
+        out = overlay.render_host(scene)
+        self.mosaic_timing = {"sources": len(self.sources["sources"]), "scene_ms": round(1e3 * (t1 - t0), 3),
+                              "render_ms": round(1e3 * (clock() - t1), 3)}
+        return out
+
+    def render_mosaic(self, device=None):
+        """The overview picture as a uint8 array [s (h + 4), s (w + 4), 3], without writing a file: the whole plane stretched as
+        read_fits stretches a tile and shrunk by block maxima to the frame [h, w], under the catalogue's sources drawn as
+        Analyzer.draw_results draws detections (contours, boxes, captions; shaded with ``mosaic_shaded``).  None (logged) when it
+        cannot be drawn.  device: None -- on the GPU where ``mosaic_device`` is on (measured ahead from a 384 x 320 mosaic with 5
+        sources up: no size threshold), with the fallback of analyze.device_or_host; True -- the device form, errors raised;
+        False -- the host statement.
+        Both forms give the same bytes."""
+        self.mosaic_timing = {}
+        if device is True:
+            return self._render_mosaic_device()
+        if device is None and self.mosaic_device and self._has_gpu():
+            from .ops import DrawUnsupported, MosaicUnsupported           # this picture only: a catalogue past MAX_ITEMS, ...
+            return analyze.device_or_host("render_mosaic_device", self._render_mosaic_device, self._render_mosaic_host,
+                                          refusal=(DrawUnsupported, MosaicUnsupported))
+        return self._render_mosaic_host()
+
+    def draw_mosaic_results(self, device=None):
+        """Write render_mosaic() as an 8-bit RGB PNG to ``mosaic_outfile`` (default mosaic_<image_id>.png).  Rank 0 only.  0, or
+        -1 when nothing could be drawn."""
+        if self.procId != self.MASTER_ID:
+            return 0
+        from . import draw as overlay
+        try:
+            canvas = self.render_mosaic(device)
+        except Exception as e:                      # a picture must not fail a run whose catalogue is already written
+            logger.error("[PROC %d] The mosaic picture could not be drawn (%s: %s)" % (self.procId, type(e).__name__, e))
+            canvas = None
+        if canvas is None:
+            return -1
+        outfile = self.mosaic_outfile or "mosaic_%s.png" % self.image_id
+        t0 = time.perf_counter()
+        overlay.write_png(outfile, canvas)
+        self.mosaic_timing["encode_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+        logger.info("[PROC %d] Mosaic picture %r written to %s" % (self.procId, tuple(canvas.shape), outfile))
+        return 0
 
     # ---- tile grid (sfinder.py:1216-1384) ---------------------------------------------------------------------
     def create_tile_tasks(self):

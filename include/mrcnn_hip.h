@@ -363,6 +363,18 @@ int mrcnn_mask_pair_stats(const void* planes, const int32_t* box, int n, int H, 
 int mrcnn_mask_union(const void* planes, int n, int H, int W, const int32_t* comp_offsets, const int32_t* member_ids, int C, int M,
                      void* out_planes, int32_t* out_count, int32_t* out_box, void* stream);
 
+/* The sources of a mosaic as the planes of its overview frame (the host statement is
+ * sfinder.source_planes_host): pool, pool_words, desc[n] as for mrcnn_tile_adjacency (x0 / y0 in mosaic pixels); planes
+ * [n][h][ceil(w / 32)] in the layout above: bit (Y, X) of plane i is set iff source i has a pixel (y, x) with y / shrink == Y and
+ * x / shrink == X; pixels outside [0, shrink h) x [0, shrink w) are dropped, the bits past w are zero, a descriptor that is not
+ * valid (w or h <= 0, ...) gives a zero plane, words past the pool read as zero.  count[n] and box[n, 4] as
+ * mrcnn_mask_planes_pack fills them.  One thread gathers one output word (no atomics), then the statistics launch of _pack.
+ * n, shrink, h or w <= 0 or a missing pointer: MRCNN_ERR_ARG; n h ceil(w / 32), shrink h or shrink w beyond 2^31 - 1:
+ * MRCNN_ERR_UNSUPPORTED; nothing is launched then.  mrcnn_sources_to_planes_check: the status for those sizes.               */
+int mrcnn_sources_to_planes_check(int n, int shrink, int h, int w);
+int mrcnn_sources_to_planes(const void* pool, int64_t pool_words, const mrcnn_tile_source* desc, int n, int shrink, int h, int w,
+                            void* planes, int32_t* count, int32_t* box, void* stream);
+
 /* The pixel work of the tester (Analyzer.compute_performances / compute_det_mask_pars, mrcnn/analyze.py:1502-1861), on the bit
  * planes and boxes of the mask graph above (boxes as _pack / _union give them; a box larger than the plane's own is allowed, a
  * smaller one hides pixels).  Nothing is allocated, nothing synchronises, no atomics.  na, nb, n, H or W <= 0: MRCNN_ERR_ARG.
@@ -530,6 +542,25 @@ size_t mrcnn_fits_tiles_workspace(const mrcnn_fits_tile* tiles_host, int T, int 
 int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY, int NX, const mrcnn_fits_tile* tiles_host,
                             const mrcnn_fits_tile* tiles_dev, int T, const double* zscale_contrasts, void* rgb, size_t rgb_bytes,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* The overview frame of a whole mosaic (the host statement is fits.mosaic_overview_host): the chain of
+ * mrcnn_fits_to_rgb on the WHOLE plane with one zscale contrast, then shrunk by block maxima:
+ *   plane   [ny, nx] float32 where it lies, native or (big_endian != 0) in FITS byte order; 4-byte aligned (16-byte aligned
+ *           planes are read with 16-byte loads).  It is read twice, once for the statistics and once for the pixels; no copy of
+ *           it is made;
+ *   G       [ny, nx] = one channel of mrcnn_fits_to_rgb(plane) with zscale_contrasts = (contrast, contrast, contrast);
+ *   out     [h, w, 3] uint8, h = ceil(ny / shrink), w = ceil(nx / shrink): out[Y, X, :] = max of G over rows shrink Y ..
+ *           min(shrink (Y + 1), ny) - 1 and columns shrink X .. min(shrink (X + 1), nx) - 1; out_bytes >= 3 h w.  A plane
+ *           without a finite pixel gives zeros.
+ * ny, nx or shrink <= 0, a contrast that is not finite, a missing or misaligned pointer, out_bytes too small: MRCNN_ERR_ARG;
+ * ny * nx > 2^31 - 1: MRCNN_ERR_UNSUPPORTED; a workspace below mrcnn_mosaic_overview_workspace(ny, nx) (24 bytes per 1024
+ * pixels; 0 for a plane the call would refuse) or not 16-byte aligned: MRCNN_ERR_WORKSPACE.  A refused call launches and writes
+ * nothing.  mrcnn_mosaic_overview_check: the status for those sizes; launches nothing.  Four launches on `stream`, nothing
+ * allocated, nothing synchronised, no floating-point atomics: bitwise the same from run to run.                              */
+int mrcnn_mosaic_overview_check(int ny, int nx, int shrink, double contrast);
+size_t mrcnn_mosaic_overview_workspace(int ny, int nx);
+int mrcnn_mosaic_overview(const void* plane, int big_endian, int ny, int nx, int shrink, double contrast, void* out, size_t out_bytes,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* detect() pre-processing (MaskRCNN.mold_inputs, mrcnn/model.py:2519-2556, for uint8 images): utils.resize_image's pixel work
  * (mrcnn/utils.py:456-561: bilinear up-scaling h x w -> oh x ow through skimage.transform.resize(order=1, mode='constant',

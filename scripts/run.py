@@ -19,7 +19,8 @@ produced.
 `detect --split_img_in_tiles --merge_tile_sources` is the reference's SFinder (caesar_mrcnn_amd/sfinder.py): sources that
 straddle tile borders are merged and one catalogue (objects gain `merged`, names S1..Sn) is written by rank 0; with
 `--compute_source_params` every object also gains the reference's parameters (nPix, S .. flux, X0 .. Y0w_wcs, Xmin .. Ymax_wcs);
-with `--tile_batch N` the mosaic is read and uploaded once and the tiles are cut, stretched and detected N at a time on the GPU.
+with `--tile_batch N` the mosaic is read and uploaded once and the tiles are cut, stretched and detected N at a time on the GPU;
+with `--draw_mosaic` the overview picture of the whole mosaic, the merged catalogue drawn on it, is written as well.
 """
 import argparse
 import json
@@ -132,6 +133,13 @@ def parse_args(argv=None):
                    help="extension, with --split_img_in_tiles --merge_tile_sources: read and upload the mosaic once, cut and stretch "
                         "the tiles on the GPU and detect them N at a time (the model is built for batches of N); needs the default "
                         "stretch flags; default 0: one file read, host stretch and detect call per tile")
+    p.add_argument('--draw_mosaic', action='store_true', default=False,
+                   help="extension, with --split_img_in_tiles --merge_tile_sources: draw the overview picture of the whole mosaic -- "
+                        "stretched as a tile is, shrunk by block maxima -- with the merged catalogue's contours, boxes and names on "
+                        "it, to mosaic_<image>.png (rendered on the GPU)")
+    p.add_argument('--mosaic_outfile', type=str, default="", help="--draw_mosaic to this file")
+    p.add_argument('--mosaic_shrink', type=int, default=0,
+                   help="with --draw_mosaic: mosaic pixels per picture pixel and side; default 0: ceil(longer side / 1024)")
     args = p.parse_args(argv)
     if (args.compute_map or args.map_outdir) and not (args.command == "test" and args.reference_tester):
         p.error("--compute_map / --map_outdir belong to `test --reference_tester`")
@@ -155,6 +163,17 @@ def draw_settings(args, ntiles=1):
     if wanted and ntiles > 1:
         logger.warning("A tiled detect draws nothing: --draw / --detect_outfile ignored")
     return wanted and ntiles == 1, getattr(args, "detect_outfile", "") or ""
+
+
+def mosaic_settings(args):
+    """(SFinder.draw_mosaic, SFinder.mosaic_outfile, SFinder.mosaic_shrink) of `detect`: --mosaic_outfile NAME implies
+    --draw_mosaic; both mean something only with --split_img_in_tiles --merge_tile_sources, elsewhere one warning and nothing."""
+    wanted = bool(getattr(args, "draw_mosaic", False) or getattr(args, "mosaic_outfile", ""))
+    tiled = args.command == "detect" and args.split_img_in_tiles and args.merge_tile_sources
+    if wanted and not tiled:
+        logger.warning("--draw_mosaic / --mosaic_outfile need `detect --split_img_in_tiles --merge_tile_sources`: ignored")
+    shrink = getattr(args, "mosaic_shrink", 0)
+    return wanted and bool(tiled), getattr(args, "mosaic_outfile", "") or "", shrink if shrink >= 1 else None
 
 
 def build_config(args, class_dict_model):
@@ -351,6 +370,7 @@ def detect_merged(args, model, cfg):
     sf.outfile_ds9 = os.path.splitext(sf.outfile_json)[0] + ".reg"
     sf.compute_params = bool(args.compute_source_params)
     sf.tile_batch = tile_batch_of(args)
+    sf.draw_mosaic, sf.mosaic_outfile, sf.mosaic_shrink = mosaic_settings(args)
     if sf.run_parallel() < 0:
         logger.error("Failed to run the tiled source finder on image %s!" % args.image)
         return -1
@@ -426,6 +446,8 @@ def main(argv=None):
     except Exception:
         logger.error("Failed to convert class dict string to dict!")
         return 1
+    if not (args.command == "detect" and args.split_img_in_tiles and args.merge_tile_sources):
+        mosaic_settings(args)                    # the one warning for flags that mean nothing here
     from caesar_mrcnn_amd import model as modellib
     cfg = build_config(args, class_dict_model)
     cfg.display()
