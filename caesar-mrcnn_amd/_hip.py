@@ -64,6 +64,16 @@ class BwdEpilogue(C.Structure):
         ("act", C.c_int32), ("dy", C.c_void_p)]
 
 
+class ConvPlan(C.Structure):
+    """mrcnn_conv_plan (include/mrcnn_hip.h): what a float32 convolution launch would do, from mrcnn_conv2d_fwd_plan."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "bm", "bn", "ksplit", "ksteps", "grid", "reduce", "mt_full", "tail_ksplit",
+                                          "tail_ksteps", "slab_bytes")]
+
+
+CONV_KERNELS = ("TILE", "BLDS", "GLDS", "BLDS_SPLITK", "BLDS_TAIL", "SK", "SK16", "SK64")      # MRCNN_CONV_*, by value
+CONV_REDUCTIONS = ("NONE", "SCALAR", "VEC", "BWD")                                            # MRCNN_CONV_RED_*
+
+
 class BwdEpilogueH16(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("out", "z", "scale", "mean", "rstd", "dgamma", "dbeta", "dbias")] + [
         ("act", C.c_int32), ("dy", C.c_void_p), ("grad_multiplier", C.c_float)]
@@ -93,6 +103,7 @@ _SIGNATURES = {
     "mrcnn_conv2d_fwd": (C.c_int, [C.POINTER(ConvDesc)] + [_P] * 9),
     "mrcnn_conv2d_fwd_ws": (C.c_int, [C.POINTER(ConvDesc)] + [_P] * 9 + [C.c_size_t, _P]),
     "mrcnn_conv2d_fwd_workspace": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "mrcnn_conv2d_fwd_plan": (C.c_int, [C.POINTER(ConvDesc)] + [_P] * 9 + [C.c_size_t, C.POINTER(BwdEpilogue), C.POINTER(ConvPlan)]),
     "mrcnn_conv2d_fwd_multi_workspace": (C.c_size_t, [C.POINTER(ConvProblem), C.c_int]),
     "mrcnn_conv2d_fwd_multi": (C.c_int, [C.POINTER(ConvProblem), C.c_int, _P, C.c_size_t, _P]),
     "mrcnn_conv2d_wgrad_multi_workspace": (C.c_size_t, [C.POINTER(WgradProblem), C.c_int]),
@@ -235,7 +246,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_overview_check", "_planes_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
+_NO_RECORD = ("_workspace", "_fwd_plan", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_overview_check", "_planes_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
 
 
 class _LibProxy(object):

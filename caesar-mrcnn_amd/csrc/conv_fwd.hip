@@ -765,8 +765,9 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_multi_kernel(const C
     else conv_splitk_epilogue_body(mp.a[g], blockIdx.x - (unsigned)mp.efirst[g]);
 }
 
+static inline bool al(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }   // 16-byte aligned (or NULL)
+
 static bool splitk_epilogue_vec_ok(const ConvArgs& a) {
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     if ((a.Cout & 3) || (a.cmod & 3) || (long long)a.M * a.Cout >= (1ll << 31)) return false;
     if (!a.dense && ((a.ons | a.ohs | a.ows) & 3)) return false;
     return al(a.slab) && al(a.out) && al(a.z) && al(a.res) && al(a.bias) && al(a.scale) && al(a.shift);
@@ -1357,117 +1358,99 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_sk64_kernel(const ConvArgs p,
     }
 }
 
-static long long sk_max_tiles() { static const long long v = getenv("MRCNN_SK_MAX_TILES") ? atoll(getenv("MRCNN_SK_MAX_TILES")) : 512; return v; }
-// applicability window, measured (ResNet-101, layer loops and whole steps): 192 .. 512 tiles of 32 x 32 and >= 16 K-steps.
-// Fewer tiles (batch-1 detect: 64) leave three quarters of the SIMDs without a wave -- the old split over 16 K slices
-// spreads wider; more tiles than two per CU run in several rounds (M = 4 096: 39 vs 33 us); short K has nothing to split.
-// In the window: res4 2a 17.3 -> 10.6 us, 2b 26.0 -> 22.2 us per layer; sparse step 29.1 -> 28.5 ms.
-static long long sk_min_tiles() { static const long long v = getenv("MRCNN_SK_MIN_TILES") ? atoll(getenv("MRCNN_SK_MIN_TILES")) : 192; return v; }
-static int sk_min_steps() { static const int v = getenv("MRCNN_SK_MIN_STEPS") ? atoi(getenv("MRCNN_SK_MIN_STEPS")) : 16; return v; }
-
-// Shapes the single-launch kernel takes: a "fast" layer (Cin % 32 == 0), Cout % 32 == 0, dense NHWC output and residual,
-// 16-byte aligned operands, at most 64 taps, buffer-addressable tensors -- and small enough that the large-tile kernels
-// would not fill the chip (the caller decides that part).
-static bool conv_sk_shape_ok(const mrcnn_conv_desc* d, const ConvArgs& a) {
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (!a.fastA || !a.dense || d->Cout % 32 || d->out_mode != MRCNN_OUT_NHWC || d->res_mode == MRCNN_RES_UP2) return false;
-    if (d->KH * d->KW > 64) return false;
-    const long long xb = (long long)d->N * d->H * d->W * d->Cin * 4 + ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
-    if (xb >= 0x7FFFFFF0LL || (long long)a.Ktot * d->Cout * 4 >= 0x7FFFFFF0LL) return false;
-    return al(a.w) && al(a.out) && al(a.z) && al(a.res) && al(a.bias) && al(a.scale) && al(a.shift) && al(a.fb_out) && al(a.fb_z) &&
-           al(a.fb_scale) && al(a.fb_mean) && al(a.fb_rstd) && al(a.fb_dy);
-}
-
-static bool conv_sk_ok(const mrcnn_conv_desc* d, const ConvArgs& a) {
-    static const bool on = !(getenv("MRCNN_SK_KERNEL") && getenv("MRCNN_SK_KERNEL")[0] == '0');
-    return on && conv_sk_shape_ok(d, a);
-}
-
-// Window of conv_fwd_sk64_kernel in workgroups (64 x 64 tiles): 64 .. 512, the range measured with tools/trunk_layer_bench.py
-// --shortk (Cout = 1024, K = 256; pair -> one launch, forward / data gradient with the backward epilogue, alone):
-//   M =  256 ( 64 workgroups) 10.9 ->  9.6 us / 17.7 -> 13.9 us      M = 1024 (256) 17.8 -> 10.4 us / 24.8 -> 14.9 us
-//   M =  512 (128)            12.0 ->  9.8 us / 18.8 -> 14.2 us      M = 2048 (512) 26.0 -> 16.2 us / 36.3 -> 26.1 us
-// Smaller and larger grids are not measured and stay on the pair.  mrcnn_tuning_set("sk64", 1) lifts the window, 0 and
-// MRCNN_SK64_KERNEL=0 (read once) restore the two-launch plan.
-static long long sk64_min_wgs() { static const long long v = getenv("MRCNN_SK64_MIN_WGS") ? atoll(getenv("MRCNN_SK64_MIN_WGS")) : 64; return v; }
-static long long sk64_max_wgs() { static const long long v = getenv("MRCNN_SK64_MAX_WGS") ? atoll(getenv("MRCNN_SK64_MAX_WGS")) : 512; return v; }
-
-// Shapes conv_fwd_sk64_kernel takes in place of a TWO-slice split-K plan: 1 x 1, stride 1, no padding, Cout % 64 == 0, a K too
-// short for conv_fwd_sk_kernel (fewer K-steps than its four waves need), and everything conv_sk_shape_ok asks.
-static bool conv_sk64_ok(const mrcnn_conv_desc* d, const ConvArgs& a, int plan_ksplit, bool plan_dma_split) {
-    static const bool on = !(getenv("MRCNN_SK64_KERNEL") && getenv("MRCNN_SK64_KERNEL")[0] == '0');
-    if (!on || g_mrcnn_sk64 == 0 || plan_ksplit != 2 || plan_dma_split) return false;
-    if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad_t || d->pad_l || d->OH != d->H || d->OW != d->W) return false;
-    if (!a.vecB || d->Cout % 64 || d->cmod != d->Cout || a.nk >= sk_min_steps() || !conv_sk_shape_ok(d, a)) return false;
-    if (g_mrcnn_sk64 == 1) return true;
-    const long long wgs = (long long)((a.M + 63) / 64) * (d->Cout / 64);
-    return wgs >= sk64_min_wgs() && wgs <= sk64_max_wgs();
-}
-
-static void launch_splitk_reduction(const ConvArgs& a, hipStream_t s);
-
-template <int BM, int BN, int WM, int WN>
-static int launch_conv(const ConvArgs& a, hipStream_t s) {
-    const int mt = (a.M + BM - 1) / BM, nt = (a.Cout + BN - 1) / BN;
-    if (a.fastA)
-        hipLaunchKernelGGL((conv_fwd_kernel<BM, BN, WM, WN, true>), dim3((unsigned)(mt * nt * a.ksplit)), dim3(WM * WN * 64), 0, s, a);
-    else
-        hipLaunchKernelGGL((conv_fwd_kernel<BM, BN, WM, WN, false>), dim3((unsigned)(mt * nt * a.ksplit)), dim3(WM * WN * 64), 0, s, a);
-    launch_splitk_reduction(a, s);
-    return mrcnn_launch_status();
-}
-
-// second pass of a split-K launch: slab sum + epilogue (or the backward epilogue of the layer below)
-static void launch_splitk_reduction(const ConvArgs& a, hipStream_t s) {
-    if (a.ksplit > 1 && a.fb_act >= 0) {         // slabs -> epilogue backward of the layer below
-        const EpiGrid g = mrcnn_epilogue_grid(a.M, a.Cout);
-        hipLaunchKernelGGL(conv_splitk_epilogue_bwd_kernel, dim3(g.row_blocks, g.chan_blocks), dim3(256), 0, s, a,
-                           g.rows_per_block, g.lg);
-    } else if (a.ksplit > 1) {
-        const long long n = (long long)a.M * a.Cout;
-        if (splitk_epilogue_vec_ok(a))
-            hipLaunchKernelGGL(conv_splitk_epilogue_vec_kernel, dim3((unsigned)cdiv64(n / 4, 256)), dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, a);
-    }
-}
-
+// Host side of the float32 convolution: thresholds (compile-time constants, each next to the measurement behind it), the
+// predicates every rule shares, the planner (which kernel, which grid, which reduction) and the launcher.
 // 128-row tiles only when they give every CU several workgroups (256 CUs x 5 resident): fewer, and the chip idles
 #ifndef CONV_BIG_TILE_MIN_BLOCKS
 #define CONV_BIG_TILE_MIN_BLOCKS 640
 #endif
+// split K below this many output tiles, into about CONV_SPLITK_TARGET workgroups (~2 per CU: more slices cost more slab traffic
+// than they hide latency)
+#define CONV_SPLITK_BELOW 768
+#define CONV_SPLITK_TARGET 512
+// LDS-DMA kernel with split-K (mid-size layers): from this many 128 x 128 tiles on, cut into about CONV_DMA_SPLIT_TARGET workgroups
+#define CONV_DMA_SPLIT_MIN_TILES 96
+#define CONV_DMA_SPLIT_TARGET 768
+// Window of conv_fwd_sk_kernel, measured (ResNet-101, layer loops and whole steps): 192 .. 512 tiles of 32 x 32 and >= 16 K-steps.
+// Fewer tiles (batch-1 detect: 64) leave three quarters of the SIMDs without a wave -- the old split over 16 K slices
+// spreads wider; more tiles than two per CU run in several rounds (M = 4 096: 39 vs 33 us); short K has nothing to split.
+// In the window: res4 2a 17.3 -> 10.6 us, 2b 26.0 -> 22.2 us per layer; sparse step 29.1 -> 28.5 ms.
+#define CONV_SK_MIN_TILES 192
+#define CONV_SK_MAX_TILES 512
+#define CONV_SK_MIN_STEPS 16
+// Window of conv_fwd_sk16_kernel (batch-1 detect: res4 / res5, the upper pyramid levels): 64 .. 2048 tiles of 16 x 16, K >= 256
+#define CONV_SK16_MIN_TILES 64
+#define CONV_SK16_MAX_TILES 2048
+#define CONV_SK16_MIN_K 256
+// Window of conv_fwd_sk64_kernel in workgroups (64 x 64 tiles): 64 .. 512, the range measured with tools/trunk_layer_bench.py
+// --shortk (Cout = 1024, K = 256; pair -> one launch, forward / data gradient with the backward epilogue, alone):
+//   M =  256 ( 64 workgroups) 10.9 ->  9.6 us / 17.7 -> 13.9 us      M = 1024 (256) 17.8 -> 10.4 us / 24.8 -> 14.9 us
+//   M =  512 (128)            12.0 ->  9.8 us / 18.8 -> 14.2 us      M = 2048 (512) 26.0 -> 16.2 us / 36.3 -> 26.1 us
+// Smaller and larger grids are not measured and stay on the pair.  mrcnn_tuning_set("sk64", 1) lifts the window, 0 restores
+// the two-launch plan.
+#define CONV_SK64_MIN_WGS 64
+#define CONV_SK64_MAX_WGS 512
+
+// tiles of bm x bn that cover M x Cout; the slabs of a launch cut into ksplit K slices
+static inline long long conv_tiles(long long M, int Cout, int bm, int bn) { return cdiv64(M, bm) * cdiv64(Cout, bn); }
+static inline size_t conv_slab_bytes(int ksplit, long long M, int Cout) { return (size_t)ksplit * M * Cout * sizeof(float); }
+// buffer addressing (32-bit descriptor range): the input plus the padding shift of the first tap, and the weights
+static inline long long conv_x_shift(const mrcnn_conv_desc* d) { return ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4; }
+static inline long long conv_x_bytes(const mrcnn_conv_desc* d) { return (long long)d->N * d->H * d->W * d->Cin * 4; }
+static inline bool conv_x_in_range(const mrcnn_conv_desc* d) { return conv_x_bytes(d) + conv_x_shift(d) < 0x7FFFFFF0LL; }
+static inline bool conv_w_in_range(const mrcnn_conv_desc* d) { return (long long)d->KH * d->KW * d->Cin * d->Cout * 4 < 0x7FFFFFF0LL; }
+// what the vector code of the backward epilogue needs of the channel count; the output tile class by width
+static inline bool conv_pow2c(int Cout) { return Cout >= 16 && (Cout & (Cout - 1)) == 0; }
+static inline int conv_tile_bn(int Cout) { return Cout <= 32 ? 32 : (Cout <= 64 ? 64 : 128); }
+
+// K-slicing rule: nk K-steps into `want` slices, at least 4 K-steps per slice, at most 16 slices, none below 8 K-steps
+struct ConvKSlices { int ksteps, ksplit; };
+static ConvKSlices conv_k_slices(int nk, long long want) {
+    ConvKSlices s = {nk, 1};
+    long long ks = want < nk / 4 ? want : nk / 4;
+    if (ks > 16) ks = 16;
+    if (nk >= 8 && ks >= 2) {
+        s.ksteps = (int)((nk + ks - 1) / ks);
+        s.ksplit = (nk + s.ksteps - 1) / s.ksteps;
+    }
+    return s;
+}
+
+// Shapes the single-launch kernels take: a "fast" layer (Cin % 32 == 0), Cout % 32 == 0, dense NHWC output and residual,
+// 16-byte aligned operands, at most 64 taps, buffer-addressable tensors -- and small enough that the large-tile kernels
+// would not fill the chip (the planner decides that part).
+static bool conv_sk_shape_ok(const mrcnn_conv_desc* d, const ConvArgs& a) {
+    if (!a.fastA || !a.dense || d->Cout % 32 || d->out_mode != MRCNN_OUT_NHWC || d->res_mode == MRCNN_RES_UP2) return false;
+    if (d->KH * d->KW > 64 || !conv_x_in_range(d) || !conv_w_in_range(d)) return false;
+    return al(a.w) && al(a.out) && al(a.z) && al(a.res) && al(a.bias) && al(a.scale) && al(a.shift) && al(a.fb_out) && al(a.fb_z) &&
+           al(a.fb_scale) && al(a.fb_mean) && al(a.fb_rstd) && al(a.fb_dy);
+}
+
 struct ConvPlan { int bm, bn, ksplit, ksteps; bool dma_split; };
 
 // Tile + split-K choice.  Large problems: 128-row tiles, no split.  Small feature maps (C3..C5, P3..P6
 // at 256^2 inputs) have only 4..128 output tiles, far fewer than the 256 CUs, so the K loop is cut into
 // up to 16 slices that run as separate workgroups (slabs summed by conv_splitk_epilogue_kernel).
-static ConvPlan plan_conv(const mrcnn_conv_desc* d, bool allow_dma_split = true) {
+static ConvPlan plan_conv(const mrcnn_conv_desc* d, bool allow_dma_split) {
     ConvPlan pl;
     const long long M = (long long)d->N * d->OH * d->OW;
     const int Cout = d->Cout;
     const int nk = (d->KH * d->KW * d->Cin + 31) / 32;
-    long long blocks;
-    if (Cout <= 32) {
-        pl.bn = 32;
-        pl.bm = ((M + 127) / 128 >= 256) ? 128 : 64;
-    } else if (Cout <= 64) {
-        pl.bn = 64;
-        pl.bm = ((M + 127) / 128 >= 256) ? 128 : 64;
+    pl.bn = conv_tile_bn(Cout);
+    if (pl.bn < 128) {
+        pl.bm = cdiv64(M, 128) >= 256 ? 128 : 64;
     } else {
-        pl.bn = 128;
-        pl.bm = (((M + 127) / 128) * ((Cout + 127) / 128) >= CONV_BIG_TILE_MIN_BLOCKS) ? 128 : 64;
-        if (pl.bm == 64 && ((M + 63) / 64) * ((Cout + 127) / 128) < 128) pl.bn = 64;   // more, smaller tiles
+        pl.bm = conv_tiles(M, Cout, 128, 128) >= CONV_BIG_TILE_MIN_BLOCKS ? 128 : 64;
+        if (pl.bm == 64 && conv_tiles(M, Cout, 64, 128) < 128) pl.bn = 64;   // more, smaller tiles
     }
     pl.dma_split = false;
     // mid-size layers (too few 128x128 tiles to fill the chip, enough K to cut): LDS-DMA kernel with split-K --
-    // each slice at least 16 K-steps of 16; MRCNN_DMA_SPLIT_MIN_TILES=0 switches it off (A/B)
-    static const long long dma_min_tiles = getenv("MRCNN_DMA_SPLIT_MIN_TILES") ? atoll(getenv("MRCNN_DMA_SPLIT_MIN_TILES")) : 96;
-    const long long t128 = ((M + 127) / 128) * (Cout / 128);
+    // each slice at least 16 K-steps of 16
+    const long long t128 = conv_tiles(M, Cout, 128, 128);
     const int nk16 = d->KH * d->KW * d->Cin / 16;
-    if (allow_dma_split && dma_min_tiles > 0 && pl.bm == 64 && Cout % 128 == 0 && d->Cin % 32 == 0 && d->KH * d->KW <= 64 &&
-        t128 >= dma_min_tiles && t128 < CONV_BIG_TILE_MIN_BLOCKS && nk16 >= 32) {
-        static const long long dma_target = getenv("MRCNN_DMA_SPLIT_TARGET") ? atoll(getenv("MRCNN_DMA_SPLIT_TARGET")) : 768;
-        long long ks = (dma_target + t128 - 1) / t128;
+    if (allow_dma_split && pl.bm == 64 && Cout % 128 == 0 && d->Cin % 32 == 0 && d->KH * d->KW <= 64 &&
+        t128 >= CONV_DMA_SPLIT_MIN_TILES && t128 < CONV_BIG_TILE_MIN_BLOCKS && nk16 >= 32) {
+        long long ks = (CONV_DMA_SPLIT_TARGET + t128 - 1) / t128;
         if (ks > nk16 / 16) ks = nk16 / 16;
         if (ks > 16) ks = 16;
         if (ks >= 2) {
@@ -1478,21 +1461,9 @@ static ConvPlan plan_conv(const mrcnn_conv_desc* d, bool allow_dma_split = true)
             return pl;
         }
     }
-    blocks = ((M + pl.bm - 1) / pl.bm) * ((Cout + pl.bn - 1) / pl.bn);
-    pl.ksplit = 1;
-    pl.ksteps = nk;
-    static const long long split_below = getenv("MRCNN_SPLITK_BELOW") ? atoll(getenv("MRCNN_SPLITK_BELOW")) : 768;
-    if (blocks < split_below && nk >= 8) {
-        static const long long target = getenv("MRCNN_SPLITK_TARGET") ? atoll(getenv("MRCNN_SPLITK_TARGET")) : 512;
-        long long want = (target + blocks - 1) / blocks;         // ~2 workgroups per CU: more slices cost more slab traffic than they hide latency
-        long long maxs = nk / 4;                               // at least 4 K-steps per slice
-        long long ks = want < maxs ? want : maxs;
-        if (ks > 16) ks = 16;
-        if (ks >= 2) {
-            pl.ksteps = (int)((nk + ks - 1) / ks);
-            pl.ksplit = (nk + pl.ksteps - 1) / pl.ksteps;
-        }
-    }
+    const long long blocks = conv_tiles(M, Cout, pl.bm, pl.bn);
+    const ConvKSlices ks = conv_k_slices(nk, blocks < CONV_SPLITK_BELOW ? (CONV_SPLITK_TARGET + blocks - 1) / blocks : 1);
+    pl.ksteps = ks.ksteps; pl.ksplit = ks.ksplit;
     return pl;
 }
 
@@ -1542,12 +1513,11 @@ static ConvTailPlan plan_conv_tail(const mrcnn_conv_desc* d) {
 
 extern "C" size_t mrcnn_conv2d_fwd_workspace(const mrcnn_conv_desc* d) {
     if (!d || d->N <= 0 || d->OH <= 0 || d->OW <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 || d->Cin <= 0) return 0;
-    ConvPlan pl = plan_conv(d);
-    if (pl.ksplit <= 1) {
-        if (pl.bm == 128 && pl.bn == 128) return plan_conv_tail(d).slab_bytes;     // 0 unless the tail split applies
-        return 0;
-    }
-    return (size_t)pl.ksplit * d->N * d->OH * d->OW * d->Cout * sizeof(float);
+    // the first stage of conv_plan_launch with the DMA split allowed: the most any launch of this descriptor uses (the
+    // single-launch kernels that replace a split plan use none of it)
+    const ConvPlan pl = plan_conv(d, true);
+    if (pl.ksplit > 1) return conv_slab_bytes(pl.ksplit, (long long)d->N * d->OH * d->OW, d->Cout);
+    return pl.bm == 128 && pl.bn == 128 ? plan_conv_tail(d).slab_bytes : 0;     // 0 unless the tail split applies
 }
 
 // argument checks + everything of ConvArgs that does not depend on the launch plan
@@ -1588,135 +1558,171 @@ static int conv_fill_args(const mrcnn_conv_desc* d, const float* x, const float*
     return MRCNN_OK;
 }
 
-static int conv_fwd_impl(const mrcnn_conv_desc* d, const float* x, const float* w,
-                         const float* bias, const float* scale, const float* shift,
-                         const float* res, float* out, float* z_out, void* workspace,
-                         size_t workspace_bytes, const mrcnn_bwd_epilogue* ep, void* stream) {
-    ConvArgs a;
-    const int rc = conv_fill_args(d, x, w, bias, scale, shift, res, out, z_out, a);
-    if (rc != MRCNN_OK) return rc;
+// Everything that decides a launch, in one place: fills the plan (mrcnn_conv_plan, include/mrcnn_hip.h: which kernel, on which
+// grid, with which K slices, and the reduction that follows).  `a` is what conv_fill_args left, with the epilogue's operands when
+// has_ep: no plan state yet, a.slab still NULL.  Nothing is allocated, no tensor is read; the environment only for the tail split.
+static int conv_plan_launch(const mrcnn_conv_desc* d, const ConvArgs& a, bool has_ep, const void* workspace, size_t workspace_bytes,
+                            mrcnn_conv_plan& p) {
     const long long M = a.M;
-    hipStream_t s = (hipStream_t)stream;
-
-    const long long xbytes_all = (long long)d->N * d->H * d->W * d->Cin * 4 + ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
-    const bool buf_ok = a.fastA && a.vecB && xbytes_all < 0x7FFFFFF0LL && (long long)a.Ktot * d->Cout * 4 < 0x7FFFFFF0LL &&
-                        !mrcnn_force_flat_glds();
-    ConvPlan pl = plan_conv(d, buf_ok);
-    size_t need = pl.ksplit > 1 ? (size_t)pl.ksplit * M * d->Cout * sizeof(float) : 0;
-    if (pl.dma_split && (!workspace || workspace_bytes < need)) {  // sized for another plan: fall back to the 64-row tiles
-        pl = plan_conv(d, false);
-        need = pl.ksplit > 1 ? (size_t)pl.ksplit * M * d->Cout * sizeof(float) : 0;
-    }
-    if (need && (!workspace || workspace_bytes < need)) {        // no room: run unsplit
-        pl.ksplit = 1;
-        pl.ksteps = a.nk;
-    }
-    a.ksplit = pl.ksplit; a.ksteps = pl.ksteps; a.slab = (float*)workspace;
-    const bool lds_dma = pl.bm == 128 && pl.bn == 128 && pl.ksplit == 1 && a.fastA && a.vecB && d->Cout % 128 == 0;
-    if (ep) {                                   // fused backward epilogue: LDS-DMA kernel, dense output, plain store
-        const long long xb = (long long)d->N * d->H * d->W * d->Cin * 4 + ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
-        const bool pow2c = d->Cout >= 16 && (d->Cout & (d->Cout - 1)) == 0;
-        auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        const bool split_ok = pl.ksplit > 1 && pow2c && al(out) && al(res) && al(ep->out) && al(ep->z) && al(ep->scale) &&
-                              al(ep->mean) && al(ep->rstd);
-        const bool dma_ok = lds_dma && xb < 0x7FFFFFF0LL && !mrcnn_force_flat_glds() && !ep->dy;   // second output: split-K path only
-        if (!(dma_ok || split_ok) || !a.dense || bias || scale || z_out || d->act != MRCNN_ACT_NONE || d->res_mode == MRCNN_RES_UP2)
+    const int Cout = d->Cout;
+    const bool x_buf = conv_x_in_range(d) && !mrcnn_force_flat_glds();      // the input through a buffer descriptor
+    const bool buf = x_buf && conv_w_in_range(d);                           // ... and the weights
+    // Tiles and K slices.  The DMA split needs buffer addressing; a DMA-split plan whose slabs do not fit the workspace (sized
+    // for another plan) is planned again without it, and a split whose slabs still do not fit runs unsplit on that plan's tiles.
+    const auto fits = [&](const ConvPlan& q) { return q.ksplit <= 1 || (workspace && workspace_bytes >= conv_slab_bytes(q.ksplit, M, Cout)); };
+    ConvPlan pl = plan_conv(d, a.fastA && a.vecB && buf);
+    if (pl.dma_split && !fits(pl)) pl = plan_conv(d, false);
+    if (!fits(pl)) { pl.ksplit = 1; pl.ksteps = a.nk; }
+    const bool split = pl.ksplit > 1;
+    const bool lds_dma = pl.bm == 128 && pl.bn == 128 && !split && a.fastA && a.vecB && Cout % 128 == 0;
+    // what the slab reduction with the backward epilogue needs: a power-of-two channel count and aligned operands
+    const bool ep_vec = conv_pow2c(Cout) && al(a.out) && al(a.res) && al(a.fb_out) && al(a.fb_z) && al(a.fb_scale) && al(a.fb_mean) &&
+                        al(a.fb_rstd);
+    if (has_ep) {           // fused backward epilogue: a split plan (any kernel but sk16) or the unsplit LDS-DMA kernel, dense output, plain store
+        const bool dma_ok = lds_dma && x_buf && !a.fb_dy;                   // second output: split-K path only
+        if (!(dma_ok || (split && ep_vec)) || !a.dense || a.bias || a.scale || a.z || d->act != MRCNN_ACT_NONE ||
+            d->res_mode == MRCNN_RES_UP2)
             return MRCNN_ERR_UNSUPPORTED;
-        if ((ep->act != MRCNN_ACT_NONE && ep->act != MRCNN_ACT_RELU) || (ep->act == MRCNN_ACT_RELU && !ep->out)) return MRCNN_ERR_ARG;
-        if (ep->dgamma && (!ep->z || !ep->mean || !ep->rstd)) return MRCNN_ERR_ARG;
-        a.fb_act = ep->act; a.fb_out = ep->out; a.fb_z = ep->z; a.fb_scale = ep->scale; a.fb_mean = ep->mean; a.fb_rstd = ep->rstd;
-        a.fb_dgamma = ep->dgamma; a.fb_dbeta = ep->dbeta; a.fb_dbias = ep->dbias;
-        a.fb_dy = ep->dy;
-        if (ep->dy && (reinterpret_cast<uintptr_t>(ep->dy) & 15)) return MRCNN_ERR_ARG;
+        if ((a.fb_act != MRCNN_ACT_NONE && a.fb_act != MRCNN_ACT_RELU) || (a.fb_act == MRCNN_ACT_RELU && !a.fb_out)) return MRCNN_ERR_ARG;
+        if (a.fb_dgamma && (!a.fb_z || !a.fb_mean || !a.fb_rstd)) return MRCNN_ERR_ARG;
+        if (!al(a.fb_dy)) return MRCNN_ERR_ARG;
     }
-    // small layer that the planner would cut into K slices: one launch instead, the four waves of a workgroup split K
-    // ... and the layers too small even for that (batch-1 detect: res4 / res5, the upper pyramid levels): 16 x 16 tiles, forward only
-    {
-        static const bool sk16_on = !(getenv("MRCNN_SK16_KERNEL") && getenv("MRCNN_SK16_KERNEL")[0] == '0');
-        static const long long sk16_min = getenv("MRCNN_SK16_MIN_TILES") ? atoll(getenv("MRCNN_SK16_MIN_TILES")) : 64;
-        const long long t32 = (long long)((a.M + 31) / 32) * (d->Cout / 32), t16 = (long long)((a.M + 15) / 16) * (d->Cout / 16);
-        // too few 32 x 32 tiles for conv_fwd_sk_kernel, or enough of them but a K too short for it (res4 2c at batch 1: K = 256)
-        const bool small = t32 < sk_min_tiles() || (t32 <= sk_max_tiles() && a.nk < sk_min_steps() && !getenv("MRCNN_SK16_NO_SHORTK"));
-        // inference only (mrcnn_tuning_set("sk16", 1) around engine.infer): in training it measured level, and the float32 replay
-        // tests sit within one proposal flip of any change in a forward layer's rounding
-        if (sk16_on && g_mrcnn_sk16 && pl.ksplit > 1 && a.fb_act < 0 && conv_sk_ok(d, a) && small && t16 >= sk16_min && t16 <= 2048 && a.Ktot >= 256) {
-            const long long xbytes = (long long)d->N * d->H * d->W * d->Cin * 4;
-            const long long shift = ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
-            a.ksplit = 1; a.ksteps = a.nk; a.slab = nullptr;
-            hipLaunchKernelGGL(conv_fwd_sk16_kernel, dim3((unsigned)t16), dim3(256), 0, s, a, (unsigned)shift, (unsigned)(xbytes + shift));
-            return mrcnn_launch_status();
+    p = mrcnn_conv_plan();
+    p.ksplit = 1; p.ksteps = a.nk; p.reduce = MRCNN_CONV_RED_NONE;
+    // Kernels in order of preference.  The three single-launch kernels replace a split plan (so they need its workspace to be
+    // there), run without slabs, and take a backward epilogue wherever the split plan would (ep_vec held), except sk16.
+    const bool sk_shape = split && conv_sk_shape_ok(d, a);
+    const long long t32 = conv_tiles(M, Cout, 32, 32), t16 = conv_tiles(M, Cout, 16, 16), wg64 = conv_tiles(M, Cout, 64, 64);
+    // sk16: too few 32 x 32 tiles for conv_fwd_sk_kernel, or enough of them but a K too short for it (res4 2c at batch 1: K = 256).
+    // Inference only (mrcnn_tuning_set("sk16", 1) around engine.infer): in training it measured level, and the float32 replay
+    // tests sit within one proposal flip of any change in a forward layer's rounding.  Forward only.
+    if (g_mrcnn_sk16 && sk_shape && !has_ep && (t32 < CONV_SK_MIN_TILES || (t32 <= CONV_SK_MAX_TILES && a.nk < CONV_SK_MIN_STEPS)) &&
+        t16 >= CONV_SK16_MIN_TILES && t16 <= CONV_SK16_MAX_TILES && a.Ktot >= CONV_SK16_MIN_K) {
+        p.kernel = MRCNN_CONV_SK16; p.bm = p.bn = 16; p.grid = (int32_t)t16;
+        return MRCNN_OK;
+    }
+    // sk64: a short-K 1 x 1 layer on a TWO-slice plan (res4 2c, the data gradient of res4 2a): stride 1, no padding, Cout % 64 == 0,
+    // a K too short for conv_fwd_sk_kernel; the two slices become accumulators, so ksteps stays the plan's slice boundary
+    if (g_mrcnn_sk64 != 0 && pl.ksplit == 2 && !pl.dma_split && sk_shape && d->KH == 1 && d->KW == 1 && d->stride == 1 && !d->pad_t &&
+        !d->pad_l && d->OH == d->H && d->OW == d->W && a.vecB && Cout % 64 == 0 && d->cmod == Cout && a.nk < CONV_SK_MIN_STEPS &&
+        (g_mrcnn_sk64 == 1 || (wg64 >= CONV_SK64_MIN_WGS && wg64 <= CONV_SK64_MAX_WGS))) {
+        p.kernel = MRCNN_CONV_SK64; p.bm = p.bn = 64; p.grid = (int32_t)wg64; p.ksplit = pl.ksplit; p.ksteps = pl.ksteps;
+        return MRCNN_OK;
+    }
+    // sk: a small layer the planner would cut into K slices: one launch, the four waves of a workgroup split K
+    if (sk_shape && !pl.dma_split && t32 >= CONV_SK_MIN_TILES && t32 <= CONV_SK_MAX_TILES && a.nk >= CONV_SK_MIN_STEPS) {
+        p.kernel = MRCNN_CONV_SK; p.bm = p.bn = 32; p.grid = (int32_t)t32;
+        return MRCNN_OK;
+    }
+    p.bm = pl.bm; p.bn = pl.bn; p.ksplit = pl.ksplit; p.ksteps = pl.ksteps;
+    p.grid = (int32_t)(conv_tiles(M, Cout, pl.bm, pl.bn) * pl.ksplit);
+    if (split) {                // second launch: slab sum + epilogue, or the backward epilogue of the layer below
+        // (a.slab is still NULL: the slabs' alignment is the workspace's)
+        p.reduce = has_ep ? MRCNN_CONV_RED_BWD : (al(workspace) && splitk_epilogue_vec_ok(a)) ? MRCNN_CONV_RED_VEC : MRCNN_CONV_RED_SCALAR;
+        p.slab_bytes = (int32_t)conv_slab_bytes(pl.ksplit, M, Cout);
+    }
+    // mid-size layer: LDS-DMA tiles, K cut into slices; else the generic tiles, split or not, unless the unsplit LDS-DMA kernel
+    // applies: buffer-addressed when input (plus the padding shift) and weights fit a 32-bit descriptor range
+    p.kernel = pl.dma_split ? MRCNN_CONV_BLDS_SPLITK : !lds_dma ? MRCNN_CONV_TILE : buf ? MRCNN_CONV_BLDS : MRCNN_CONV_GLDS;
+    if (p.kernel != MRCNN_CONV_BLDS) return MRCNN_OK;
+    const ConvTailPlan tp = plan_conv_tail(d);
+    if (tp.ok && a.dense && d->res_mode != MRCNN_RES_UP2 && d->out_mode == MRCNN_OUT_NHWC && workspace && workspace_bytes >= tp.slab_bytes &&
+        al(workspace) && (!has_ep || (ep_vec && !a.fb_dy))) {
+        // whole rounds: unsplit kernel with its fused epilogue; tail tiles: K slices + slab reduction on the tail rows
+        p.kernel = MRCNN_CONV_BLDS_TAIL;
+        p.grid = tp.mt_full * (Cout / 128);
+        p.mt_full = tp.mt_full; p.tail_ksplit = tp.ksplit; p.tail_ksteps = tp.ksteps; p.slab_bytes = (int32_t)tp.slab_bytes;
+        ConvArgs r = a;         // the reduction's problem: the tail rows
+        r.M = (int)(M - (long long)tp.mt_full * 128);
+        p.reduce = has_ep ? MRCNN_CONV_RED_BWD : splitk_epilogue_vec_ok(r) ? MRCNN_CONV_RED_VEC : MRCNN_CONV_RED_SCALAR;
+    }
+    return MRCNN_OK;
+}
+
+template <int BM, int BN, int WM, int WN>
+static void launch_conv_tile(const ConvArgs& a, unsigned grid, hipStream_t s) {
+    if (a.fastA) hipLaunchKernelGGL((conv_fwd_kernel<BM, BN, WM, WN, true>), dim3(grid), dim3(WM * WN * 64), 0, s, a);
+    else hipLaunchKernelGGL((conv_fwd_kernel<BM, BN, WM, WN, false>), dim3(grid), dim3(WM * WN * 64), 0, s, a);
+}
+
+// second pass of a split-K launch: slab sum + epilogue (or the backward epilogue of the layer below)
+static void launch_splitk_reduction(const ConvArgs& a, int reduce, hipStream_t s) {
+    const long long n = (long long)a.M * a.Cout;
+    if (reduce == MRCNN_CONV_RED_BWD) {         // slabs -> epilogue backward of the layer below
+        const EpiGrid g = mrcnn_epilogue_grid(a.M, a.Cout);
+        hipLaunchKernelGGL(conv_splitk_epilogue_bwd_kernel, dim3(g.row_blocks, g.chan_blocks), dim3(256), 0, s, a,
+                           g.rows_per_block, g.lg);
+    } else if (reduce == MRCNN_CONV_RED_VEC)
+        hipLaunchKernelGGL(conv_splitk_epilogue_vec_kernel, dim3((unsigned)cdiv64(n / 4, 256)), dim3(256), 0, s, a);
+    else if (reduce == MRCNN_CONV_RED_SCALAR)
+        hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, a);
+}
+
+// issue a plan: one switch over the kernel, then the reduction
+static int conv_launch(const mrcnn_conv_desc* d, ConvArgs& a, const mrcnn_conv_plan& p, void* workspace, hipStream_t s) {
+    const unsigned x_shift = (unsigned)conv_x_shift(d), x_records = (unsigned)(conv_x_bytes(d) + conv_x_shift(d));
+    const dim3 grid((unsigned)p.grid), wg(256);
+    a.ksplit = p.ksplit; a.ksteps = p.ksteps;
+    a.slab = p.kernel == MRCNN_CONV_SK || p.kernel == MRCNN_CONV_SK16 || p.kernel == MRCNN_CONV_SK64 ? nullptr : (float*)workspace;
+    switch (p.kernel) {
+    case MRCNN_CONV_SK16: hipLaunchKernelGGL(conv_fwd_sk16_kernel, grid, wg, 0, s, a, x_shift, x_records); break;
+    case MRCNN_CONV_SK64: hipLaunchKernelGGL(conv_fwd_sk64_kernel, grid, wg, 0, s, a, x_records); break;       // no padding: no shift
+    case MRCNN_CONV_SK: hipLaunchKernelGGL(conv_fwd_sk_kernel, grid, wg, 0, s, a, x_shift, x_records); break;
+    case MRCNN_CONV_BLDS_SPLITK: hipLaunchKernelGGL(conv_fwd_blds_splitk_kernel, grid, wg, 0, s, a, x_shift, x_records); break;
+    case MRCNN_CONV_BLDS: hipLaunchKernelGGL(conv_fwd_blds_kernel, grid, wg, 0, s, a, x_shift, x_records); break;
+    case MRCNN_CONV_GLDS: hipLaunchKernelGGL(conv_fwd_glds_kernel, grid, wg, 0, s, a); break;
+    case MRCNN_CONV_BLDS_TAIL: {
+        hipLaunchKernelGGL(conv_fwd_blds_kernel, grid, wg, 0, s, a, x_shift, x_records);
+        const int mt = (a.M + 127) / 128, nt = a.Cout / 128;
+        ConvArgs t = a;
+        t.mtile0 = p.mt_full; t.ksplit = p.tail_ksplit; t.ksteps = p.tail_ksteps;
+        hipLaunchKernelGGL(conv_fwd_blds_splitk_kernel, dim3((unsigned)((mt - p.mt_full) * nt * p.tail_ksplit)), wg, 0, s, t, x_shift,
+                           x_records);
+        const long long m1 = (long long)p.mt_full * 128, off = m1 * d->Cout;
+        ConvArgs r = t;                       // the reduction sees the tail rows as a problem of its own (dense NHWC)
+        r.M = (int)(a.M - m1); r.mtile0 = 0;
+        r.out = a.out + off;
+        if (a.z) r.z = a.z + off;
+        if (a.res) r.res = a.res + off;
+        if (a.fb_act >= 0) {
+            if (a.fb_out) r.fb_out = a.fb_out + off;
+            if (a.fb_z) r.fb_z = a.fb_z + off;
         }
-    }
-    // short-K 1 x 1 layer on a two-slice plan (res4 2c, the data gradient of res4 2a): one launch, the two slices as accumulators;
-    // a.ksteps stays the plan's slice boundary.  With a backward epilogue this point is reached only where split_ok held.
-    if (conv_sk64_ok(d, a, pl.ksplit, pl.dma_split)) {
-        a.slab = nullptr;
-        hipLaunchKernelGGL(conv_fwd_sk64_kernel, dim3((unsigned)(((a.M + 63) / 64) * (d->Cout / 64))), dim3(256), 0, s, a,
-                           (unsigned)((long long)a.M * d->Cin * 4));
+        launch_splitk_reduction(r, p.reduce, s);
         return mrcnn_launch_status();
     }
-    if (pl.ksplit > 1 && !pl.dma_split && conv_sk_ok(d, a) && (long long)((a.M + 31) / 32) * (d->Cout / 32) <= sk_max_tiles() &&
-        (long long)((a.M + 31) / 32) * (d->Cout / 32) >= sk_min_tiles() && a.nk >= sk_min_steps()) {
-        const long long xbytes = (long long)d->N * d->H * d->W * d->Cin * 4;
-        const long long shift = ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
-        a.ksplit = 1; a.ksteps = a.nk; a.slab = nullptr;
-        hipLaunchKernelGGL(conv_fwd_sk_kernel, dim3((unsigned)(((a.M + 31) / 32) * (d->Cout / 32))), dim3(256), 0, s, a, (unsigned)shift,
-                           (unsigned)(xbytes + shift));
-        return mrcnn_launch_status();
+    default:
+        if (p.bn == 32) p.bm == 128 ? launch_conv_tile<128, 32, 4, 1>(a, grid.x, s) : launch_conv_tile<64, 32, 2, 1>(a, grid.x, s);
+        else if (p.bn == 64) p.bm == 128 ? launch_conv_tile<128, 64, 2, 2>(a, grid.x, s) : launch_conv_tile<64, 64, 2, 2>(a, grid.x, s);
+        else p.bm == 128 ? launch_conv_tile<128, 128, 2, 2>(a, grid.x, s) : launch_conv_tile<64, 128, 2, 2>(a, grid.x, s);
     }
-    if (pl.dma_split && pl.ksplit > 1) {        // mid-size layer: LDS-DMA tiles, K cut into slices, slabs reduced by a second launch
-        const int mt = (a.M + 127) / 128, nt = a.Cout / 128;
-        const long long xbytes = (long long)d->N * d->H * d->W * d->Cin * 4;
-        const long long shift = ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
-        hipLaunchKernelGGL(conv_fwd_blds_splitk_kernel, dim3((unsigned)(mt * nt * a.ksplit)), dim3(256), 0, s, a, (unsigned)shift,
-                           (unsigned)(xbytes + shift));
-        launch_splitk_reduction(a, s);
-        return mrcnn_launch_status();
+    launch_splitk_reduction(a, p.reduce, s);
+    return mrcnn_launch_status();
+}
+
+// fill args, plan, launch; with plan_out the plan is handed back and nothing is launched (mrcnn_conv2d_fwd_plan)
+static int conv_fwd_impl(const mrcnn_conv_desc* d, const float* x, const float* w, const float* bias, const float* scale,
+                         const float* shift, const float* res, float* out, float* z_out, void* workspace, size_t workspace_bytes,
+                         const mrcnn_bwd_epilogue* ep, void* stream, mrcnn_conv_plan* plan_out = nullptr) {
+    ConvArgs a;
+    mrcnn_conv_plan p;
+    int rc = conv_fill_args(d, x, w, bias, scale, shift, res, out, z_out, a);
+    if (rc != MRCNN_OK) return rc;
+    if (ep) {               // the operands of the backward epilogue, where the kernels and the alignment rules look for them
+        a.fb_act = ep->act; a.fb_out = ep->out; a.fb_z = ep->z; a.fb_scale = ep->scale; a.fb_mean = ep->mean; a.fb_rstd = ep->rstd;
+        a.fb_dgamma = ep->dgamma; a.fb_dbeta = ep->dbeta; a.fb_dbias = ep->dbias; a.fb_dy = ep->dy;
     }
-    if (lds_dma) {
-        const int mt = (a.M + 127) / 128, nt = a.Cout / 128;
-        // buffer-addressed variant when the input (plus the padding shift) fits a 32-bit descriptor range
-        const long long xbytes = (long long)d->N * d->H * d->W * d->Cin * 4;
-        const long long shift = ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
-        const long long wbytes = (long long)a.Ktot * d->Cout * 4;
-        if (xbytes + shift < 0x7FFFFFF0LL && wbytes < 0x7FFFFFF0LL && !mrcnn_force_flat_glds()) {
-            const ConvTailPlan tp = plan_conv_tail(d);
-            auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-            const bool pow2c = d->Cout >= 16 && (d->Cout & (d->Cout - 1)) == 0;
-            const bool tail_ok = tp.ok && a.dense && d->res_mode != MRCNN_RES_UP2 && d->out_mode == MRCNN_OUT_NHWC && workspace &&
-                                 workspace_bytes >= tp.slab_bytes && al(workspace) &&
-                                 (a.fb_act < 0 || (pow2c && !ep->dy && al(out) && al(res) && al(ep->out) && al(ep->z) && al(ep->scale) &&
-                                                   al(ep->mean) && al(ep->rstd)));
-            if (!tail_ok) {
-                hipLaunchKernelGGL(conv_fwd_blds_kernel, dim3((unsigned)(mt * nt)), dim3(256), 0, s, a, (unsigned)shift,
-                                   (unsigned)(xbytes + shift));
-                return mrcnn_launch_status();
-            }
-            // whole rounds: unsplit kernel with its fused epilogue; tail tiles: K slices + slab reduction on the tail rows
-            hipLaunchKernelGGL(conv_fwd_blds_kernel, dim3((unsigned)(tp.mt_full * nt)), dim3(256), 0, s, a, (unsigned)shift,
-                               (unsigned)(xbytes + shift));
-            ConvArgs t = a;
-            t.mtile0 = tp.mt_full; t.ksplit = tp.ksplit; t.ksteps = tp.ksteps; t.slab = (float*)workspace;
-            hipLaunchKernelGGL(conv_fwd_blds_splitk_kernel, dim3((unsigned)((mt - tp.mt_full) * nt * tp.ksplit)), dim3(256), 0, s, t,
-                               (unsigned)shift, (unsigned)(xbytes + shift));
-            const long long m1 = (long long)tp.mt_full * 128, off = m1 * d->Cout;
-            ConvArgs r = t;                       // the reduction sees the tail rows as a problem of its own (dense NHWC)
-            r.M = (int)(a.M - m1); r.mtile0 = 0;
-            r.out = a.out + off;
-            if (a.z) r.z = a.z + off;
-            if (a.res) r.res = a.res + off;
-            if (a.fb_act >= 0) {
-                if (a.fb_out) r.fb_out = a.fb_out + off;
-                if (a.fb_z) r.fb_z = a.fb_z + off;
-            }
-            launch_splitk_reduction(r, s);
-        } else
-            hipLaunchKernelGGL(conv_fwd_glds_kernel, dim3((unsigned)(mt * nt)), dim3(256), 0, s, a);
-        return mrcnn_launch_status();
-    }
-    if (pl.bn == 32) return pl.bm == 128 ? launch_conv<128, 32, 4, 1>(a, s) : launch_conv<64, 32, 2, 1>(a, s);
-    if (pl.bn == 64) return pl.bm == 128 ? launch_conv<128, 64, 2, 2>(a, s) : launch_conv<64, 64, 2, 2>(a, s);
-    return pl.bm == 128 ? launch_conv<128, 128, 2, 2>(a, s) : launch_conv<64, 128, 2, 2>(a, s);
+    rc = conv_plan_launch(d, a, ep != nullptr, workspace, workspace_bytes, p);
+    if (rc != MRCNN_OK) return rc;
+    if (plan_out) { *plan_out = p; return MRCNN_OK; }
+    return conv_launch(d, a, p, workspace, (hipStream_t)stream);
+}
+
+extern "C" int mrcnn_conv2d_fwd_plan(const mrcnn_conv_desc* d, const float* x, const float* w, const float* bias, const float* scale,
+                                     const float* shift, const float* res, float* out, float* z_out, void* workspace,
+                                     size_t workspace_bytes, const mrcnn_bwd_epilogue* ep, mrcnn_conv_plan* plan) {
+    if (!plan) return MRCNN_ERR_ARG;
+    return conv_fwd_impl(d, x, w, bias, scale, shift, res, out, z_out, workspace, workspace_bytes, ep, nullptr, plan);
 }
 
 // The 16 GEMMs of a Winograd F(2x2, 3x3) layer in one launch of the LDS-DMA kernel: V [nb][rows][K] . U [nb][K][Cout] ->
@@ -1725,18 +1731,19 @@ static int conv_fwd_impl(const mrcnn_conv_desc* d, const float* x, const float* 
 extern "C" int mrcnn_gemm_batched_f32(const float* V, const float* U, float* Mt, int nb, int rows, int K, int Cout, void* stream) {
     if (!V || !U || !Mt || nb <= 0 || rows <= 0 || rows % 128 || K <= 0 || K % 16 || Cout <= 0 || Cout % 128) return MRCNN_ERR_ARG;
     const long long M = (long long)nb * rows;
-    if (M >= (1LL << 31) || M * K * 4 >= 0x7FFFFFF0LL || (long long)K * Cout * 4 >= 0x7FFFFFF0LL) return MRCNN_ERR_UNSUPPORTED;
+    if (M >= (1LL << 31)) return MRCNN_ERR_UNSUPPORTED;
     mrcnn_conv_desc d = {};
     d.N = (int)M; d.H = 1; d.W = 1; d.Cin = K; d.Cout = Cout; d.KH = 1; d.KW = 1; d.stride = 1; d.pad_t = 0; d.pad_l = 0; d.OH = 1; d.OW = 1;
     d.act = MRCNN_ACT_NONE; d.res_mode = MRCNN_RES_NONE; d.out_mode = MRCNN_OUT_NHWC; d.cmod = Cout;
     d.out_n_stride = Cout; d.out_h_stride = Cout; d.out_w_stride = Cout;
+    if (!conv_x_in_range(&d) || !conv_w_in_range(&d)) return MRCNN_ERR_UNSUPPORTED;
     ConvArgs a;
     const int rc = conv_fill_args(&d, V, U, nullptr, nullptr, nullptr, nullptr, Mt, nullptr, a);
     if (rc != MRCNN_OK) return rc;
     if (!a.fastA || !a.vecB || !a.dense) return MRCNN_ERR_UNSUPPORTED;
     a.bat_rows = rows;
-    const int mt = (int)(M / 128), nt = Cout / 128;
-    hipLaunchKernelGGL(conv_fwd_blds_kernel, dim3((unsigned)(mt * nt)), dim3(256), 0, (hipStream_t)stream, a, 0u, (unsigned)(M * K * 4));
+    hipLaunchKernelGGL(conv_fwd_blds_kernel, dim3((unsigned)conv_tiles(M, Cout, 128, 128)), dim3(256), 0, (hipStream_t)stream, a, 0u,
+                       (unsigned)conv_x_bytes(&d));
     return mrcnn_launch_status();
 }
 
@@ -1770,31 +1777,24 @@ struct ConvMultiPlan { int bn, ks[CONV_MULTI_MAX], ksteps[CONV_MULTI_MAX]; size_
 
 static int plan_conv_multi(const mrcnn_conv_problem* pr, int n, ConvMultiPlan& pl) {
     if (!pr || n < 1 || n > CONV_MULTI_MAX) return MRCNN_ERR_ARG;
-    auto bn_of = [](int Cout) { return Cout <= 32 ? 32 : (Cout <= 64 ? 64 : 128); };
-    pl.bn = bn_of(pr[0].d.Cout);
+    pl.bn = conv_tile_bn(pr[0].d.Cout);
     long long tiles = 0;
     for (int g = 0; g < n; ++g) {
         const mrcnn_conv_desc& d = pr[g].d;
         if (d.N <= 0 || d.OH <= 0 || d.OW <= 0 || d.Cout <= 0 || d.KH <= 0 || d.KW <= 0 || d.Cin <= 0) return MRCNN_ERR_ARG;
-        if (bn_of(d.Cout) != pl.bn) return MRCNN_ERR_UNSUPPORTED;
-        const long long M = (long long)d.N * d.OH * d.OW;
-        tiles += ((M + 63) / 64) * ((d.Cout + pl.bn - 1) / pl.bn);
+        if (conv_tile_bn(d.Cout) != pl.bn) return MRCNN_ERR_UNSUPPORTED;
+        tiles += conv_tiles((long long)d.N * d.OH * d.OW, d.Cout, 64, pl.bn);
     }
     if (tiles >= (1 << 20)) return MRCNN_ERR_UNSUPPORTED;
-    const long long want = tiles < 768 ? (1024 + tiles - 1) / tiles : 1;   // as plan_conv, on the launch as a whole
+    // plan_conv's rule on the launch as a whole, towards twice as many workgroups
+    const long long want = tiles < CONV_SPLITK_BELOW ? (2 * CONV_SPLITK_TARGET + tiles - 1) / tiles : 1;
     pl.bytes = 0;
     for (int g = 0; g < n; ++g) {
         const mrcnn_conv_desc& d = pr[g].d;
-        const int nk = (d.KH * d.KW * d.Cin + 31) / 32;
-        long long ks = want < nk / 4 ? want : nk / 4;
-        if (ks > 16) ks = 16;
-        pl.ks[g] = 1; pl.ksteps[g] = nk;
-        if (nk >= 8 && ks >= 2) {
-            pl.ksteps[g] = (int)((nk + ks - 1) / ks);
-            pl.ks[g] = (nk + pl.ksteps[g] - 1) / pl.ksteps[g];
-        }
+        const ConvKSlices ks = conv_k_slices((d.KH * d.KW * d.Cin + 31) / 32, want);
+        pl.ks[g] = ks.ksplit; pl.ksteps[g] = ks.ksteps;
         pl.slab_off[g] = pl.bytes;
-        if (pl.ks[g] > 1) pl.bytes += (((size_t)pl.ks[g] * d.N * d.OH * d.OW * d.Cout * sizeof(float)) + 255) & ~(size_t)255;
+        if (pl.ks[g] > 1) pl.bytes += (conv_slab_bytes(pl.ks[g], (long long)d.N * d.OH * d.OW, d.Cout) + 255) & ~(size_t)255;
     }
     return MRCNN_OK;
 }
@@ -1816,7 +1816,7 @@ extern "C" int mrcnn_conv2d_fwd_multi(const mrcnn_conv_problem* problems, int n,
     ConvMultiPlan pl;
     int rc = plan_conv_multi(problems, n, pl);
     if (rc != MRCNN_OK) return rc;
-    if (pl.bytes && (!workspace || workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(workspace) & 15))) return MRCNN_ERR_ARG;
+    if (pl.bytes && (!workspace || workspace_bytes < pl.bytes || !al(workspace))) return MRCNN_ERR_ARG;
     ConvMultiArgs mp;
     mp.n = n;
     bool fast = true;
@@ -1830,7 +1830,7 @@ extern "C" int mrcnn_conv2d_fwd_multi(const mrcnn_conv_problem* problems, int n,
         a.ksplit = pl.ks[g]; a.ksteps = pl.ksteps[g];
         a.slab = pl.ks[g] > 1 ? (float*)((char*)workspace + pl.slab_off[g]) : nullptr;
         mp.first[g] = (int)blocks;
-        blocks += (long long)((a.M + 63) / 64) * ((a.Cout + pl.bn - 1) / pl.bn) * a.ksplit;
+        blocks += conv_tiles(a.M, a.Cout, 64, pl.bn) * a.ksplit;
         mp.efirst[g] = (int)eblocks;
         mp.evec[g] = 0;
         if (a.ksplit > 1) {

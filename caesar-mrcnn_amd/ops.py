@@ -69,6 +69,22 @@ def conv2d(x, w, bias=None, scale=None, shift=None, res=None, stride=1, padding=
     return out
 
 
+def conv2d_plan(d, x=16, w=16, bias=None, scale=None, shift=None, res=None, out=16, z_out=None, workspace=None,
+                workspace_bytes=None, ep=None):
+    """(status, _hip.ConvPlan) of the launch conv2d (ep None) or conv2d_dgrad_ep (ep a _hip.BwdEpilogue) would issue for the
+    descriptor d.  Host only: the operands are addresses (only their nullness and alignment count; tensors are taken by
+    their address), nothing is launched.  workspace_bytes None: what conv2d passes, mrcnn_conv2d_fwd_workspace(d), at a
+    16-byte aligned address when that is not 0."""
+    adr = lambda t: t if t is None or isinstance(t, int) else ptr(t)
+    if workspace_bytes is None:
+        workspace_bytes = _hip.lib().mrcnn_conv2d_fwd_workspace(C.byref(d))
+        workspace = 16 if workspace_bytes else None
+    plan = _hip.ConvPlan()
+    rc = _hip.lib().mrcnn_conv2d_fwd_plan(C.byref(d), adr(x), adr(w), adr(bias), adr(scale), adr(shift), adr(res), adr(out), adr(z_out),
+                                          adr(workspace), workspace_bytes, C.byref(ep) if ep is not None else None, C.byref(plan))
+    return rc, plan
+
+
 ERR_UNSUPPORTED = -4
 
 

@@ -134,6 +134,37 @@ int mrcnn_conv2d_dgrad_ep(const mrcnn_conv_desc* d, const float* dz, const float
                           float* dz_below, const mrcnn_bwd_epilogue* ep, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* Host-only query: what mrcnn_conv2d_fwd_ws (ep == NULL) or mrcnn_conv2d_dgrad_ep (ep != NULL; x = dz, w = w_t) would
+ * launch for these arguments, and the status it would return.  Launches nothing and never dereferences a tensor pointer:
+ * only nullness and 16-byte alignment are looked at, so it runs without a GPU (the tail split then assumes the MI355X's
+ * 256 CUs).  Reads the same switches as the launch (tuning keys "sk16" / "sk64", MRCNN_CONV_TAIL_SPLIT,
+ * MRCNN_CONV_FLAT_GLDS).  *plan is written only with MRCNN_OK.                                                      */
+#define MRCNN_CONV_TILE 0          /* conv_fwd_kernel<bm, bn> (six tile shapes), K cut into ksplit slices of ksteps */
+#define MRCNN_CONV_BLDS 1          /* conv_fwd_blds_kernel: LDS-DMA 128 x 128 tiles, buffer addressing */
+#define MRCNN_CONV_GLDS 2          /* conv_fwd_glds_kernel: the same with flat addressing */
+#define MRCNN_CONV_BLDS_SPLITK 3   /* conv_fwd_blds_splitk_kernel: LDS-DMA tiles, K slices of ksteps steps of 16 */
+#define MRCNN_CONV_BLDS_TAIL 4     /* conv_fwd_blds_kernel on mt_full row tiles + conv_fwd_blds_splitk_kernel on the others */
+#define MRCNN_CONV_SK 5            /* conv_fwd_sk_kernel: 32 x 32 tiles, the four waves split K */
+#define MRCNN_CONV_SK16 6          /* conv_fwd_sk16_kernel: 16 x 16 tiles */
+#define MRCNN_CONV_SK64 7          /* conv_fwd_sk64_kernel: 64 x 64 tiles, two K slices of ksteps as accumulators */
+#define MRCNN_CONV_RED_NONE 0      /* the kernel stores the result */
+#define MRCNN_CONV_RED_SCALAR 1    /* conv_splitk_epilogue_kernel */
+#define MRCNN_CONV_RED_VEC 2       /* conv_splitk_epilogue_vec_kernel */
+#define MRCNN_CONV_RED_BWD 3       /* conv_splitk_epilogue_bwd_kernel: the slab sum carries the backward epilogue */
+typedef struct mrcnn_conv_plan {
+    int32_t kernel;                          /* MRCNN_CONV_* */
+    int32_t bm, bn;                          /* output tile of that kernel */
+    int32_t ksplit, ksteps;                  /* K slices and K-steps per slice the kernel runs with */
+    int32_t grid;                            /* workgroups of the (first) launch */
+    int32_t reduce;                          /* MRCNN_CONV_RED_*: the launch that follows */
+    int32_t mt_full, tail_ksplit, tail_ksteps;   /* MRCNN_CONV_BLDS_TAIL: row tiles left unsplit, slices of the others */
+    int32_t slab_bytes;                      /* workspace the launch uses (a split plan stays below 2^30 bytes) */
+} mrcnn_conv_plan;
+int mrcnn_conv2d_fwd_plan(const mrcnn_conv_desc* d, const float* x, const float* w, const float* bias,
+                          const float* scale, const float* shift, const float* res, float* out,
+                          float* z_out, void* workspace, size_t workspace_bytes,
+                          const mrcnn_bwd_epilogue* ep, mrcnn_conv_plan* plan);
+
 /* Frozen BatchNorm (KL.BatchNormalization with training=False, mrcnn/model.py:57-72; eps = Keras
  * default 1e-3):  scale = gamma*rsqrt(var+eps), shift = beta - mean*scale, for n channels.          */
 int mrcnn_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var,

@@ -36,15 +36,16 @@ CONV_CASES = [
     (2, 16, 16, 64, 256, 1, 1, "valid", 1, True, 1),     # residual add + relu
     (2, 16, 16, 512, 256, 1, 1, "valid", 0, False, 2),   # FPN lateral + nearest-up2 add
     (5, 7, 7, 256, 1024, 7, 1, "valid", 1, True, 0),     # class head FC as 7x7 VALID conv, K = 12544
-    (1, 33, 17, 64, 64, 3, 1, "same", 0, False, 0),      # ragged M, 64x64 tile
-    (8, 64, 64, 64, 256, 1, 1, "valid", 1, True, 0),     # 128x128 tiles
-    (8, 64, 64, 64, 64, 3, 1, "same", 1, True, 0),       # 128x64 tiles
+    (1, 33, 17, 64, 64, 3, 1, "same", 0, False, 0),      # ragged M (561 = 35 x 16 + 1): conv_fwd_sk16_kernel (64x64 tiles with the key at 0)
+    (8, 64, 64, 64, 256, 1, 1, "valid", 1, True, 0),     # 64x128 tiles, unsplit (512 tiles of 128x128: below the 640 of the LDS-DMA kernel)
+    (8, 64, 64, 64, 64, 3, 1, "same", 1, True, 0),       # 128x64 tiles, two K slices
     (16, 64, 64, 256, 12, 1, 1, "valid", 0, False, 0),   # 128x32 tiles, ragged Cout
     (1, 8, 8, 512, 6, 1, 1, "valid", 0, False, 0),       # 64x32 tiles, scalar B loads
     (4, 28, 28, 256, 4, 1, 1, "valid", 2, False, 0),     # mask logits + sigmoid
-    (64, 14, 14, 256, 256, 3, 1, "same", 1, True, 1),    # LDS-DMA 128x128 kernel: padded taps, residual
-    (90, 13, 11, 128, 256, 3, 1, "same", 1, False, 0),   # LDS-DMA kernel, ragged M (12870 = 100 x 128 + 70), odd H/W
-    (3, 64, 64, 256, 128, 1, 1, "valid", 0, False, 0),   # LDS-DMA kernel, 1x1, one N tile
+    (64, 14, 14, 256, 256, 3, 1, "same", 1, True, 1),    # LDS-DMA kernel with split-K (196 tiles of 128x128, 4 slices): padded taps, residual
+    (90, 13, 11, 128, 256, 3, 1, "same", 1, False, 0),   # LDS-DMA split-K kernel, ragged M (12870 = 100 x 128 + 70), odd H/W
+    (3, 64, 64, 256, 128, 1, 1, "valid", 0, False, 0),   # conv_fwd_sk64_kernel: 1x1, two slices of 4 K-steps, 384 workgroups (96 tiles of 128x128
+                                                         # but K too short for the LDS-DMA split)
     (457, 14, 14, 64, 256, 3, 1, "same", 1, True, 1),    # LDS-DMA kernel with the TAIL SPLIT: 700 x 2 tiles = 1.09 rounds of 1280 slots ->
                                                          # 640 row tiles unsplit, 60 (ragged M = 89572) as 4 K slices + slab reduction; BN, residual, z
     # conv_fwd_sk16_kernel (16 x 16 tiles, four waves split K): the batch-1 detect shapes, too small for the 32 x 32 single-launch kernel
@@ -52,7 +53,8 @@ CONV_CASES = [
     (1, 16, 16, 256, 256, 3, 1, "same", 1, True, 0),     # res4 2b: padded taps, 18 K-steps per wave
     (1, 16, 16, 256, 1024, 1, 1, "valid", 1, True, 1),   # res4 2c: K = 256 (2 K-steps per wave), shortcut added before the ReLU
     (1, 8, 8, 2048, 512, 1, 1, "valid", 1, True, 0),     # res5 2a: 128 tiles
-    (1, 7, 9, 256, 128, 3, 1, "same", 0, False, 1),      # ragged M (63 = 3 x 16 + 15), odd map, residual, no BN
+    (1, 7, 9, 256, 128, 3, 1, "same", 0, False, 1),      # ragged M (63), odd map, residual, no BN: 32 tiles of 16 x 16 are below that kernel's
+                                                         # 64 -- 64x64 tiles, 15 K slices
     (1, 16, 16, 512, 256, 1, 2, "valid", 1, True, 0),    # stride-2 1 x 1 (first block of a stage): 64 pixels out
 ]
 # the three layers whose width is the class count (NUM_CLASSES = 2, 5, 6, 17): mask logits + sigmoid on 5 ROIs (3920 rows: ragged
@@ -64,6 +66,12 @@ for _nc in HEAD_CLASS_COUNTS:
                    (5, 7, 7, 256, _nc, 1, 1, "valid", 2, False, 0),
                    (77, 1, 1, 1024, _nc, 1, 1, "valid", 0, False, 0),
                    (77, 1, 1, 1024, 4 * _nc, 1, 1, "valid", 0, False, 0)]
+# kernels no case above reaches (tests/test_conv_plan_cpu.py asks the planner for every case): the smallest shapes that do
+CONV_CASES += [
+    (10, 64, 64, 64, 256, 1, 1, "valid", 1, True, 0),    # 640 tiles of 128x128: conv_fwd_blds_kernel, unsplit
+    (4, 16, 16, 1024, 256, 1, 1, "valid", 1, True, 0),   # conv_fwd_sk_kernel (32 x 32 tiles): res4 2a of the training step, 256 tiles, 32 K-steps
+    (3, 7, 9, 256, 128, 3, 1, "same", 0, False, 1),      # the (1, 7, 9, ...) case on 189 rows (11 x 16 + 13): 96 tiles, conv_fwd_sk16_kernel
+]
 
 
 @pytest.fixture
@@ -1178,6 +1186,13 @@ import caesar_mrcnn_amd
 from caesar_mrcnn_amd import ops
 rng = np.random.default_rng(3)
 dev = torch.device("cuda:0")
+# forward kernel: it serves unsplit plans of >= 640 tiles of 128 x 128 (CONV_CASES' conv_fwd_blds_kernel shape)
+xb = torch.tensor(rng.standard_normal((10, 64, 64, 64)).astype(np.float32))
+wb = torch.tensor((rng.standard_normal((1, 1, 64, 256)) / 8.0).astype(np.float32))
+yb = orc.conv2d_nhwc(xb, wb, None, 1, "valid")
+gotb = ops.conv2d(xb.to(dev), wb.to(dev), None, None, None, None, 1, "valid")
+torch.cuda.synchronize()
+assert float((gotb.cpu() - yb).abs().max()) <= 2e-4 * float(yb.abs().max())
 x = torch.tensor(rng.standard_normal((90, 13, 11, 128)).astype(np.float32), requires_grad=True)
 w = torch.tensor((rng.standard_normal((3, 3, 128, 256)) / 34.0).astype(np.float32), requires_grad=True)
 y = orc.conv2d_nhwc(x, w, None, 1, "same")
