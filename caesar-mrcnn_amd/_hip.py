@@ -126,6 +126,11 @@ _SIGNATURES = {
     "mrcnn_unpack_mask_bits": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P]),
     "mrcnn_augment_warp_u8": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P]),
     "mrcnn_augment_warp_mask_bits": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P]),
+    "mrcnn_mask_bits_stats_check": (C.c_int, [C.c_int] * 4),
+    "mrcnn_mask_bits_stats_workspace": (C.c_size_t, [C.c_int]),
+    "mrcnn_mask_bits_stats": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "mrcnn_mask_bits_gather_check": (C.c_int, [C.c_int] * 5),
+    "mrcnn_mask_bits_gather": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "mrcnn_tile_adjacency": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, C.c_int, _P, _P]),
     "mrcnn_tile_union": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     "mrcnn_source_params": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int, _P, _P, _P, C.c_int64, C.c_double,
@@ -246,7 +251,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_fwd_plan", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_overview_check", "_planes_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
+_NO_RECORD = ("_workspace", "_fwd_plan", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_overview_check", "_planes_check", "_stats_check", "_gather_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
 
 
 class _LibProxy(object):

@@ -43,7 +43,9 @@ the masks are bool [H, W, N]; anything else takes the host statement, which give
 bit-packed (numpy.packbits, the layout of mrcnn_unpack_mask_bits) and are warped without unpacking; the results come back
 to the host on purpose (load_image_gt drops empty instances and data_generator skips images without one: both decisions
 are the host's).  The work goes to the loader threads' one side stream (loader_stream.py), and only that stream is
-synchronised.
+synchronised.  data_generator(device_samples=True) keeps both on the device instead (gtprep.py): it draws the plan with
+`draw_plan`, warps tensors with `warp_device` -- the core `apply` runs on, too -- and brings back only the instances' pixel
+counts and boxes, from which the host takes the same two decisions.
 """
 import threading
 
@@ -164,14 +166,28 @@ class ReferenceAugmenter(object):
                 mask = warp_host(mask, m, "mask")
         return image, mask
 
-    def __call__(self, image, mask):
+    def draw_plan(self):
+        """The plan `__call__` would draw next, drawn the same way (the instance's RandomState, under its lock)."""
         with self._lock:
-            stages = self.draw(self._rng)
-        return self.apply(image, mask, stages)
+            return self.draw(self._rng)
+
+    def __call__(self, image, mask):
+        return self.apply(image, mask, self.draw_plan())
+
+    def warp_device(self, img, bits, mats):
+        """The tensor-in / tensor-out core of the device path: img [H, W, C] uint8 (C <= 4) and bits [H, W, nb] bit-packed masks
+        (or None), both on the device, after every stage of `mats`; the inputs may be overwritten (ping-pong buffers).  The
+        caller holds the loader stream (loader_stream.py) and has made it current; nothing synchronises here."""
+        from . import ops
+        img = self._warp_all(img, mats, ops.augment_warp_u8)
+        if bits is not None:
+            bits = self._warp_all(bits, mats, ops.augment_warp_mask_bits)
+        if mats:
+            self.device_calls += 1
+        return img, bits
 
     def _apply_device(self, image, mask, mats, device):
         import torch
-        from . import ops
         from .loader_stream import loader_stream
         H, W, C = image.shape
         N = mask.shape[2]
@@ -184,15 +200,14 @@ class ReferenceAugmenter(object):
                 packed = np.concatenate([packed, np.zeros((H, W, pad), np.uint8)], axis=2)
         with loader_stream(device) as st:
             with torch.cuda.stream(st):
-                img = self._warp_all(torch.from_numpy(image).to(device, non_blocking=True), mats, ops.augment_warp_u8)
+                img, bits = self.warp_device(torch.from_numpy(image).to(device, non_blocking=True),
+                                             torch.from_numpy(packed).to(device, non_blocking=True) if N else None, mats)
                 host_img = torch.empty((H, W, C), dtype=torch.uint8, pin_memory=True)
                 host_img.copy_(img, non_blocking=True)
                 if N:
-                    bits = self._warp_all(torch.from_numpy(packed).to(device, non_blocking=True), mats, ops.augment_warp_mask_bits)
                     host_bits = torch.empty(tuple(packed.shape), dtype=torch.uint8, pin_memory=True)
                     host_bits.copy_(bits, non_blocking=True)
             st.synchronize()
-            self.device_calls += 1
         out_img = host_img.numpy().copy()
         if not N:
             return out_img, mask

@@ -77,6 +77,11 @@ class Config(object):
     # FITS tiles of the training / validation datasets: NaN fill, zscale, normalisation and the uint8 RGB conversion of
     # utils.read_fits (mrcnn/utils.py:1088-1157) on the GPU (mrcnn_fits_to_rgb; byte-identical images), from the loader threads
     DEVICE_FITS = os.environ.get("MRCNN_DEVICE_FITS", "1") != "0"
+    # extension: MaskRCNN.train's generators assemble every training sample on the GPU (gtprep.py, csrc/gtprep.hip): the image
+    # and the bit-packed instance masks go up once, padding, augmentation, the mask reductions (kept instances, boxes), the
+    # instance selection and the molding run there and only a [N, 5] table comes back; the batch reaches the step as device
+    # tensors.  Same batches as the host path.  Off by default (DESIGN.md 4.18 has the measurements).
+    DEVICE_SAMPLES = False
     # extension: None (float32 everywhere, the reference's precision) | "float16" | "bfloat16": run the 3x3
     # convolutions of the mask head on the 16-bit matrix cores (csrc/conv_h16.hip; float32 master weights,
     # accumulation and gradients; HEAD_LOSS_SCALE guards float16 gradients)

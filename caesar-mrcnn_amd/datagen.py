@@ -21,6 +21,11 @@ def load_image_gt(dataset, config, image_id, augment=False, augmentation=None, u
     ``f(image, mask) -> (image, mask)`` that preserves shapes."""
     image = dataset.load_image(image_id)
     mask, class_ids = dataset.load_mask(image_id)
+    return image_gt_from_arrays(dataset, config, image_id, image, mask, class_ids, augment, augmentation, use_mini_mask)
+
+
+def image_gt_from_arrays(dataset, config, image_id, image, mask, class_ids, augment=False, augmentation=None, use_mini_mask=False):
+    """load_image_gt after the two dataset calls: everything from resize_image on, for arrays that are already loaded."""
     original_shape = image.shape
     image, window, scale, padding, crop = utils.resize_image(
         image, min_dim=config.IMAGE_MIN_DIM, min_scale=config.IMAGE_MIN_SCALE, max_dim=config.IMAGE_MAX_DIM,
@@ -99,10 +104,25 @@ def build_rpn_targets(image_shape, anchors, gt_class_ids, gt_boxes, config, rng=
 
 
 def data_generator(dataset, config, shuffle=True, augment=False, augmentation=None, batch_size=1,
-                   no_augmentation_sources=None, rank=0, world_size=1, seed=None, device_targets=False):
+                   no_augmentation_sources=None, rank=0, world_size=1, seed=None, device_targets=False,
+                   device_samples=False, device=None):
     """Yields ([images, image_meta, rpn_match, rpn_bbox, gt_class_ids, gt_boxes, gt_masks], []) forever
     (model.py:1721-1904).  With world_size > 1 each rank walks its own stride of the (identically
-    shuffled) image list -- the data-parallel replacement of tf.split in parallel_model.py:60-62."""
+    shuffled) image list -- the data-parallel replacement of tf.split in parallel_model.py:60-62.
+    device_samples (with `device`, a torch GPU device): every sample is assembled on that GPU (gtprep.DeviceSampler, DESIGN.md
+    4.18) and the list -- a gtprep.DeviceBatch, whose `ready` event the consumer's stream waits on -- carries `images` as a
+    float32 [B, H, W, 3] and `gt_masks` as a uint8 [B, H, W, MAX_GT_INSTANCES] device tensor; the other five items, the host's
+    decisions and its random numbers are those of the host path.  Configurations the device path does not take keep the host
+    path for the whole generator (one log line says why), single samples it does not take are built on the host and uploaded
+    into the same batch."""
+    sampler = None
+    if device_samples:
+        from . import gtprep
+        why = gtprep.generator_refusal(config, device, augment, augmentation)
+        if why is None:
+            sampler = gtprep.DeviceSampler(config, device)
+        else:
+            logger.info("data_generator: device_samples asked for, samples stay on the host: %s", why)
     b = 0
     image_index = -1
     image_ids = np.copy(dataset.image_ids)
@@ -128,18 +148,27 @@ def data_generator(dataset, config, shuffle=True, augment=False, augmentation=No
                 raise EmptyShareError("data_generator: rank %d found no image with instances in two passes over its share of "
                                  "the %d images" % (rank, len(image_ids)))
             image_id = image_ids[image_index]
-            if dataset.image_info[image_id]['source'] in no_augmentation_sources:
-                image, image_meta, gt_class_ids, gt_boxes, gt_masks = load_image_gt(
-                    dataset, config, image_id, augment=augment, augmentation=None, use_mini_mask=config.USE_MINI_MASK)
+            sample = None                                   # a gtprep.DeviceSample when this image was built on the device
+            image_aug = None if dataset.image_info[image_id]['source'] in no_augmentation_sources else augmentation
+            if sampler is not None:
+                got = sampler.load(dataset, image_id, image_aug)
+                if got[0] == "device":
+                    sample = got[1]
+                    image_meta, gt_class_ids, gt_boxes, gt_sel = sample.image_meta, sample.class_ids, sample.bbox, sample.sel
+                    image_shape = sample.shape
+                else:                                       # this sample alone: host statement on the arrays already loaded
+                    image, image_meta, gt_class_ids, gt_boxes, gt_masks = image_gt_from_arrays(
+                        dataset, config, image_id, got[1], got[2], got[3], augmentation=image_aug)
+                    image_shape = image.shape
             else:
                 image, image_meta, gt_class_ids, gt_boxes, gt_masks = load_image_gt(
-                    dataset, config, image_id, augment=augment, augmentation=augmentation,
-                    use_mini_mask=config.USE_MINI_MASK)
+                    dataset, config, image_id, augment=augment, augmentation=image_aug, use_mini_mask=config.USE_MINI_MASK)
+                image_shape = image.shape
             if not np.any(gt_class_ids > 0):
                 continue
             barren = 0
             if not device_targets:
-                rpn_match, rpn_bbox = build_rpn_targets(image.shape, anchors, gt_class_ids, gt_boxes, config)
+                rpn_match, rpn_bbox = build_rpn_targets(image_shape, anchors, gt_class_ids, gt_boxes, config)
             if b == 0:
                 batch_image_meta = np.zeros((batch_size,) + image_meta.shape, dtype=image_meta.dtype)
                 if not device_targets:
@@ -147,9 +176,13 @@ def data_generator(dataset, config, shuffle=True, augment=False, augmentation=No
                     batch_rpn_bbox = np.zeros([batch_size, config.RPN_TRAIN_ANCHORS_PER_IMAGE, 4], dtype=rpn_bbox.dtype)
                 else:
                     batch_rpn_match = batch_rpn_bbox = None
-                batch_images = np.zeros((batch_size,) + image.shape, dtype=np.float32)
                 batch_gt_class_ids = np.zeros((batch_size, config.MAX_GT_INSTANCES), dtype=np.int32)
                 batch_gt_boxes = np.zeros((batch_size, config.MAX_GT_INSTANCES, 4), dtype=np.int32)
+            if b == 0 and sampler is not None:
+                # both on the device, every plane written there (gtprep.DeviceSampler.emit: kept instances, then zeros)
+                batch_images, batch_gt_masks = sampler.new_batch(batch_size, image_shape)
+            elif b == 0:
+                batch_images = np.zeros((batch_size,) + image.shape, dtype=np.float32)
                 # the reference's batch carries MAX_GT_INSTANCES mask planes per image ([B, 256, 256, 300] bool = 78.6 MB on the run.py
                 # path, almost all padding): allocating, zeroing and freeing that array cost the consumer ~3 ms per step.  With
                 # device_targets (the product's own loop) the batch keeps only as many planes as its fullest image has (rounded up to
@@ -159,20 +192,36 @@ def data_generator(dataset, config, shuffle=True, augment=False, augmentation=No
                 mask_list = []
             if gt_boxes.shape[0] > config.MAX_GT_INSTANCES:
                 ids = np.random.choice(np.arange(gt_boxes.shape[0]), config.MAX_GT_INSTANCES, replace=False)
-                gt_class_ids, gt_boxes, gt_masks = gt_class_ids[ids], gt_boxes[ids], gt_masks[:, :, ids]
+                if sample is not None:
+                    gt_class_ids, gt_boxes, gt_sel = gt_class_ids[ids], gt_boxes[ids], gt_sel[ids]
+                else:
+                    gt_class_ids, gt_boxes, gt_masks = gt_class_ids[ids], gt_boxes[ids], gt_masks[:, :, ids]
             batch_image_meta[b] = image_meta
             if not device_targets:
                 batch_rpn_match[b] = rpn_match[:, np.newaxis]
                 batch_rpn_bbox[b] = rpn_bbox
-            batch_images[b] = utils.mold_image(image.astype(np.float32), config)
+            if sample is not None:
+                sampler.emit(sample, gt_sel, batch_images[b], batch_gt_masks[b])
+            elif sampler is not None:
+                sampler.emit_host(utils.mold_image(image.astype(np.float32), config), gt_masks, batch_images[b], batch_gt_masks[b])
+            else:
+                batch_images[b] = utils.mold_image(image.astype(np.float32), config)
             batch_gt_class_ids[b, :gt_class_ids.shape[0]] = gt_class_ids
             batch_gt_boxes[b, :gt_boxes.shape[0]] = gt_boxes
-            if device_targets:
+            if sampler is None and device_targets:
                 mask_list.append(gt_masks)
-            else:
+            elif sampler is None:
                 batch_gt_masks[b, :, :, :gt_masks.shape[-1]] = gt_masks
             b += 1
-            if b >= batch_size:
+            if b >= batch_size and sampler is not None:
+                from .gtprep import DeviceBatch
+                batch = DeviceBatch([batch_images, batch_image_meta, batch_rpn_match, batch_rpn_bbox, batch_gt_class_ids,
+                                     batch_gt_boxes, batch_gt_masks])
+                batch.ready = sampler.ready_event()
+                batch_images = batch_gt_masks = None         # the consumer's: this generator never writes them again
+                yield batch, []
+                b = 0
+            elif b >= batch_size:
                 if device_targets:
                     planes = max(8, (max(m.shape[-1] for m in mask_list) + 7) // 8 * 8)
                     batch_gt_masks = np.zeros((batch_size,) + mask_list[0].shape[:2] + (planes,), dtype=mask_list[0].dtype)

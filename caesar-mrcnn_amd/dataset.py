@@ -197,13 +197,14 @@ class SourceDataset(Dataset):
         m, _ = self.load_mask(image_id)
         return m if binary else m.astype(int)
 
-    def load_image(self, image_id):
+    def load_image(self, image_id, device_out=False):
         # self.device (set by MaskRCNN.train when Config.DEVICE_FITS): NaN fill / zscale / RGB on that GPU, same bytes back
+        # (device_out: the image of that branch stays on the GPU as a uint8 tensor, see fits.read_fits)
         image, _ = fits.read_fits(self.image_info[image_id]['path'], stretch=self.apply_zscale,
                                   zscale_contrasts=self.zscale_contrasts, normalize=True,
                                   convertToRGB=self.convert_to_rgb, to_uint8=self.convert_to_uint8,
                                   stretch_biascontrast=self.apply_biascontrast, bias=self.bias, contrast=self.contrast,
-                                  device=getattr(self, "device", None))
+                                  device=getattr(self, "device", None), device_out=device_out)
         return image
 
     def image_uuid(self, image_id):

@@ -206,13 +206,15 @@ def gray2rgb(data_float, to_uint8=True):
 
 
 def read_fits(filename, xmin=-1, xmax=-1, ymin=-1, ymax=-1, stretch=True, normalize=True, convertToRGB=True,
-              zscale_contrasts=[0.25, 0.25, 0.25], to_uint8=True, stretch_biascontrast=False, contrast=1, bias=0.5, device=None):
+              zscale_contrasts=[0.25, 0.25, 0.25], to_uint8=True, stretch_biascontrast=False, contrast=1, bias=0.5, device=None,
+              device_out=False):
     """Tile of a FITS image as the network's input image (utils.py:1033-1163): NaN -> min, per-channel
     zscale, normalise by the channel maximum, uint8 RGB.  Returns (image, header) or None on error.
     device: a torch GPU device -- the numeric part (everything after the header parse and the tile cut) runs there
     (mrcnn_fits_to_rgb; the file's big-endian floats cross PCIe as they are) when the flags are the run.py ones (stretch,
     normalize, convertToRGB, to_uint8, no bias / contrast stretch); the uint8 image comes back to the host, identical to the
-    host path's."""
+    host path's.  device_out: the image of that device branch stays there, as a uint8 [H, W, 3] torch tensor (the device sample
+    path of datagen.data_generator); a call that does not take the branch returns the host array as ever."""
     if len(zscale_contrasts) != 3:
         logger.warning("Size of input zscale_contrasts is !=3, ignoring inputs and using default (0.25,0.25,0.25)...")
         zscale_contrasts = [0.25, 0.25, 0.25]
@@ -238,7 +240,7 @@ def read_fits(filename, xmin=-1, xmax=-1, ymin=-1, ymax=-1, stretch=True, normal
         logger.error('ERROR: Invalid/unsupported number of channels found in file %s (nchan=%d)!' % (filename, data.ndim))
         return None
     if on_device and out.size and out.shape[0] * out.shape[1] <= DEVICE_TILE_MAX_PIXELS:
-        return _read_fits_device(out, zscale_contrasts, device), header
+        return _read_fits_device(out, zscale_contrasts, device, device_out), header
     out = out.astype(np.float32)
     out[np.isnan(out)] = np.nanmin(out)
     # The reference runs the whole per-channel chain three times (utils.py:1101-1157); the channels differ only in their
@@ -298,8 +300,9 @@ def mosaic_overview_host(plane, shrink, contrast=0.25):
     return np.repeat(O[:, :, None], 3, axis=2)
 
 
-def _read_fits_device(tile, zscale_contrasts, device):
-    """The cut tile (still in the file's dtype / byte order) -> uint8 [H, W, 3] through ops.fits_to_rgb; returns a host array.
+def _read_fits_device(tile, zscale_contrasts, device, device_out=False):
+    """The cut tile (still in the file's dtype / byte order) -> uint8 [H, W, 3] through ops.fits_to_rgb; returns a host array
+    (device_out: the device tensor, allocated on the loader stream, where its consumers run too).
     Called from loader threads while the main thread issues training steps: the three launches go to ONE side stream shared
     by all loader threads (its own hardware queue beside the step's three; a stream per thread would wrap onto the step's
     queues and wait behind a whole step) under a lock (the stream's scratch buffer is shared), and only that stream is
@@ -316,10 +319,11 @@ def _read_fits_device(tile, zscale_contrasts, device):
     with loader_stream(device) as st:
         with torch.cuda.stream(st):
             rgb = ops.fits_to_rgb(raw.to(device, non_blocking=True), H, W, zscale_contrasts, big_endian=big)
-            host = torch.empty((H, W, 3), dtype=torch.uint8, pin_memory=True)
-            host.copy_(rgb, non_blocking=True)
-        st.synchronize()
-    return host.numpy().copy()
+            if not device_out:
+                host = torch.empty((H, W, 3), dtype=torch.uint8, pin_memory=True)
+                host.copy_(rgb, non_blocking=True)
+        st.synchronize()                                            # (device_out too: `raw` is pageable and freed on return)
+    return rgb if device_out else host.numpy().copy()
 
 
 def read_table(filename):

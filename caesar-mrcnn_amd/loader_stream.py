@@ -1,5 +1,5 @@
 """The loader threads' side stream: ONE stream per device, shared by every loader thread and by every kind of loader work
-(fits._read_fits_device, augment.ReferenceAugmenter), under one lock.
+(fits._read_fits_device, augment.ReferenceAugmenter, gtprep.DeviceSampler), under one lock.
 
 HIP maps streams onto a handful of hardware queues (4 by default) in the order they are first used.  A training step
 already uses three streams (engine._side_streams: the default stream, the weight-gradient and the auxiliary stream), so

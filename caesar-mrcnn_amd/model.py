@@ -202,7 +202,8 @@ class MaskRCNN(object):
         """Generator batch -> device tensors of engine.forward_backward.  With rpn_match / rpn_bbox None the RPN
         targets are built on the GPU from the GT boxes (``rpn_keys`` [B, A] uniform floats, drawn here when not
         given).  Only the GT-mask planes of real instances cross PCIe, bit-packed (8 instances per byte); the unpacking and
-        the MAX_GT_INSTANCES padding are written on the device."""
+        the MAX_GT_INSTANCES padding are written on the device.  A batch of data_generator(device_samples=True) brings `images`
+        and `gt_masks` as device tensors: they are taken as they are, after this stream has waited on the batch's event."""
         import torch
         from . import ops
         dev = self.engine.dev
@@ -229,7 +230,22 @@ class MaskRCNN(object):
         else:
             rpn_match_d, rpn_bbox_d = t(rpn_match, np.int32), t(rpn_bbox, np.float32)
         G = np.asarray(gt_class_ids).shape[1]                             # planes on the device: MAX_GT_INSTANCES, like the class ids
-        have = gt_masks.shape[-1]                                         # planes in the batch (data_generator(device_targets=True) trims the padding)
+        if torch.is_tensor(images):
+            # data_generator(device_samples=True): both tensors were written on the loader stream.  This stream waits for the
+            # batch's hand-off event (no host synchronisation) and declares its use of the two buffers, so that the caching
+            # allocator -- they belong to the loader stream's pool -- reuses them only after the step that reads them has run.
+            assert torch.is_tensor(gt_masks) and gt_masks.dtype == torch.uint8 and tuple(gt_masks.shape) == (B, H, W, G)
+            assert images.dtype == torch.float32 and images.is_cuda and images.device == gt_masks.device
+            cur = torch.cuda.current_stream(dev)
+            ready = getattr(inputs, "ready", None)
+            if ready is not None:
+                cur.wait_event(ready)
+            images.record_stream(cur)
+            gt_masks.record_stream(cur)
+            self.last_mask_h2d_bytes = 0
+            return (images, rpn_match_d, rpn_bbox_d, cls_d, t(gtn, np.float32), gt_masks, t(active, np.int32),
+                    t(rand_keys, np.float32))
+        have = gt_masks.shape[-1]                                        # planes in the batch (data_generator(device_targets=True) trims the padding)
         used = np.flatnonzero(np.any(np.asarray(gt_class_ids) != 0, axis=0))
         n_used = min(int(used[-1]) + 1 if used.size else 0, have)
         if n_used < have and gt_masks[..., n_used:].any():
@@ -290,12 +306,14 @@ class MaskRCNN(object):
         from .augment import ReferenceAugmenter
         if isinstance(augmentation, ReferenceAugmenter) and augmentation.device is None:
             augmentation.device = self.engine.dev             # its warps on the loader stream (augment.py)
+        # Config.DEVICE_SAMPLES: the generators assemble their samples on the engine's GPU (gtprep.py)
+        dev_s = dict(device_samples=True, device=self.engine.dev) if getattr(cfg, "DEVICE_SAMPLES", False) else {}
         train_gen = Prefetcher([data_generator(train_dataset, cfg, shuffle=True, augmentation=augmentation,
                                                batch_size=cfg.IMAGES_PER_GPU, no_augmentation_sources=no_augmentation_sources,
-                                               rank=rank, world_size=world, seed=1234 + 1000 * k, device_targets=dev_t)
+                                               rank=rank, world_size=world, seed=1234 + 1000 * k, device_targets=dev_t, **dev_s)
                                 for k in range(nw)], depth=2 * nw + 2)
         val_gen = Prefetcher([data_generator(val_dataset, cfg, shuffle=True, batch_size=cfg.IMAGES_PER_GPU, rank=rank,
-                                             world_size=world, seed=4321, device_targets=dev_t)], depth=2)
+                                             world_size=world, seed=4321, device_targets=dev_t, **dev_s)], depth=2)
         if rank == 0 and not os.path.exists(self.log_dir):
             os.makedirs(self.log_dir)
         log("\nStarting at epoch {}. LR={}\n".format(self.epoch, learning_rate))

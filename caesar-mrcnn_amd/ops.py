@@ -1012,6 +1012,92 @@ def augment_warp_mask_bits(packed, m, out=None):
     return out
 
 
+class GtPrepUnsupported(_hip.HipPathError):
+    """Masks past a cap of mrcnn_mask_bits_stats / mrcnn_mask_bits_gather (include/mrcnn_hip.h: a frame side above 8192, more than
+    4096 instances, bits per pixel or output planes): the caller takes the host statement (datagen.mask_bits_stats_host /
+    mask_bits_gather_host)."""
+
+
+GTPREP_MAX_SIDE, GTPREP_MAX_INSTANCES = 8192, 4096          # MRCNN_GTPREP_MAX_* (include/mrcnn_hip.h)
+
+
+def _gtprep_packed(packed, what):
+    if not torch.is_tensor(packed) or packed.dtype != torch.uint8 or packed.dim() != 3:
+        raise ValueError("%s: packed must be a uint8 [H, W, nb] tensor" % what)
+    H, W, nb = (int(v) for v in packed.shape)
+    if H < 1 or W < 1 or nb < 1 or nb % 4:
+        raise ValueError("%s: packed %r must be non-empty with whole 32-bit words per pixel (nb %% 4 == 0)" % (what, (H, W, nb)))
+    return H, W, nb
+
+
+def _gtprep_refusal(rc, what):
+    if rc == ERR_UNSUPPORTED:
+        raise GtPrepUnsupported("%s: past a cap of the kernel (status %d)" % (what, rc))
+    if rc:
+        raise ValueError("%s refuses the request (status %d)" % (what, rc))
+
+
+def gtprep_check(H, W, nb, n, G):
+    """Raises what mask_bits_stats (n instances) and mask_bits_gather (G planes) would raise for masks of these sizes; launches
+    nothing (the device sample path asks before it draws an augmentation plan)."""
+    L = _hip.lib()
+    _gtprep_refusal(L.mrcnn_mask_bits_stats_check(int(H), int(W), int(nb), int(n)), "mrcnn_mask_bits_stats")
+    _gtprep_refusal(L.mrcnn_mask_bits_gather_check(int(H), int(W), int(nb), 0, int(G)), "mrcnn_mask_bits_gather")
+
+
+def mask_bits_stats(packed, n):
+    """Pixel count and box of every instance of bit-packed masks, on the device: packed [H, W, nb] uint8 =
+    np.packbits(mask != 0, axis=-1, bitorder="little") with nb % 4 == 0 (the layout of augment_warp_mask_bits), n instances ->
+    (count [n] int32, box [n, 4] int32), equal to np.sum(mask, axis=(0, 1)) and utils.extract_bboxes(mask)
+    (datagen.mask_bits_stats_host).  Bits >= n are ignored.  The two results are views of ONE int32 buffer of 5 n values (count,
+    then box: ``count._base``), so a caller brings both to the host in one copy.  ValueError for malformed input,
+    GtPrepUnsupported past a cap; neither allocates or launches anything."""
+    H, W, nb = _gtprep_packed(packed, "mask_bits_stats")
+    n = int(n)
+    if n < 1 or n > 8 * nb:
+        raise ValueError("mask_bits_stats: n = %d instances do not fit %d bytes per pixel" % (n, nb))
+    L = _hip.lib()
+    _gtprep_refusal(L.mrcnn_mask_bits_stats_check(H, W, nb, n), "mrcnn_mask_bits_stats")
+    _need_cuda(packed)
+    table = torch.empty((5 * n,), dtype=torch.int32, device=packed.device)
+    count, box = table[:n], table[n:].view(n, 4)
+    ws = workspace(L.mrcnn_mask_bits_stats_workspace(nb), packed.device, "gtprep")
+    check(L.mrcnn_mask_bits_stats(ptr(packed), H, W, nb, n, ptr(count), ptr(box), ptr(ws), ws.numel(), current_stream()),
+          "mrcnn_mask_bits_stats")
+    return count, box
+
+
+def mask_bits_gather(packed, sel, G, out=None):
+    """Selected instances of bit-packed masks as uint8 planes, on the device: out[y, x, j] = bit sel[j] of pixel (y, x) for
+    j < len(sel), 0 up to G -- mask[:, :, sel] padded to G planes (datagen.mask_bits_gather_host).  packed as for
+    mask_bits_stats; sel: int32 indices (NumPy / list: checked against 0 <= sel < 8 nb here, then uploaded); out: a contiguous
+    uint8 [H, W, G] device tensor, e.g. one image of the [B, H, W, G] batch.  ValueError for malformed input, GtPrepUnsupported
+    past a cap; neither allocates, launches or writes anything."""
+    import numpy as np
+    H, W, nb = _gtprep_packed(packed, "mask_bits_gather")
+    G = int(G)
+    sel_h = np.asarray(sel)
+    if sel_h.ndim != 1 or (sel_h.size and not np.issubdtype(sel_h.dtype, np.integer)):
+        raise ValueError("mask_bits_gather: sel must be a 1-D integer table")
+    k = int(sel_h.size)
+    if G < 1 or k > G:
+        raise ValueError("mask_bits_gather: %d selected instances for G = %d planes" % (k, G))
+    if k and (int(sel_h.min()) < 0 or int(sel_h.max()) >= 8 * nb):
+        raise ValueError("mask_bits_gather: sel must lie in [0, %d)" % (8 * nb))
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (H, W, G)
+                            or not out.is_contiguous() or out.device != packed.device):
+        raise ValueError("mask_bits_gather: out must be a contiguous uint8 [%d, %d, %d] tensor on packed's device" % (H, W, G))
+    L = _hip.lib()
+    _gtprep_refusal(L.mrcnn_mask_bits_gather_check(H, W, nb, k, G), "mrcnn_mask_bits_gather")
+    _need_cuda(packed)
+    if out is None:
+        out = torch.empty((H, W, G), dtype=torch.uint8, device=packed.device)
+    # (through pinned memory: the caller need not synchronise before the host table goes away)
+    sel_d = torch.from_numpy(np.ascontiguousarray(sel_h, dtype=np.int32)).pin_memory().to(packed.device, non_blocking=True) if k else None
+    check(L.mrcnn_mask_bits_gather(ptr(packed), H, W, nb, ptr(sel_d), k, G, ptr(out), current_stream()), "mrcnn_mask_bits_gather")
+    return out                               # (sel_d goes back to the allocator of this stream: reused in stream order only)
+
+
 def tile_upload(pool, desc, device):
     """Sources of a mosaic for tile_adjacency / tile_union (include/mrcnn_hip.h: mrcnn_tile_source): pool = uint32 words (NumPy),
     desc [n, 6] int32 = (x0, y0, w, h, word_offset, words_per_row).  Checks every descriptor against the pool and uploads both

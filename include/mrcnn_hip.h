@@ -229,6 +229,35 @@ int mrcnn_unpack_mask_bits(const void* packed, void* out, int64_t npix, int nbyt
 int mrcnn_augment_warp_u8(const void* src, int H, int W, int C, const double* m, void* dst, void* stream);
 int mrcnn_augment_warp_mask_bits(const void* src, int H, int W, int nbytes_per_pixel, const double* m, void* dst, void* stream);
 
+/* Ground truth of a training sample from its bit-packed instance masks, without unpacking them.  packed [H, W, nb] uint8 =
+ * numpy.packbits(mask != 0, axis=-1, bitorder="little") padded with zero bytes to nb % 4 == 0 (4-byte aligned: it is read as
+ * 32-bit words; the layout mrcnn_augment_warp_mask_bits reads and writes).  Integer arithmetic only: exact, the same from run
+ * to run.  All pointers are device pointers; nothing is allocated on the device.
+ *   mrcnn_mask_bits_stats   replaces np.sum(mask, axis=(0, 1)) of load_image_gt (mrcnn/model.py:1361-1363) and the per-instance
+ *                           loop of utils.extract_bboxes (mrcnn/utils.py:49-77): for every instance k < n, count[k] = its
+ *                           pixels and box[k] = (y1, x1, y2 + 1, x2 + 1) int32, (0, 0, 0, 0) when it has none.  Bits >= n of the
+ *                           last word(s) are ignored, whatever they hold.  ws: mrcnn_mask_bits_stats_workspace(nb) bytes
+ *                           (20 per bit of a pixel's words), 4-byte aligned, initialised by the call; smaller:
+ *                           MRCNN_ERR_WORKSPACE.  Three launches: table reset, ballots + integer atomics, boxes.
+ *   mrcnn_mask_bits_gather  replaces mask[:, :, keep], the MAX_GT_INSTANCES subsample gt_masks[:, :, ids] and the copy into the
+ *                           zeroed batch planes (mrcnn/model.py:1364, 1831-1835, 1866-1870): out[y, x, j] = bit sel[j] of
+ *                           pixel (y, x) for j < k and 0 for k <= j < G; out [H, W, G] uint8 is one image's slice of the
+ *                           [B, H, W, G] batch.  sel: k int32 on the device, 0 <= sel[j] < 8 nb (an entry outside gives 0).
+ *                           k == 0 writes zeros.  One launch; 32-bit stores when G % 4 == 0 and out is 4-byte aligned, else
+ *                           bytes.
+ * Malformed (MRCNN_ERR_ARG): H, W, nb or G <= 0, nb % 4 != 0, n <= 0, n > 8 nb, k < 0, k > G, a missing or misaligned pointer.
+ * Caps (past any: MRCNN_ERR_UNSUPPORTED, use the host statement): H, W <= MRCNN_GTPREP_MAX_SIDE; n, 8 nb and G <=
+ * MRCNN_GTPREP_MAX_INSTANCES (the stats table is one workspace slot per bit).  A refused call launches and writes nothing.
+ * The _check entries give the status for those sizes and launch nothing.                                                      */
+#define MRCNN_GTPREP_MAX_SIDE 8192
+#define MRCNN_GTPREP_MAX_INSTANCES 4096
+int mrcnn_mask_bits_stats_check(int H, int W, int nb, int n);
+size_t mrcnn_mask_bits_stats_workspace(int nb);
+int mrcnn_mask_bits_stats(const void* packed, int H, int W, int nb, int n, int* count, int* box, void* ws, size_t ws_bytes,
+                          void* stream);
+int mrcnn_mask_bits_gather_check(int H, int W, int nb, int k, int G);
+int mrcnn_mask_bits_gather(const void* packed, int H, int W, int nb, const int* sel, int k, int G, void* out, void* stream);
+
 /* Stitching of sources across tile borders (SFinder.merge_edge_sources, mrcnn/sfinder.py:711-935).  Sources are row-major bit
  * masks of their bounding boxes in mosaic coordinates: ONE pool of 32-bit words and a descriptor per source; pixel (x, y) of a
  * source is bit (x - x0) & 31 of word word_offset + (y - y0) * words_per_row + ((x - x0) >> 5), least significant bit first

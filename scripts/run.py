@@ -87,6 +87,11 @@ def parse_args(argv=None):
     p.add_argument('--reference_augmentation', action='store_true', default=False,
                    help="extension: augment with the reference's imgaug pipeline (0-2 of flip lr / flip ud / rotate -90..90 / "
                         "translate +-30%%), warped on the GPU; default: flips + 90-degree rotations")
+    p.add_argument('--device_samples', action='store_true', default=False,
+                   help="extension: `train` assembles its samples on the GPU (padding, --reference_augmentation warps, kept "
+                        "instances, boxes, batch planes; Config.DEVICE_SAMPLES); with the default flip / rot90 augmentation "
+                        "the samples stay on the host and a log line says so: combine with --reference_augmentation or "
+                        "--no_augmentation")
     p.add_argument('--reference_tester', action='store_true', default=False,
                    help="extension: `test` runs the reference's ModelTester (masks merged and selected first, its matching rule, "
                         "confusion matrix and purity, completeness.csv and reliability.csv); needs a JSON dataloader; default: the "
@@ -213,6 +218,7 @@ def build_config(args, class_dict_model):
     cfg.SPLIT_IMG_IN_TILES = args.split_img_in_tiles
     cfg.TILE_XSIZE, cfg.TILE_YSIZE, cfg.TILE_XSTEP, cfg.TILE_YSTEP = args.tile_xsize, args.tile_ysize, args.tile_xstep, args.tile_ystep
     cfg.HEAD_DTYPE = args.head_dtype or None
+    cfg.DEVICE_SAMPLES = bool(args.device_samples)
     return cfg
 
 
