@@ -79,6 +79,23 @@ class BwdEpilogueH16(C.Structure):
         ("act", C.c_int32), ("dy", C.c_void_p), ("grad_multiplier", C.c_float)]
 
 
+class H16Plan(C.Structure):
+    """mrcnn_h16_plan (include/mrcnn_hip.h): what a 16-bit forward / data-gradient launch would do, from mrcnn_conv2d_fwd_h16_plan."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "zout", "grid", "threads", "ptiles", "mtile0", "rem_grid", "rem_mtile0", "ep_vec", "dense",
+                                          "fused_ep", "reserved")] + [("trace", C.c_uint64)]
+
+
+class H16WgradPlan(C.Structure):
+    """mrcnn_h16_wgrad_plan: what a 16-bit weight-gradient launch would do, from mrcnn_conv2d_wgrad_h16_plan."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "splits", "chunk", "nk", "itiles", "ntiles", "grid", "reduce", "reduce_grid", "xcd_order")] + [
+        (n, C.c_int64) for n in ("table_bytes", "slab_bytes", "workspace_bytes")]
+
+
+H16_KERNELS = ("S64", "T128", "RING", "BIG", "WAVE128", "PHASE", "PHASE_DECONV", "SLAB")       # MRCNN_H16_*, by value
+H16_WGRAD_KERNELS = ("TABLE", "PHASE")                                                        # MRCNN_H16_WGRAD_*
+H16_REDUCTIONS = ("SCALAR", "VEC")                                                            # MRCNN_H16_RED_*
+
+
 class DetectionDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("R", C.c_int32), ("C", C.c_int32), ("max_instances", C.c_int32),
                 ("min_confidence", C.c_float), ("nms_threshold", C.c_float), ("bbox_std_dev", C.c_float * 4)]
@@ -194,9 +211,11 @@ _SIGNATURES = {
     "mrcnn_conv2d_fwd_h16_res": (C.c_int, [C.POINTER(ConvDesc), C.c_int] + [_P] * 9),
     "mrcnn_conv2d_fwd_h16_supported": (C.c_int, [C.POINTER(ConvDesc), C.c_int]),
     "mrcnn_conv2d_dgrad_ep_h16": (C.c_int, [C.POINTER(ConvDesc), C.c_int, _P, _P, _P, _P, C.POINTER(BwdEpilogueH16), _P]),
+    "mrcnn_conv2d_fwd_h16_plan": (C.c_int, [C.POINTER(ConvDesc), C.c_int] + [_P] * 8 + [C.POINTER(BwdEpilogueH16), C.POINTER(H16Plan)]),
     "mrcnn_conv2d_dgrad_ep": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, C.POINTER(BwdEpilogue), _P, C.c_size_t, _P]),
     "mrcnn_conv2d_wgrad_h16_workspace": (C.c_size_t, [C.POINTER(ConvDesc)]),
     "mrcnn_conv2d_wgrad_h16": (C.c_int, [C.POINTER(ConvDesc), C.c_int, _P, _P, _P, _P, C.c_size_t, C.c_int, C.c_float, _P]),
+    "mrcnn_conv2d_wgrad_h16_plan": (C.c_int, [C.POINTER(ConvDesc), C.c_int, _P, _P, _P, _P, C.c_size_t, C.POINTER(H16WgradPlan)]),
     "mrcnn_mask_out_fwd_h16": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P]),
     "mrcnn_mask_out_bwd_h16": (C.c_int, [C.c_int] + [_P] * 8 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "mrcnn_weights_to_h16": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -251,7 +270,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_fwd_plan", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_overview_check", "_planes_check", "_stats_check", "_gather_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
+_NO_RECORD = ("_workspace", "_fwd_plan", "_h16_plan", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_overview_check", "_planes_check", "_stats_check", "_gather_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
 
 
 class _LibProxy(object):

@@ -1943,7 +1943,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_h16_kernel(const WgradH16Ar
 //              shifted base; only the tap's validity needs (oh, ow), two multiply-high divisions per piece.  No table, no
 //              ordinary global load in the loop (the counted vmcnt waits see DMA pieces only).  Rows past the split's end
 //              fall outside the dY descriptor (zeros); X rows there are switched off too (0 x NaN).
-static void h16_magic(unsigned d, unsigned* mg, unsigned* sh);
+// x / d for x < 2^31 as (umulhi(x, mg) >> sh): mg = ceil(2^(31+s) / d), s = ceil(log2 d), sh = s - 1; d = 1 -> mg = 0 (no division)
+static void h16_magic(unsigned d, unsigned* mg, unsigned* sh) {
+    if (d <= 1) { *mg = 0; *sh = 0; return; }
+    unsigned sft = 0;
+    while ((1ull << sft) < d) ++sft;
+    *mg = (unsigned)(((1ull << (31 + sft)) + d - 1) / d);
+    *sh = sft - 1;
+}
 
 struct WgradH16PArgs {
     const void* x; const void* dy; float* out;
@@ -2165,326 +2172,325 @@ __global__ void wgrad_h16_reduce_vec_kernel(const float* __restrict__ slabs, flo
     *(f32x4*)(dw + 4 * i) = s;
 }
 
-struct WgradH16Plan { int splits, chunk; size_t table_bytes, slab_bytes; };
+// ---- host side: the switches, then plan / fill / launch per entry point --------------------------------------------------------
+// Every environment variable and tuning global this file reads, read here and nowhere else (meanings: DESIGN.md, switch table).
+// Per call, because tests and tools/ flip them inside one process: MRCNN_H16_SMALL (0 / 1, else -1), MRCNN_H16_TILE, MRCNN_H16_RING
+// and MRCNN_H16P_NO_SPLIT (set or not), MRCNN_H16P_GRID, MRCNN_H16W_DBG, MRCNN_H16P_TRACE, MRCNN_WGRAD_H16_PHASE (default 1), the
+// tuning keys h16_phase and h16_slab.  Once per process: MRCNN_H16_SLAB (counts where the key is -1), MRCNN_H16S_EP_VEC,
+// MRCNN_WGRAD_XCD, MRCNN_MASK_OUT_BWD_V8.
+struct H16Switches {
+    int small; const char* tile; bool ring, no_split, grid_set; int grid, wave_dbg; unsigned long long trace;
+    bool phase, slab, ep_vec; int wgrad_phase, wgrad_xcd, mask_out_bwd_v8;
+};
+extern char** environ;
 
-static WgradH16Plan plan_wgrad_h16(const mrcnn_conv_desc* d) {
-    WgradH16Plan pl;
-    const long long M = (long long)d->N * d->OH * d->OW;
-    const long long tiles = (long long)(d->KH * d->KW * d->Cin / 256) * (d->Cout / 128);
-    long long splits = 768 / (tiles > 0 ? tiles : 1);           // 3 workgroups per CU (48 KiB LDS each)
-    const long long max_splits = (M + 511) / 512;
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (splits > 64) splits = 64;
-    long long chunk = ((M + splits - 1) / splits + 31) / 32 * 32;
-    splits = (M + chunk - 1) / chunk;
-    pl.splits = (int)splits; pl.chunk = (int)chunk;
-    pl.table_bytes = (size_t)(M + 32) * sizeof(PixelEntry);
-    pl.slab_bytes = (size_t)splits * d->KH * d->KW * d->Cin * d->Cout * sizeof(float);
-    return pl;
+static H16Switches h16_switches() {
+    static const struct { bool ep_vec, slab; int xcd, v8; } once = {
+        !(getenv("MRCNN_H16S_EP_VEC") && getenv("MRCNN_H16S_EP_VEC")[0] == '0'),
+        getenv("MRCNN_H16_SLAB") && getenv("MRCNN_H16_SLAB")[0] == '1',
+        getenv("MRCNN_WGRAD_XCD") ? atoi(getenv("MRCNN_WGRAD_XCD")) : 1,
+        getenv("MRCNN_MASK_OUT_BWD_V8") ? atoi(getenv("MRCNN_MASK_OUT_BWD_V8")) : 1};
+    // the per-call ones in ONE pass over the environment, first letter compared inline: a getenv each is a pass each, and a pass
+    // with a strncmp call per entry measured 0.1 ms per 512 x 512 step (~350 launches) slower on the host than two getenvs
+    enum { SMALL, TILE, RING, NO_SPLIT, GRID, WAVE_DBG, TRACE, WGRAD_PHASE, COUNT };
+    static const char* const name[COUNT] = {"H16_SMALL=", "H16_TILE=", "H16_RING=", "H16P_NO_SPLIT=", "H16P_GRID=", "H16W_DBG=", "H16P_TRACE=",
+                                            "WGRAD_H16_PHASE="};
+    static const size_t len[COUNT] = {10, 9, 9, 14, 10, 9, 11, 16};
+    const char* v[COUNT] = {};
+    for (char** e = environ; e && *e; ++e) {
+        if ((*e)[0] != 'M' || strncmp(*e, "MRCNN_", 6)) continue;
+        for (int i = 0; i < COUNT; ++i)
+            if (!v[i] && (*e)[6] == name[i][0] && !strncmp(*e + 6, name[i], len[i])) v[i] = *e + 6 + len[i];
+    }
+    auto num = [&v](int i, int unset) { return v[i] ? atoi(v[i]) : unset; };
+    H16Switches s;
+    s.small = v[SMALL] && (v[SMALL][0] == '0' || v[SMALL][0] == '1') ? v[SMALL][0] - '0' : -1;
+    s.tile = v[TILE]; s.ring = v[RING] != nullptr; s.no_split = v[NO_SPLIT] != nullptr; s.grid_set = v[GRID] != nullptr; s.grid = num(GRID, 0);
+    s.wave_dbg = num(WAVE_DBG, 0); s.trace = v[TRACE] ? strtoull(v[TRACE], nullptr, 0) : 0ull; s.wgrad_phase = num(WGRAD_PHASE, 1);
+    s.phase = g_mrcnn_h16_phase != 0; s.slab = g_mrcnn_h16_slab < 0 ? once.slab : g_mrcnn_h16_slab != 0;
+    s.ep_vec = once.ep_vec; s.wgrad_xcd = once.xcd; s.mask_out_bwd_v8 = once.v8;
+    return s;
 }
 
-// Phased kernel (conv_wgrad_h16p_kernel): stride 1, output as large as the input, 256-channel tiles on both sides, one
-// workgroup per CU in one round, enough K-steps per split for the pipeline to matter.
-struct WgradH16PPlan { int ok, splits, chunk, nk, itiles, ntiles; size_t slab_bytes; };
-
-static WgradH16PPlan plan_wgrad_h16p(const mrcnn_conv_desc* d) {
-    WgradH16PPlan pl;
-    memset(&pl, 0, sizeof(pl));
-    // MRCNN_WGRAD_H16_PHASE (read per call: tests and A/B timings switch it): 0 never, 1 where it pays (default), 2 on every
-    // shape the kernel can take (tests: short and ragged pixel ranges)
-    const char* env = getenv("MRCNN_WGRAD_H16_PHASE");
-    const int enabled = env ? atoi(env) : 1;
-    const long long M = (long long)d->N * d->OH * d->OW;
-    if (!enabled || d->stride != 1 || d->OH != d->H || d->OW != d->W || d->Cin % 256 || d->Cout % 256 || d->KH * d->KW > 64 ||
-        d->pad_t < 0 || d->pad_l < 0 || d->pad_t >= d->KH || d->pad_l >= d->KW || M * d->Cout * 2 >= 0xFFFFFF00LL)
-        return pl;
-    const int cus = mrcnn_num_cus();
-    pl.itiles = d->KH * d->KW * d->Cin / 256; pl.ntiles = d->Cout / 256;
-    const long long tiles = (long long)pl.itiles * pl.ntiles;
-    long long splits = cus / tiles;
-    if (splits < 1) splits = 1;
-    if (splits > 64) splits = 64;
-    const long long chunk = ((M + splits - 1) / splits + 63) / 64 * 64;
-    splits = (M + chunk - 1) / chunk;
-    if (enabled < 2 && (chunk < 64 * 32 || tiles * splits * 2 < cus)) return pl;   // short K loops / half-empty chip: the table kernel's case
-    pl.ok = 1; pl.splits = (int)splits; pl.chunk = (int)chunk; pl.nk = (int)(chunk / 64);
-    pl.slab_bytes = (size_t)splits * d->KH * d->KW * d->Cin * d->Cout * sizeof(float);
-    return pl;
+// One definition each: 16-byte alignment (NULL counts as aligned), plain NHWC output, the operands' extents, the workspace layout.
+static bool h16_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static bool h16_dense(const mrcnn_conv_desc* d) {
+    return d->out_mode == MRCNN_OUT_NHWC && d->out_w_stride == d->Cout && d->out_h_stride == (int64_t)d->OW * d->Cout &&
+           d->out_n_stride == (int64_t)d->OH * d->OW * d->Cout;
 }
+struct H16Extent { long long M, xbytes, shift_b, wbytes, ybytes; };      // output rows; bytes of x, of its padding shift, of w, of the output
+static H16Extent h16_extent(const mrcnn_conv_desc* d) {
+    const long long M = (long long)d->N * d->OH * d->OW;
+    return {M, (long long)d->N * d->H * d->W * d->Cin * 2, ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 2,
+            (long long)d->KH * d->KW * d->Cin * d->Cout * 2, M * d->Cout * 2};
+}
+struct H16Operands { const void *x, *w_t; const float *bias, *scale, *shift; const void* res; void *out, *z_out; const mrcnn_bwd_epilogue_h16* ep; };
+static char* h16_align256(void* p, size_t bytes = 0) { return (char*)((reinterpret_cast<uintptr_t>(p) + bytes + 255) & ~(uintptr_t)255); }
 
+#define H16_LAUNCH(dtype, stream, kernel, grid, threads, args, ...)                                                                    \
+    do {                                                                                                                              \
+        if ((dtype) == MRCNN_DTYPE_F16) hipLaunchKernelGGL((kernel<_Float16, ##__VA_ARGS__>), dim3((unsigned)(grid)), dim3(threads), 0, stream, args); \
+        else hipLaunchKernelGGL((kernel<__bf16, ##__VA_ARGS__>), dim3((unsigned)(grid)), dim3(threads), 0, stream, args);              \
+    } while (0)
+
+// ---- weight gradient ----------------------------------------------------------------------------------------------------------
 static int wgrad_h16_shape_ok(const mrcnn_conv_desc* d) {
     return d && d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 &&
            d->OH > 0 && d->OW > 0 && d->KH * d->KW <= 64 && d->Cin % 256 == 0 && d->Cout % 128 == 0;
 }
 
+// Pixel split of M rows into `splits` chunks of a multiple of `step` rows; the split count follows from the chunk.
+static void h16_wgrad_split(long long M, long long splits, int step, int32_t* out_splits, int32_t* out_chunk) {
+    if (splits < 1) splits = 1;
+    if (splits > 64) splits = 64;
+    const long long chunk = ((M + splits - 1) / splits + step - 1) / step * step;
+    *out_chunk = (int)chunk; *out_splits = (int)((M + chunk - 1) / chunk);
+}
+
+// The phased kernel (256 x 256 tiles, one workgroup per CU in one round) where its shape rules hold and dw is 16-byte aligned (vec_ok;
+// the slabs are by the workspace layout), else the table-driven one (256 x 128 tiles, 3 workgroups per CU: splits towards 768
+// workgroups, one per 512 rows at most); the workspace has room for either kernel's slabs.  DESIGN 4.1 "selection".
+static void h16_wgrad_plan(const mrcnn_conv_desc* d, const H16Switches& sw, int cus, bool vec_ok, mrcnn_h16_wgrad_plan* p) {
+    memset(p, 0, sizeof(*p));
+    const long long M = h16_extent(d).M, ktot = (long long)d->KH * d->KW * d->Cin, n = ktot * d->Cout;
+    mrcnn_h16_wgrad_plan t = *p, ph = *p;
+    const long long ttiles = (ktot / 256) * (d->Cout / 128);
+    h16_wgrad_split(M, std::min<long long>(768 / (ttiles > 0 ? ttiles : 1), (M + 511) / 512), 32, &t.splits, &t.chunk);
+    t.kernel = MRCNN_H16_WGRAD_TABLE; t.grid = (int)(ttiles * t.splits);
+    bool phased = sw.wgrad_phase && d->stride == 1 && d->OH == d->H && d->OW == d->W && d->Cin % 256 == 0 && d->Cout % 256 == 0 &&
+                  d->KH * d->KW <= 64 && d->pad_t >= 0 && d->pad_l >= 0 && d->pad_t < d->KH && d->pad_l < d->KW && M * d->Cout * 2 < 0xFFFFFF00LL;
+    if (phased) {
+        ph.kernel = MRCNN_H16_WGRAD_PHASE; ph.itiles = (int)(ktot / 256); ph.ntiles = d->Cout / 256;
+        const long long tiles = (long long)ph.itiles * ph.ntiles;
+        h16_wgrad_split(M, cus / tiles, 64, &ph.splits, &ph.chunk);
+        ph.nk = ph.chunk / 64; ph.grid = (int)(tiles * ph.splits);
+        // short K loops / half-empty chip: the table kernel's case
+        phased = sw.wgrad_phase >= 2 || !(ph.chunk < 64 * 32 || tiles * ph.splits * 2 < cus);
+    }
+    const long long tslab = t.splits * n * 4, pslab = phased ? ph.splits * n * 4 : 0;
+    *p = phased && vec_ok ? ph : t;
+    p->xcd_order = sw.wgrad_xcd;
+    p->reduce = vec_ok && n % 4 == 0 ? MRCNN_H16_RED_VEC : MRCNN_H16_RED_SCALAR;      // (phased: Cout % 256 == 0, so n % 4 == 0)
+    p->reduce_grid = (int)(p->reduce == MRCNN_H16_RED_VEC ? cdiv64(n / 4, 256) : cdiv64(n, 256));
+    p->table_bytes = (M + 32) * (long long)sizeof(PixelEntry);
+    p->slab_bytes = p->kernel == MRCNN_H16_WGRAD_PHASE ? pslab : tslab;
+    p->workspace_bytes = p->table_bytes + std::max(tslab, pslab) + 512;
+}
+
 extern "C" size_t mrcnn_conv2d_wgrad_h16_workspace(const mrcnn_conv_desc* d) {
     if (!wgrad_h16_shape_ok(d)) return 0;
-    const WgradH16Plan pl = plan_wgrad_h16(d);
-    const WgradH16PPlan pp = plan_wgrad_h16p(d);
-    const size_t slabs = pl.slab_bytes > pp.slab_bytes ? pl.slab_bytes : pp.slab_bytes;
-    return pl.table_bytes + slabs + 512;
+    mrcnn_h16_wgrad_plan p;
+    h16_wgrad_plan(d, h16_switches(), mrcnn_num_cus(), true, &p);
+    return (size_t)p.workspace_bytes;
+}
+
+extern "C" int mrcnn_conv2d_wgrad_h16_plan(const mrcnn_conv_desc* d, int dtype, const void* x, const void* dy, const float* dw,
+                                           const void* workspace, size_t workspace_bytes, mrcnn_h16_wgrad_plan* plan) {
+    if (!wgrad_h16_shape_ok(d) || !x || !dy || !dw || !workspace || !h16_dtype_ok(dtype) || !plan) return MRCNN_ERR_ARG;
+    if (!h16_aligned(x) || !h16_aligned(dy)) return MRCNN_ERR_ARG;
+    const H16Extent e = h16_extent(d);
+    if (e.M >= (1LL << 30) || e.xbytes + e.shift_b >= 0x7FFFFF00LL || e.ybytes >= 0x7FFFFF00LL) return MRCNN_ERR_ARG;
+    mrcnn_h16_wgrad_plan p;
+    h16_wgrad_plan(d, h16_switches(), mrcnn_num_cus(), h16_aligned(dw), &p);
+    if (workspace_bytes < (size_t)p.workspace_bytes) return MRCNN_ERR_WORKSPACE;
+    *plan = p;
+    return MRCNN_OK;
 }
 
 extern "C" int mrcnn_conv2d_wgrad_h16(const mrcnn_conv_desc* d, int dtype, const void* x, const void* dy, float* dw,
                                       void* workspace, size_t workspace_bytes, int beta_acc, float multiplier, void* stream) {
-    if (!wgrad_h16_shape_ok(d) || !x || !dy || !dw || !workspace || !h16_dtype_ok(dtype)) return MRCNN_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(dy) & 15)) return MRCNN_ERR_ARG;
-    const long long M = (long long)d->N * d->OH * d->OW;
-    const long long xbytes = (long long)d->N * d->H * d->W * d->Cin * 2;
-    const long long shift_b = ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 2;
-    if (M >= (1LL << 30) || xbytes + shift_b >= 0x7FFFFF00LL || M * d->Cout * 2 >= 0x7FFFFF00LL) return MRCNN_ERR_ARG;
-    const WgradH16Plan pl = plan_wgrad_h16(d);
-    if (workspace_bytes < mrcnn_conv2d_wgrad_h16_workspace(d)) return MRCNN_ERR_WORKSPACE;
-    char* ws = (char*)((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    PixelEntry* table = (PixelEntry*)ws;
-    float* slabs = (float*)(ws + ((pl.table_bytes + 255) & ~(size_t)255));
+    mrcnn_h16_wgrad_plan p;
+    const int rc = mrcnn_conv2d_wgrad_h16_plan(d, dtype, x, dy, dw, workspace, workspace_bytes, &p);
+    if (rc != MRCNN_OK) return rc;
+    const H16Extent e = h16_extent(d);
+    PixelEntry* table = (PixelEntry*)h16_align256(workspace);
+    float* slabs = (float*)h16_align256(table, (size_t)p.table_bytes);
+    const int ktot = d->KH * d->KW * d->Cin;
     hipStream_t s = (hipStream_t)stream;
-    const WgradH16PPlan pp = plan_wgrad_h16p(d);
-    if (pp.ok && ((reinterpret_cast<uintptr_t>(slabs) | reinterpret_cast<uintptr_t>(dw)) & 15) == 0) {
+    if (p.kernel == MRCNN_H16_WGRAD_PHASE) {
         WgradH16PArgs b;
         b.x = x; b.dy = dy; b.out = slabs;
         b.H = d->H; b.W = d->W; b.Cin = d->Cin; b.Cout = d->Cout; b.KW = d->KW; b.pad_t = d->pad_t; b.pad_l = d->pad_l;
-        b.M = (int)M; b.Ktot = d->KH * d->KW * d->Cin; b.chunk = pp.chunk; b.nk = pp.nk; b.itiles = pp.itiles; b.ntiles = pp.ntiles;
-        b.ohw = d->OH * d->OW;
-        { const char* xe = getenv("MRCNN_WGRAD_XCD"); b.xcd_order = xe ? atoi(xe) : 1; }
-        b.x_shift = (unsigned)shift_b; b.x_records = (unsigned)(xbytes + shift_b);
+        b.M = (int)e.M; b.Ktot = ktot; b.chunk = p.chunk; b.nk = p.nk; b.itiles = p.itiles; b.ntiles = p.ntiles;
+        b.ohw = d->OH * d->OW; b.xcd_order = p.xcd_order;
+        b.x_shift = (unsigned)e.shift_b; b.x_records = (unsigned)(e.xbytes + e.shift_b);
         h16_magic((unsigned)(d->OH * d->OW), &b.mg_ohw, &b.sh_ohw);
         h16_magic((unsigned)d->OW, &b.mg_ow, &b.sh_ow);
-        const unsigned pblocks = (unsigned)(pp.itiles * pp.ntiles * pp.splits);
-        if (dtype == MRCNN_DTYPE_F16) hipLaunchKernelGGL(conv_wgrad_h16p_kernel<_Float16>, dim3(pblocks), dim3(512), 0, s, b);
-        else hipLaunchKernelGGL(conv_wgrad_h16p_kernel<__bf16>, dim3(pblocks), dim3(512), 0, s, b);
-        const long long n = (long long)b.Ktot * b.Cout;                  // Cout % 256 == 0: the vector reduction always fits
-        hipLaunchKernelGGL(wgrad_h16_reduce_vec_kernel, dim3((unsigned)cdiv64(n / 4, 256)), dim3(256), 0, s, slabs, dw, n / 4,
-                           pp.splits, beta_acc, multiplier);
-        return mrcnn_launch_status();
+        H16_LAUNCH(dtype, s, conv_wgrad_h16p_kernel, p.grid, 512, b);
+    } else {
+        const int rows = (int)e.M + 32;
+        hipLaunchKernelGGL(pixel_table_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, table, d->N, d->H, d->W, d->Cin,
+                           d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->OH, d->OW, (int)e.M, rows, (unsigned)e.shift_b, 2);
+        WgradH16Args a;
+        a.x = x; a.dy = dy; a.out = slabs; a.table = table;
+        a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW; a.OH = d->OH; a.OW = d->OW;
+        a.M = (int)e.M; a.Ktot = ktot; a.splits = p.splits; a.chunk = p.chunk; a.xcd_order = p.xcd_order;
+        a.x_shift = (unsigned)e.shift_b; a.x_records = (unsigned)(e.xbytes + e.shift_b);
+        H16_LAUNCH(dtype, s, conv_wgrad_h16_kernel, p.grid, 256, a);
     }
-    const int rows = (int)M + 32;
-    hipLaunchKernelGGL(pixel_table_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, table, d->N, d->H, d->W, d->Cin,
-                       d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->OH, d->OW, (int)M, rows, (unsigned)shift_b, 2);
-    WgradH16Args a;
-    a.x = x; a.dy = dy; a.out = slabs; a.table = table;
-    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW; a.OH = d->OH; a.OW = d->OW;
-    a.M = (int)M; a.Ktot = d->KH * d->KW * d->Cin; a.splits = pl.splits; a.chunk = pl.chunk;
-    a.x_shift = (unsigned)shift_b; a.x_records = (unsigned)(xbytes + shift_b);
-    static const int xcd_env = getenv("MRCNN_WGRAD_XCD") ? atoi(getenv("MRCNN_WGRAD_XCD")) : 1;
-    a.xcd_order = xcd_env;
-    const unsigned blocks = (unsigned)((a.Ktot / 256) * (a.Cout / 128) * pl.splits);
-    if (dtype == MRCNN_DTYPE_F16)
-        hipLaunchKernelGGL(conv_wgrad_h16_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, a);
+    const long long n = (long long)ktot * d->Cout;
+    if (p.reduce == MRCNN_H16_RED_VEC)
+        hipLaunchKernelGGL(wgrad_h16_reduce_vec_kernel, dim3((unsigned)p.reduce_grid), dim3(256), 0, s, slabs, dw, n / 4, p.splits, beta_acc, multiplier);
     else
-        hipLaunchKernelGGL(conv_wgrad_h16_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, a);
-    const long long n = (long long)a.Ktot * a.Cout;
-    if (n % 4 == 0 && ((reinterpret_cast<uintptr_t>(slabs) | reinterpret_cast<uintptr_t>(dw)) & 15) == 0)
-        hipLaunchKernelGGL(wgrad_h16_reduce_vec_kernel, dim3((unsigned)cdiv64(n / 4, 256)), dim3(256), 0, s, slabs, dw, n / 4,
-                           pl.splits, beta_acc, multiplier);
-    else
-        hipLaunchKernelGGL(wgrad_h16_reduce_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, slabs, dw, n, pl.splits,
-                           beta_acc, multiplier);
+        hipLaunchKernelGGL(wgrad_h16_reduce_kernel, dim3((unsigned)p.reduce_grid), dim3(256), 0, s, slabs, dw, n, p.splits, beta_acc, multiplier);
     return mrcnn_launch_status();
 }
 
-
-// x / d for x < 2^31 as (umulhi(x, mg) >> sh): mg = ceil(2^(31+s) / d), s = ceil(log2 d), sh = s - 1; d = 1 -> mg = 0 (no division)
-static void h16_magic(unsigned d, unsigned* mg, unsigned* sh) {
-    if (d <= 1) { *mg = 0; *sh = 0; return; }
-    unsigned sft = 0;
-    while ((1ull << sft) < d) ++sft;
-    *mg = (unsigned)(((1ull << (31 + sft)) + d - 1) / d);
-    *sh = sft - 1;
-}
-
-static thread_local const mrcnn_bwd_epilogue_h16* g_h16_fb = nullptr;   // set around the call by mrcnn_conv2d_dgrad_ep_h16
-
-// Which 16-bit forward kernel a shape takes: 2 = small tile (64 x 64), 1 = large tile (256 x 128 / 256 x 256), 0 = none.
-static int h16_fwd_kernel_for(const mrcnn_conv_desc* d, const void* res) {
+// ---- forward / data gradient --------------------------------------------------------------------------------------------------
+// Which tiles a shape takes: 2 = small (64 x 64), 1 = large (256 x 128 / 256 x 256), 0 = none.
+static int h16_tile_class(const mrcnn_conv_desc* d, bool has_res, const H16Switches& sw) {
     if (!d || d->Cin % 32 || d->KH * d->KW > 64) return 0;
-    const long long M = (long long)d->N * d->OH * d->OW;
-    const bool dense = d->out_mode == MRCNN_OUT_NHWC && d->out_w_stride == d->Cout && d->out_h_stride == (int64_t)d->OW * d->Cout &&
-                       d->out_n_stride == (int64_t)d->OH * d->OW * d->Cout;
-    const bool large_ok = d->Cout % 128 == 0 && !res && (dense || d->out_mode == MRCNN_OUT_DECONV2);
+    const bool large_ok = d->Cout % 128 == 0 && !has_res && (h16_dense(d) || d->out_mode == MRCNN_OUT_DECONV2);
     const bool small_ok = d->Cin % 64 == 0 && d->Cout % 64 == 0 && d->out_mode == MRCNN_OUT_NHWC && d->cmod == d->Cout;
-    const char* force = getenv("MRCNN_H16_SMALL");                   // A/B: 0 = never, 1 = whenever possible
-    if (force && force[0] == '0') return large_ok ? 1 : 0;
-    if (force && force[0] == '1') return small_ok ? 2 : (large_ok ? 1 : 0);
-    // the large tiles need a few hundred workgroups to fill the chip; below that the short dependent chains of the small
-    // tiles win (and they are the only ones with a residual port and strided output)
-    const long long large_wgs = ((M + 255) / 256) * (d->Cout / 128);
+    if (sw.small == 0) return large_ok ? 1 : 0;
+    if (sw.small == 1) return small_ok ? 2 : (large_ok ? 1 : 0);
+    const long long large_wgs = cdiv64(h16_extent(d).M, 256) * (d->Cout / 128);
     if (large_ok && (large_wgs >= 384 || !small_ok)) return 1;
     return small_ok ? 2 : 0;
 }
 
 extern "C" int mrcnn_conv2d_fwd_h16_supported(const mrcnn_conv_desc* d, int has_res) {
-    return h16_fwd_kernel_for(d, has_res ? (const void*)d : nullptr) != 0;
+    return h16_tile_class(d, has_res != 0, h16_switches()) != 0;
 }
 
-extern "C" int mrcnn_conv2d_fwd_h16_res(const mrcnn_conv_desc* d, int dtype, const void* x, const void* w_t, const float* bias,
-                                        const float* scale, const float* shift, const void* res, void* out, void* z_out,
-                                        void* stream) {
+// Validates the call, then states the selection as rules in order of preference: small tile (backward epilogue or tile class);
+// wave128 where asked for; the phased persistent kernel (deconvolution / slab / per-tap form, a short last round handed to the small
+// tile); big where asked for; ring where asked for; 256 x 128.  DESIGN 4.1 "selection" has the reasons and measurements.
+// Launches nothing, calls no HIP function and looks at nullness and 16-byte alignment of the operands only.
+static int h16_fwd_plan(const mrcnn_conv_desc* d, int dtype, const H16Operands& o, const H16Switches& sw, int cus, mrcnn_h16_plan* p) {
+    const void *x = o.x, *w_t = o.w_t, *res = o.res, *out = o.out, *z_out = o.z_out, *bias = o.bias, *scale = o.scale, *shift = o.shift;
+    const mrcnn_bwd_epilogue_h16* ep = o.ep;
+    if (ep && ((ep->act != MRCNN_ACT_NONE && ep->act != MRCNN_ACT_RELU) || (ep->act == MRCNN_ACT_RELU && !ep->out))) return MRCNN_ERR_ARG;
+    if (ep && ep->dgamma && (!ep->z || !ep->mean || !ep->rstd)) return MRCNN_ERR_ARG;
     if (!d || !x || !w_t || !out || !h16_dtype_ok(dtype)) return MRCNN_ERR_ARG;
     if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 || d->stride <= 0 ||
         d->OH <= 0 || d->OW <= 0 || d->KH * d->KW > 64)
         return MRCNN_ERR_ARG;
     if (d->res_mode == MRCNN_RES_UP2 || (d->res_mode == MRCNN_RES_SAME) != (res != nullptr)) return MRCNN_ERR_ARG;
-    int which = h16_fwd_kernel_for(d, res);
-    if (!which) return MRCNN_ERR_ARG;
-    if (d->out_mode == MRCNN_OUT_DECONV2) {
-        if (d->Cout != 4 * d->cmod || d->cmod % 128 || z_out) return MRCNN_ERR_ARG;
-    } else if (d->out_mode != MRCNN_OUT_NHWC || d->cmod != d->Cout) {
+    const int cls = h16_tile_class(d, res != nullptr, sw);
+    if (!cls) return MRCNN_ERR_ARG;
+    if (d->out_mode == MRCNN_OUT_DECONV2 ? (d->Cout != 4 * d->cmod || d->cmod % 128 || z_out) : (d->out_mode != MRCNN_OUT_NHWC || d->cmod != d->Cout))
         return MRCNN_ERR_ARG;
-    }
     if (scale && !shift) return MRCNN_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w_t) & 15)) return MRCNN_ERR_ARG;
-    const long long M = (long long)d->N * d->OH * d->OW;
-    const long long xbytes = (long long)d->N * d->H * d->W * d->Cin * 2;
-    const long long shift_b = ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 2;
-    const long long wbytes = (long long)d->KH * d->KW * d->Cin * d->Cout * 2;
-    if (M >= (1LL << 31) || xbytes + shift_b >= 0x7FFFFFF0LL || wbytes >= 0x7FFFFFF0LL) return MRCNN_ERR_ARG;
-    ConvH16Args a;
-    a.x = x; a.wt = w_t; a.bias = bias; a.scale = scale; a.shift = shift; a.out = out; a.z = z_out; a.res = res;
-    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW;
-    a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.OH = d->OH; a.OW = d->OW; a.act = d->act;
-    a.M = (int)M; a.Ktot = d->KH * d->KW * d->Cin;
-    a.x_shift = (unsigned)shift_b; a.x_records = (unsigned)(xbytes + shift_b); a.w_records = (unsigned)wbytes;
-    a.out_records = (unsigned)std::min<long long>(M * d->Cout * 2, 0xFFFFFFF0LL);
-    a.out_mode = d->out_mode; a.cmod = d->cmod; a.ons = d->out_n_stride; a.ohs = d->out_h_stride; a.ows = d->out_w_stride;
-    a.dense = d->out_mode == MRCNN_OUT_NHWC && d->out_w_stride == d->Cout && d->out_h_stride == (int64_t)d->OW * d->Cout &&
-              d->out_n_stride == (int64_t)d->OH * d->OW * d->Cout;
-    a.ptiles = 0; a.mtile0 = 0;
-    a.dbg = nullptr;
-    h16_magic((unsigned)(d->OH * d->OW), &a.mg_ohw, &a.sh_ohw);
-    h16_magic((unsigned)d->OW, &a.mg_ow, &a.sh_ow);
-    if (const char* t = getenv("MRCNN_H16P_TRACE")) a.dbg = (unsigned long long*)strtoull(t, nullptr, 0);   // device buffer of 1024 x u64
-    a.fb_act = -1; a.fb_out = a.fb_z = nullptr; a.fb_scale = a.fb_mean = a.fb_rstd = nullptr;
-    a.fb_dgamma = a.fb_dbeta = a.fb_dbias = nullptr; a.fb_dy = nullptr; a.fb_gmul = 1.f;
-    if (g_h16_fb) {                              // mrcnn_conv2d_dgrad_ep_h16: small-tile kernel only, dense, plain store
-        if (which != 2 && !(d->Cin % 64 == 0 && d->Cout % 64 == 0)) return MRCNN_ERR_UNSUPPORTED;
-        if (!a.dense || bias || scale || z_out || d->act != MRCNN_ACT_NONE || d->stride != 1) return MRCNN_ERR_UNSUPPORTED;
-        which = 2;
-        const mrcnn_bwd_epilogue_h16* ep = g_h16_fb;
-        a.fb_act = ep->act; a.fb_out = ep->out; a.fb_z = ep->z; a.fb_scale = ep->scale; a.fb_mean = ep->mean; a.fb_rstd = ep->rstd;
-        a.fb_dgamma = ep->dgamma; a.fb_dbeta = ep->dbeta; a.fb_dbias = ep->dbias; a.fb_dy = ep->dy; a.fb_gmul = ep->grad_multiplier;
+    if (!h16_aligned(x) || !h16_aligned(w_t)) return MRCNN_ERR_ARG;
+    const H16Extent e = h16_extent(d);
+    if (e.M >= (1LL << 31) || e.xbytes + e.shift_b >= 0x7FFFFFF0LL || e.wbytes >= 0x7FFFFFF0LL) return MRCNN_ERR_ARG;
+    const bool dense = h16_dense(d);
+    if (ep) {                                    // small-tile kernel only, dense, plain store
+        if (cls != 2 && !(d->Cin % 64 == 0 && d->Cout % 64 == 0)) return MRCNN_ERR_UNSUPPORTED;
+        if (!dense || bias || scale || z_out || d->act != MRCNN_ACT_NONE || d->stride != 1) return MRCNN_ERR_UNSUPPORTED;
     }
-    {   // 16-byte epilogue of the small-tile kernel: every tensor it touches 16-byte aligned, pixel strides multiples of 8 elements
-        static const bool on = !(getenv("MRCNN_H16S_EP_VEC") && getenv("MRCNN_H16S_EP_VEC")[0] == '0');
-        auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        a.ep_vec = on && d->Cout % 64 == 0 && al(a.out) && al(a.z) && al(a.res) && al(a.fb_out) && al(a.fb_z) && al(a.fb_dy) &&
-                   a.ons % 8 == 0 && a.ohs % 8 == 0 && a.ows % 8 == 0;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (which == 2) {
-        const unsigned blocks = (unsigned)(((M + 63) / 64) * (d->Cout / 64));
-        if (dtype == MRCNN_DTYPE_F16) hipLaunchKernelGGL(conv_fwd_h16s_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(conv_fwd_h16s_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, a);
-        return mrcnn_launch_status();
-    }
-    // Large tiles (read per call so that tests and A/B timings can switch: MRCNN_H16_TILE = big | small | ring):
-    //   big    256 x 256, 8 waves, 4-stage ring, one workgroup per CU -- Cout % 256 == 0
-    //   phase  256 x 256, 8 waves in two staggered groups, persistent (default from one full round of tiles on)
-    //   small  256 x 128, 4 waves, double buffered, 3 workgroups per CU (the round-1 kernel; the default below that)
-    //   ring   256 x 128 with a 3-slot ring (round-1 experiment)
-    const char* tile = getenv("MRCNN_H16_TILE");
-    const long long big_tiles = ((M + 255) / 256) * (d->Cout / 256);
-    // small and big stop at ~30 % of the matrix peak (745-810 TFLOP/s on the mask-head shape): per K-step a wave spends
-    // about as long issuing its LDS-DMA pieces and waiting for operand reads as the matrix pipe needs for its MFMAs, and
-    // the two waves of a SIMD do it in lockstep.  De-phasing them with duplicated bodies or a selector loop made hipcc spill
-    // the accumulators; the phased kernel gets the stagger from one extra barrier instead (1.0-1.06 PFLOP/s here, 1.15-1.2
-    // where the tiles are whole rounds; measured shader clock under it: 1.96 GHz, tools/h16p_trace.py).
-    bool big = false;
-    if (tile && !strcmp(tile, "big")) big = d->Cout % 256 == 0;
-    if (tile && !strcmp(tile, "wave128") && d->Cout % 256 == 0 && a.dense && !res && d->Cin % 32 == 0 &&
-        !((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(z_out)) & 15)) {
-        const unsigned blocks = (unsigned)big_tiles;
-        if (const char* dbg = getenv("MRCNN_H16W_DBG")) a.mtile0 = atoi(dbg);      // timing experiments: 1 = no MFMAs, 2 = no operand reads
-        if (dtype == MRCNN_DTYPE_F16) hipLaunchKernelGGL((conv_fwd_h16_kernel<_Float16, 4, 2, 2, 4>), dim3(blocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv_fwd_h16_kernel<__bf16, 4, 2, 2, 4>), dim3(blocks), dim3(256), 0, s, a);
-        return mrcnn_launch_status();
+    memset(p, 0, sizeof(*p));
+    p->dense = dense; p->fused_ep = ep != nullptr; p->trace = sw.trace;
+    // 16-byte epilogue of the small-tile kernel: every tensor it touches 16-byte aligned, pixel strides multiples of 8 elements
+    p->ep_vec = sw.ep_vec && d->Cout % 64 == 0 && h16_aligned(out) && h16_aligned(z_out) && h16_aligned(res) &&
+                (!ep || (h16_aligned(ep->out) && h16_aligned(ep->z) && h16_aligned(ep->dy))) && d->out_n_stride % 8 == 0 &&
+                d->out_h_stride % 8 == 0 && d->out_w_stride % 8 == 0;
+    auto take = [p](int kernel, long long grid, int threads) { p->kernel = kernel; p->grid = (int)(unsigned)grid; p->threads = threads; return MRCNN_OK; };
+    const long long small_cols = d->Cout / 64, big_tiles = cdiv64(e.M, 256) * (d->Cout / 256);
+    auto tile = [&sw](const char* name) { return sw.tile && !strcmp(sw.tile, name); };
+    if (ep || cls == 2) return take(MRCNN_H16_S64, cdiv64(e.M, 64) * small_cols, 256);
+    if (tile("wave128") && d->Cout % 256 == 0 && dense && !res && d->Cin % 32 == 0 && h16_aligned(out) && h16_aligned(z_out)) {
+        p->mtile0 = sw.wave_dbg; return take(MRCNN_H16_WAVE128, big_tiles, 256);
     }
     // the transposed convolution's pixel-shuffle store (MRCNN_OUT_DECONV2) is the same kernel with another row address
     const bool deconv_p = d->out_mode == MRCNN_OUT_DECONV2 && d->cmod % 64 == 0 && d->cmod <= 512 && d->Cout == 4 * d->cmod && !z_out;
-    const bool phased_ok = d->Cout % 256 == 0 && (deconv_p || (d->Cout <= 512 && a.dense)) && d->Cin % 64 == 0 && d->KH * d->KW <= 31 &&
-                           !res && (d->act == MRCNN_ACT_NONE || d->act == MRCNN_ACT_RELU) && M * d->Cout * 2 < 0xFFFFFFF0LL;
-    // phase: persistent 256 x 256 tiles (see conv_fwd_h16p_kernel), the default where a shape has at least one full round of
-    // them; a last partial round of at most half the CUs goes to the small-tile kernel instead (a 256-row tile costs a full
-    // tile time however few there are; 64-row tiles spread the same rows over the whole chip)
-    const int cus = mrcnn_num_cus();
-    const bool want_phase = tile ? !strcmp(tile, "phase") : (big_tiles >= cus && g_mrcnn_h16_phase);
-    if (phased_ok && want_phase) {
+    const bool phased_ok = d->Cout % 256 == 0 && (deconv_p || (d->Cout <= 512 && dense)) && d->Cin % 64 == 0 && d->KH * d->KW <= 31 &&
+                           !res && (d->act == MRCNN_ACT_NONE || d->act == MRCNN_ACT_RELU) && e.ybytes < 0xFFFFFFF0LL;
+    if (phased_ok && (sw.tile ? tile("phase") : (big_tiles >= cus && sw.phase))) {
         const int ntn = d->Cout / 256;
         long long own = big_tiles;
         const long long full = big_tiles / cus * cus / ntn * ntn;
-        if (full > 0 && big_tiles - full > 0 && (big_tiles - full) * 2 <= cus && !getenv("MRCNN_H16P_NO_SPLIT") && !deconv_p) own = full;
-        a.ptiles = (int)own;
-        unsigned blocks = (unsigned)std::min<long long>(own, cus);   // one workgroup per CU (LDS)
-        if (const char* g = getenv("MRCNN_H16P_GRID")) blocks = (unsigned)std::min<long long>(own, atoi(g));   // experiments
-        // slab form (conv_fwd_h16q_kernel): 3 x 3 / stride 1 / pad 1 on maps no wider than 14 pixels (halo of W + 1 <= 15 rows), an
-        // even number of 64-channel chunks (the two slab buffers alternate by chunk parity across tiles): the mask head's layers
-        // OFF by default: correct (test_conv_fwd_h16_slab) and 8-12 % SLOWER than the per-tap staging on the mask-head layer (0.419 ->
-        // 0.474 ms; with the border masks knocked out 0.422-0.431 ms: halving the pixel pieces buys nothing, the masks cost) --
-        // tools/h16_slab_probe.py, DESIGN 4.1c
-        static const bool slab_env = getenv("MRCNN_H16_SLAB") && getenv("MRCNN_H16_SLAB")[0] == '1';
-        const bool slab_on = g_mrcnn_h16_slab < 0 ? slab_env : g_mrcnn_h16_slab != 0;
-        const bool slab = slab_on && !deconv_p && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
-                          d->OH == d->H && d->OW == d->W && d->W <= 14 && d->Cin % 128 == 0 && a.dense && d->Cout <= 512;
-        if (slab) {
-            if (dtype == MRCNN_DTYPE_F16) {
-                if (z_out) hipLaunchKernelGGL((conv_fwd_h16q_kernel<_Float16, true>), dim3(blocks), dim3(512), 0, s, a);
-                else hipLaunchKernelGGL((conv_fwd_h16q_kernel<_Float16, false>), dim3(blocks), dim3(512), 0, s, a);
-            } else {
-                if (z_out) hipLaunchKernelGGL((conv_fwd_h16q_kernel<__bf16, true>), dim3(blocks), dim3(512), 0, s, a);
-                else hipLaunchKernelGGL((conv_fwd_h16q_kernel<__bf16, false>), dim3(blocks), dim3(512), 0, s, a);
-            }
-        } else if (deconv_p) {
-            if (dtype == MRCNN_DTYPE_F16) hipLaunchKernelGGL((conv_fwd_h16p_kernel<_Float16, false, true>), dim3(blocks), dim3(512), 0, s, a);
-            else hipLaunchKernelGGL((conv_fwd_h16p_kernel<__bf16, false, true>), dim3(blocks), dim3(512), 0, s, a);
-        } else if (dtype == MRCNN_DTYPE_F16) {
-            if (z_out) hipLaunchKernelGGL((conv_fwd_h16p_kernel<_Float16, true, false>), dim3(blocks), dim3(512), 0, s, a);
-            else hipLaunchKernelGGL((conv_fwd_h16p_kernel<_Float16, false, false>), dim3(blocks), dim3(512), 0, s, a);
-        } else {
-            if (z_out) hipLaunchKernelGGL((conv_fwd_h16p_kernel<__bf16, true, false>), dim3(blocks), dim3(512), 0, s, a);
-            else hipLaunchKernelGGL((conv_fwd_h16p_kernel<__bf16, false, false>), dim3(blocks), dim3(512), 0, s, a);
-        }
+        if (full > 0 && big_tiles - full > 0 && (big_tiles - full) * 2 <= cus && !sw.no_split && !deconv_p) own = full;
         if (own < big_tiles) {
-            const long long mdone = own / ntn * 256;
-            a.mtile0 = (int)(mdone / 64);
-            const unsigned rblocks = (unsigned)(((M - mdone + 63) / 64) * (d->Cout / 64));
-            if (dtype == MRCNN_DTYPE_F16) hipLaunchKernelGGL(conv_fwd_h16s_kernel<_Float16>, dim3(rblocks), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL(conv_fwd_h16s_kernel<__bf16>, dim3(rblocks), dim3(256), 0, s, a);
+            p->rem_mtile0 = (int)(own / ntn * 4);                                  // 256-row tiles done, in 64-row tiles
+            p->rem_grid = (int)(unsigned)(cdiv64(e.M - own / ntn * 256, 64) * small_cols);
         }
-        return mrcnn_launch_status();
+        const bool slab = sw.slab && !deconv_p && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
+                          d->OH == d->H && d->OW == d->W && d->W <= 14 && d->Cin % 128 == 0 && dense && d->Cout <= 512;
+        p->ptiles = (int)own; p->zout = z_out != nullptr;
+        return take(slab ? MRCNN_H16_SLAB : deconv_p ? MRCNN_H16_PHASE_DECONV : MRCNN_H16_PHASE,
+                    std::min<long long>(own, sw.grid_set ? sw.grid : cus), 512);      // one workgroup per CU (LDS)
     }
-    const bool ring = (tile && !strcmp(tile, "ring")) || getenv("MRCNN_H16_RING") != nullptr;
-    if (big) {
-        const unsigned blocks = (unsigned)big_tiles;
-        if (dtype == MRCNN_DTYPE_F16) hipLaunchKernelGGL((conv_fwd_h16_kernel<_Float16, 4, 2, 4>), dim3(blocks), dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((conv_fwd_h16_kernel<__bf16, 4, 2, 4>), dim3(blocks), dim3(512), 0, s, a);
-        return mrcnn_launch_status();
+    if (tile("big") && d->Cout % 256 == 0) return take(MRCNN_H16_BIG, big_tiles, 512);
+    return take(tile("ring") || sw.ring ? MRCNN_H16_RING : MRCNN_H16_T128, cdiv64(e.M, 256) * (d->Cout / 128), 256);
+}
+
+extern "C" int mrcnn_conv2d_fwd_h16_plan(const mrcnn_conv_desc* d, int dtype, const void* x, const void* w_t, const float* bias,
+                                         const float* scale, const float* shift, const void* res, const void* out, const void* z_out,
+                                         const mrcnn_bwd_epilogue_h16* ep, mrcnn_h16_plan* plan) {
+    mrcnn_h16_plan p;
+    const H16Operands o = {x, w_t, bias, scale, shift, res, const_cast<void*>(out), const_cast<void*>(z_out), ep};
+    const int rc = plan ? h16_fwd_plan(d, dtype, o, h16_switches(), mrcnn_num_cus(), &p) : MRCNN_ERR_ARG;
+    if (rc == MRCNN_OK) *plan = p;
+    return rc;
+}
+
+static ConvH16Args h16_fwd_args(const mrcnn_conv_desc* d, const H16Operands& o, const mrcnn_h16_plan& p) {
+    const H16Extent e = h16_extent(d);
+    ConvH16Args a;
+    a.x = o.x; a.wt = o.w_t; a.bias = o.bias; a.scale = o.scale; a.shift = o.shift; a.out = o.out; a.z = o.z_out; a.res = o.res;
+    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW;
+    a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.OH = d->OH; a.OW = d->OW; a.act = d->act;
+    a.M = (int)e.M; a.Ktot = d->KH * d->KW * d->Cin;
+    a.x_shift = (unsigned)e.shift_b; a.x_records = (unsigned)(e.xbytes + e.shift_b); a.w_records = (unsigned)e.wbytes;
+    a.out_records = (unsigned)std::min<long long>(e.ybytes, 0xFFFFFFF0LL);
+    a.out_mode = d->out_mode; a.cmod = d->cmod; a.ons = d->out_n_stride; a.ohs = d->out_h_stride; a.ows = d->out_w_stride;
+    a.dense = p.dense; a.ptiles = p.ptiles; a.mtile0 = p.mtile0; a.ep_vec = p.ep_vec; a.dbg = (unsigned long long*)p.trace;
+    h16_magic((unsigned)(d->OH * d->OW), &a.mg_ohw, &a.sh_ohw);
+    h16_magic((unsigned)d->OW, &a.mg_ow, &a.sh_ow);
+    static const mrcnn_bwd_epilogue_h16 none = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, -1, nullptr, 1.f};
+    const mrcnn_bwd_epilogue_h16& ep = o.ep ? *o.ep : none;
+    a.fb_act = ep.act; a.fb_out = ep.out; a.fb_z = ep.z; a.fb_scale = ep.scale; a.fb_mean = ep.mean; a.fb_rstd = ep.rstd;
+    a.fb_dgamma = ep.dgamma; a.fb_dbeta = ep.dbeta; a.fb_dbias = ep.dbias; a.fb_dy = ep.dy; a.fb_gmul = ep.grad_multiplier;
+    return a;
+}
+
+static int h16_fwd_launch(const ConvH16Args& a, const mrcnn_h16_plan& p, int dtype, hipStream_t s) {
+    switch (p.kernel) {
+    case MRCNN_H16_S64: H16_LAUNCH(dtype, s, conv_fwd_h16s_kernel, p.grid, p.threads, a); break;
+    case MRCNN_H16_T128: H16_LAUNCH(dtype, s, conv_fwd_h16_kernel, p.grid, p.threads, a, 2, 2, 2); break;
+    case MRCNN_H16_RING: H16_LAUNCH(dtype, s, conv_fwd_h16_kernel, p.grid, p.threads, a, 3, 2, 2); break;
+    case MRCNN_H16_BIG: H16_LAUNCH(dtype, s, conv_fwd_h16_kernel, p.grid, p.threads, a, 4, 2, 4); break;
+    case MRCNN_H16_WAVE128: H16_LAUNCH(dtype, s, conv_fwd_h16_kernel, p.grid, p.threads, a, 4, 2, 2, 4); break;
+    case MRCNN_H16_PHASE_DECONV: H16_LAUNCH(dtype, s, conv_fwd_h16p_kernel, p.grid, p.threads, a, false, true); break;
+    case MRCNN_H16_PHASE:
+        if (p.zout) H16_LAUNCH(dtype, s, conv_fwd_h16p_kernel, p.grid, p.threads, a, true, false);
+        else H16_LAUNCH(dtype, s, conv_fwd_h16p_kernel, p.grid, p.threads, a, false, false);
+        break;
+    case MRCNN_H16_SLAB:
+        if (p.zout) H16_LAUNCH(dtype, s, conv_fwd_h16q_kernel, p.grid, p.threads, a, true);
+        else H16_LAUNCH(dtype, s, conv_fwd_h16q_kernel, p.grid, p.threads, a, false);
+        break;
+    default: return MRCNN_ERR_ARG;
     }
-    const unsigned blocks = (unsigned)(((M + 255) / 256) * (d->Cout / 128));
-    if (ring) {
-        if (dtype == MRCNN_DTYPE_F16) hipLaunchKernelGGL((conv_fwd_h16_kernel<_Float16, 3, 2, 2>), dim3(blocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv_fwd_h16_kernel<__bf16, 3, 2, 2>), dim3(blocks), dim3(256), 0, s, a);
-    } else if (dtype == MRCNN_DTYPE_F16)
-        hipLaunchKernelGGL((conv_fwd_h16_kernel<_Float16, 2, 2, 2>), dim3(blocks), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((conv_fwd_h16_kernel<__bf16, 2, 2, 2>), dim3(blocks), dim3(256), 0, s, a);
+    if (p.rem_grid) {                            // the partial last round of a phased launch, on 64-row tiles from rem_mtile0 on
+        ConvH16Args r = a; r.mtile0 = p.rem_mtile0;
+        H16_LAUNCH(dtype, s, conv_fwd_h16s_kernel, p.rem_grid, 256, r);
+    }
     return mrcnn_launch_status();
+}
+
+static int h16_conv(const mrcnn_conv_desc* d, int dtype, const H16Operands& o, void* stream) {
+    mrcnn_h16_plan p;
+    const int rc = h16_fwd_plan(d, dtype, o, h16_switches(), mrcnn_num_cus(), &p);
+    return rc != MRCNN_OK ? rc : h16_fwd_launch(h16_fwd_args(d, o, p), p, dtype, (hipStream_t)stream);
+}
+
+extern "C" int mrcnn_conv2d_fwd_h16_res(const mrcnn_conv_desc* d, int dtype, const void* x, const void* w_t, const float* bias,
+                                        const float* scale, const float* shift, const void* res, void* out, void* z_out, void* stream) {
+    return h16_conv(d, dtype, {x, w_t, bias, scale, shift, res, out, z_out, nullptr}, stream);
 }
 
 extern "C" int mrcnn_conv2d_fwd_h16(const mrcnn_conv_desc* d, int dtype, const void* x, const void* w_t, const float* bias,
                                     const float* scale, const float* shift, void* out, void* z_out, void* stream) {
-    return mrcnn_conv2d_fwd_h16_res(d, dtype, x, w_t, bias, scale, shift, nullptr, out, z_out, stream);
+    return h16_conv(d, dtype, {x, w_t, bias, scale, shift, nullptr, out, z_out, nullptr}, stream);
 }
 
 extern "C" int mrcnn_conv2d_dgrad_ep_h16(const mrcnn_conv_desc* d, int dtype, const void* dz, const void* w_t, const void* res,
                                          void* dz_below, const mrcnn_bwd_epilogue_h16* ep, void* stream) {
     if (!ep) return MRCNN_ERR_ARG;
-    if ((ep->act != MRCNN_ACT_NONE && ep->act != MRCNN_ACT_RELU) || (ep->act == MRCNN_ACT_RELU && !ep->out)) return MRCNN_ERR_ARG;
-    if (ep->dgamma && (!ep->z || !ep->mean || !ep->rstd)) return MRCNN_ERR_ARG;
-    g_h16_fb = ep;
-    const int rc = mrcnn_conv2d_fwd_h16_res(d, dtype, dz, w_t, nullptr, nullptr, nullptr, res, dz_below, nullptr, stream);
-    g_h16_fb = nullptr;
-    return rc;
+    return h16_conv(d, dtype, {dz, w_t, nullptr, nullptr, nullptr, res, dz_below, nullptr, ep}, stream);
 }
 
 extern "C" int mrcnn_mask_out_fwd_h16(int dtype, const void* up, const float* w_mask, const float* b_mask, float* mask_out,
@@ -2514,8 +2520,7 @@ template <typename T>
 static void launch_mask_out_bwd_h16(const float* dm, const float* m, const void* up, const float* wm, void* dzg, float* dw, float* dbm,
                                     float* dbd, long long npix, int H, int W, int Cd, int C, float ls, hipStream_t s) {
     const dim3 grid((unsigned)cdiv64(npix, 512)), block(Cd);
-    static const int v8 = getenv("MRCNN_MASK_OUT_BWD_V8") ? atoi(getenv("MRCNN_MASK_OUT_BWD_V8")) : 1;
-    if (v8 && Cd == 256 && C <= 4 && ((reinterpret_cast<uintptr_t>(up) | reinterpret_cast<uintptr_t>(dzg)) & 15) == 0) {
+    if (h16_switches().mask_out_bwd_v8 && Cd == 256 && C <= 4 && ((reinterpret_cast<uintptr_t>(up) | reinterpret_cast<uintptr_t>(dzg)) & 15) == 0) {
         hipLaunchKernelGGL((mask_out_bwd_h16_v8_kernel<T, 4>), grid, dim3(256), 0, s, dm, m, (const T*)up, wm, (T*)dzg, dw, dbm, dbd, npix,
                            H, W, C, ls);
         return;

@@ -2078,6 +2078,29 @@ def conv2d_h16_supported(x_shape, kshape, stride=1, padding="same", res=False):
     return bool(_hip.lib().mrcnn_conv2d_fwd_h16_supported(C.byref(d), 1 if res else 0))
 
 
+def conv2d_h16_plan(d, dtype=torch.float16, x=16, w_t=16, bias=None, scale=None, shift=None, res=None, out=16, z_out=None, ep=None):
+    """(status, _hip.H16Plan) of the launch conv2d_h16 (ep None) or conv2d_dgrad_ep_h16 (ep a _hip.BwdEpilogueH16; x = dz) would
+    issue for the descriptor d.  Host only, like conv2d_plan: operands are addresses (or tensors, taken by their address), only
+    their nullness and 16-byte alignment count, nothing is launched."""
+    adr = lambda t: t if t is None or isinstance(t, int) else ptr(t)
+    plan = _hip.H16Plan()
+    rc = _hip.lib().mrcnn_conv2d_fwd_h16_plan(C.byref(d), _H16[dtype], adr(x), adr(w_t), adr(bias), adr(scale), adr(shift), adr(res),
+                                              adr(out), adr(z_out), C.byref(ep) if ep is not None else None, C.byref(plan))
+    return rc, plan
+
+
+def conv2d_wgrad_h16_plan(d, dtype=torch.float16, x=16, dy=16, dw=16, workspace=256, workspace_bytes=None):
+    """(status, _hip.H16WgradPlan) of the launch conv2d_wgrad_h16 would issue; host only.  workspace_bytes None: what
+    conv2d_wgrad_h16 passes, mrcnn_conv2d_wgrad_h16_workspace(d)."""
+    adr = lambda t: t if t is None or isinstance(t, int) else ptr(t)
+    if workspace_bytes is None:
+        workspace_bytes = _hip.lib().mrcnn_conv2d_wgrad_h16_workspace(C.byref(d))
+    plan = _hip.H16WgradPlan()
+    rc = _hip.lib().mrcnn_conv2d_wgrad_h16_plan(C.byref(d), _H16[dtype], adr(x), adr(dy), adr(dw), adr(workspace), workspace_bytes,
+                                                C.byref(plan))
+    return rc, plan
+
+
 def deconv2x2_h16(x, w_t, bias, Cd, act=ACT_RELU):
     """Conv2DTranspose(2x2, stride 2) on 16-bit x [N,H,W,Cin]: w_t = W^T [4*Cd, Cin] of the GEMM matrix."""
     _need_cuda(x, w_t, bias)

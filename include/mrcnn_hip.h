@@ -739,6 +739,32 @@ typedef struct mrcnn_bwd_epilogue_h16 {
 } mrcnn_bwd_epilogue_h16;
 int mrcnn_conv2d_dgrad_ep_h16(const mrcnn_conv_desc* d, int dtype, const void* dz, const void* w_t, const void* res,
                               void* dz_below, const mrcnn_bwd_epilogue_h16* ep, void* stream);
+/* Host-only query: what mrcnn_conv2d_fwd_h16_res (ep == NULL) or mrcnn_conv2d_dgrad_ep_h16 (ep != NULL; x = dz, out = dz_below)
+ * would launch for these arguments, and the status it would return.  Launches nothing and never dereferences a tensor pointer:
+ * only nullness and 16-byte alignment are looked at, so it runs without a GPU (the rules that count CUs then assume the MI355X's
+ * 256).  Reads the same switches as the launch -- per call: MRCNN_H16_SMALL, MRCNN_H16_TILE, MRCNN_H16_RING, MRCNN_H16P_NO_SPLIT,
+ * MRCNN_H16P_GRID, MRCNN_H16W_DBG, MRCNN_H16P_TRACE and the tuning keys "h16_phase" / "h16_slab"; once per process:
+ * MRCNN_H16_SLAB, MRCNN_H16S_EP_VEC.  *plan is written only with MRCNN_OK.                                                   */
+#define MRCNN_H16_S64 0            /* conv_fwd_h16s_kernel: 64 x 64 tiles (residual port, strided output, backward epilogue) */
+#define MRCNN_H16_T128 1           /* conv_fwd_h16_kernel<T, 2, 2, 2>: 256 x 128, double buffered */
+#define MRCNN_H16_RING 2           /* <T, 3, 2, 2>: the same with a 3-slot ring */
+#define MRCNN_H16_BIG 3            /* <T, 4, 2, 4>: 256 x 256, 4-stage ring */
+#define MRCNN_H16_WAVE128 4        /* <T, 4, 2, 2, 4>: 256 x 256, four waves of 128 x 128 */
+#define MRCNN_H16_PHASE 5          /* conv_fwd_h16p_kernel<T, zout, false>: persistent phased 256 x 256 tiles */
+#define MRCNN_H16_PHASE_DECONV 6   /* conv_fwd_h16p_kernel<T, false, true>: the same with the pixel-shuffle store */
+#define MRCNN_H16_SLAB 7           /* conv_fwd_h16q_kernel<T, zout>: the phased tile with slab-plus-halo staging */
+typedef struct mrcnn_h16_plan {
+    int32_t kernel, zout;          /* MRCNN_H16_*; the kernel's ZOUT template argument (phased kernels with a z_out) */
+    int32_t grid, threads;         /* workgroups and threads per workgroup of the (first) launch */
+    int32_t ptiles, mtile0;        /* ConvH16Args of that launch: tiles a persistent launch owns (0 otherwise); MRCNN_H16W_DBG */
+    int32_t rem_grid, rem_mtile0;  /* the small-tile launch for a partial last round: workgroups (0 = none), its first 64-row tile */
+    int32_t ep_vec, dense, fused_ep;   /* 16-byte epilogue of the small tile; plain NHWC output; ep given */
+    int32_t reserved;
+    uint64_t trace;                /* MRCNN_H16P_TRACE: the address the phased kernel stamps (0 = none) */
+} mrcnn_h16_plan;
+int mrcnn_conv2d_fwd_h16_plan(const mrcnn_conv_desc* d, int dtype, const void* x, const void* w_t, const float* bias,
+                              const float* scale, const float* shift, const void* res, const void* out, const void* z_out,
+                              const mrcnn_bwd_epilogue_h16* ep, mrcnn_h16_plan* plan);
 int mrcnn_weights_to_h16(const float* w_hwio, void* wt_fwd, void* wt_dgrad, int KH, int KW, int Cin, int Cout,
                          int dtype, void* stream);
 /* All 16-bit weight images of a model in one launch.  table: n_layers records {int64 offset of the float32 HWIO kernel in
@@ -751,6 +777,24 @@ int mrcnn_weights_to_h16_batched(const float* params, const void* table, int n_l
 size_t mrcnn_conv2d_wgrad_h16_workspace(const mrcnn_conv_desc* d);
 int mrcnn_conv2d_wgrad_h16(const mrcnn_conv_desc* d, int dtype, const void* x, const void* dy, float* dw,
                            void* workspace, size_t workspace_bytes, int beta_acc, float multiplier, void* stream);
+/* Host-only query, as mrcnn_conv2d_fwd_h16_plan: what mrcnn_conv2d_wgrad_h16 would launch and the status it would return.
+ * Switches: MRCNN_WGRAD_H16_PHASE (per call), MRCNN_WGRAD_XCD (once per process).                                        */
+#define MRCNN_H16_WGRAD_TABLE 0    /* pixel_table_kernel + conv_wgrad_h16_kernel: 256 x 128 tiles, table driven */
+#define MRCNN_H16_WGRAD_PHASE 1    /* conv_wgrad_h16p_kernel: phased 256 x 256 tiles */
+#define MRCNN_H16_RED_SCALAR 0     /* wgrad_h16_reduce_kernel */
+#define MRCNN_H16_RED_VEC 1        /* wgrad_h16_reduce_vec_kernel: n % 4 == 0, slabs and dw 16-byte aligned */
+typedef struct mrcnn_h16_wgrad_plan {
+    int32_t kernel;                /* MRCNN_H16_WGRAD_* */
+    int32_t splits, chunk;         /* pixel splits (= slabs) and rows per split */
+    int32_t nk, itiles, ntiles;    /* phased kernel: K-steps of 64 rows per split, 256-row tiles of KH*KW*Cin, 256-column tiles */
+    int32_t grid;                  /* workgroups of the gradient kernel */
+    int32_t reduce, reduce_grid;   /* MRCNN_H16_RED_* and its workgroups */
+    int32_t xcd_order;             /* MRCNN_WGRAD_XCD */
+    int64_t table_bytes, slab_bytes;   /* workspace: pixel table (reserved for either kernel), then 256-byte aligned the slabs */
+    int64_t workspace_bytes;       /* what mrcnn_conv2d_wgrad_h16_workspace answers: room for either kernel's slabs */
+} mrcnn_h16_wgrad_plan;
+int mrcnn_conv2d_wgrad_h16_plan(const mrcnn_conv_desc* d, int dtype, const void* x, const void* dy, const float* dw,
+                                const void* workspace, size_t workspace_bytes, mrcnn_h16_wgrad_plan* plan);
 /* mrcnn_epilogue_bwd on 16-bit tensors (act NONE / RELU, C a power of two >= 16): dz_out 16 bit; the float32 channel
  * sums dgamma / dbeta / dbias are multiplied by grad_multiplier (1 / loss scale) before they are added.          */
 int mrcnn_epilogue_bwd_h16(int dtype, const void* dout, const void* out, const void* z, const float* scale,
@@ -764,7 +808,8 @@ int mrcnn_epilogue_bwd_h16_dy(int dtype, const void* dout, const void* out, cons
 /* Output stage of the mask head on a 16-bit deconvolution output `up` [M,H,W,Cd] (mrcnn_conv2d_fwd_h16 with out_mode
  * MRCNN_OUT_DECONV2 writes it): mask_out [M,H,W,C] float32 = sigmoid(up . w_mask + b_mask); and the one-pass backward
  * of mrcnn_mask_out_bwd with dzg written in 16 bits times loss_scale (the sums dw_mask / db_mask / db_deconv stay
- * float32 and unscaled).  Cd % 256 == 0 (forward), C <= 16.                                                        */
+ * float32 and unscaled).  Cd % 256 == 0 (forward), C <= 16.  MRCNN_MASK_OUT_BWD_V8=0 (read once per process, with the
+ * other switches of the 16-bit file) keeps the backward off its 16-byte form.                                        */
 int mrcnn_mask_out_fwd_h16(int dtype, const void* up, const float* w_mask, const float* b_mask, float* mask_out,
                            int64_t npix, int Cd, int C, void* stream);
 int mrcnn_mask_out_bwd_h16(int dtype, const float* d_mask_out, const float* mask_out, const void* up, const float* w_mask,
