@@ -91,6 +91,25 @@ class H16WgradPlan(C.Structure):
         (n, C.c_int64) for n in ("table_bytes", "slab_bytes", "workspace_bytes")]
 
 
+class WgradPlan(C.Structure):
+    """mrcnn_wgrad_plan: what a float32 weight-gradient launch would do, from mrcnn_conv2d_wgrad_plan."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "bi", "bn", "fast", "splits", "chunk", "grid", "table_grid", "reduce", "reduce_grid", "lds_bytes",
+                                          "reserved")] + [(n, C.c_int64) for n in ("slab_bytes", "table_bytes", "workspace_bytes")]
+
+
+WGRAD_MULTI_MAX = 16                                                                          # MRCNN_WGRAD_MULTI_MAX
+
+
+class WgradMultiPlan(C.Structure):
+    """mrcnn_wgrad_multi_plan: what mrcnn_conv2d_wgrad_multi would launch, from mrcnn_conv2d_wgrad_multi_plan."""
+    _fields_ = [(n, C.c_int32) for n in ("n", "grid", "reduce_grid", "reserved")] + [
+        ("splits", C.c_int32 * WGRAD_MULTI_MAX), ("chunk", C.c_int32 * WGRAD_MULTI_MAX),
+        ("first", C.c_int32 * (WGRAD_MULTI_MAX + 1)), ("rfirst", C.c_int32 * (WGRAD_MULTI_MAX + 1)),
+        ("slab_offset", C.c_int64 * WGRAD_MULTI_MAX), ("slab_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
+
+
+WGRAD_KERNELS = ("TILE", "BLDS", "BLDS_TABLE", "GLDS")                                        # MRCNN_WGRAD_*, by value
+WGRAD_REDUCTIONS = ("NONE", "SCALAR", "VEC")                                                  # MRCNN_WGRAD_RED_*
 H16_KERNELS = ("S64", "T128", "RING", "BIG", "WAVE128", "PHASE", "PHASE_DECONV", "SLAB")       # MRCNN_H16_*, by value
 H16_WGRAD_KERNELS = ("TABLE", "PHASE")                                                        # MRCNN_H16_WGRAD_*
 H16_REDUCTIONS = ("SCALAR", "VEC")                                                            # MRCNN_H16_RED_*
@@ -127,6 +146,8 @@ _SIGNATURES = {
     "mrcnn_conv2d_wgrad_multi": (C.c_int, [C.POINTER(WgradProblem), C.c_int, _P, C.c_size_t, _P]),
     "mrcnn_conv2d_wgrad": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, C.c_size_t, C.c_int, _P]),
     "mrcnn_conv2d_wgrad_workspace": (C.c_size_t, [C.POINTER(ConvDesc)]),
+    "mrcnn_conv2d_wgrad_plan": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, C.c_size_t, C.POINTER(WgradPlan)]),
+    "mrcnn_conv2d_wgrad_multi_plan": (C.c_int, [C.POINTER(WgradProblem), C.c_int, _P, C.c_size_t, C.POINTER(WgradMultiPlan)]),
     "mrcnn_weight_flip_transpose": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mrcnn_weight_flip_transpose_batched": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "mrcnn_bn_fold": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_int64, _P]),
@@ -270,7 +291,7 @@ _tape_owner = None    # the thread that opened it: calls from any other thread (
 
 # entry points that launch nothing (pure queries / process state): never recorded
 # (mrcnn_allreduce_grad is appended by its caller, parallel.RcclComm.reduce: the other mrcnn_allreduce_* calls are set-up)
-_NO_RECORD = ("_workspace", "_fwd_plan", "_h16_plan", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_overview_check", "_planes_check", "_stats_check", "_gather_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
+_NO_RECORD = ("_workspace", "_fwd_plan", "_h16_plan", "_wgrad_plan", "_wgrad_multi_plan", "_tiles_check", "_outline_check", "_draw_check", "_components_check", "_catalog_check", "_overview_check", "_planes_check", "_stats_check", "_gather_check", "_supported", "_status_offset", "_version", "mrcnn_allreduce_", "_scratch", "_floats", "_bwd_rows")
 
 
 class _LibProxy(object):

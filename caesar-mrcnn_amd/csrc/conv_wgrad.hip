@@ -9,7 +9,6 @@
 // slabs that a second kernel sums in a fixed order, so dW is bitwise reproducible.
 #include "common.h"
 #include <type_traits>
-#include <cstdlib>
 
 struct WgradArgs {
     const float* x; const float* dy; float* out;   // out: dw (splits==1) or slabs
@@ -506,207 +505,249 @@ __global__ void wgrad_reduce_vec_kernel(const float* __restrict__ slabs, float* 
     *(f32x4*)(dw + 4 * i) = mrcnn_slab_sum<f32x4>(s, slabs, 4 * n4, 4 * i, splits);
 }
 
-struct WgradPlan { int bi, bn, splits, chunk, fast; };
+// ---------------------------------------------------------------------------------------------------
+// Host side: validate, plan, launch.  One plan (mrcnn_wgrad_plan / mrcnn_wgrad_multi_plan, include/mrcnn_hip.h) states what
+// a launch does; the workspace queries, the host-only *_plan entry points and the launches all read it.
+// tests/golden/wgrad_plan_table.json pins it row by row.
+#define WGRAD_TARGET_WGS 1024        // workgroups a launch aims at: four per CU (what a launch gets beside another stream's kernels;
+                                     // 1280 = all five slots per CU -- the 36 transform-domain GEMMs of a Winograd layer go 48 tiles
+                                     // x 21 -> x 26 splits -- measured 0.3 ms slower on the dense step)
+#define WGRAD_MIN_PIXELS 128         // a pixel split contracts at least this many pixels
+#define WGRAD_MAX_SPLITS 64
+#define WGRAD_TABLE_MIN_PIXELS 65536 // layers with at least this many output pixels address X through the pixel table (one extra tiny launch)
+#define WGRAD_TABLE_MAX_TAPS 64      // the table's tap mask has 64 bits
+#define WGRAD_BUFFER_RANGE 0x7FFFFFF0LL
 
-static WgradPlan plan_wgrad(const mrcnn_conv_desc* d) {
-    WgradPlan pl;
-    const long long M = (long long)d->N * d->OH * d->OW;
-    const int Ktot = d->KH * d->KW * d->Cin;
-    pl.fast = 1;
-    if (d->Cin % 128 == 0) pl.bi = 128;
-    else if (d->Cin % 64 == 0) pl.bi = 64;
-    else { pl.bi = 64; pl.fast = 0; }
-    pl.bn = d->Cout >= 128 ? 128 : (d->Cout >= 64 ? 64 : 32);
-    const long long tiles = (long long)((Ktot + pl.bi - 1) / pl.bi) * ((d->Cout + pl.bn - 1) / pl.bn);
-    long long splits = 1024 / (tiles > 0 ? tiles : 1);
-    static const long long min_px = getenv("MRCNN_WGRAD_MIN_PIXELS") ? atoll(getenv("MRCNN_WGRAD_MIN_PIXELS")) : 128;
-    const long long max_splits = (M + min_px - 1) / min_px;       // at least min_px pixels per split
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (splits > 64) splits = 64;
-    long long chunk = ((M + splits - 1) / splits + 31) / 32 * 32;
-    splits = (M + chunk - 1) / chunk;
-    pl.splits = (int)splits;
-    pl.chunk = (int)chunk;
-    return pl;
+static inline long long wgrad_pixels(const mrcnn_conv_desc* d) { return (long long)d->N * d->OH * d->OW; }
+static inline bool wgrad_dims_positive(const mrcnn_conv_desc* d) {
+    return d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 && d->OH > 0 && d->OW > 0;
+}
+static inline bool wgrad_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// X as the LDS-DMA kernels' buffer descriptor sees it: the base moved back by the padding (x_shift bytes), x_records bytes long
+static inline long long wgrad_x_bytes(const mrcnn_conv_desc* d) { return (long long)d->N * d->H * d->W * d->Cin * 4; }
+static inline long long wgrad_x_shift(const mrcnn_conv_desc* d) { return ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4; }
+// both operands within a 32-bit buffer descriptor; + 16 pixel rows: offsets of rows past the tensor must not wrap before the
+// range check sees them
+static inline bool wgrad_in_buffer_range(const mrcnn_conv_desc* d) {
+    return wgrad_x_bytes(d) + wgrad_x_shift(d) + 16LL * d->H * d->W * d->Cin * 4 < WGRAD_BUFFER_RANGE &&
+           wgrad_pixels(d) * d->Cout * 4 < WGRAD_BUFFER_RANGE;
+}
+// whole 128 x 128 tiles of dW inside one filter tap: the LDS-DMA kernels (buffer addressed, or flat where a tensor is out of range)
+static inline bool wgrad_dma_shape(const mrcnn_conv_desc* d) { return d->Cin % 128 == 0 && d->Cout % 128 == 0; }
+static inline bool wgrad_wants_table(const mrcnn_conv_desc* d) {
+    return wgrad_dma_shape(d) && d->KH * d->KW <= WGRAD_TABLE_MAX_TAPS && wgrad_pixels(d) >= WGRAD_TABLE_MIN_PIXELS;
+}
+static inline size_t wgrad_table_bytes(const mrcnn_conv_desc* d) {
+    return wgrad_wants_table(d) ? (size_t)(wgrad_pixels(d) + WGRAD_BP) * sizeof(PixelEntry) + 256 : 0;
+}
+static inline size_t wgrad_slab_bytes(const mrcnn_conv_desc* d, int splits) {
+    return splits > 1 ? (size_t)splits * d->KH * d->KW * d->Cin * d->Cout * sizeof(float) : 0;
+}
+static inline long long wgrad_tiles(const mrcnn_conv_desc* d, int bi, int bn) {
+    return (((long long)d->KH * d->KW * d->Cin + bi - 1) / bi) * ((d->Cout + bn - 1) / bn);
 }
 
-// layers with at least this many output pixels address X through the pixel table (one extra tiny launch)
-#define WGRAD_TABLE_MIN_PIXELS 65536
-static size_t wgrad_table_bytes(const mrcnn_conv_desc* d) {
-    const long long M = (long long)d->N * d->OH * d->OW;
-    const bool lds_dma = d->Cin % 128 == 0 && d->Cout % 128 == 0 && d->KH * d->KW <= 64;
-    return (lds_dma && M >= WGRAD_TABLE_MIN_PIXELS) ? (size_t)(M + WGRAD_BP) * sizeof(PixelEntry) + 256 : 0;
+// `want` splits of M pixels -> splits of `chunk` pixels each: at least WGRAD_MIN_PIXELS per split, at most WGRAD_MAX_SPLITS,
+// chunks whole 32-pixel steps (which can lower the count again)
+static void wgrad_pixel_split(long long want, long long M, int32_t* splits, int32_t* chunk) {
+    const long long cap = (M + WGRAD_MIN_PIXELS - 1) / WGRAD_MIN_PIXELS;
+    long long s = want > cap ? cap : want;
+    if (s < 1) s = 1;
+    if (s > WGRAD_MAX_SPLITS) s = WGRAD_MAX_SPLITS;
+    const long long c = ((M + s - 1) / s + 31) / 32 * 32;
+    *chunk = (int32_t)c;
+    *splits = c != 0 ? (int32_t)((M + c - 1) / c) : 1;
+}
+
+// what depends on the descriptor alone (all the workspace query needs): tile, kernel family, pixel split, workspace
+static void wgrad_plan_shape(const mrcnn_conv_desc* d, mrcnn_wgrad_plan* p) {
+    *p = mrcnn_wgrad_plan{};
+    p->bi = d->Cin % 128 == 0 ? 128 : 64;
+    p->fast = d->Cin % 64 == 0;                     // the tile sits inside one filter tap
+    p->bn = d->Cout >= 128 ? 128 : (d->Cout >= 64 ? 64 : 32);
+    if (!wgrad_dma_shape(d)) p->kernel = MRCNN_WGRAD_TILE;
+    else p->kernel = wgrad_in_buffer_range(d) && !mrcnn_force_flat_glds() ? MRCNN_WGRAD_BLDS : MRCNN_WGRAD_GLDS;
+    const long long tiles = wgrad_tiles(d, p->bi, p->bn);
+    wgrad_pixel_split(WGRAD_TARGET_WGS / (tiles > 0 ? tiles : 1), wgrad_pixels(d), &p->splits, &p->chunk);
+    p->grid = (int32_t)(tiles * p->splits);
+    p->lds_bytes = p->kernel == MRCNN_WGRAD_BLDS ? g_mrcnn_wgrad_lds_pad : 0;
+    p->table_bytes = (int64_t)wgrad_table_bytes(d);
+    p->slab_bytes = (int64_t)wgrad_slab_bytes(d, p->splits);
+    p->workspace_bytes = p->slab_bytes + p->table_bytes;
 }
 
 extern "C" size_t mrcnn_conv2d_wgrad_workspace(const mrcnn_conv_desc* d) {
     if (!d || d->N <= 0 || d->Cin <= 0 || d->Cout <= 0) return 0;
-    WgradPlan pl = plan_wgrad(d);
-    const size_t slabs = pl.splits > 1 ? (size_t)pl.splits * d->KH * d->KW * d->Cin * d->Cout * sizeof(float) : 0;
-    return slabs + wgrad_table_bytes(d);
+    mrcnn_wgrad_plan p;
+    wgrad_plan_shape(d, &p);
+    return (size_t)p.workspace_bytes;
+}
+
+extern "C" int mrcnn_conv2d_wgrad_plan(const mrcnn_conv_desc* d, const float* x, const float* dy, const float* dw,
+                                       const void* workspace, size_t workspace_bytes, mrcnn_wgrad_plan* plan) {
+    if (!d || !x || !dy || !dw || !plan) return MRCNN_ERR_ARG;
+    if (!wgrad_dims_positive(d) || wgrad_pixels(d) >= (1LL << 31)) return MRCNN_ERR_ARG;
+    if (!wgrad_aligned16(x) || !wgrad_aligned16(dy)) return MRCNN_ERR_ARG;
+    mrcnn_wgrad_plan p;
+    wgrad_plan_shape(d, &p);
+    if (p.splits > 1 && (!workspace || workspace_bytes < (size_t)p.slab_bytes)) return MRCNN_ERR_WORKSPACE;
+    // the pixel table where the workspace holds it behind the slabs; a shorter one runs the kernel without it
+    if (p.kernel == MRCNN_WGRAD_BLDS && p.table_bytes && workspace && workspace_bytes >= (size_t)p.workspace_bytes) {
+        p.kernel = MRCNN_WGRAD_BLDS_TABLE;
+        p.table_grid = (int32_t)cdiv64(wgrad_pixels(d) + WGRAD_BP, 256);
+    }
+    if (p.splits > 1) {
+        const long long n = (long long)d->KH * d->KW * d->Cin * d->Cout;
+        p.reduce = n % 4 == 0 && wgrad_aligned16(workspace) && wgrad_aligned16(dw) ? MRCNN_WGRAD_RED_VEC : MRCNN_WGRAD_RED_SCALAR;
+        p.reduce_grid = (int32_t)(p.reduce == MRCNN_WGRAD_RED_VEC ? cdiv64(n / 4, 256) : cdiv64(n, 256));
+    }
+    *plan = p;
+    return MRCNN_OK;
+}
+
+static WgradArgs wgrad_args(const mrcnn_conv_desc* d, const float* x, const float* dy, float* out, int fast, int splits, int chunk,
+                            int acc) {
+    WgradArgs a;
+    a.x = x; a.dy = dy; a.out = out;
+    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW;
+    a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.OH = d->OH; a.OW = d->OW;
+    a.M = (int)wgrad_pixels(d); a.Ktot = d->KH * d->KW * d->Cin; a.fast = fast; a.splits = splits; a.chunk = chunk;
+    a.acc = acc;
+    a.d_ohw = make_fastdiv((unsigned)(d->OH * d->OW)); a.d_ow = make_fastdiv((unsigned)d->OW);
+    a.table = nullptr;
+    return a;
 }
 
 template <int BI, int BN, int WM, int WN>
-static void launch_wgrad(const WgradArgs& a, hipStream_t s) {
-    const int blocks = ((a.Ktot + BI - 1) / BI) * ((a.Cout + BN - 1) / BN) * a.splits;
-    hipLaunchKernelGGL((conv_wgrad_kernel<BI, BN, WM, WN>), dim3((unsigned)blocks), dim3(WM * WN * 64), 0, s, a);
+static void launch_wgrad_tile(const WgradArgs& a, unsigned grid, hipStream_t s) {
+    hipLaunchKernelGGL((conv_wgrad_kernel<BI, BN, WM, WN>), dim3(grid), dim3(WM * WN * 64), 0, s, a);
 }
 
 extern "C" int mrcnn_conv2d_wgrad(const mrcnn_conv_desc* d, const float* x, const float* dy, float* dw,
                                   float* workspace, size_t workspace_bytes, int beta_acc, void* stream) {
-    if (!d || !x || !dy || !dw) return MRCNN_ERR_ARG;
-    if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 ||
-        d->stride <= 0 || d->OH <= 0 || d->OW <= 0)
-        return MRCNN_ERR_ARG;
-    const long long M = (long long)d->N * d->OH * d->OW;
-    if (M >= (1LL << 31)) return MRCNN_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(dy) & 15)) return MRCNN_ERR_ARG;
-    WgradPlan pl = plan_wgrad(d);
-    const size_t slab_bytes = pl.splits > 1 ? (size_t)pl.splits * d->KH * d->KW * d->Cin * d->Cout * sizeof(float) : 0;
-    if (pl.splits > 1 && (!workspace || workspace_bytes < slab_bytes)) return MRCNN_ERR_WORKSPACE;
-    WgradArgs a;
-    a.x = x; a.dy = dy; a.out = pl.splits > 1 ? workspace : dw;
-    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW;
-    a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.OH = d->OH; a.OW = d->OW;
-    a.M = (int)M; a.Ktot = d->KH * d->KW * d->Cin; a.fast = pl.fast; a.splits = pl.splits; a.chunk = pl.chunk;
-    a.acc = beta_acc;
-    a.d_ohw = make_fastdiv((unsigned)(d->OH * d->OW)); a.d_ow = make_fastdiv((unsigned)d->OW);
+    mrcnn_wgrad_plan p;
+    const int rc = mrcnn_conv2d_wgrad_plan(d, x, dy, dw, workspace, workspace_bytes, &p);
+    if (rc != MRCNN_OK) return rc;
+    WgradArgs a = wgrad_args(d, x, dy, p.splits > 1 ? workspace : dw, p.fast, p.splits, p.chunk, beta_acc);
+    const unsigned x_shift = (unsigned)wgrad_x_shift(d), x_records = (unsigned)(wgrad_x_bytes(d) + wgrad_x_shift(d));
+    const unsigned grid = (unsigned)p.grid;
     hipStream_t s = (hipStream_t)stream;
-    if (pl.fast && pl.bi == 128 && pl.bn == 128 && d->Cout % 128 == 0 && a.Ktot % 128 == 0) {
-        const int blocks = (a.Ktot / 128) * (a.Cout / 128) * a.splits;
-        const long long xbytes = (long long)d->N * d->H * d->W * d->Cin * 4;
-        const long long shift = ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
-        const long long ybytes = M * d->Cout * 4;
-        // + 16 pixel rows: offsets of rows past the tensor must not wrap before the range check sees them
-        if (xbytes + shift + 16LL * d->H * d->W * d->Cin * 4 < 0x7FFFFFF0LL && ybytes < 0x7FFFFFF0LL && !mrcnn_force_flat_glds()) {
-            const size_t tb = wgrad_table_bytes(d);
-            a.table = nullptr;
-            if (tb && workspace && workspace_bytes >= slab_bytes + tb) {
-                char* q = (char*)workspace + slab_bytes;
-                a.table = (const PixelEntry*)((reinterpret_cast<uintptr_t>(q) + 255) & ~(uintptr_t)255);
-                const int rows = (int)M + WGRAD_BP;
-                hipLaunchKernelGGL(pixel_table_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, (PixelEntry*)a.table, d->N,
-                                   d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->OH, d->OW, (int)M, rows,
-                                   (unsigned)shift, 4);
-                hipLaunchKernelGGL((conv_wgrad_blds_kernel<WGRAD_BP, true>), dim3((unsigned)blocks), dim3(256),
-                                   (size_t)g_mrcnn_wgrad_lds_pad, s, a, (unsigned)shift, (unsigned)(xbytes + shift));
-            } else {
-                hipLaunchKernelGGL((conv_wgrad_blds_kernel<WGRAD_BP, false>), dim3((unsigned)blocks), dim3(256),
-                                   (size_t)g_mrcnn_wgrad_lds_pad, s, a, (unsigned)shift, (unsigned)(xbytes + shift));
-            }
-        }
-        else
-            hipLaunchKernelGGL((conv_wgrad_glds_kernel<128, 128, WGRAD_BP>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    } else if (pl.bi == 128) {
-        if (pl.bn == 128) launch_wgrad<128, 128, 2, 2>(a, s);
-        else if (pl.bn == 64) launch_wgrad<128, 64, 2, 2>(a, s);
-        else launch_wgrad<128, 32, 4, 1>(a, s);
-    } else {
-        if (pl.bn == 128) launch_wgrad<64, 128, 2, 2>(a, s);
-        else if (pl.bn == 64) launch_wgrad<64, 64, 2, 2>(a, s);
-        else launch_wgrad<64, 32, 2, 1>(a, s);
+    switch (p.kernel) {
+    case MRCNN_WGRAD_BLDS_TABLE: {
+        const uintptr_t q = reinterpret_cast<uintptr_t>(workspace) + (size_t)p.slab_bytes;
+        a.table = (const PixelEntry*)((q + 255) & ~(uintptr_t)255);
+        hipLaunchKernelGGL(pixel_table_kernel, dim3((unsigned)p.table_grid), dim3(256), 0, s, (PixelEntry*)a.table, d->N, d->H, d->W,
+                           d->Cin, d->KH, d->KW, d->stride, d->pad_t, d->pad_l, d->OH, d->OW, a.M, a.M + WGRAD_BP, x_shift, 4);
+        hipLaunchKernelGGL((conv_wgrad_blds_kernel<WGRAD_BP, true>), dim3(grid), dim3(256), (size_t)p.lds_bytes, s, a, x_shift, x_records);
+        break;
     }
-    if (pl.splits > 1) {
-        const long long n = (long long)a.Ktot * a.Cout;
-        if (n % 4 == 0 && ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(dw)) & 15) == 0)
-            hipLaunchKernelGGL(wgrad_reduce_vec_kernel, dim3((unsigned)cdiv64(n / 4, 256)), dim3(256), 0, s,
-                               (const float*)workspace, dw, n / 4, pl.splits, beta_acc);
-        else
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, workspace, dw, n,
-                               pl.splits, beta_acc);
+    case MRCNN_WGRAD_BLDS:
+        hipLaunchKernelGGL((conv_wgrad_blds_kernel<WGRAD_BP, false>), dim3(grid), dim3(256), (size_t)p.lds_bytes, s, a, x_shift, x_records);
+        break;
+    case MRCNN_WGRAD_GLDS:
+        hipLaunchKernelGGL((conv_wgrad_glds_kernel<128, 128, WGRAD_BP>), dim3(grid), dim3(256), 0, s, a);
+        break;
+    default:
+        if (p.bi == 128 && p.bn == 128) launch_wgrad_tile<128, 128, 2, 2>(a, grid, s);
+        else if (p.bi == 128 && p.bn == 64) launch_wgrad_tile<128, 64, 2, 2>(a, grid, s);
+        else if (p.bi == 128) launch_wgrad_tile<128, 32, 4, 1>(a, grid, s);
+        else if (p.bn == 128) launch_wgrad_tile<64, 128, 2, 2>(a, grid, s);
+        else if (p.bn == 64) launch_wgrad_tile<64, 64, 2, 2>(a, grid, s);
+        else launch_wgrad_tile<64, 32, 2, 1>(a, grid, s);
     }
+    const long long n = (long long)a.Ktot * a.Cout;
+    if (p.reduce == MRCNN_WGRAD_RED_VEC)
+        hipLaunchKernelGGL(wgrad_reduce_vec_kernel, dim3((unsigned)p.reduce_grid), dim3(256), 0, s, (const float*)workspace, dw, n / 4,
+                           p.splits, beta_acc);
+    else if (p.reduce == MRCNN_WGRAD_RED_SCALAR)
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)p.reduce_grid), dim3(256), 0, s, workspace, dw, n, p.splits, beta_acc);
     return mrcnn_launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------
-// mrcnn_conv2d_wgrad_multi: the weight gradients of up to 4 layers in one launch (+ one for their slab reductions).
-// On the small feature maps of the backbone a weight gradient is 16-36 output tiles with a few hundred pixels to
+// mrcnn_conv2d_wgrad_multi: the weight gradients of up to WGRAD_MULTI_MAX layers in one launch (+ one for their slab
+// reductions).  On the small feature maps of the backbone a weight gradient is 16-36 output tiles with a few hundred pixels to
 // contract: ~30 us of mostly latency per launch plus its reduction, three per bottleneck block, and together they
-// had become the longest chain of the backward pass (knock-out run: 2 ms of the step).  LDS-DMA kernel only.
-struct WgradMultiPlan { int splits[WGRAD_MULTI_MAX], chunk[WGRAD_MULTI_MAX]; size_t slab_off[WGRAD_MULTI_MAX], bytes; };
+// had become the longest chain of the backward pass (knock-out run: 2 ms of the step).  LDS-DMA kernel only, no pixel table.
+static_assert(WGRAD_MULTI_MAX == MRCNN_WGRAD_MULTI_MAX, "mrcnn_wgrad_multi_plan holds one entry per problem");
 
-static bool plan_wgrad_multi(const mrcnn_wgrad_problem* pr, int n, WgradMultiPlan& pl) {
+// a problem the shared launch takes: the buffer-addressed LDS-DMA kernel without a pixel table (pure GEMM rows -- a 1 x 1
+// layer on a 1 x 1 map -- have no pixel decomposition to pay for and need none at any size)
+static bool wgrad_multi_fits(const mrcnn_conv_desc* d) {
+    const bool gemm = d->KH == 1 && d->KW == 1 && d->H == 1 && d->W == 1 && d->stride == 1;
+    return wgrad_dims_positive(d) && wgrad_dma_shape(d) && d->KH * d->KW <= WGRAD_TABLE_MAX_TAPS && (!wgrad_wants_table(d) || gemm) &&
+           wgrad_in_buffer_range(d);
+}
+
+// the descriptors' part of the plan (all the workspace query needs, and what it answers whatever MRCNN_CONV_FLAT_GLDS says)
+static bool wgrad_multi_plan_shape(const mrcnn_wgrad_problem* pr, int n, mrcnn_wgrad_multi_plan* p) {
     if (!pr || n < 1 || n > WGRAD_MULTI_MAX) return false;
     long long tiles = 0;
     for (int g = 0; g < n; ++g) {
-        const mrcnn_conv_desc& d = pr[g].d;
-        if (d.N <= 0 || d.H <= 0 || d.W <= 0 || d.Cin <= 0 || d.Cout <= 0 || d.KH <= 0 || d.KW <= 0 || d.stride <= 0 ||
-            d.OH <= 0 || d.OW <= 0)
-            return false;
-        const long long M = (long long)d.N * d.OH * d.OW;
-        const long long Ktot = (long long)d.KH * d.KW * d.Cin;
-        const bool gemm = d.KH == 1 && d.KW == 1 && d.H == 1 && d.W == 1 && d.stride == 1;     // pure GEMM rows: no pixel decomposition to pay for
-        if (d.Cin % 128 || d.Cout % 128 || d.KH * d.KW > 64 || (M >= WGRAD_TABLE_MIN_PIXELS && !gemm)) return false;
-        const long long xbytes = (long long)d.N * d.H * d.W * d.Cin * 4;
-        const long long shift = ((long long)d.pad_t * d.W + d.pad_l) * d.Cin * 4;
-        if (xbytes + shift + 16LL * d.H * d.W * d.Cin * 4 >= 0x7FFFFFF0LL || M * d.Cout * 4 >= 0x7FFFFFF0LL) return false;
-        tiles += (Ktot / 128) * (d.Cout / 128);
+        if (!wgrad_multi_fits(&pr[g].d)) return false;
+        tiles += wgrad_tiles(&pr[g].d, 128, 128);
     }
-    // workgroups the launch aims at: 1024 = four per CU (what a launch gets beside another stream's kernels); MRCNN_WGRAD_MULTI_TARGET
-    // for A/B (1280 = all five slots per CU: the 36 transform-domain GEMMs of a Winograd layer go 48 tiles x 21 -> x 26 splits)
-    static const long long target = getenv("MRCNN_WGRAD_MULTI_TARGET") ? atoll(getenv("MRCNN_WGRAD_MULTI_TARGET")) : 1024;
-    const long long want = target / (tiles > 0 ? tiles : 1);
-    pl.bytes = 0;
+    *p = mrcnn_wgrad_multi_plan{};
+    p->n = n;
+    const long long want = WGRAD_TARGET_WGS / (tiles > 0 ? tiles : 1);
+    long long blocks = 0, rblocks = 0;
     for (int g = 0; g < n; ++g) {
-        const mrcnn_conv_desc& d = pr[g].d;
-        const long long M = (long long)d.N * d.OH * d.OW;
-        long long splits = want;
-        const long long max_splits = (M + 127) / 128;
-        if (splits > max_splits) splits = max_splits;
-        if (splits < 1) splits = 1;
-        if (splits > 64) splits = 64;
-        const long long chunk = ((M + splits - 1) / splits + 31) / 32 * 32;
-        splits = (M + chunk - 1) / chunk;
-        pl.splits[g] = (int)splits; pl.chunk[g] = (int)chunk;
-        pl.slab_off[g] = pl.bytes;
-        if (splits > 1) pl.bytes += (((size_t)splits * d.KH * d.KW * d.Cin * d.Cout * sizeof(float)) + 255) & ~(size_t)255;
+        const mrcnn_conv_desc* d = &pr[g].d;
+        wgrad_pixel_split(want, wgrad_pixels(d), &p->splits[g], &p->chunk[g]);
+        p->slab_offset[g] = p->slab_bytes;
+        p->slab_bytes += (int64_t)((wgrad_slab_bytes(d, p->splits[g]) + 255) & ~(size_t)255);
+        p->first[g] = (int32_t)blocks;
+        blocks += wgrad_tiles(d, 128, 128) * p->splits[g];
+        p->rfirst[g] = (int32_t)rblocks;
+        if (p->splits[g] > 1) rblocks += cdiv64((long long)d->KH * d->KW * d->Cin * d->Cout / 4, 256);      // blocks of 256 float4
     }
+    for (int g = n; g <= WGRAD_MULTI_MAX; ++g) { p->first[g] = (int32_t)blocks; p->rfirst[g] = (int32_t)rblocks; }
+    p->grid = (int32_t)blocks;
+    p->reduce_grid = (int32_t)rblocks;
+    p->workspace_bytes = p->slab_bytes + 256;
     return true;
 }
 
 extern "C" size_t mrcnn_conv2d_wgrad_multi_workspace(const mrcnn_wgrad_problem* problems, int n) {
-    WgradMultiPlan pl;
-    if (!plan_wgrad_multi(problems, n, pl)) return 0;
-    return pl.bytes + 256;
+    mrcnn_wgrad_multi_plan p;
+    return wgrad_multi_plan_shape(problems, n, &p) ? (size_t)p.workspace_bytes : 0;
+}
+
+extern "C" int mrcnn_conv2d_wgrad_multi_plan(const mrcnn_wgrad_problem* problems, int n, const void* workspace, size_t workspace_bytes,
+                                             mrcnn_wgrad_multi_plan* plan) {
+    mrcnn_wgrad_multi_plan p;
+    if (!plan) return MRCNN_ERR_ARG;
+    if (!wgrad_multi_plan_shape(problems, n, &p) || mrcnn_force_flat_glds()) return MRCNN_ERR_UNSUPPORTED;
+    if (p.slab_bytes && (!workspace || workspace_bytes < (size_t)p.slab_bytes || !wgrad_aligned16(workspace))) return MRCNN_ERR_WORKSPACE;
+    for (int g = 0; g < n; ++g) {
+        const mrcnn_wgrad_problem& q = problems[g];
+        if (!q.x || !q.dy || !q.dw) return MRCNN_ERR_ARG;
+        if (!wgrad_aligned16(q.x) || !wgrad_aligned16(q.dy) || !wgrad_aligned16(q.dw)) return MRCNN_ERR_UNSUPPORTED;
+    }
+    *plan = p;
+    return MRCNN_OK;
 }
 
 extern "C" int mrcnn_conv2d_wgrad_multi(const mrcnn_wgrad_problem* problems, int n, float* workspace, size_t workspace_bytes,
                                         void* stream) {
-    WgradMultiPlan pl;
-    if (!plan_wgrad_multi(problems, n, pl) || mrcnn_force_flat_glds()) return MRCNN_ERR_UNSUPPORTED;
-    if (pl.bytes && (!workspace || workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(workspace) & 15))) return MRCNN_ERR_WORKSPACE;
+    mrcnn_wgrad_multi_plan p;
+    const int rc = mrcnn_conv2d_wgrad_multi_plan(problems, n, workspace, workspace_bytes, &p);
+    if (rc != MRCNN_OK) return rc;
     WgradMultiArgs mp;
     mp.n = n;
-    long long blocks = 0, rblocks = 0;
     for (int g = 0; g < n; ++g) {
         const mrcnn_wgrad_problem& q = problems[g];
-        const mrcnn_conv_desc* d = &q.d;
-        if (!q.x || !q.dy || !q.dw) return MRCNN_ERR_ARG;
-        if ((reinterpret_cast<uintptr_t>(q.x) | reinterpret_cast<uintptr_t>(q.dy) | reinterpret_cast<uintptr_t>(q.dw)) & 15)
-            return MRCNN_ERR_UNSUPPORTED;
-        const long long M = (long long)d->N * d->OH * d->OW;
-        WgradArgs& a = mp.a[g];
-        a.x = q.x; a.dy = q.dy;
-        a.out = pl.splits[g] > 1 ? (float*)((char*)workspace + pl.slab_off[g]) : q.dw;
-        a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW;
-        a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.OH = d->OH; a.OW = d->OW;
-        a.M = (int)M; a.Ktot = d->KH * d->KW * d->Cin; a.fast = 1; a.splits = pl.splits[g]; a.chunk = pl.chunk[g];
-        a.acc = q.accumulate;
-        a.d_ohw = make_fastdiv((unsigned)(d->OH * d->OW)); a.d_ow = make_fastdiv((unsigned)d->OW);
-        a.table = nullptr;
-        const long long xbytes = (long long)d->N * d->H * d->W * d->Cin * 4;
-        const long long shift = ((long long)d->pad_t * d->W + d->pad_l) * d->Cin * 4;
-        mp.x_shift[g] = (unsigned)shift; mp.x_records[g] = (unsigned)(xbytes + shift);
+        float* out = p.splits[g] > 1 ? (float*)((char*)workspace + p.slab_offset[g]) : q.dw;
+        mp.a[g] = wgrad_args(&q.d, q.x, q.dy, out, 1, p.splits[g], p.chunk[g], q.accumulate);
+        mp.x_shift[g] = (unsigned)wgrad_x_shift(&q.d);
+        mp.x_records[g] = (unsigned)(wgrad_x_bytes(&q.d) + wgrad_x_shift(&q.d));
         mp.dw[g] = q.dw;
-        mp.first[g] = (int)blocks;
-        blocks += (long long)(a.Ktot / 128) * (a.Cout / 128) * a.splits;
-        mp.rfirst[g] = (int)rblocks;
-        if (a.splits > 1) rblocks += cdiv64((long long)a.Ktot * a.Cout / 4, 256);
     }
-    for (int g = n; g <= WGRAD_MULTI_MAX; ++g) { mp.first[g] = (int)blocks; mp.rfirst[g] = (int)rblocks; }
+    for (int g = 0; g <= WGRAD_MULTI_MAX; ++g) { mp.first[g] = p.first[g]; mp.rfirst[g] = p.rfirst[g]; }
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL((conv_wgrad_blds_multi_kernel<WGRAD_BP>), dim3((unsigned)blocks), dim3(256), 0, s, mp);
-    if (rblocks > 0) hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3((unsigned)rblocks), dim3(256), 0, s, mp);
+    hipLaunchKernelGGL((conv_wgrad_blds_multi_kernel<WGRAD_BP>), dim3((unsigned)p.grid), dim3(256), 0, s, mp);
+    if (p.reduce_grid > 0) hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3((unsigned)p.reduce_grid), dim3(256), 0, s, mp);
     return mrcnn_launch_status();
 }
 

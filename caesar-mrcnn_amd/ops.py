@@ -293,9 +293,36 @@ def conv2d_wgrad(x, dy, w_shape, stride=1, padding="same", dw=None, accumulate=F
     return dw
 
 
+def conv2d_wgrad_plan(d, x=16, dy=16, dw=16, workspace=256, workspace_bytes=None):
+    """(status, _hip.WgradPlan) of the launch conv2d_wgrad would issue for the descriptor d.  Host only, like conv2d_plan:
+    operands are addresses (or tensors, taken by their address), only their nullness and 16-byte alignment count, nothing is
+    launched.  workspace_bytes None: what conv2d_wgrad needs at least, mrcnn_conv2d_wgrad_workspace(d) (its grow-only scratch
+    buffer may be larger)."""
+    adr = lambda t: t if t is None or isinstance(t, int) else ptr(t)
+    if workspace_bytes is None:
+        workspace_bytes = _hip.lib().mrcnn_conv2d_wgrad_workspace(C.byref(d))
+    plan = _hip.WgradPlan()
+    rc = _hip.lib().mrcnn_conv2d_wgrad_plan(C.byref(d), adr(x), adr(dy), adr(dw), adr(workspace), workspace_bytes, C.byref(plan))
+    return rc, plan
+
+
+def conv2d_wgrad_multi_plan(descs, workspace=256, workspace_bytes=None):
+    """(status, _hip.WgradMultiPlan) of the launch conv2d_wgrad_multi would issue for the descriptors `descs`, every operand at
+    an aligned address; host only.  workspace_bytes None: mrcnn_conv2d_wgrad_multi_workspace's answer."""
+    n = len(descs)
+    arr = (_hip.WgradProblem * max(n, 1))()
+    for q, d in zip(arr, descs):
+        q.d, q.x, q.dy, q.dw = d, 16, 16, 16
+    if workspace_bytes is None:
+        workspace_bytes = _hip.lib().mrcnn_conv2d_wgrad_multi_workspace(arr, n)
+    plan = _hip.WgradMultiPlan()
+    rc = _hip.lib().mrcnn_conv2d_wgrad_multi_plan(arr, n, workspace, workspace_bytes, C.byref(plan))
+    return rc, plan
+
+
 def conv2d_wgrad_multi(items):
-    """The weight gradients of up to 4 layers in one launch (mrcnn_conv2d_wgrad_multi).  items: [(x, dy, w_shape, stride,
-    padding, dw, accumulate)].  Returns False (nothing launched) when a layer does not fit the shared kernel."""
+    """The weight gradients of up to _hip.WGRAD_MULTI_MAX layers in one launch (mrcnn_conv2d_wgrad_multi).  items: [(x, dy,
+    w_shape, stride, padding, dw, accumulate)].  Returns False (nothing launched) when a layer does not fit the shared kernel."""
     n = len(items)
     arr = (_hip.WgradProblem * n)()
     for q, (x, dy, w_shape, stride, padding, dw, accumulate) in zip(arr, items):

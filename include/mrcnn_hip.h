@@ -73,6 +73,32 @@ int mrcnn_conv2d_fwd_ws(const mrcnn_conv_desc* d, const float* x, const float* w
 int mrcnn_conv2d_wgrad(const mrcnn_conv_desc* d, const float* x, const float* dy, float* dw,
                        float* workspace, size_t workspace_bytes, int beta_acc, void* stream);
 size_t mrcnn_conv2d_wgrad_workspace(const mrcnn_conv_desc* d);
+/* Host-only query, as mrcnn_conv2d_fwd_plan: what mrcnn_conv2d_wgrad would launch for these arguments and the status it would
+ * return.  Launches nothing and never dereferences a tensor pointer: only nullness and 16-byte alignment are looked at, so it
+ * runs without a GPU.  Reads what the launch reads: the tuning key "wgrad_lds_pad" (per call) and MRCNN_CONV_FLAT_GLDS (once per
+ * process).  *plan is written only with MRCNN_OK.                                                                           */
+#define MRCNN_WGRAD_TILE 0         /* conv_wgrad_kernel<bi, bn> (six tile shapes) */
+#define MRCNN_WGRAD_BLDS 1         /* conv_wgrad_blds_kernel<16, false>: LDS-DMA 128 x 128 tiles, buffer addressing */
+#define MRCNN_WGRAD_BLDS_TABLE 2   /* pixel_table_kernel, then conv_wgrad_blds_kernel<16, true>: X addressed through the pixel table */
+#define MRCNN_WGRAD_GLDS 3         /* conv_wgrad_glds_kernel: the same tiles with flat addressing */
+#define MRCNN_WGRAD_RED_NONE 0     /* one pixel split: the kernel stores (or accumulates into) dw */
+#define MRCNN_WGRAD_RED_SCALAR 1   /* wgrad_reduce_kernel */
+#define MRCNN_WGRAD_RED_VEC 2      /* wgrad_reduce_vec_kernel: KH*KW*Cin*Cout % 4 == 0, workspace and dw 16-byte aligned */
+typedef struct mrcnn_wgrad_plan {
+    int32_t kernel;                /* MRCNN_WGRAD_* */
+    int32_t bi, bn, fast;          /* dW tile (rows of KH*KW*Cin x columns of Cout); fast: Cin % 64 == 0, a tile lies inside one tap */
+    int32_t splits, chunk;         /* pixel splits (= slabs when > 1) and pixels per split */
+    int32_t grid, table_grid;      /* workgroups of the gradient kernel; of pixel_table_kernel (0 = not launched) */
+    int32_t reduce, reduce_grid;   /* MRCNN_WGRAD_RED_* and its workgroups */
+    int32_t lds_bytes;             /* dynamic LDS of the gradient kernel ("wgrad_lds_pad"; the BLDS kernels only) */
+    int32_t reserved;
+    int64_t slab_bytes;            /* workspace the launch needs: the slabs, from the workspace's start */
+    int64_t table_bytes;           /* room the query adds for the pixel table (256-byte aligned behind the slabs); a workspace that
+                                      holds the slabs but not the table runs MRCNN_WGRAD_BLDS instead of _BLDS_TABLE */
+    int64_t workspace_bytes;       /* what mrcnn_conv2d_wgrad_workspace answers: slab_bytes + table_bytes */
+} mrcnn_wgrad_plan;
+int mrcnn_conv2d_wgrad_plan(const mrcnn_conv_desc* d, const float* x, const float* dy, const float* dw, const void* workspace,
+                            size_t workspace_bytes, mrcnn_wgrad_plan* plan);
 
 /* w_t[(KH-1-kh, KW-1-kw, co), ci] = w[(kh,kw,ci), co]: the weights of the data-gradient convolution. */
 int mrcnn_weight_flip_transpose(const float* w, float* w_t, int KH, int KW, int Cin, int Cout,
@@ -99,11 +125,15 @@ size_t mrcnn_conv2d_fwd_multi_workspace(const mrcnn_conv_problem* problems, int 
 int mrcnn_conv2d_fwd_multi(const mrcnn_conv_problem* problems, int n, void* workspace, size_t workspace_bytes,
                            void* stream);
 
-/* The weight gradients of up to 4 layers in one launch (+ one for their slab reductions): TF autodiff of the three
- * Conv2D layers of a bottleneck block (mrcnn/model.py:99-172) on the small feature maps, where each is a few dozen
- * output tiles with a few hundred pixels to contract.  Every problem is an ordinary mrcnn_conv2d_wgrad (accumulate !=
- * 0 adds to dw); all must fit the LDS-DMA kernel (Cin, Cout multiples of 128, fewer than 65 536 output pixels,
- * 16-byte aligned buffers), else MRCNN_ERR_UNSUPPORTED (workspace query: 0) and nothing is launched.             */
+/* The weight gradients of up to MRCNN_WGRAD_MULTI_MAX layers in one launch (+ one for their slab reductions): TF autodiff of
+ * the three Conv2D layers of a bottleneck block (mrcnn/model.py:99-172) on the small feature maps, where each is a few dozen
+ * output tiles with a few hundred pixels to contract, and the transform-domain GEMMs of a Winograd layer.  Every problem is an
+ * ordinary mrcnn_conv2d_wgrad (accumulate != 0 adds to dw); all must fit the LDS-DMA kernel without a pixel table (Cin, Cout
+ * multiples of 128, at most 64 taps, both tensors within a 32-bit buffer descriptor, fewer than 65 536 output pixels unless the
+ * problem is a pure GEMM -- 1 x 1, stride 1, on a 1 x 1 map -- and 16-byte aligned buffers), else MRCNN_ERR_UNSUPPORTED
+ * (workspace query: 0) and nothing is launched.  With MRCNN_CONV_FLAT_GLDS set the launch (and its plan) refuse every call
+ * with MRCNN_ERR_UNSUPPORTED while the workspace query still answers the bytes: the query looks at the descriptors alone.     */
+#define MRCNN_WGRAD_MULTI_MAX 16
 typedef struct mrcnn_wgrad_problem {
     mrcnn_conv_desc d;
     const float* x; const float* dy; float* dw;
@@ -112,6 +142,22 @@ typedef struct mrcnn_wgrad_problem {
 size_t mrcnn_conv2d_wgrad_multi_workspace(const mrcnn_wgrad_problem* problems, int n);
 int mrcnn_conv2d_wgrad_multi(const mrcnn_wgrad_problem* problems, int n, float* workspace, size_t workspace_bytes,
                              void* stream);
+/* Host-only query, as mrcnn_conv2d_wgrad_plan: what mrcnn_conv2d_wgrad_multi would launch (conv_wgrad_blds_multi_kernel, then
+ * wgrad_reduce_multi_kernel where a problem has slabs; no dynamic LDS) and the status it would return.  Workgroups first[g] ..
+ * first[g + 1] - 1 of the gradient launch and rfirst[g] .. rfirst[g + 1] - 1 of the reduction (blocks of 256 float4) belong to
+ * problem g; entries from n on repeat the totals.  *plan is written only with MRCNN_OK.                                        */
+typedef struct mrcnn_wgrad_multi_plan {
+    int32_t n;
+    int32_t grid, reduce_grid;                        /* workgroups of the two launches (reduce_grid 0: no reduction launch) */
+    int32_t reserved;
+    int32_t splits[MRCNN_WGRAD_MULTI_MAX], chunk[MRCNN_WGRAD_MULTI_MAX];
+    int32_t first[MRCNN_WGRAD_MULTI_MAX + 1], rfirst[MRCNN_WGRAD_MULTI_MAX + 1];
+    int64_t slab_offset[MRCNN_WGRAD_MULTI_MAX];       /* where problem g's slabs start in the workspace (256-byte steps) */
+    int64_t slab_bytes;                               /* workspace the launch needs */
+    int64_t workspace_bytes;                          /* what mrcnn_conv2d_wgrad_multi_workspace answers: slab_bytes + 256 */
+} mrcnn_wgrad_multi_plan;
+int mrcnn_conv2d_wgrad_multi_plan(const mrcnn_wgrad_problem* problems, int n, const void* workspace, size_t workspace_bytes,
+                                  mrcnn_wgrad_multi_plan* plan);
 
 /* Data-gradient convolution fused with the epilogue backward of the layer below (TF autodiff through Conv2D, then
  * through the lower layer's Activation / BatchNorm / bias): y = conv(dz, w_t) (+ res) is d(loss)/d(out_below); stored is

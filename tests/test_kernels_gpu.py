@@ -368,6 +368,8 @@ WGRAD_CASES = [
     (3, 13, 11, 128, 256, 3, 1, "same"),        # LDS-DMA wgrad: M = 429 (pixel tail inside a 16-row piece), odd H/W
     (90, 13, 11, 128, 256, 3, 1, "same"),       # LDS-DMA wgrad + LDS-DMA dgrad, ragged M
     (459, 13, 11, 128, 128, 3, 1, "same"),      # M = 65637 >= 65536: pixel-table addressing, tail inside a step
+    (2, 8, 8, 64, 32, 1, 1, "valid"),           # conv_wgrad_kernel<64, 32>: Cin % 128 != 0, Cout < 64
+    (2, 8, 8, 128, 192, 1, 1, "valid"),         # conv_wgrad_kernel<128, 128>: Cin % 128 == 0, Cout >= 128 but Cout % 128 != 0
 ]
 # weight and data gradients of the class-count-wide layers (see CONV_CASES): Cout & 3 != 0 in the weight gradient, Cin = K = 2, 5,
 # 6, 17 / 8, 20, 24, 68 in the data gradient (no 32-channel fast path)
