@@ -169,6 +169,9 @@ _SIGNATURES = {
     "mrcnn_mask_bits_stats": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "mrcnn_mask_bits_gather_check": (C.c_int, [C.c_int] * 5),
     "mrcnn_mask_bits_gather": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "mrcnn_mask_bits_zoom_check": (C.c_int, [C.c_int] * 9),
+    "mrcnn_mask_bits_zoom": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       _P, _P]),
     "mrcnn_tile_adjacency": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, C.c_int, _P, _P]),
     "mrcnn_tile_union": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     "mrcnn_source_params": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int, _P, _P, _P, C.c_int64, C.c_double,
@@ -217,6 +220,7 @@ _SIGNATURES = {
     "mrcnn_catalog_window_flags": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "mrcnn_catalog_nan_fill": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "mrcnn_mold_image_u8": (C.c_int, [_P] + [C.c_int] * 9 + [C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
+    "mrcnn_resize_image_u8": (C.c_int, [_P] + [C.c_int] * 9 + [_P, _P, C.c_size_t, _P]),
     "mrcnn_add_inplace": (C.c_int, [_P, _P, C.c_int64, _P]),
     "mrcnn_softmax_rows": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "mrcnn_roialign_fwd": (C.c_int, [C.POINTER(RoiAlignDesc)] + [_P] * 8),

@@ -82,6 +82,11 @@ class Config(object):
     # instance selection and the molding run there and only a [N, 5] table comes back; the batch reaches the step as device
     # tensors.  Same batches as the host path.  Off by default (DESIGN.md 4.18 has the measurements).
     DEVICE_SAMPLES = False
+    # extension: with DEVICE_SAMPLES, an image resize_image scales (any cut-out whose short side is not IMAGE_MIN_DIM) is scaled on
+    # the GPU too -- the bilinear image resize with a uint8 result (csrc/mold.hip) and scipy's nearest-neighbour mask zoom on the
+    # packed masks (csrc/gtprep.hip) -- instead of being handed to the host.  Nothing without DEVICE_SAMPLES.  Same batches.  Off
+    # by default (DESIGN.md 4.19 has the measurements).
+    DEVICE_SAMPLE_RESIZE = False
     # extension: None (float32 everywhere, the reference's precision) | "float16" | "bfloat16": run the 3x3
     # convolutions of the mask head on the 16-bit matrix cores (csrc/conv_h16.hip; float32 master weights,
     # accumulation and gradients; HEAD_LOSS_SCALE guards float16 gradients)

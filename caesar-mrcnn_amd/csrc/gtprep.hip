@@ -3,7 +3,8 @@
 //   * _ = np.sum(mask, axis=(0, 1)) > 0 and utils.extract_bboxes(mask) (mrcnn/utils.py:49-77)     -> mrcnn_mask_bits_stats
 //   * mask[:, :, _idx], gt_masks[:, :, ids] and the copy into the zero [H, W, MAX_GT_INSTANCES] batch planes
 //                                                                                                  -> mrcnn_mask_bits_gather
-// Both read the loader's bit-packed layout [H, W, nb] (numpy.packbits(mask != 0, axis=-1, bitorder="little"), nb a whole number of
+// and, for an image resize_image scales, utils.resize_mask before them (mrcnn/utils.py:564-583)   -> mrcnn_mask_bits_zoom
+// All read the loader's bit-packed layout [H, W, nb] (numpy.packbits(mask != 0, axis=-1, bitorder="little"), nb a whole number of
 // 32-bit words: what mrcnn_augment_warp_mask_bits reads and writes), so the planes never exist unpacked before the batch tensor.
 // Integer arithmetic throughout: the results do not depend on the order the partial results arrive in.
 #include "common.h"
@@ -108,6 +109,28 @@ __global__ __launch_bounds__(256) void gtprep_gather_kernel(const unsigned* __re
     }
 }
 
+// utils.resize_mask on the packed layout: scipy.ndimage.zoom(mask, [s, s, 1], order=0) copies, per output pixel, one input pixel
+// or the constant 0, the row chosen by the output row alone and the column by the output column alone (iy / ix: scipy's own
+// choices, gtprep.zoom_index_tables; an entry outside [0, h) / [0, w), -1 by convention, is the constant), and np.pad puts the
+// result at (top, left) of the zero canvas.  A thread owns one 32-bit word (32 instances) of one canvas pixel: consecutive threads
+// store consecutive words.
+__global__ __launch_bounds__(256) void gtprep_zoom_kernel(const unsigned* __restrict__ words, int h, int w, int nw,
+                                                          const int* __restrict__ iy, int oh, const int* __restrict__ ix, int ow, int top,
+                                                          int left, int OW, long long total, unsigned* __restrict__ out) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const long long pix = t / nw;
+    const int k = (int)(t - pix * nw);
+    const int X = (int)(pix % OW), Y = (int)(pix / OW);
+    const int oy = Y - top, ox = X - left;
+    unsigned v = 0u;                                               // np.pad(..., constant_values=0), zoom's cval
+    if (oy >= 0 && oy < oh && ox >= 0 && ox < ow) {
+        const int sy = iy[oy], sx = ix[ox];
+        if ((unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w) v = words[((long long)sy * w + sx) * nw + k];
+    }
+    out[t] = v;
+}
+
 static int gtprep_frame_status(int H, int W, int nb) {
     if (H <= 0 || W <= 0 || nb <= 0 || nb % 4 != 0) return MRCNN_ERR_ARG;
     if (H > MRCNN_GTPREP_MAX_SIDE || W > MRCNN_GTPREP_MAX_SIDE || nb > MRCNN_GTPREP_MAX_INSTANCES / 8) return MRCNN_ERR_UNSUPPORTED;
@@ -166,5 +189,24 @@ extern "C" int mrcnn_mask_bits_gather(const void* packed, int H, int W, int nb, 
     else
         hipLaunchKernelGGL(gtprep_gather_kernel<false>, grid, block, 0, (hipStream_t)stream, (const unsigned*)packed, npix, nb / 4, sel, k,
                            G, (unsigned char*)out);
+    return mrcnn_launch_status();
+}
+
+extern "C" int mrcnn_mask_bits_zoom_check(int h, int w, int nb, int oh, int ow, int top, int left, int OH, int OW) {
+    const int src = gtprep_frame_status(h, w, nb), dst = gtprep_frame_status(OH, OW, nb);
+    if (src == MRCNN_ERR_ARG || dst == MRCNN_ERR_ARG) return MRCNN_ERR_ARG;
+    if (oh <= 0 || ow <= 0 || top < 0 || left < 0 || oh > OH - top || ow > OW - left) return MRCNN_ERR_ARG;
+    return src ? src : dst;
+}
+
+extern "C" int mrcnn_mask_bits_zoom(const void* packed, int h, int w, int nb, const int* iy, int oh, const int* ix, int ow, int top,
+                                    int left, int OH, int OW, void* out, void* stream) {
+    const int rc = mrcnn_mask_bits_zoom_check(h, w, nb, oh, ow, top, left, OH, OW);
+    if (rc) return rc;
+    if (!packed || !iy || !ix || !out || ((uintptr_t)packed & 3) || ((uintptr_t)out & 3)) return MRCNN_ERR_ARG;
+    const int nw = nb / 4;
+    const long long total = (long long)OH * OW * nw;                   // <= 2^26 * 2^7
+    hipLaunchKernelGGL(gtprep_zoom_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned*)packed, h,
+                       w, nw, iy, oh, ix, ow, top, left, OW, total, (unsigned*)out);
     return mrcnn_launch_status();
 }

@@ -105,7 +105,7 @@ def build_rpn_targets(image_shape, anchors, gt_class_ids, gt_boxes, config, rng=
 
 def data_generator(dataset, config, shuffle=True, augment=False, augmentation=None, batch_size=1,
                    no_augmentation_sources=None, rank=0, world_size=1, seed=None, device_targets=False,
-                   device_samples=False, device=None):
+                   device_samples=False, device=None, device_resize=False):
     """Yields ([images, image_meta, rpn_match, rpn_bbox, gt_class_ids, gt_boxes, gt_masks], []) forever
     (model.py:1721-1904).  With world_size > 1 each rank walks its own stride of the (identically
     shuffled) image list -- the data-parallel replacement of tf.split in parallel_model.py:60-62.
@@ -114,13 +114,16 @@ def data_generator(dataset, config, shuffle=True, augment=False, augmentation=No
     float32 [B, H, W, 3] and `gt_masks` as a uint8 [B, H, W, MAX_GT_INSTANCES] device tensor; the other five items, the host's
     decisions and its random numbers are those of the host path.  Configurations the device path does not take keep the host
     path for the whole generator (one log line says why), single samples it does not take are built on the host and uploaded
-    into the same batch."""
+    into the same batch -- among them every image resize_image scales, unless device_resize asks for those on the device too
+    (DESIGN.md 4.19).  device_resize without device_samples does nothing (one log line says so)."""
     sampler = None
+    if device_resize and not device_samples:
+        logger.info("data_generator: device_resize asked for without device_samples: ignored")
     if device_samples:
         from . import gtprep
         why = gtprep.generator_refusal(config, device, augment, augmentation)
         if why is None:
-            sampler = gtprep.DeviceSampler(config, device)
+            sampler = gtprep.DeviceSampler(config, device, resize=device_resize)
         else:
             logger.info("data_generator: device_samples asked for, samples stay on the host: %s", why)
     b = 0

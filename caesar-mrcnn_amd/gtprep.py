@@ -5,7 +5,9 @@ twice on the host -- np.sum(mask, axis=(0, 1)) picks the instances that kept a p
 -- and copy the kept planes into the zeroed [H, W, MAX_GT_INSTANCES] batch.  This module states both on the loader's
 bit-packed layout (`mask_bits_stats_host`, `mask_bits_gather_host`: the answers csrc/gtprep.hip is held to) and builds a
 sample with them on the device (`DeviceSampler`): the pixels go up once and never come back, only the [N, 5] table of counts
-and boxes does.
+and boxes does.  An image resize_image scales is scaled there too when asked for: utils.resize_mask's
+nearest-neighbour zoom as two index tables taken from scipy itself (`zoom_index_tables`) and its statement on the packed
+layout (`mask_bits_zoom_host`), the image by ops.resize_image_u8.
 
 Layout: packed [H, W, nb] uint8 = np.packbits(mask != 0, axis=-1, bitorder="little"), padded with zero bytes to nb % 4 == 0
 (`mask_bits_pack`); instance j is bit j & 7 of byte j >> 3.  It is what ops.augment_warp_mask_bits reads and writes.
@@ -16,8 +18,10 @@ import numpy as np
 
 from . import utils
 
-# samples data_generator(device_samples=True) built on the device / handed to the host path one by one (scale != 1, ...)
-counters = {"device": 0, "host": 0}
+# samples data_generator(device_samples=True) built on the device / handed to the host path one by one (a scale other than 1
+# without device_resize, ...); "scaled": those of "device" that were scaled there (device_resize=True)
+counters = {"device": 0, "host": 0, "scaled": 0}
+ZOOM_CACHE_ENTRIES = 256          # (h, w, scale) keys a DeviceSampler keeps index tables for; the oldest goes first
 _counters_lock = threading.Lock()
 
 
@@ -66,6 +70,40 @@ def mask_bits_gather_host(packed, sel, G):
     return out
 
 
+def zoom_index_tables(h, w, scale):
+    """(iy [oh] int32, ix [ow] int32): the input row / column scipy.ndimage.zoom(mask, [scale, scale, 1], order=0) copies into
+    every output row / column of an [h, w, N] mask, -1 where it writes its constant 0 instead (the last coordinate can land a
+    hair past n - 1).  The zoom is separable and its choice on an axis depends on that axis alone, so the tables are scipy's own
+    answers on the two 1-D ramps 1 .. n -- its coordinate arithmetic is not restated here."""
+    import warnings
+    import scipy.ndimage
+    tables = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for n in (int(h), int(w)):
+            tables.append((scipy.ndimage.zoom(np.arange(1, n + 1), scale, order=0) - 1).astype(np.int32))
+    return tables[0], tables[1]
+
+
+def mask_bits_zoom_host(packed, iy, ix, top, left, OH, OW):
+    """uint8 [OH, OW, nb]: pixel (top + y, left + x) = packed pixel (iy[y], ix[x]), zeros where a table entry is -1 and outside
+    the len(iy) x len(ix) window -- utils.resize_mask (zoom by the tables of zoom_index_tables, then np.pad) on packed masks."""
+    packed = np.asarray(packed)
+    iy, ix = np.asarray(iy, dtype=np.int64).reshape(-1), np.asarray(ix, dtype=np.int64).reshape(-1)
+    if packed.dtype != np.uint8 or packed.ndim != 3 or min(packed.shape) < 1 or not iy.size or not ix.size:
+        raise ValueError("packed must be a non-empty uint8 [h, w, nb] and the tables non-empty")
+    h, w, nb = packed.shape
+    if iy.min() < -1 or iy.max() >= h or ix.min() < -1 or ix.max() >= w:
+        raise ValueError("the tables must lie in [-1, h) and [-1, w)")
+    if top < 0 or left < 0 or top + iy.size > OH or left + ix.size > OW:
+        raise ValueError("the zoomed window does not fit the canvas")
+    padded = np.zeros((h + 1, w + 1, nb), np.uint8)                         # row / column -1: the constant
+    padded[:h, :w] = packed
+    out = np.zeros((int(OH), int(OW), nb), np.uint8)
+    out[top:top + iy.size, left:left + ix.size] = padded[iy][:, ix]
+    return out
+
+
 def generator_refusal(config, device, augment, augmentation):
     """Why a whole generator keeps the host path although device samples were asked for (None: it need not)."""
     from .augment import ReferenceAugmenter
@@ -91,21 +129,38 @@ def generator_refusal(config, device, augment, augmentation):
 class DeviceSample(object):
     """One image's ground truth after DeviceSampler.load: the padded, augmented uint8 image and the bit-packed masks on the
     device, the kept instances' class ids / boxes / bit indices and image_meta on the host."""
-    __slots__ = ("img", "bits", "shape", "sel", "class_ids", "bbox", "image_meta")
+    __slots__ = ("img", "bits", "shape", "sel", "class_ids", "bbox", "image_meta", "scaled")
 
 
 class DeviceSampler(object):
     """Builds training samples on `device`, on the loader threads' one side stream under its lock (loader_stream.py)."""
 
-    def __init__(self, config, device):
+    def __init__(self, config, device, resize=False):
+        """resize: an image resize_image scales is scaled on the device too (Config.DEVICE_SAMPLE_RESIZE, DESIGN.md 4.19);
+        without it such a sample is the host's."""
+        import collections
         import torch
         self.config = config
         self.device = torch.device(device)
+        self.resize = bool(resize)
+        self._zoom = collections.OrderedDict()        # (h, w, scale) -> [iy, ix, iy on the device, ix on the device]
+
+    def zoom_tables(self, h, w, scale):
+        """The cache entry of zoom_index_tables(h, w, scale): datasets repeat their sizes.  At most ZOOM_CACHE_ENTRIES are kept."""
+        key = (int(h), int(w), float(scale))
+        entry = self._zoom.get(key)
+        if entry is None:
+            iy, ix = zoom_index_tables(h, w, scale)
+            entry = self._zoom[key] = [iy, ix, None, None]
+            while len(self._zoom) > ZOOM_CACHE_ENTRIES:
+                self._zoom.popitem(last=False)
+        return entry
 
     def load(self, dataset, image_id, augmentation):
         """("device", DeviceSample) -- or ("host", image, mask, class_ids), the loaded arrays of a sample that only the host
-        path takes (a scale other than 1, an image that is not uint8 [h, w, C <= 4], masks that are not bool / 0-1 uint8
-        [h, w, N >= 1], sizes past a cap of the kernels).  That decision is taken before the augmentation plan is drawn."""
+        path takes (a scale other than 1 unless `resize`, an image that is not uint8 [h, w, C <= 4], masks that are not bool /
+        0-1 uint8 [h, w, N >= 1], sizes past a cap of the kernels).  That decision is taken before the augmentation plan is
+        drawn."""
         import torch
         from . import ops
         from .loader_stream import loader_stream
@@ -128,14 +183,23 @@ class DeviceSampler(object):
             return host()                       # (values above 1 interpolate differently in the host warp than their bits do)
         h, w, C = shape
         N = mask.shape[2]
-        scale, _, padding, window = utils.resize_plan(shape, min_dim=cfg.IMAGE_MIN_DIM, max_dim=cfg.IMAGE_MAX_DIM,
-                                                      min_scale=cfg.IMAGE_MIN_SCALE, mode=cfg.IMAGE_RESIZE_MODE)
-        if scale != 1:
+        scale, (oh, ow), padding, window = utils.resize_plan(shape, min_dim=cfg.IMAGE_MIN_DIM, max_dim=cfg.IMAGE_MAX_DIM,
+                                                             min_scale=cfg.IMAGE_MIN_SCALE, mode=cfg.IMAGE_RESIZE_MODE)
+        scaled = scale != 1
+        if scaled and not self.resize:
             return host()
         (top, bottom), (left, right) = padding[0], padding[1]
-        OH, OW = h + top + bottom, w + left + right
+        OH, OW = oh + top + bottom, ow + left + right
         G = cfg.MAX_GT_INSTANCES
+        zoom = None
         try:
+            if scaled:
+                if oh < 1 or ow < 1:
+                    return host()
+                zoom = self.zoom_tables(h, w, scale)
+                if zoom[0].size != oh or zoom[1].size != ow:              # scipy rounds the zoomed size its own way: the host's
+                    return host()
+                ops.gtprep_zoom_check(h, w, 4 * (-(-N // 32)), oh, ow, top, left, OH, OW)
             ops.gtprep_check(OH, OW, 4 * (-(-N // 32)), N, G)
         except ops.GtPrepUnsupported:
             return host()
@@ -147,7 +211,12 @@ class DeviceSampler(object):
             with torch.cuda.stream(st):
                 img = image if on_dev else torch.from_numpy(np.ascontiguousarray(image)).to(dev, non_blocking=True)
                 bits = torch.from_numpy(packed).to(dev, non_blocking=True)
-                if (OH, OW) != (h, w):                                    # np.pad of resize_image / resize_mask
+                if scaled:                                                # resize_image / resize_mask, their np.pad included
+                    if zoom[2] is None:
+                        zoom[2], zoom[3] = (torch.from_numpy(t).to(dev, non_blocking=True) for t in zoom[:2])
+                    img = ops.resize_image_u8(img.contiguous(), (oh, ow), (top, left), (OH, OW))
+                    bits = ops.mask_bits_zoom(bits, zoom[2], zoom[3], (top, left), (OH, OW))
+                elif (OH, OW) != (h, w):                                  # np.pad of resize_image / resize_mask
                     canvas = torch.zeros((OH, OW, C), dtype=torch.uint8, device=dev)
                     canvas[top:top + h, left:left + w] = img
                     planes = torch.zeros((OH, OW, nb), dtype=torch.uint8, device=dev)
@@ -163,7 +232,7 @@ class DeviceSampler(object):
         count, box = table[:N], table[N:].reshape(N, 4)
         keep = count > 0
         s = DeviceSample()
-        s.img, s.bits, s.shape = img, bits, (OH, OW, C)
+        s.img, s.bits, s.shape, s.scaled = img, bits, (OH, OW, C), scaled
         s.sel = np.flatnonzero(keep).astype(np.int32)
         s.class_ids = class_ids[keep]
         s.bbox = box[keep].astype(np.int32)
@@ -194,6 +263,8 @@ class DeviceSampler(object):
                 ops.mask_bits_gather(sample.bits, sel, self.config.MAX_GT_INSTANCES, out=out_masks)
                 ops.mold_image_u8(sample.img, (OH, OW), (0, 0), (OH, OW), self.config.MEAN_PIXEL, out=out_image)
         _count("device")
+        if sample.scaled:
+            _count("scaled")
 
     def emit_host(self, molded, gt_masks, out_image, out_masks):
         """A host-built sample (float32 molded image, [H, W, k] masks) into the same batch slots."""

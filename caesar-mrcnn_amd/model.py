@@ -307,7 +307,11 @@ class MaskRCNN(object):
         if isinstance(augmentation, ReferenceAugmenter) and augmentation.device is None:
             augmentation.device = self.engine.dev             # its warps on the loader stream (augment.py)
         # Config.DEVICE_SAMPLES: the generators assemble their samples on the engine's GPU (gtprep.py)
-        dev_s = dict(device_samples=True, device=self.engine.dev) if getattr(cfg, "DEVICE_SAMPLES", False) else {}
+        # Config.DEVICE_SAMPLE_RESIZE: images the loader has to scale included
+        dev_r = bool(getattr(cfg, "DEVICE_SAMPLE_RESIZE", False))
+        dev_s = dict(device_samples=True, device=self.engine.dev, device_resize=dev_r) if getattr(cfg, "DEVICE_SAMPLES", False) else {}
+        if dev_r and not dev_s:
+            log("DEVICE_SAMPLE_RESIZE without DEVICE_SAMPLES: ignored")
         train_gen = Prefetcher([data_generator(train_dataset, cfg, shuffle=True, augmentation=augmentation,
                                                batch_size=cfg.IMAGES_PER_GPU, no_augmentation_sources=no_augmentation_sources,
                                                rank=rank, world_size=world, seed=1234 + 1000 * k, device_targets=dev_t, **dev_s)

@@ -1072,6 +1072,12 @@ def gtprep_check(H, W, nb, n, G):
     _gtprep_refusal(L.mrcnn_mask_bits_gather_check(int(H), int(W), int(nb), 0, int(G)), "mrcnn_mask_bits_gather")
 
 
+def gtprep_zoom_check(h, w, nb, oh, ow, top, left, OH, OW):
+    """Raises what mask_bits_zoom would raise for these sizes; launches nothing."""
+    _gtprep_refusal(_hip.lib().mrcnn_mask_bits_zoom_check(int(h), int(w), int(nb), int(oh), int(ow), int(top), int(left), int(OH),
+                                                          int(OW)), "mrcnn_mask_bits_zoom")
+
+
 def mask_bits_stats(packed, n):
     """Pixel count and box of every instance of bit-packed masks, on the device: packed [H, W, nb] uint8 =
     np.packbits(mask != 0, axis=-1, bitorder="little") with nb % 4 == 0 (the layout of augment_warp_mask_bits), n instances ->
@@ -1123,6 +1129,87 @@ def mask_bits_gather(packed, sel, G, out=None):
     sel_d = torch.from_numpy(np.ascontiguousarray(sel_h, dtype=np.int32)).pin_memory().to(packed.device, non_blocking=True) if k else None
     check(L.mrcnn_mask_bits_gather(ptr(packed), H, W, nb, ptr(sel_d), k, G, ptr(out), current_stream()), "mrcnn_mask_bits_gather")
     return out                               # (sel_d goes back to the allocator of this stream: reused in stream order only)
+
+
+def _zoom_table(t, n_in, device, what):
+    """An index table of mask_bits_zoom on `device`: a NumPy / list table is checked against -1 <= t < n_in here and uploaded; a
+    device tensor is taken as it is (the kernel reads any entry outside [0, n_in) as the constant)."""
+    import numpy as np
+    if torch.is_tensor(t):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() < 1 or not t.is_contiguous() or t.device != device:
+            raise ValueError("mask_bits_zoom: %s must be a contiguous 1-D int32 table on packed's device" % what)
+        return t, int(t.numel())
+    t_h = np.asarray(t)
+    if t_h.ndim != 1 or t_h.size < 1 or not np.issubdtype(t_h.dtype, np.integer):
+        raise ValueError("mask_bits_zoom: %s must be a non-empty 1-D integer table" % what)
+    if int(t_h.min()) < -1 or int(t_h.max()) >= n_in:
+        raise ValueError("mask_bits_zoom: %s must lie in [-1, %d)" % (what, n_in))
+    return np.ascontiguousarray(t_h, dtype=np.int32), int(t_h.size)
+
+
+def mask_bits_zoom(packed, iy, ix, pad_tl, canvas_hw, out=None):
+    """utils.resize_mask on bit-packed masks, on the device: packed [h, w, nb] uint8 (as for mask_bits_stats) -> uint8
+    [OH, OW, nb], canvas_hw = (OH, OW): pixel (top + y, left + x) = packed pixel (iy[y], ix[x]), pad_tl = (top, left), zeros where
+    a table entry is -1 and everywhere outside the len(iy) x len(ix) window -- scipy.ndimage.zoom(order=0) with the tables of
+    gtprep.zoom_index_tables, then np.pad (gtprep.mask_bits_zoom_host).  iy, ix: int32 tables, NumPy / list (checked against
+    [-1, h) / [-1, w) here, then uploaded) or device tensors.  ValueError for malformed input, GtPrepUnsupported past a cap;
+    neither allocates, launches or writes anything."""
+    h, w, nb = _gtprep_packed(packed, "mask_bits_zoom")
+    iy, oh = _zoom_table(iy, h, packed.device, "iy")
+    ix, ow = _zoom_table(ix, w, packed.device, "ix")
+    try:
+        (top, left), (OH, OW) = (int(v) for v in pad_tl), (int(v) for v in canvas_hw)
+    except (TypeError, ValueError):
+        raise ValueError("mask_bits_zoom: pad_tl and canvas_hw must be pairs of integers")
+    if not packed.is_contiguous() or packed.data_ptr() % 4:
+        raise ValueError("mask_bits_zoom: packed must be contiguous and 4-byte aligned")
+    if top < 0 or left < 0 or OH < 1 or OW < 1 or top + oh > OH or left + ow > OW:
+        raise ValueError("mask_bits_zoom: a %d x %d window at %r does not fit the %d x %d canvas" % (oh, ow, (top, left), OH, OW))
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (OH, OW, nb)
+                            or not out.is_contiguous() or out.device != packed.device or out.data_ptr() % 4):
+        raise ValueError("mask_bits_zoom: out must be a contiguous, 4-byte aligned uint8 [%d, %d, %d] tensor on packed's device"
+                         % (OH, OW, nb))
+    L = _hip.lib()
+    _gtprep_refusal(L.mrcnn_mask_bits_zoom_check(h, w, nb, oh, ow, top, left, OH, OW), "mrcnn_mask_bits_zoom")
+    _need_cuda(packed)
+    if out is None:
+        out = torch.empty((OH, OW, nb), dtype=torch.uint8, device=packed.device)
+    if not torch.is_tensor(iy):                  # (through pinned memory, as mask_bits_gather's table)
+        iy = torch.from_numpy(iy).pin_memory().to(packed.device, non_blocking=True)
+    if not torch.is_tensor(ix):
+        ix = torch.from_numpy(ix).pin_memory().to(packed.device, non_blocking=True)
+    check(L.mrcnn_mask_bits_zoom(ptr(packed), h, w, nb, ptr(iy), oh, ptr(ix), ow, top, left, OH, OW, ptr(out), current_stream()),
+          "mrcnn_mask_bits_zoom")
+    return out
+
+
+def resize_image_u8(src, out_hw, pad_tl, canvas_hw, out=None):
+    """utils.resize_image's pixel work on the device, for the training loader: src [h, w, C] uint8 device (C <= 4) -> uint8
+    [OH, OW, C]: the image scaled to out_hw (bilinear, float64, clipped to the image's range, truncated to uint8 -- the value
+    mold_image_u8 computes before it subtracts the mean; a copy when out_hw == (h, w)) at pad_tl inside a zero canvas.  ValueError
+    for malformed input; it allocates, launches and writes nothing."""
+    if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.dim() != 3 or not src.is_contiguous():
+        raise ValueError("resize_image_u8: src must be a contiguous uint8 [h, w, C] tensor")
+    h, w, C_ = (int(v) for v in src.shape)
+    if h < 1 or w < 1 or not 1 <= C_ <= 4:
+        raise ValueError("resize_image_u8: src %r must be non-empty with 1 to 4 channels" % ((h, w, C_),))
+    try:
+        (oh, ow), (top, left), (OH, OW) = (int(v) for v in out_hw), (int(v) for v in pad_tl), (int(v) for v in canvas_hw)
+    except (TypeError, ValueError):
+        raise ValueError("resize_image_u8: out_hw, pad_tl and canvas_hw must be pairs of integers")
+    if oh < 1 or ow < 1 or top < 0 or left < 0 or top + oh > OH or left + ow > OW or max(OH, OW) >= 2 ** 31:
+        raise ValueError("resize_image_u8: a %d x %d image at %r does not fit the %d x %d canvas" % (oh, ow, (top, left), OH, OW))
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (OH, OW, C_)
+                            or not out.is_contiguous() or out.device != src.device or out.data_ptr() == src.data_ptr()):
+        raise ValueError("resize_image_u8: out must be a contiguous uint8 [%d, %d, %d] tensor on src's device, not src itself"
+                         % (OH, OW, C_))
+    _need_cuda(src)
+    if out is None:
+        out = torch.empty((OH, OW, C_), dtype=torch.uint8, device=src.device)
+    ws = workspace(64, src.device, "mold")
+    check(_hip.lib().mrcnn_resize_image_u8(ptr(src), h, w, C_, oh, ow, top, left, OH, OW, ptr(out), ptr(ws), ws.numel(),
+                                           current_stream()), "mrcnn_resize_image_u8")
+    return out
 
 
 def tile_upload(pool, desc, device):

@@ -291,6 +291,15 @@ int mrcnn_augment_warp_mask_bits(const void* src, int H, int W, int nbytes_per_p
  *                           [B, H, W, G] batch.  sel: k int32 on the device, 0 <= sel[j] < 8 nb (an entry outside gives 0).
  *                           k == 0 writes zeros.  One launch; 32-bit stores when G % 4 == 0 and out is 4-byte aligned, else
  *                           bytes.
+ *   mrcnn_mask_bits_zoom    replaces utils.resize_mask (mrcnn/utils.py:564-583) for an image resize_image scales:
+ *                           scipy.ndimage.zoom(mask, [s, s, 1], order=0) [3P] and np.pad, in one launch.  The zoom copies one
+ *                           input pixel or the constant 0 per output pixel, the row chosen by the output row and the column by
+ *                           the output column: iy [oh], ix [ow] int32 on the device are those choices, taken from scipy itself
+ *                           (gtprep.zoom_index_tables); an entry outside [0, h) / [0, w) (-1 by convention) is the constant.
+ *                           out [OH, OW, nb] (4-byte aligned): pixel (top + y, left + x) = packed pixel (iy[y], ix[x]) for
+ *                           y < oh, x < ow, zero words everywhere else.  One thread per canvas pixel and 32-bit word.  The
+ *                           caps hold for h x w and for OH x OW; MRCNN_ERR_ARG also for oh, ow <= 0, top, left < 0,
+ *                           top + oh > OH, left + ow > OW.
  * Malformed (MRCNN_ERR_ARG): H, W, nb or G <= 0, nb % 4 != 0, n <= 0, n > 8 nb, k < 0, k > G, a missing or misaligned pointer.
  * Caps (past any: MRCNN_ERR_UNSUPPORTED, use the host statement): H, W <= MRCNN_GTPREP_MAX_SIDE; n, 8 nb and G <=
  * MRCNN_GTPREP_MAX_INSTANCES (the stats table is one workspace slot per bit).  A refused call launches and writes nothing.
@@ -303,6 +312,9 @@ int mrcnn_mask_bits_stats(const void* packed, int H, int W, int nb, int n, int* 
                           void* stream);
 int mrcnn_mask_bits_gather_check(int H, int W, int nb, int k, int G);
 int mrcnn_mask_bits_gather(const void* packed, int H, int W, int nb, const int* sel, int k, int G, void* out, void* stream);
+int mrcnn_mask_bits_zoom_check(int h, int w, int nb, int oh, int ow, int top, int left, int OH, int OW);
+int mrcnn_mask_bits_zoom(const void* packed, int h, int w, int nb, const int* iy, int oh, const int* ix, int ow, int top, int left,
+                         int OH, int OW, void* out, void* stream);
 
 /* Stitching of sources across tile borders (SFinder.merge_edge_sources, mrcnn/sfinder.py:711-935).  Sources are row-major bit
  * masks of their bounding boxes in mosaic coordinates: ONE pool of 32-bit words and a descriptor per source; pixel (x, y) of a
@@ -676,6 +688,11 @@ int mrcnn_mosaic_overview(const void* plane, int big_endian, int ny, int nx, int
  * round(w * scale)) and the padding as the reference does.  mean_pixel: C doubles on the HOST.  workspace: >= 8 bytes.   */
 int mrcnn_mold_image_u8(const void* src, int h, int w, int C, int oh, int ow, int top, int left, int OH, int OW,
                         const double* mean_pixel, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The first half alone, for the training loader (load_image_gt augments between resize_image and mold_image,
+ * mrcnn/model.py:1300-1359): out [OH, OW, C] uint8 = utils.resize_image(src) -- the same float64 bilinear, clip to the source's
+ * min / max and truncation per value, zero padding.  Same arguments, refusals and workspace.                              */
+int mrcnn_resize_image_u8(const void* src, int h, int w, int C, int oh, int ow, int top, int left, int OH, int OW, void* out,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* Elementwise helpers on flat buffers. */
 int mrcnn_add_inplace(float* dst, const float* src, int64_t n, void* stream);

@@ -92,6 +92,10 @@ def parse_args(argv=None):
                         "instances, boxes, batch planes; Config.DEVICE_SAMPLES); with the default flip / rot90 augmentation "
                         "the samples stay on the host and a log line says so: combine with --reference_augmentation or "
                         "--no_augmentation")
+    p.add_argument('--device_sample_resize', action='store_true', default=False,
+                   help="extension: with --device_samples, images the loader has to scale (cut-outs whose short side is not "
+                        "--imgsize) are scaled on the GPU too, image and masks (Config.DEVICE_SAMPLE_RESIZE); without "
+                        "--device_samples it is ignored and a log line says so")
     p.add_argument('--reference_tester', action='store_true', default=False,
                    help="extension: `test` runs the reference's ModelTester (masks merged and selected first, its matching rule, "
                         "confusion matrix and purity, completeness.csv and reliability.csv); needs a JSON dataloader; default: the "
@@ -219,6 +223,9 @@ def build_config(args, class_dict_model):
     cfg.TILE_XSIZE, cfg.TILE_YSIZE, cfg.TILE_XSTEP, cfg.TILE_YSTEP = args.tile_xsize, args.tile_ysize, args.tile_xstep, args.tile_ystep
     cfg.HEAD_DTYPE = args.head_dtype or None
     cfg.DEVICE_SAMPLES = bool(args.device_samples)
+    cfg.DEVICE_SAMPLE_RESIZE = bool(getattr(args, "device_sample_resize", False)) and cfg.DEVICE_SAMPLES
+    if getattr(args, "device_sample_resize", False) and not cfg.DEVICE_SAMPLES:
+        logger.warning("--device_sample_resize needs --device_samples: ignored")
     return cfg
 
 
