@@ -268,6 +268,7 @@ _SIGNATURES = {
     "mrcnn_winograd_input_g": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),
     "mrcnn_winograd_weights_g": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mrcnn_winograd_output_g": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),
+    "mrcnn_winograd_chain": (C.c_int, [_P] * 6 + [C.c_int] * 6 + [_P]),
     "mrcnn_winograd_output_bwd_rows": (C.c_int, [C.POINTER(WinoGroup), C.c_int, C.c_int]),
     "mrcnn_winograd_output_bwd_g": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),
     "mrcnn_winograd_output_bwd_zmask_g": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WinoGroup), _P]),

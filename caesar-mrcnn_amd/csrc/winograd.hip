@@ -5,6 +5,8 @@
 //   winograd_input_kernel    x [N, H, W, C]            -> V [16][T][C],   T = N (H/2)(W/2) tiles   (reads x once through L2, writes 4 x its size)
 //   16 GEMMs                 V[xi] [T, C] . U[xi] [C, Cout] -> Mt [16][T][Cout]                     (conv_fwd_blds_kernel, batched over xi)
 //   winograd_output_kernel   Mt -> out [N, H, W, Cout] with the convolution's epilogue (bias, frozen-BN affine, activation, z)
+// (between two such layers of the training forward, winograd_chain_kernel: the output transform of the first and the input transform of
+// the second in one pass, the activated tensor between them kept in LDS)
 // plus winograd_weight_kernel U = G g G^T once per weight update.  For the 2 x 2 tile the transforms are exact additions / halvings
 // in float32 (B^T, A^T have entries 0, +-1; G has 0, 1, +-1/2), so the result differs from the direct kernel by summation order
 // only, and H and W must be even (mask head: 14 x 14); the 4 x 4 tile takes any extent (its last tiles hang over the edge).
@@ -255,6 +257,147 @@ __device__ __forceinline__ typename WinoVec<CV>::type wino_buffer_load(__amdgpu_
         r[0] = __uint_as_float(v[0]); r[1] = __uint_as_float(v[1]); r[2] = __uint_as_float(v[2]); r[3] = __uint_as_float(v[3]);
     }
     return r;
+}
+
+// ---- the forward chain: output transform + epilogue of layer l and input transform of layer l + 1 in one pass ------------------
+// Mixed tiling only (H, W = 2 mod 4: a x b tiles of 4 x 4, a of 4 x 2, b of 2 x 4, one 2 x 2).  A workgroup owns ONE map and CS of its
+// channels: lane = channel pair (L = CS / 2 lanes), 256 / L tiles in flight.  Phase 1 walks the map's tiles of all four groups --
+// wino_output_tile's arithmetic, operation for operation, with all of a tile's transform-domain values requested before the first
+// addition --, stores z when asked and leaves the activated H x W x CS map in LDS; phase 2 cuts the next layer's input tiles from
+// it (zero halo) and writes B^T d B as winograd_input_kernel does.  The activated output never reaches memory.  Mt and V hold
+// the four groups end to end, each [nb][Tp][C] (the same offsets: the next layer's Cin is this layer's Cout).
+struct WinoChainGeo {
+    int a, b;                      // H / 4, W / 4
+    unsigned tp[4];                // rows per transform-domain matrix of each group
+    long long off[4];              // first float of each group in Mt / V
+};
+
+template <int OTH, int OTW>
+__device__ __forceinline__ void wino_chain_out_tile(__amdgpu_buffer_rsrc_t rsrc, unsigned mstride, unsigned t, int oh0, int ow0, int c,
+                                                    int cl, const WinoVec<2>::type bi, const WinoVec<2>::type sc,
+                                                    const WinoVec<2>::type sh, int act, float* __restrict__ z, float* map, int W,
+                                                    int C, int CS) {
+    typedef WinoVec<2>::type vec;
+    constexpr int ITH = OTH + 2, ITW = OTW + 2;
+    vec m[ITH][ITW];
+    const unsigned moff = (t * (unsigned)C + (unsigned)c) * 4u;
+#pragma unroll
+    for (int r = 0; r < ITH; ++r)
+#pragma unroll
+        for (int k = 0; k < ITW; ++k) m[r][k] = wino_buffer_load<2>(rsrc, moff, (unsigned)(r * ITW + k) * mstride);
+    vec s[OTH][ITW];
+#pragma unroll
+    for (int k = 0; k < ITW; ++k) {              // A^T down the rows of every column k
+        vec col[ITH], o[OTH];
+#pragma unroll
+        for (int r = 0; r < ITH; ++r) col[r] = m[r][k];
+        wino_at<OTH>(col, o);
+#pragma unroll
+        for (int a = 0; a < OTH; ++a) s[a][k] = o[a];
+    }
+#pragma unroll
+    for (int a = 0; a < OTH; ++a) {
+        vec y[OTW];
+        wino_at<OTW>(s[a], y);
+#pragma unroll
+        for (int b = 0; b < OTW; ++b) {           // the mixed tiling has no overhang: every output lies inside the map
+            const int pix = (oh0 + a) * W + ow0 + b;
+            vec zv, o;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                zv[e] = y[b][e] + bi[e];
+                float v = sc[e] * zv[e] + sh[e];
+                if (act == MRCNN_ACT_RELU) v = fmaxf(v, 0.f);
+                o[e] = v;
+            }
+            if (z) *(vec*)(z + (unsigned)(pix * C + c)) = zv;      // z: this map's
+            *(vec*)(map + pix * CS + cl) = o;
+        }
+    }
+}
+
+template <int OTH, int OTW>
+__device__ __forceinline__ void wino_chain_in_tile(const float* map, float* __restrict__ Vg, long long Tp, unsigned t, int oh0, int ow0, int c,
+                                                   int cl, int H, int W, int C, int CS) {
+    typedef WinoVec<2>::type vec;
+    constexpr int ITH = OTH + 2, ITW = OTW + 2;
+    const int ih0 = oh0 - 1, iw0 = ow0 - 1;
+    vec tt[ITH][ITW];
+#pragma unroll
+    for (int s = 0; s < ITW; ++s) {              // columns of the tile: B^T applied down the rows
+        vec col[ITH], o[ITH];
+#pragma unroll
+        for (int r = 0; r < ITH; ++r) {
+            const int ih = ih0 + r, iw = iw0 + s;
+            vec val = {};
+            if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) val = *(const vec*)(map + (ih * W + iw) * CS + cl);
+            col[r] = val;
+        }
+        wino_bt<OTH>(col, o);
+#pragma unroll
+        for (int r = 0; r < ITH; ++r) tt[r][s] = o[r];
+    }
+#pragma unroll
+    for (int r = 0; r < ITH; ++r) {              // then along each row
+        vec v[ITW];
+        wino_bt<OTW>(tt[r], v);
+#pragma unroll
+        for (int s = 0; s < ITW; ++s) *(vec*)(Vg + ((long long)(r * ITW + s) * Tp + t) * C + c) = v[s];
+    }
+}
+
+__global__ __launch_bounds__(256, 3) void winograd_chain_kernel(const float* __restrict__ Mt, float* __restrict__ z, const float* __restrict__ bias,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             float* __restrict__ V, int H, int W, int C, int act, int lg,
+                                                             const WinoChainGeo geo) {
+    typedef WinoVec<2>::type vec;
+    extern __shared__ __attribute__((aligned(16))) float wino_chain_map[];     // [H][W][CS]
+    const int L = 1 << lg, CS = 2 << lg, slots = 256 >> lg;
+    const int slices = C / CS;
+    const int n = (int)(blockIdx.x / (unsigned)slices), slice = (int)(blockIdx.x - (unsigned)n * slices);
+    const int slot = threadIdx.x >> lg, cl = (threadIdx.x & (L - 1)) * 2;
+    const int c = slice * CS + cl;
+    const int a = geo.a, b = geo.b, n0 = a * b, per_map = n0 + a + b + 1;
+    vec bi = {}, sc, sh = {};
+    sc[0] = sc[1] = 1.f;
+    if (bias) bi = *(const vec*)(bias + c);
+    if (scale) { sc = *(const vec*)(scale + c); sh = *(const vec*)(shift + c); }
+    // one descriptor per group, made where the base is plainly uniform (the host checks that every group fits 4 GiB)
+    const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void*)(Mt + geo.off[0]), 0, 0xFFFFFFF0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)(Mt + geo.off[1]), 0, 0xFFFFFFF0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc((void*)(Mt + geo.off[2]), 0, 0xFFFFFFF0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r3 = __builtin_amdgcn_make_buffer_rsrc((void*)(Mt + geo.off[3]), 0, 0xFFFFFFF0u, 0x00020000);
+    const unsigned cb = (unsigned)C * 4u;
+    float* zn = z ? z + (long long)n * H * W * C : nullptr;     // a map of <= 2048 pixels: 32-bit offsets inside it
+    for (int it = slot; it < per_map; it += slots) {
+        if (it < n0) {
+            const int th = it / b, tw = it - th * b;
+            wino_chain_out_tile<4, 4>(r0, geo.tp[0] * cb, (unsigned)n * n0 + it, 4 * th, 4 * tw, c, cl, bi, sc, sh, act, zn, wino_chain_map, W, C, CS);
+        } else if (it < n0 + a) {
+            const int th = it - n0;
+            wino_chain_out_tile<4, 2>(r1, geo.tp[1] * cb, (unsigned)n * a + th, 4 * th, W - 2, c, cl, bi, sc, sh, act, zn, wino_chain_map, W, C, CS);
+        } else if (it < n0 + a + b) {
+            const int tw = it - n0 - a;
+            wino_chain_out_tile<2, 4>(r2, geo.tp[2] * cb, (unsigned)n * b + tw, H - 2, 4 * tw, c, cl, bi, sc, sh, act, zn, wino_chain_map, W, C, CS);
+        } else {
+            wino_chain_out_tile<2, 2>(r3, geo.tp[3] * cb, (unsigned)n, H - 2, W - 2, c, cl, bi, sc, sh, act, zn, wino_chain_map, W, C, CS);
+        }
+    }
+    __syncthreads();
+    for (int it = slot; it < per_map; it += slots) {
+        if (it < n0) {
+            const int th = it / b, tw = it - th * b;
+            wino_chain_in_tile<4, 4>(wino_chain_map, V + geo.off[0], geo.tp[0], (unsigned)n * n0 + it, 4 * th, 4 * tw, c, cl, H, W, C, CS);
+        } else if (it < n0 + a) {
+            const int th = it - n0;
+            wino_chain_in_tile<4, 2>(wino_chain_map, V + geo.off[1], geo.tp[1], (unsigned)n * a + th, 4 * th, W - 2, c, cl, H, W, C, CS);
+        } else if (it < n0 + a + b) {
+            const int tw = it - n0 - a;
+            wino_chain_in_tile<2, 4>(wino_chain_map, V + geo.off[2], geo.tp[2], (unsigned)n * b + tw, H - 2, 4 * tw, c, cl, H, W, C, CS);
+        } else {
+            wino_chain_in_tile<2, 2>(wino_chain_map, V + geo.off[3], geo.tp[3], (unsigned)n, H - 2, W - 2, c, cl, H, W, C, CS);
+        }
+    }
 }
 
 // The output transform of a DATA gradient together with the epilogue backward of the layer below (what mrcnn_conv2d_dgrad_ep does
@@ -706,6 +849,43 @@ extern "C" int mrcnn_winograd_output_g(const float* Mt, float* out, float* z, co
     const WinoGrp k = {g->th_n, g->tw_n, g->oh0, g->ow0};
     const dim3 g4((unsigned)cdiv64(T * C / 4, 256)), g2((unsigned)cdiv64(T * C / 2, 256));
     WINO_LAUNCH_G(winograd_output_kernel, g, g4, g2, Mt, out, z, bias, scale, shift, N, H, W, C, T, wino_rows(T), act, k);
+    return mrcnn_launch_status();
+}
+
+// ---- forward chain: output transform + epilogue of a layer and the input transform of the next, mixed tiling -------------------------
+// channels per workgroup: the widest slice whose H x W map leaves three workgroups per CU their LDS (14 x 14 x 64 floats = 49 KiB)
+static int wino_chain_slice(int H, int W) {
+    for (int cs = 64; cs >= 8; cs >>= 1)
+        if ((long long)H * W * cs * 4 <= 53 * 1024) return cs;
+    return (long long)H * W * 8 * 4 <= 64 * 1024 ? 8 : 0;
+}
+
+extern "C" int mrcnn_winograd_chain(const float* Mt, float* z_out, const float* bias, const float* scale, const float* shift, float* V_next,
+                                    int N, int H, int W, int C, int act, int tile, void* stream) {
+    if (!Mt || !V_next || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (scale && !shift)) return MRCNN_ERR_ARG;
+    if (act != MRCNN_ACT_NONE && act != MRCNN_ACT_RELU) return MRCNN_ERR_UNSUPPORTED;
+    if (tile != MRCNN_WINO_TILE_MIXED || H % 4 != 2 || W % 4 != 2 || H <= 4 || W <= 4 || C % 128) return MRCNN_ERR_UNSUPPORTED;
+    const int cs = wino_chain_slice(H, W);
+    if (!cs) return MRCNN_ERR_UNSUPPORTED;
+    WinoChainGeo geo;
+    geo.a = H / 4; geo.b = W / 4;
+    const long long tiles[4] = {(long long)N * geo.a * geo.b, (long long)N * geo.a, (long long)N * geo.b, N};
+    const int nb[4] = {36, 24, 24, 16};
+    long long off = 0;
+    for (int i = 0; i < 4; ++i) {
+        const long long tp = wino_rows(tiles[i]);
+        // tile ids and the byte offsets into a group's matrices are 32-bit
+        if (tiles[i] >= (1LL << 31) || nb[i] * tp * C * 4 >= (1LL << 32)) return MRCNN_ERR_UNSUPPORTED;
+        geo.tp[i] = (unsigned)tp;
+        geo.off[i] = off;
+        off += nb[i] * tp * C;
+    }
+    const long long wgs = (long long)N * (C / cs);
+    if (wgs >= (1LL << 31)) return MRCNN_ERR_UNSUPPORTED;
+    int lg = 0;
+    while ((2 << lg) < cs) ++lg;                                // lanes per tile = cs / 2
+    hipLaunchKernelGGL(winograd_chain_kernel, dim3((unsigned)wgs), dim3(256), (size_t)H * W * cs * 4, (hipStream_t)stream, Mt, z_out, bias, scale,
+                       shift, V_next, H, W, C, act, lg, geo);
     return mrcnn_launch_status();
 }
 

@@ -66,6 +66,9 @@ SWITCHES = (
     # matrix-core flops through three launches per layer; False keeps the direct kernels
     ("winograd", "MRCNN_WINOGRAD", True, _on, "ti"),
     ("winograd_wgrad", "MRCNN_WINOGRAD_WGRAD", True, _on, "t"),     # weight gradients through the same domain
+    # training mask head: a layer's output transform, epilogue and the next layer's input transform in one launch; the activated
+    # output in between is not written (ops.conv2d_winograd_chain).  False: the separate launches (A/B)
+    ("winograd_chain", "MRCNN_WINOGRAD_CHAIN", True, _on, "t"),
     # the trunk's large 3x3 layers (FPN smoothing, RPN shared convolution on levels of >= trunk_winograd_min_rows pixels)
     # through F(2x2, 3x3) in the forward pass (A/B switch, see DESIGN 4.1e for the measurement)
     ("trunk_winograd", "MRCNN_WINOGRAD_TRUNK", True, _on, "ti"),
@@ -595,6 +598,46 @@ class MaskRCNNEngine(object):
         ops.conv2d_winograd(x, self._wino_U(op, 0, x.shape, train, infer_tile), op.b, op.scale, op.shift, act, out=out, z_out=z, keep_v=V)
         return out, (Ctx(x, z, out, act, WINO, V) if train else None)
 
+    def _wino_link_ok(self, op, nxt, xshape):
+        """Whether layer `op` (input shape xshape) hands its output to `nxt` in the transform domain.  Both take the Winograd path
+        with the mixed tiling; the successor keeps its V (its weight gradient then needs no x) and the backward takes op's ReLU
+        mask from z (the fused data-gradient epilogue of a BatchNorm layer), so nobody reads the activated output."""
+        tile = ops.winograd_tile(tuple(xshape))
+        oshape = tuple(xshape[:3]) + (op.wshape[3],)
+        return (self.winograd_chain and self.winograd_wgrad and self.fused_dgrad_epilogue and op.bn is not None and
+                tile == ops.TILE_MIXED and ops.winograd_chain_ok(tuple(xshape), op.wshape[3], tile) and
+                self._wino_ok(nxt, oshape) and ops.winograd_tile(oshape) == tile)
+
+    def _wino_chained_fwd(self, layers, x, act):
+        """Training forward of consecutive 3 x 3 layers, [(x, ctx) = _wino_fwd(op, x, act, True) or op.forward(...)] with the layers
+        that _wino_link_ok allows linked: a linked layer writes its successor's input transform V instead of its activated output,
+        so its context has out = None and its successor's x = None (and V always)."""
+        ctxs = []
+        shape, V = tuple(x.shape), None             # V: the current layer's input transform where the layer below wrote it
+        for i, op in enumerate(layers):
+            if V is None and not self._wino_ok(op, shape):
+                x, c = op.forward(x, act, train=True)
+                ctxs.append(c)
+                shape = tuple(x.shape)
+                continue
+            nxt = layers[i + 1] if i + 1 < len(layers) else None
+            oshape = shape[:3] + (op.wshape[3],)
+            ready = V is not None
+            U = self._wino_U(op, 0, shape)
+            z = ops.empty(oshape, torch.float32, self.dev) if op.bn else None
+            if not ready and self.winograd_wgrad:
+                V = ops.empty((ops.winograd_v_floats(shape),), torch.float32, self.dev)
+            if nxt is not None and self._wino_link_ok(op, nxt, shape):
+                Vn = ops.empty((ops.winograd_v_floats(oshape),), torch.float32, self.dev)
+                out = ops.conv2d_winograd_chain(shape if ready else x, U, Vn, op.b, op.scale, op.shift, act, z_out=z, keep_v=V, v_ready=ready)
+            else:
+                Vn = None
+                out = ops.empty(oshape, torch.float32, self.dev)
+                ops.conv2d_winograd(shape if ready else x, U, op.b, op.scale, op.shift, act, out=out, z_out=z, keep_v=V, v_ready=ready)
+            ctxs.append(Ctx(x, z, out, act, WINO, V))
+            x, shape, V = out, oshape, Vn
+        return x, ctxs
+
     # ---- independent small convolutions in one launch (mrcnn_conv2d_fwd_multi) ------------------------
     def _forward_multi(self, layers, xs, act=ACT_NONE, train=False):
         """[ConvOp.forward(x, act) for layer, x in zip(layers, xs)] as one launch; falls back to the loop.  With trunk_winograd the
@@ -903,7 +946,9 @@ class MaskRCNNEngine(object):
             pooled = ops.roialign(rois, fms, cfg.MASK_POOL_SIZE, image_area)
             x = pooled.view(B * R, cfg.MASK_POOL_SIZE, cfg.MASK_POOL_SIZE, -1)
         ctxs = []
-        if self.head_dtype is None:
+        if self.head_dtype is None and train:
+            x, ctxs = self._wino_chained_fwd([self.op("mrcnn_mask_conv%d" % i) for i in range(1, 5)], x, ACT_RELU)
+        elif self.head_dtype is None:
             for i in range(1, 5):
                 op = self.op("mrcnn_mask_conv%d" % i)
                 if self._wino_ok(op, x.shape):
@@ -1159,7 +1204,7 @@ class MaskRCNNEngine(object):
             dz = self._dgrad_ep(dzg, dc.wt, "valid", chain[0][0], chain[0][1])
             for k, (op, c) in enumerate(chain):
                 if c.V is not None:
-                    wgrad(partial(ops.conv2d_wgrad_winograd, c.V, tuple(c.x.shape), dz, op.dw), c.V, dz)
+                    wgrad(partial(ops.conv2d_wgrad_winograd, c.V, tuple(dz.shape[:3]) + (op.wshape[2],), dz, op.dw), c.V, dz)     # (c.x: None behind a linked layer)
                 else:
                     wgrad(partial(ops.conv2d_wgrad, c.x, dz, op.wshape, op.stride, op.padding, dw=op.dw), c.x, dz)
                 wino = c.path == WINO

@@ -1992,11 +1992,15 @@ def winograd_weights(w, out=None, tile=2):
     return out
 
 
-def _winograd_run(x, U, finish, keep_v=None, after_input=None):
+def _winograd_run(x, U, finish, keep_v=None, after_input=None, v_ready=False, finish_all=None):
     """Per tile group: input transform, the group's transform-domain GEMMs, then finish(group, Mt) -- the output transform the caller
     wants.  V of all groups lives in one flat buffer (keep_v: kept for the weight gradient), Mt is a per-stream scratch buffer
-    reused group after group (stream order)."""
-    N, H, W, Cin = x.shape
+    reused group after group (stream order).
+    v_ready: keep_v already holds the input transform (the layer below wrote it, conv2d_winograd_chain) and x is the input's SHAPE.
+    finish_all: the groups' GEMMs run first, each into its own part of an Mt that holds all groups end to end (as V does), then
+    finish_all(Mt) once; finish is not called."""
+    N, H, W, Cin = x if v_ready else x.shape
+    assert not v_ready or keep_v is not None
     tile = _wino_tile_of(U)
     Us = U if isinstance(U, (list, tuple)) else [U]
     cout = Us[0].shape[2]
@@ -2005,20 +2009,27 @@ def _winograd_run(x, U, finish, keep_v=None, after_input=None):
     nvs = [lib.mrcnn_winograd_group_floats(C.byref(g), N, Cin) for g in groups]
     nms = [lib.mrcnn_winograd_group_floats(C.byref(g), N, cout) for g in groups]
     nv = sum(nvs)
-    V = keep_v if keep_v is not None else workspace(nv * 4, x.device, "winograd_v")[:nv * 4].view(torch.float32)
+    dev = Us[0].device
+    V = keep_v if keep_v is not None else workspace(nv * 4, dev, "winograd_v")[:nv * 4].view(torch.float32)
     assert keep_v is None or (keep_v.numel() == nv and keep_v.dtype == torch.float32)
-    Mt = workspace(max(nms) * 4, x.device, "winograd_m")
-    off = 0
+    Mt = workspace((max(nms) if finish_all is None else sum(nms)) * 4, dev, "winograd_m")
+    off = moff = 0
     for gi, (g, u) in enumerate(zip(groups, Us)):
         Vg = V[off:off + nvs[gi]]
         off += nvs[gi]
-        check(lib.mrcnn_winograd_input_g(ptr(x), ptr(Vg), N, H, W, Cin, C.byref(g), current_stream()), "mrcnn_winograd_input_g")
+        if not v_ready:
+            check(lib.mrcnn_winograd_input_g(ptr(x), ptr(Vg), N, H, W, Cin, C.byref(g), current_stream()), "mrcnn_winograd_input_g")
         if gi == 0 and after_input is not None:
             after_input()                # e.g. an event: a second chain on another stream starts one transform behind this one
         nb = _wino_nb(g)
         rows = nvs[gi] // (nb * Cin)
-        check(lib.mrcnn_winograd_gemm(ptr(Vg), ptr(u), ptr(Mt), nb, rows, Cin, cout, current_stream()), "mrcnn_winograd_gemm")
-        finish(g, Mt)
+        check(lib.mrcnn_winograd_gemm(ptr(Vg), ptr(u), ptr(Mt) + moff * 4, nb, rows, Cin, cout, current_stream()), "mrcnn_winograd_gemm")
+        if finish_all is None:
+            finish(g, Mt)
+        else:
+            moff += nms[gi]
+    if finish_all is not None:
+        finish_all(Mt)
 
 
 def winograd_v_floats(xshape, tile=None):
@@ -2029,21 +2040,73 @@ def winograd_v_floats(xshape, tile=None):
     return sum(lib.mrcnn_winograd_group_floats(C.byref(g), N, Cin) for g in winograd_groups(H, W, tile))
 
 
-def conv2d_winograd(x, U, bias=None, scale=None, shift=None, act=ACT_NONE, out=None, z_out=None, keep_v=None, after_input=None):
-    """3 x 3 'same' stride-1 convolution with its epilogue through the Winograd domain (U = winograd_weights(w, tile=...))."""
-    _need_cuda(x, bias, scale, shift, out, z_out, keep_v)
-    N, H, W, _ = x.shape
-    cout = (U[0] if isinstance(U, (list, tuple)) else U).shape[2]
+def conv2d_winograd(x, U, bias=None, scale=None, shift=None, act=ACT_NONE, out=None, z_out=None, keep_v=None, after_input=None,
+                    v_ready=False):
+    """3 x 3 'same' stride-1 convolution with its epilogue through the Winograd domain (U = winograd_weights(w, tile=...)).
+    v_ready: keep_v already holds the input transform (conv2d_winograd_chain of the layer below wrote it) and x is the input's
+    shape: no input transform runs."""
+    _need_cuda(None if v_ready else x, bias, scale, shift, out, z_out, keep_v)
+    N, H, W, _ = x if v_ready else x.shape
+    U0 = U[0] if isinstance(U, (list, tuple)) else U
+    cout = U0.shape[2]
     if out is None:
-        out = empty((N, H, W, cout), torch.float32, x.device)
+        out = empty((N, H, W, cout), torch.float32, U0.device)
     lib = _hip.lib()
 
     def finish(g, Mt):
         check(lib.mrcnn_winograd_output_g(ptr(Mt), ptr(out), ptr(z_out), ptr(bias), ptr(scale), ptr(shift), N, H, W, cout, act, C.byref(g),
                                           current_stream()), "mrcnn_winograd_output_g")
 
-    _winograd_run(x, U, finish, keep_v, after_input)
+    _winograd_run(x, U, finish, keep_v, after_input, v_ready)
     return out
+
+
+def winograd_chain_ok(xshape, cout, tile):
+    """Layers conv2d_winograd_chain runs as one launch behind their GEMMs (mrcnn_winograd_chain's conditions): the mixed tiling,
+    channels in whole 128s, a map of at most 2048 pixels."""
+    _, H, W, _ = xshape
+    return tile == TILE_MIXED and H % 4 == 2 and W % 4 == 2 and H > 4 and W > 4 and cout % 128 == 0 and H * W <= 2048
+
+
+def conv2d_winograd_chain(x, U, next_v, bias=None, scale=None, shift=None, act=ACT_NONE, z_out=None, keep_v=None, v_ready=False):
+    """conv2d_winograd(x, U, ...) of a layer whose activated output has ONE reader, the input transform of the next 3 x 3 layer
+    (same tiling): the groups' GEMMs run first, into an Mt that holds all groups, then one launch applies the output transform and
+    the epilogue (z_out) and writes the next layer's input transform into next_v (winograd_v_floats of this layer's output shape) --
+    same bits as the separate launches; the activated output is not written.  The next layer runs as
+    conv2d_winograd(shape, U2, ..., keep_v=next_v, v_ready=True).  Returns None, or -- where the one-launch kernel refuses the shape
+    -- the activated output after the separate launches (output transforms, then the input transforms into next_v)."""
+    _need_cuda(None if v_ready else x, bias, scale, shift, z_out, keep_v, next_v)
+    N, H, W, _ = x if v_ready else x.shape
+    Us = U if isinstance(U, (list, tuple)) else [U]
+    cout = Us[0].shape[2]
+    tile = _wino_tile_of(U)
+    groups = winograd_groups(H, W, tile)
+    lib = _hip.lib()
+    nms = [lib.mrcnn_winograd_group_floats(C.byref(g), N, cout) for g in groups]
+    assert next_v.numel() == sum(nms) and next_v.dtype == torch.float32
+    res = []
+
+    def finish_all(Mt):
+        rc = lib.mrcnn_winograd_chain(ptr(Mt), ptr(z_out), ptr(bias), ptr(scale), ptr(shift), ptr(next_v), N, H, W, cout, act, tile,
+                                      current_stream())
+        if rc != ERR_UNSUPPORTED:
+            check(rc, "mrcnn_winograd_chain")
+            return
+        out = empty((N, H, W, cout), torch.float32, next_v.device)
+        off = 0
+        for g, nm in zip(groups, nms):
+            check(lib.mrcnn_winograd_output_g(ptr(Mt) + off * 4, ptr(out), ptr(z_out), ptr(bias), ptr(scale), ptr(shift), N, H, W, cout, act,
+                                              C.byref(g), current_stream()), "mrcnn_winograd_output_g")
+            off += nm
+        off = 0
+        for g, nm in zip(groups, nms):
+            check(lib.mrcnn_winograd_input_g(ptr(out), ptr(next_v) + off * 4, N, H, W, cout, C.byref(g), current_stream()),
+                  "mrcnn_winograd_input_g")
+            off += nm
+        res.append(out)
+
+    _winograd_run(x, U, None, keep_v, None, v_ready, finish_all)
+    return res[0] if res else None
 
 
 def conv2d_dgrad_ep_winograd(dz, Ut, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, act, fwd_shift=None):

@@ -982,6 +982,16 @@ int mrcnn_gemm_batched_f32(const float* V, const float* U, float* Mt, int nb, in
 int mrcnn_winograd_gemm(const float* V, const float* U, float* Mt, int nb, int rows, int K, int Cout, void* stream);
 int mrcnn_winograd_output_g(const float* Mt, float* out, float* z_out, const float* bias, const float* scale, const float* shift,
                             int N, int H, int W, int C, int act, const mrcnn_wino_group* g, void* stream);
+/* Two 3 x 3 layers in a row, mixed tiling (H, W = 2 mod 4, > 4: H/4 x W/4 tiles of 4 x 4, H/4 of 4 x 2, W/4 of 2 x 4, one 2 x 2): the
+ * output transform and epilogue of the first layer (mrcnn_winograd_output_g of all four groups: z_out = y + bias, stored unless
+ * NULL; activated = act(scale z + shift)) and the input transform of the second (mrcnn_winograd_input_g of all four groups) as ONE
+ * launch -- the activated output stays in LDS and is not written anywhere.  Mt and V_next hold the four groups end to end in the
+ * order above, each of mrcnn_winograd_group_floats(g, N, C) floats.  z_out and V_next equal the separate calls' bit for bit.
+ * MRCNN_ERR_UNSUPPORTED, nothing launched: another tiling (tile != MRCNN_WINO_TILE_MIXED), extents not 2 mod 4, C % 128 != 0, a
+ * map of more than 2048 pixels, a group of 4 GiB or more -- use the separate calls. */
+#define MRCNN_WINO_TILE_MIXED 6
+int mrcnn_winograd_chain(const float* Mt, float* z_out, const float* bias, const float* scale, const float* shift, float* V_next,
+                         int N, int H, int W, int C, int act, int tile, void* stream);
 /* Data gradient: output transform of a group + epilogue backward of the layer below: g = y * act'(out_below), dz_below = g * scale.
  * Channel sums (of g, of g (z_below - mean) rstd when mean / rstd are given, of dz) leave as partials: the launch writes
  * mrcnn_winograd_output_bwd_rows(g, N, C) rows of [3][C] floats (one per workgroup, plain stores; partials may be NULL: no sums).
