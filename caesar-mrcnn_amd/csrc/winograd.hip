@@ -258,6 +258,13 @@ __device__ __forceinline__ typename WinoVec<CV>::type wino_buffer_load(__amdgpu_
     }
     return r;
 }
+// its store twin (two floats)
+__device__ __forceinline__ void wino_buffer_store2(const WinoVec<2>::type v, __amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 d;
+    d[0] = __float_as_uint(v[0]); d[1] = __float_as_uint(v[1]);
+    __builtin_amdgcn_raw_buffer_store_b64(d, rsrc, (int)voff, (int)soff, 0);
+}
 
 // ---- the forward chain: output transform + epilogue of layer l and input transform of layer l + 1 in one pass ------------------
 // Mixed tiling only (H, W = 2 mod 4: a x b tiles of 4 x 4, a of 4 x 2, b of 2 x 4, one 2 x 2).  A workgroup owns ONE map and CS of its
@@ -558,6 +565,225 @@ __global__ __launch_bounds__(WINO_SUMS_COLS * WINO_SUMS_SLICES) void winograd_bw
         atomicAdd(&dst[j - k * C], v);
     }
 }
+
+// ---- the backward chain: the data gradient's output transform + epilogue backward of the layer below, and BOTH transforms of the
+// resulting dz -- the input transform for the next data gradient and the weight gradient's A dz A^T -- in one pass ----------------
+// winograd_chain_kernel's plan (mixed tiling, a workgroup = one map x CS channels, lane = channel pair).  Phase 1 is
+// winograd_output_bwd_kernel<.., MASK = 1>'s arithmetic, operation for operation, on the map's tiles of all four groups; dz stays in
+// LDS [H][W][CS] (and is stored when dz_out is given).  Phase 2 cuts both kinds of tiles from it: V = B^T dz B (zero halo) as
+// winograd_input_kernel writes it and dM = A dz A^T as winograd_dy_kernel does, four groups end to end at WinoChainGeo's offsets.
+// The channel sums stay in registers over both phases, meet in the map's LDS (free by then) in slot order and leave as the
+// workgroup's CS columns of row n of partials [N][3][C]: plain stores, every element written by exactly one workgroup, so
+// winograd_bwd_sums_kernel adds the N rows up as it does the per-workgroup rows of the separate launches.
+template <int OTH, int OTW, bool DZ>
+__device__ __forceinline__ void wino_bwd_chain_out_tile(__amdgpu_buffer_rsrc_t rsrc, unsigned mstride, unsigned t, int oh0, int ow0, int c,
+                                                        int cl, __amdgpu_buffer_rsrc_t rz, __amdgpu_buffer_rsrc_t rdz,
+                                                        const WinoVec<2>::type sc, const WinoVec<2>::type fsh, const WinoVec<2>::type mu,
+                                                        const WinoVec<2>::type rs, int want_dg, float* map, WinoVec<2>::type& a_db,
+                                                        WinoVec<2>::type& a_dg, WinoVec<2>::type& a_bias, int W, int C, int CS) {
+    typedef WinoVec<2>::type vec;
+    constexpr int ITH = OTH + 2, ITW = OTW + 2;
+    vec m[ITH][ITW], zz[OTH][OTW];
+    const unsigned moff = (t * (unsigned)C + (unsigned)c) * 4u;
+    const unsigned zoff = (unsigned)((oh0 * W + ow0) * C + c) * 4u;     // z: this map's; the outputs' offsets from the tile's first are uniform
+#pragma unroll
+    for (int r = 0; r < ITH; ++r)
+#pragma unroll
+        for (int k = 0; k < ITW; ++k) m[r][k] = wino_buffer_load<2>(rsrc, moff, (unsigned)(r * ITW + k) * mstride);
+#pragma unroll
+    for (int a = 0; a < OTH; ++a)
+#pragma unroll
+        for (int b = 0; b < OTW; ++b) zz[a][b] = wino_buffer_load<2>(rz, zoff, (unsigned)((a * W + b) * C) * 4u);
+    vec s[OTH][ITW];
+#pragma unroll
+    for (int k = 0; k < ITW; ++k) {              // A^T down the rows of every column k
+        vec col[ITH], o[OTH];
+#pragma unroll
+        for (int r = 0; r < ITH; ++r) col[r] = m[r][k];
+        wino_at<OTH>(col, o);
+#pragma unroll
+        for (int a = 0; a < OTH; ++a) s[a][k] = o[a];
+    }
+#pragma unroll
+    for (int a = 0; a < OTH; ++a) {
+        vec y[OTW];
+        wino_at<OTW>(s[a], y);
+#pragma unroll
+        for (int b = 0; b < OTW; ++b) {           // the mixed tiling has no overhang: every output lies inside the map
+            const int pix = (oh0 + a) * W + ow0 + b;
+            vec gg = y[b], dz;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const float v = sc[e] * zz[a][b][e] + fsh[e];
+                gg[e] = v > 0.f ? gg[e] : 0.f;
+                dz[e] = gg[e] * sc[e];
+            }
+            if (DZ) wino_buffer_store2(dz, rdz, zoff, (unsigned)((a * W + b) * C) * 4u);
+            *(vec*)(map + pix * CS + cl) = dz;
+            if (want_dg) {
+#pragma unroll
+                for (int e = 0; e < 2; ++e) a_dg[e] += gg[e] * (zz[a][b][e] - mu[e]) * rs[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 2; ++e) { a_db[e] += gg[e]; a_bias[e] += dz[e]; }
+        }
+    }
+}
+
+// Both transforms of the tile at (oh0, ow0), cut from the map with ONE read of its (OTH + 2) x (OTW + 2) window -- rows and columns
+// past the map's edge (the halo) read a row of CS zeros kept behind the map, so no read is conditional --: from the window's inner OTH x OTW values
+// dM = A d A^T in winograd_dy_kernel's sequence, from the whole window V = B^T d B in wino_chain_in_tile's.  Stores go through
+// one buffer resource per group: one address register per lane for all of a tile's matrices, as the loads of phase 1.
+template <int OTH, int OTW>
+__device__ __forceinline__ void wino_bwd_chain_cut_tile(const float* map, __amdgpu_buffer_rsrc_t rv, __amdgpu_buffer_rsrc_t rdm, bool want_dm,
+                                                        unsigned mstride, unsigned t, int oh0, int ow0, int c, int cl, int H, int W, int C,
+                                                        int CS) {
+    typedef WinoVec<2>::type vec;
+    constexpr int ITH = OTH + 2, ITW = OTW + 2;
+    const unsigned off = (t * (unsigned)C + (unsigned)c) * 4u;
+    const int zero = H * W * CS + cl;            // the row of zeros behind the map
+    int roff[ITH], coff[ITW];
+    bool rok[ITH], cok[ITW];
+#pragma unroll
+    for (int r = 0; r < ITH; ++r) {
+        const int ih = oh0 - 1 + r;
+        rok[r] = (unsigned)ih < (unsigned)H;
+        roff[r] = ih * W * CS;
+    }
+#pragma unroll
+    for (int s = 0; s < ITW; ++s) {
+        const int iw = ow0 - 1 + s;
+        cok[s] = (unsigned)iw < (unsigned)W;
+        coff[s] = iw * CS + cl;
+    }
+    vec d[ITH][ITW];
+#pragma unroll
+    for (int r = 0; r < ITH; ++r)
+#pragma unroll
+        for (int s = 0; s < ITW; ++s) d[r][s] = *(const vec*)(map + ((rok[r] && cok[s]) ? roff[r] + coff[s] : zero));
+    if (want_dm) {
+        vec u[ITH][OTW];
+#pragma unroll
+        for (int b = 0; b < OTW; ++b) {          // A down the rows of every output column b
+            vec col[OTH], o[ITH];
+#pragma unroll
+            for (int a = 0; a < OTH; ++a) col[a] = d[a + 1][b + 1];
+            wino_a<OTH>(col, o);
+#pragma unroll
+            for (int r = 0; r < ITH; ++r) u[r][b] = o[r];
+        }
+#pragma unroll
+        for (int r = 0; r < ITH; ++r) {          // (A d) A^T
+            vec m[ITW];
+            wino_a<OTW>(u[r], m);
+#pragma unroll
+            for (int k = 0; k < ITW; ++k) wino_buffer_store2(m[k], rdm, off, (unsigned)(r * ITW + k) * mstride);
+        }
+    }
+    vec tt[ITH][ITW];
+#pragma unroll
+    for (int s = 0; s < ITW; ++s) {              // columns of the tile: B^T applied down the rows
+        vec col[ITH], o[ITH];
+#pragma unroll
+        for (int r = 0; r < ITH; ++r) col[r] = d[r][s];
+        wino_bt<OTH>(col, o);
+#pragma unroll
+        for (int r = 0; r < ITH; ++r) tt[r][s] = o[r];
+    }
+#pragma unroll
+    for (int r = 0; r < ITH; ++r) {              // then along each row
+        vec v[ITW];
+        wino_bt<OTW>(tt[r], v);
+#pragma unroll
+        for (int s = 0; s < ITW; ++s) wino_buffer_store2(v[s], rv, off, (unsigned)(r * ITW + s) * mstride);
+    }
+}
+
+#define WINO_RSRC(p) __builtin_amdgcn_make_buffer_rsrc((void*)(p), 0, 0xFFFFFFF0u, 0x00020000)
+template <bool DZ>
+__global__ __launch_bounds__(256, 3) void winograd_bwd_chain_kernel(const float* __restrict__ Mt, const float* __restrict__ below_z,
+                                                                 const float* __restrict__ scale, const float* __restrict__ fwd_shift,
+                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                 float* __restrict__ partials, float* __restrict__ V,
+                                                                 float* __restrict__ dM, float* __restrict__ dz_out, int H, int W, int C,
+                                                                 int lg, const WinoChainGeo geo) {
+    typedef WinoVec<2>::type vec;
+    extern __shared__ __attribute__((aligned(16))) float wino_bwd_chain_map[];     // [H * W + 1][CS], the last row zeros; afterwards the sums [3][slots][CS]
+    float* map = wino_bwd_chain_map;
+    const int L = 1 << lg, CS = 2 << lg, slots = 256 >> lg;
+    const int slices = C / CS;
+    const int n = (int)(blockIdx.x / (unsigned)slices), slice = (int)(blockIdx.x - (unsigned)n * slices);
+    const int slot = threadIdx.x >> lg, cl = (threadIdx.x & (L - 1)) * 2;
+    const int c = slice * CS + cl;
+    const int a = geo.a, b = geo.b, n0 = a * b, per_map = n0 + a + b + 1;
+    const int want_dg = partials && mean;
+    const bool want_dm = dM != nullptr;
+    const unsigned cb = (unsigned)C * 4u;
+    vec a_db = {}, a_dg = {}, a_bias = {};
+    if (slot == 0) *(vec*)(map + H * W * CS + cl) = vec{};
+    {
+        const vec sc = *(const vec*)(scale + c), fsh = *(const vec*)(fwd_shift + c);
+        vec mu = {}, rs = {};
+        if (want_dg) { mu = *(const vec*)(mean + c); rs = *(const vec*)(rstd + c); }
+        // one descriptor per group, made where the base is plainly uniform (the host checks that every group fits 4 GiB); z and dz:
+        // this map's (<= 2048 pixels: 32-bit offsets inside it)
+        const long long mapoff = (long long)n * H * W * C;
+        const __amdgpu_buffer_rsrc_t rz = WINO_RSRC(below_z + mapoff), rdz = WINO_RSRC(dz_out + mapoff);
+        for (int it = slot; it < per_map; it += slots) {
+            if (it < n0) {
+                const int th = it / b, tw = it - th * b;
+                wino_bwd_chain_out_tile<4, 4, DZ>(WINO_RSRC(Mt + geo.off[0]), geo.tp[0] * cb, (unsigned)n * n0 + it, 4 * th, 4 * tw, c, cl, rz, rdz, sc,
+                                                  fsh, mu, rs, want_dg, map, a_db, a_dg, a_bias, W, C, CS);
+            } else if (it < n0 + a) {
+                const int th = it - n0;
+                wino_bwd_chain_out_tile<4, 2, DZ>(WINO_RSRC(Mt + geo.off[1]), geo.tp[1] * cb, (unsigned)n * a + th, 4 * th, W - 2, c, cl, rz, rdz, sc,
+                                                  fsh, mu, rs, want_dg, map, a_db, a_dg, a_bias, W, C, CS);
+            } else if (it < n0 + a + b) {
+                const int tw = it - n0 - a;
+                wino_bwd_chain_out_tile<2, 4, DZ>(WINO_RSRC(Mt + geo.off[2]), geo.tp[2] * cb, (unsigned)n * b + tw, H - 2, 4 * tw, c, cl, rz, rdz, sc,
+                                                  fsh, mu, rs, want_dg, map, a_db, a_dg, a_bias, W, C, CS);
+            } else {
+                wino_bwd_chain_out_tile<2, 2, DZ>(WINO_RSRC(Mt + geo.off[3]), geo.tp[3] * cb, (unsigned)n, H - 2, W - 2, c, cl, rz, rdz, sc, fsh, mu,
+                                                  rs, want_dg, map, a_db, a_dg, a_bias, W, C, CS);
+            }
+        }
+    }
+    __syncthreads();
+    for (int it = slot; it < per_map; it += slots) {
+        if (it < n0) {
+            const int th = it / b, tw = it - th * b;
+            wino_bwd_chain_cut_tile<4, 4>(map, WINO_RSRC(V + geo.off[0]), WINO_RSRC(dM + geo.off[0]), want_dm, geo.tp[0] * cb, (unsigned)n * n0 + it,
+                                          4 * th, 4 * tw, c, cl, H, W, C, CS);
+        } else if (it < n0 + a) {
+            const int th = it - n0;
+            wino_bwd_chain_cut_tile<4, 2>(map, WINO_RSRC(V + geo.off[1]), WINO_RSRC(dM + geo.off[1]), want_dm, geo.tp[1] * cb, (unsigned)n * a + th,
+                                          4 * th, W - 2, c, cl, H, W, C, CS);
+        } else if (it < n0 + a + b) {
+            const int tw = it - n0 - a;
+            wino_bwd_chain_cut_tile<2, 4>(map, WINO_RSRC(V + geo.off[2]), WINO_RSRC(dM + geo.off[2]), want_dm, geo.tp[2] * cb, (unsigned)n * b + tw,
+                                          H - 2, 4 * tw, c, cl, H, W, C, CS);
+        } else {
+            wino_bwd_chain_cut_tile<2, 2>(map, WINO_RSRC(V + geo.off[3]), WINO_RSRC(dM + geo.off[3]), want_dm, geo.tp[3] * cb, (unsigned)n, H - 2,
+                                          W - 2, c, cl, H, W, C, CS);
+        }
+    }
+    if (!partials) return;
+    __syncthreads();                                            // the map has been read: its LDS takes the sums, 3 * 256 * 2 floats
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        map[(0 * slots + slot) * CS + cl + e] = a_db[e];
+        map[(1 * slots + slot) * CS + cl + e] = a_dg[e];
+        map[(2 * slots + slot) * CS + cl + e] = a_bias[e];
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < 3 * CS; j += 256) {
+        const int k = j / CS, cc = j - k * CS;
+        float v = map[k * slots * CS + cc];
+        for (int r = 1; r < slots; ++r) v += map[(k * slots + r) * CS + cc];
+        partials[((long long)n * 3 + k) * C + slice * CS + cc] = v;
+    }
+}
+#undef WINO_RSRC
 
 // Weight gradient through the same domain: dU[xi] = V[xi]^T . dM[xi] (ITH * ITW GEMMs contracting over the tiles: 1 x 1 weight
 // gradients for the float32 weight-gradient kernel), with V = B^T d B the forward's input transform (kept from the forward
@@ -860,30 +1086,40 @@ static int wino_chain_slice(int H, int W) {
     return (long long)H * W * 8 * 4 <= 64 * 1024 ? 8 : 0;
 }
 
-extern "C" int mrcnn_winograd_chain(const float* Mt, float* z_out, const float* bias, const float* scale, const float* shift, float* V_next,
-                                    int N, int H, int W, int C, int act, int tile, void* stream) {
-    if (!Mt || !V_next || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (scale && !shift)) return MRCNN_ERR_ARG;
-    if (act != MRCNN_ACT_NONE && act != MRCNN_ACT_RELU) return MRCNN_ERR_UNSUPPORTED;
+// the shapes both chain kernels take, and their launch geometry: channel slice cs, lg = log2(lanes per tile), workgroups
+static int wino_chain_plan(int N, int H, int W, int C, int tile, WinoChainGeo* geo, int* cs_out, int* lg_out, long long* wgs_out) {
     if (tile != MRCNN_WINO_TILE_MIXED || H % 4 != 2 || W % 4 != 2 || H <= 4 || W <= 4 || C % 128) return MRCNN_ERR_UNSUPPORTED;
     const int cs = wino_chain_slice(H, W);
     if (!cs) return MRCNN_ERR_UNSUPPORTED;
-    WinoChainGeo geo;
-    geo.a = H / 4; geo.b = W / 4;
-    const long long tiles[4] = {(long long)N * geo.a * geo.b, (long long)N * geo.a, (long long)N * geo.b, N};
+    geo->a = H / 4; geo->b = W / 4;
+    const long long tiles[4] = {(long long)N * geo->a * geo->b, (long long)N * geo->a, (long long)N * geo->b, N};
     const int nb[4] = {36, 24, 24, 16};
     long long off = 0;
     for (int i = 0; i < 4; ++i) {
         const long long tp = wino_rows(tiles[i]);
         // tile ids and the byte offsets into a group's matrices are 32-bit
         if (tiles[i] >= (1LL << 31) || nb[i] * tp * C * 4 >= (1LL << 32)) return MRCNN_ERR_UNSUPPORTED;
-        geo.tp[i] = (unsigned)tp;
-        geo.off[i] = off;
+        geo->tp[i] = (unsigned)tp;
+        geo->off[i] = off;
         off += nb[i] * tp * C;
     }
     const long long wgs = (long long)N * (C / cs);
     if (wgs >= (1LL << 31)) return MRCNN_ERR_UNSUPPORTED;
     int lg = 0;
     while ((2 << lg) < cs) ++lg;                                // lanes per tile = cs / 2
+    *cs_out = cs; *lg_out = lg; *wgs_out = wgs;
+    return MRCNN_OK;
+}
+
+extern "C" int mrcnn_winograd_chain(const float* Mt, float* z_out, const float* bias, const float* scale, const float* shift, float* V_next,
+                                    int N, int H, int W, int C, int act, int tile, void* stream) {
+    if (!Mt || !V_next || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (scale && !shift)) return MRCNN_ERR_ARG;
+    if (act != MRCNN_ACT_NONE && act != MRCNN_ACT_RELU) return MRCNN_ERR_UNSUPPORTED;
+    WinoChainGeo geo;
+    int cs, lg;
+    long long wgs;
+    const int rc = wino_chain_plan(N, H, W, C, tile, &geo, &cs, &lg, &wgs);
+    if (rc != MRCNN_OK) return rc;
     hipLaunchKernelGGL(winograd_chain_kernel, dim3((unsigned)wgs), dim3(256), (size_t)H * W * cs * 4, (hipStream_t)stream, Mt, z_out, bias, scale,
                        shift, V_next, H, W, C, act, lg, geo);
     return mrcnn_launch_status();
@@ -958,6 +1194,30 @@ extern "C" int mrcnn_winograd_output_bwd_sums(const float* partials, int rows, i
     const dim3 grid((unsigned)cdiv64(3LL * C, WINO_SUMS_COLS));
     hipLaunchKernelGGL(winograd_bwd_sums_kernel, grid, dim3(WINO_SUMS_COLS * WINO_SUMS_SLICES), 0, (hipStream_t)stream, partials, rows, C,
                        dgamma, dbeta, dbias);
+    return mrcnn_launch_status();
+}
+
+// ---- backward chain: the four output transforms + epilogue backward, and the input and dy transforms of that dz, one launch -------
+extern "C" int mrcnn_winograd_bwd_chain(const float* Mt, const float* below_z, const float* scale, const float* shift, const float* mean,
+                                        const float* rstd, float* partials, float* V_next, float* dM, float* dz_out, int N, int H, int W,
+                                        int C, int tile, void* stream) {
+    if (!Mt || !V_next || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (!mean != !rstd)) return MRCNN_ERR_ARG;
+    if (!below_z || !scale || !shift) return MRCNN_ERR_UNSUPPORTED;     // no activation below / mask from the activated output: the separate launches
+    WinoChainGeo geo;
+    int cs, lg;
+    long long wgs;
+    const int rc = wino_chain_plan(N, H, W, C, tile, &geo, &cs, &lg, &wgs);
+    if (rc != MRCNN_OK) return rc;
+    if ((long long)N * 3 * C >= (1LL << 31)) return MRCNN_ERR_UNSUPPORTED;
+    size_t lds = ((size_t)H * W + 1) * cs * 4;                                     // the map and a row of zeros for the halo (<= 53.25 KiB: three per CU)
+    if (lds > 64 * 1024) return MRCNN_ERR_UNSUPPORTED;
+    if (lds < 3 * 256 * 2 * sizeof(float)) lds = 3 * 256 * 2 * sizeof(float);     // the channel sums meet in the map's place
+    if (dz_out)
+        hipLaunchKernelGGL(winograd_bwd_chain_kernel<true>, dim3((unsigned)wgs), dim3(256), lds, (hipStream_t)stream, Mt, below_z, scale, shift, mean,
+                           rstd, partials, V_next, dM, dz_out, H, W, C, lg, geo);
+    else
+        hipLaunchKernelGGL(winograd_bwd_chain_kernel<false>, dim3((unsigned)wgs), dim3(256), lds, (hipStream_t)stream, Mt, below_z, scale, shift, mean,
+                           rstd, partials, V_next, dM, dz_out, H, W, C, lg, geo);
     return mrcnn_launch_status();
 }
 

@@ -69,6 +69,10 @@ SWITCHES = (
     # training mask head: a layer's output transform, epilogue and the next layer's input transform in one launch; the activated
     # output in between is not written (ops.conv2d_winograd_chain).  False: the separate launches (A/B)
     ("winograd_chain", "MRCNN_WINOGRAD_CHAIN", True, _on, "t"),
+    # its backward twin: the data gradient's output transform + epilogue backward and BOTH transforms of that dz (the next data
+    # gradient's input transform, the weight gradient's A dz A^T) in one launch; dz in between is not written
+    # (ops.conv2d_dgrad_ep_winograd's chain form).  False: the separate launches (A/B)
+    ("winograd_bwd_chain", "MRCNN_WINOGRAD_BWD_CHAIN", True, _on, "t"),
     # the trunk's large 3x3 layers (FPN smoothing, RPN shared convolution on levels of >= trunk_winograd_min_rows pixels)
     # through F(2x2, 3x3) in the forward pass (A/B switch, see DESIGN 4.1e for the measurement)
     ("trunk_winograd", "MRCNN_WINOGRAD_TRUNK", True, _on, "ti"),
@@ -607,6 +611,16 @@ class MaskRCNNEngine(object):
         return (self.winograd_chain and self.winograd_wgrad and self.fused_dgrad_epilogue and op.bn is not None and
                 tile == ops.TILE_MIXED and ops.winograd_chain_ok(tuple(xshape), op.wshape[3], tile) and
                 self._wino_ok(nxt, oshape) and ops.winograd_tile(oshape) == tile)
+
+    def _wino_bwd_link_ok(self, ctx, below, bctx, shape, bshape):
+        """Whether the data gradient of a layer (context ctx, its dz of `shape`) hands dz of the layer `below` (of bshape) on in the
+        transform domain only.  Both layers ran the Winograd path with the mixed tiling, the layer below has BatchNorm and ReLU with
+        a kept z (its mask comes from z) and kept its forward V (its weight gradient takes A dz A^T as it is), so dz has exactly
+        two readers, both transforms of it."""
+        tile = ops.winograd_tile(shape)
+        return (self.winograd_bwd_chain and self.fused_dgrad_epilogue and ctx.path == WINO and bctx.path == WINO and
+                below.bn is not None and bctx.act == ACT_RELU and bctx.z is not None and bctx.V is not None and
+                tile == ops.TILE_MIXED and ops.winograd_tile(bshape) == tile and ops.winograd_chain_ok(shape, bshape[3], tile))
 
     def _wino_chained_fwd(self, layers, x, act):
         """Training forward of consecutive 3 x 3 layers, [(x, ctx) = _wino_fwd(op, x, act, True) or op.forward(...)] with the layers
@@ -1202,24 +1216,42 @@ class MaskRCNNEngine(object):
             # every data-gradient convolution applies the epilogue backward of the layer below in its own epilogue
             # (mrcnn_conv2d_dgrad_ep): the gradient w.r.t. the activated output is never written or re-read
             dz = self._dgrad_ep(dzg, dc.wt, "valid", chain[0][0], chain[0][1])
+            # behind a linked boundary (_wino_bwd_link_ok) a layer's dz exists only as its two transforms: Vd = B^T dz B for its
+            # data gradient, dM = A dz A^T for its weight gradient (written on this stream, read on the weight-gradient stream:
+            # arena tensors, operands of the fork); dz is then None and `shape` stands for it
+            shape, Vd, dM = tuple(dz.shape), None, None
             for k, (op, c) in enumerate(chain):
-                if c.V is not None:
-                    wgrad(partial(ops.conv2d_wgrad_winograd, c.V, tuple(dz.shape[:3]) + (op.wshape[2],), dz, op.dw), c.V, dz)     # (c.x: None behind a linked layer)
+                if dM is not None:
+                    wgrad(partial(ops.conv2d_wgrad_winograd, c.V, shape[:3] + (op.wshape[2],), shape, op.dw, dm_ready=dM), c.V, dM)
+                elif c.V is not None:
+                    wgrad(partial(ops.conv2d_wgrad_winograd, c.V, shape[:3] + (op.wshape[2],), dz, op.dw), c.V, dz)     # (c.x: None behind a linked layer)
                 else:
                     wgrad(partial(ops.conv2d_wgrad, c.x, dz, op.wshape, op.stride, op.padding, dw=op.dw), c.x, dz)
                 wino = c.path == WINO
+                ready = Vd is not None
+                src = shape if ready else dz
+                assert wino or not ready
                 if k + 1 < len(chain):
                     below, bctx = chain[k + 1]
+                    bshape = shape[:3] + (op.wshape[2],)
                     if wino and self.fused_dgrad_epilogue and below.bn is not None:
-                        dz = ops.conv2d_dgrad_ep_winograd(dz, self._wino_U(op, 1, dz.shape), bctx.out if bctx.act != ACT_NONE else None,
+                        Vn = dMn = None
+                        if self._wino_bwd_link_ok(c, below, bctx, shape, bshape):
+                            nv = ops.winograd_v_floats(bshape)
+                            Vn, dMn = ops.empty((nv,), torch.float32, self.dev), ops.empty((nv,), torch.float32, self.dev)
+                        dz = ops.conv2d_dgrad_ep_winograd(src, self._wino_U(op, 1, shape), bctx.out if bctx.act != ACT_NONE else None,
                                                           bctx.z, below.scale, below.mean, below.rstd, below.dgamma, below.dbeta,
-                                                          below.db, bctx.act, fwd_shift=below.shift)
+                                                          below.db, bctx.act, fwd_shift=below.shift, next_v=Vn, next_dm=dMn,
+                                                          keep_v=Vd, v_ready=ready)
+                        Vd, dM = Vn, dMn
                     elif wino:
-                        dz = below.epilogue_bwd(ops.conv2d_winograd(dz, self._wino_U(op, 1, dz.shape)), bctx)[0]
+                        dz = below.epilogue_bwd(ops.conv2d_winograd(src, self._wino_U(op, 1, shape), keep_v=Vd, v_ready=ready), bctx)[0]
+                        Vd = dM = None
                     else:
                         dz = self._dgrad_ep(dz, op.wt, op.dgrad_padding, below, bctx)
+                    shape = bshape
                 elif wino:
-                    d = ops.conv2d_winograd(dz, self._wino_U(op, 1, dz.shape))
+                    d = ops.conv2d_winograd(src, self._wino_U(op, 1, shape), keep_v=Vd, v_ready=ready)
                 else:
                     d = op.dgrad(dz, c)
         else:

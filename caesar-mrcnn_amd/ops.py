@@ -2109,55 +2109,112 @@ def conv2d_winograd_chain(x, U, next_v, bias=None, scale=None, shift=None, act=A
     return res[0] if res else None
 
 
-def conv2d_dgrad_ep_winograd(dz, Ut, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, act, fwd_shift=None):
+def conv2d_dgrad_ep_winograd(dz, Ut, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, act, fwd_shift=None,
+                             next_v=None, next_dm=None, dz_out=None, keep_v=None, v_ready=False, mt_ready=None):
     """Data gradient of a 3 x 3 'same' convolution (Ut = winograd_weights of the flipped / transposed kernel) fused with the
     epilogue backward of the layer below: returns dz_below, channel sums are added to dgamma / dbeta / dbias.
     fwd_shift: the shift of the layer below's forward epilogue out = max(scale * z + shift, 0) -- with it (and z, scale) the ReLU
-    mask is recomputed from z, bit for bit the forward's decision, and below_out is not read (18 % of the pass's bytes)."""
-    _need_cuda(dz, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, fwd_shift)
-    N, H, W, _ = dz.shape
-    cout = (Ut[0] if isinstance(Ut, (list, tuple)) else Ut).shape[2]
-    out = empty((N, H, W, cout), torch.float32, dz.device)
+    mask is recomputed from z, bit for bit the forward's decision, and below_out is not read (18 % of the pass's bytes).
+    The chain form (next_v given: winograd_v_floats of dz_below's shape): dz_below has two readers, both transforms of it -- the
+    input transform of the NEXT data gradient and A dz A^T of the layer below's weight gradient.  The groups' GEMMs run first into
+    an Mt that holds all groups, then one launch (mrcnn_winograd_bwd_chain) applies the output transforms and the epilogue backward
+    and writes both transforms, into next_v and next_dm (same size; None: not wanted) -- same bits as the separate launches;
+    dz_below itself is stored only into dz_out (None: not at all).  The next data gradient then runs with its dz a SHAPE,
+    keep_v=next_v, v_ready=True, the weight gradient as conv2d_wgrad_winograd(..., dm_ready=next_dm).  Returns dz_out, or --
+    where the one-launch kernel refuses the shape or the epilogue -- dz_below after the separate launches (output transforms,
+    then the input and dy transforms into next_v / next_dm).
+    keep_v / v_ready: this data gradient's own input transform, written by the chain form of the layer above.
+    mt_ready (chain form only): the transform-domain product Mt of all groups end to end, made by the caller -- no input transform
+    and no GEMM runs, dz is a SHAPE and Ut only says the tiling and the channel count (the transforms take any channel count in
+    whole 4s; the GEMM of this module wants whole 128s)."""
+    assert mt_ready is None or next_v is not None
+    v_ready = v_ready or mt_ready is not None
+    _need_cuda(mt_ready, None if v_ready else dz, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, fwd_shift, next_v, next_dm, dz_out, keep_v)
+    N, H, W, _ = dz if v_ready else dz.shape
+    U0 = Ut[0] if isinstance(Ut, (list, tuple)) else Ut
+    cout, dev = U0.shape[2], U0.device
+    tile = _wino_tile_of(Ut)
+    groups = winograd_groups(H, W, tile)
     lib = _hip.lib()
     zmask = act == ACT_RELU and fwd_shift is not None and below_z is not None and scale is not None
     if dgamma is None:
         mean = rstd = None
     # channel sums: every group's workgroups write one row of partials [3][cout] each into one per-stream buffer, group after
-    # group; one launch after the last group adds the rows up (fixed order) onto dgamma / dbeta / dbias
+    # group (the chain form: one row per map); one launch after the last group adds the rows up (fixed order) onto dgamma /
+    # dbeta / dbias
     want_sums = dgamma is not None or dbeta is not None or dbias is not None
-    rows = [lib.mrcnn_winograd_output_bwd_rows(C.byref(g), N, cout) for g in winograd_groups(H, W, _wino_tile_of(Ut))]
+    rows = [lib.mrcnn_winograd_output_bwd_rows(C.byref(g), N, cout) for g in groups]
     assert min(rows) > 0, "channel count does not fit the Winograd data-gradient transform"
-    part = ptr(workspace(sum(rows) * 3 * cout * 4, dz.device, "winograd_bwd_sums")) if want_sums else None
+    chain = next_v is not None
+    part = ptr(workspace(max(sum(rows), N if chain else 0) * 3 * cout * 4, dev, "winograd_bwd_sums")) if want_sums else None
     done = []
+    res = []
 
-    def finish(g, Mt):
+    def finish(g, Mt, out, moff=0):
         p = None
         if want_sums:
             p = part + sum(done) * 3 * cout * 4
             done.append(rows[len(done)])
         if zmask:
-            check(lib.mrcnn_winograd_output_bwd_zmask_g(ptr(Mt), ptr(out), ptr(below_z), ptr(scale), ptr(fwd_shift), ptr(mean), ptr(rstd),
-                                                        p, N, H, W, cout, C.byref(g), current_stream()),
+            check(lib.mrcnn_winograd_output_bwd_zmask_g(ptr(Mt) + moff * 4, ptr(out), ptr(below_z), ptr(scale), ptr(fwd_shift), ptr(mean),
+                                                        ptr(rstd), p, N, H, W, cout, C.byref(g), current_stream()),
                   "mrcnn_winograd_output_bwd_zmask_g")
             return
-        check(lib.mrcnn_winograd_output_bwd_g(ptr(Mt), ptr(out), ptr(below_out), ptr(below_z), ptr(scale), ptr(mean), ptr(rstd),
+        check(lib.mrcnn_winograd_output_bwd_g(ptr(Mt) + moff * 4, ptr(out), ptr(below_out), ptr(below_z), ptr(scale), ptr(mean), ptr(rstd),
                                               p, N, H, W, cout, act, C.byref(g), current_stream()),
               "mrcnn_winograd_output_bwd_g")
 
-    _winograd_run(dz, Ut, finish)
+    def finish_all(Mt):
+        nms = [lib.mrcnn_winograd_group_floats(C.byref(g), N, cout) for g in groups]
+        assert next_v.numel() == sum(nms) and next_v.dtype == torch.float32
+        assert next_dm is None or (next_dm.numel() == sum(nms) and next_dm.dtype == torch.float32)
+        rc = ERR_UNSUPPORTED
+        if zmask:
+            rc = lib.mrcnn_winograd_bwd_chain(ptr(Mt), ptr(below_z), ptr(scale), ptr(fwd_shift), ptr(mean), ptr(rstd), part, ptr(next_v),
+                                              ptr(next_dm), ptr(dz_out), N, H, W, cout, tile, current_stream())
+        if rc != ERR_UNSUPPORTED:
+            check(rc, "mrcnn_winograd_bwd_chain")
+            done.append(N)
+            res.append(dz_out)
+            return
+        out = dz_out if dz_out is not None else empty((N, H, W, cout), torch.float32, dev)
+        off = 0
+        for g, nm in zip(groups, nms):
+            finish(g, Mt, out, off)
+            off += nm
+        off = 0
+        for g, nm in zip(groups, nms):
+            check(lib.mrcnn_winograd_input_g(ptr(out), ptr(next_v) + off * 4, N, H, W, cout, C.byref(g), current_stream()),
+                  "mrcnn_winograd_input_g")
+            if next_dm is not None:
+                check(lib.mrcnn_winograd_dy_g(ptr(out), ptr(next_dm) + off * 4, N, H, W, cout, C.byref(g), current_stream()),
+                      "mrcnn_winograd_dy_g")
+            off += nm
+        res.append(out)
+
+    if mt_ready is not None:
+        finish_all(mt_ready)
+    elif chain:
+        _winograd_run(dz, Ut, None, keep_v, None, v_ready, finish_all)
+    else:
+        assert dz_out is None or tuple(dz_out.shape) == (N, H, W, cout)
+        res.append(dz_out if dz_out is not None else empty((N, H, W, cout), torch.float32, dev))
+        _winograd_run(dz, Ut, lambda g, Mt: finish(g, Mt, res[0]), keep_v, None, v_ready)
     if want_sums:
         check(lib.mrcnn_winograd_output_bwd_sums(part, sum(done), cout, ptr(dgamma), ptr(dbeta), ptr(dbias), current_stream()),
               "mrcnn_winograd_output_bwd_sums")
-    return out
+    return res[0]
 
 
-def conv2d_wgrad_winograd(V, xshape, dz, dw, accumulate=False, tile=None):
+def conv2d_wgrad_winograd(V, xshape, dz, dw, accumulate=False, tile=None, dm_ready=None):
     """Weight gradient of a 3 x 3 'same' convolution through the Winograd domain: V = the forward's input transform of x
     (conv2d_winograd(..., keep_v=V)), dz [N, H, W, Cout] -> dw [3, 3, Cin, Cout] float32.  tile: the forward's (default:
-    winograd_tile(xshape), what the forward chose for this shape)."""
-    _need_cuda(V, dz, dw)
+    winograd_tile(xshape), what the forward chose for this shape).
+    dm_ready: A dz A^T of all groups end to end, as the chain form of conv2d_dgrad_ep_winograd wrote it (next_dm): no transform of
+    dz runs, and dz may be its SHAPE."""
+    _need_cuda(V, None if dm_ready is not None else dz, dw, dm_ready)
     N, H, W, Cin = xshape
-    cout = dz.shape[3]
+    cout = (dz if isinstance(dz, (tuple, list)) else dz.shape)[3]
     if tile is None:
         tile = winograd_tile(xshape)
     groups = winograd_groups(H, W, tile)
@@ -2165,16 +2222,21 @@ def conv2d_wgrad_winograd(V, xshape, dz, dw, accumulate=False, tile=None):
     nvs = [lib.mrcnn_winograd_group_floats(C.byref(g), N, Cin) for g in groups]
     nms = [lib.mrcnn_winograd_group_floats(C.byref(g), N, cout) for g in groups]
     assert V.numel() == sum(nvs), "V was made with another tiling"
-    dM_all = workspace(max(nms) * 4, dz.device, "winograd_dm")
-    dU_all = workspace(36 * Cin * cout * 4, dz.device, "winograd_du")
-    off = 0
+    assert dm_ready is None or (dm_ready.numel() == sum(nms) and dm_ready.dtype == torch.float32), "dM was made with another tiling"
+    dM_all = workspace(max(nms) * 4, V.device, "winograd_dm") if dm_ready is None else None
+    dU_all = workspace(36 * Cin * cout * 4, V.device, "winograd_du")
+    off = moff = 0
     for gi, g in enumerate(groups):
         nb = _wino_nb(g)
         rows = nms[gi] // (nb * cout)
         T = N * g.th_n * g.tw_n
-        dM = dM_all[:nms[gi] * 4].view(torch.float32).view(nb, rows, cout)
         dU = dU_all[:nb * Cin * cout * 4].view(torch.float32).view(nb, Cin, cout)
-        check(lib.mrcnn_winograd_dy_g(ptr(dz), ptr(dM), N, H, W, cout, C.byref(g), current_stream()), "mrcnn_winograd_dy_g")
+        if dm_ready is None:
+            dM = dM_all[:nms[gi] * 4].view(torch.float32).view(nb, rows, cout)
+            check(lib.mrcnn_winograd_dy_g(ptr(dz), ptr(dM), N, H, W, cout, C.byref(g), current_stream()), "mrcnn_winograd_dy_g")
+        else:
+            dM = dm_ready[moff:moff + nms[gi]].view(nb, rows, cout)
+            moff += nms[gi]
         Vv = V[off:off + nvs[gi]].view(nb, rows, Cin)
         off += nvs[gi]
         items = [(Vv[k, :T].view(T, 1, 1, Cin), dM[k, :T].view(T, 1, 1, cout), (1, 1, Cin, cout), 1, "valid", dU[k].view(1, 1, Cin, cout), False)

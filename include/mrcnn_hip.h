@@ -1007,6 +1007,17 @@ int mrcnn_winograd_output_bwd_zmask_g(const float* Mt, float* dz_below, const fl
                                       const float* mean, const float* rstd, float* partials, int N, int H, int W, int C,
                                       const mrcnn_wino_group* g, void* stream);
 int mrcnn_winograd_output_bwd_sums(const float* partials, int rows, int C, float* dgamma, float* dbeta, float* dbias, void* stream);
+/* The backward twin of mrcnn_winograd_chain, between the data gradients of two 3 x 3 layers (mixed tiling): ONE launch does
+ * mrcnn_winograd_output_bwd_zmask_g of all four groups (Mt: the groups end to end), and from the dz it keeps in LDS both
+ * mrcnn_winograd_input_g (V_next, for the next data gradient) and mrcnn_winograd_dy_g (dM, for the weight gradient of the layer
+ * below) of all four groups, end to end as Mt.  dM may be NULL (not written); dz_out may be NULL, else dz is stored too.  dz, V_next
+ * and dM equal the separate calls' bit for bit.  partials (may be NULL: no sums): N rows of [3][C], one per map, plain stores;
+ * mrcnn_winograd_output_bwd_sums(partials, N, C, ...) adds them up.
+ * MRCNN_ERR_UNSUPPORTED, nothing launched: the shapes mrcnn_winograd_chain refuses, or a layer below without z / scale / shift
+ * (no ReLU mask from z) -- use the separate calls. */
+int mrcnn_winograd_bwd_chain(const float* Mt, const float* below_z, const float* scale, const float* shift, const float* mean,
+                             const float* rstd, float* partials, float* V_next, float* dM, float* dz_out, int N, int H, int W, int C,
+                             int tile, void* stream);
 /* weight gradient: dM = A dy A^T (adjoint of the output transform) [(oth + 2)(otw + 2)][rows][C]; dU[xi] = V[xi]^T . dM[xi] are
  * 1 x 1 weight gradients (mrcnn_conv2d_wgrad on the first `tiles` rows of each matrix); dW = G^T dU G (accumulate != 0: added to dW). */
 int mrcnn_winograd_dy_g(const float* dy, float* dM, int N, int H, int W, int C, const mrcnn_wino_group* g, void* stream);
