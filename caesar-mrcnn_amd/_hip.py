@@ -130,6 +130,12 @@ class DrawDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("H", "W", "scale", "n_planes", "n_items", "n_texts", "n_glyphs", "n_colours", "shaded", "pad")]
 
 
+class FitsChain(C.Structure):
+    """mrcnn_fits_chain (include/mrcnn_hip.h): the read_fits flags of mrcnn_fits_to_image / mrcnn_fits_tiles_to_image."""
+    _fields_ = [(n, C.c_int32) for n in ("zscale", "biascontrast", "normalize", "out_kind")] + [
+        ("zscale_contrasts", C.c_double * 3), ("bias", C.c_double), ("contrast", C.c_double)]
+
+
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 RES_NONE, RES_SAME, RES_UP2 = 0, 1, 2
 OUT_NHWC, OUT_DECONV2 = 0, 1
@@ -209,6 +215,10 @@ _SIGNATURES = {
     "mrcnn_fits_tiles_workspace": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
     "mrcnn_fits_tiles_to_rgb": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_double), _P, C.c_size_t, _P,
                                           C.c_size_t, _P]),
+    "mrcnn_fits_image_check": (C.c_int, [C.POINTER(FitsChain), C.c_int, C.c_int]),
+    "mrcnn_fits_to_image": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(FitsChain), _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "mrcnn_fits_tiles_to_image": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(FitsChain), _P, C.c_size_t, _P,
+                                            C.c_size_t, _P]),
     "mrcnn_mosaic_overview_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double]),
     "mrcnn_mosaic_overview_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "mrcnn_mosaic_overview": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.c_size_t, _P, C.c_size_t, _P]),

@@ -426,6 +426,318 @@ extern "C" int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY
     return mrcnn_launch_status();
 }
 
+// ---- every flag combination of read_fits: mrcnn_fits_to_image / mrcnn_fits_tiles_to_image (include/mrcnn_hip.h) -----------------
+// The host statement, per channel c of zscale contrast zc (caesar-mrcnn_amd/fits.py:read_fits):
+//   c = out (float32, NaN-filled)
+//   zscale:        c = float32(stretch_img(c, zc))                                   fits_zscale_* and fits_stretch above
+//   biascontrast:  c = float32(clip((float64(c) - bias) * contrast + 0.5, 0, 1))     three separately rounded float64 operations
+//   normalize, or an RGB output:  c = c / max(c)                                     float32
+//   uint8 RGB: round(255 c)      float32 RGB: c * 255      gray: channel 0 as it is
+// Launches: the statistics pass as above; with zscale its one workgroup, without it fits_minmax_kernel (a reduction of the chunk
+// table: minimum = the NaN fill, maximum, NaN count -- no sampling, no sort, no fit); one pixel pass.  The channel maximum is
+// not reduced over the pixels: every step of the map is monotone and correctly rounded, so it is the chain applied to the tile's
+// maximum (contrast >= 0) or minimum (contrast < 0); a NaN at either end (inf * 0) makes numpy's max -- and the channel -- NaN.
+// The thread that writes a tile's FitsParams (thread 0 of the zscale workgroup or of the reduction) finishes the three maxima.
+// The pixel pass: a lane owns FOUR consecutive pixels, the group aligned in the POOL (pixel_offset + i a multiple of 4), so a
+// tile that starts anywhere in the pools still loads one aligned float4 and stores 12 bytes (uint8 RGB: one dwordx3), 48 bytes
+// (float32 RGB: three dwordx4) or 16 bytes (gray: one dwordx4) at their natural alignment; the partial groups at a tile's two
+// ends, and every group when a base pointer is not 16-byte aligned, store pixel by pixel.  Channels of equal zscale contrast
+// (all three without zscale) are computed once, as the host does.
+struct FitsChainDev {
+    int zscale, biascontrast, divide, out_kind;
+    int src[3];                                          // channel c repeats channel src[c] <= c
+    int vec;                                             // the pools' base pointers are 16-byte aligned
+    double bias, contrast;
+};
+
+__device__ __forceinline__ float fits_biascontrast(float c, double bias, double contrast) {
+#pragma clang fp contract(off)
+    double o = (double)c - bias;                         // (the library is built with -ffp-contract=off as well)
+    o = o * contrast;
+    o = o + 0.5;
+    o = (o != o) ? o : (o > 0.0 ? o : 0.0);              // np.clip(o, 0, 1): a NaN stays
+    o = (o != o) ? o : (o < 1.0 ? o : 1.0);
+    return (float)o;
+}
+
+// a channel's value of a (NaN-filled) pixel before the normalisation
+__device__ __forceinline__ float fits_chain_value(float v, const FitsChannel& ch, const FitsChainDev& d) {
+    float c = v;
+    if (d.zscale) c = fits_stretch(v, ch);
+    if (d.biascontrast) c = fits_biascontrast(c, d.bias, d.contrast);
+    return c;
+}
+
+// The maxima of the whole chain, by the ONE thread that wrote *params: ch[c].cmax comes in as the channel's value at the tile's
+// maximum before the bias / contrast stretch and goes out as the maximum of the finished channel (see the head of this part).
+__device__ __forceinline__ void fits_chain_finish(FitsParams* __restrict__ params, const FitsChainDev& d) {
+    if (params->all_nan || !d.biascontrast) return;
+    for (int c = 0; c < 3; ++c) {
+        const FitsChannel ch = params->ch[c];
+        const float lo = fits_biascontrast(d.zscale ? fits_stretch(params->fill, ch) : params->fill, d.bias, d.contrast);
+        float hi = fits_biascontrast(ch.cmax, d.bias, d.contrast);
+        if (lo != lo || hi != hi) hi = NAN;
+        else if (d.contrast < 0.0) hi = lo;
+        params->ch[c].cmax = hi;
+    }
+}
+
+// the reduction of one tile's chunk table that replaces the zscale workgroup: ONE workgroup of 256 threads
+__device__ __forceinline__ void fits_minmax_body(long long n, int nchunks, const FitsChunk* __restrict__ chunks, const FitsChainDev& d,
+                                                 FitsParams* __restrict__ params) {
+    __shared__ float s_mn[256], s_mx[256];
+    __shared__ int s_nan[256];
+    const int tid = threadIdx.x;
+    float mn = INFINITY, mx = -INFINITY;
+    int nn = 0;                                          // <= 4096 * 1024 pixels
+    for (int k = tid; k < nchunks; k += 256) {
+        const FitsChunk c = chunks[k];
+        mn = fminf(mn, c.mn); mx = fmaxf(mx, c.mx); nn += c.n_nan;
+    }
+    s_mn[tid] = mn; s_mx[tid] = mx; s_nan[tid] = nn;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+            s_mn[tid] = fminf(s_mn[tid], s_mn[tid + s]);
+            s_mx[tid] = fmaxf(s_mx[tid], s_mx[tid + s]);
+            s_nan[tid] += s_nan[tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        params->fill = s_mn[0];                          // np.nanmin(out)
+        params->all_nan = (long long)s_nan[0] == n;
+        FitsChannel ch;
+        ch.vmin32 = 0.f; ch.divide = 0; ch.range = 0.0; ch.pad = 0;
+        ch.cmax = s_mx[0];                               // no stretch: the channel is the tile
+        for (int c = 0; c < 3; ++c) params->ch[c] = ch;
+        fits_chain_finish(params, d);
+    }
+}
+
+__global__ __launch_bounds__(256) void fits_minmax_kernel(long long n, int nchunks, const FitsChunk* __restrict__ chunks, const FitsChainDev d,
+                                                          FitsParams* __restrict__ params) {
+    fits_minmax_body(n, nchunks, chunks, d, params);
+}
+
+__global__ __launch_bounds__(256) void fits_tiles_minmax_kernel(const mrcnn_fits_tile* __restrict__ tiles, const FitsChunk* __restrict__ chunks,
+                                                                const FitsChainDev d, FitsParams* __restrict__ params) {
+    const mrcnn_fits_tile t = tiles[blockIdx.x];
+    const long long n = (long long)t.w * t.h;
+    fits_minmax_body(n, (int)fits_tile_chunks(n), chunks + t.chunk_offset, d, params + blockIdx.x);
+}
+
+// the zscale workgroup of the older entries, then the maxima of the whole chain (thread 0 wrote the parameters it now reads)
+__global__ __launch_bounds__(1024) void fits_zscale_chain_kernel(const float* __restrict__ vals, long long n, int nchunks,
+                                                                 const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
+                                                                 const FitsChainDev d, FitsParams* __restrict__ params) {
+    fits_zscale_body(vals, n, nchunks, chunks, c0, c1, c2, params);
+    if (threadIdx.x == 0) fits_chain_finish(params, d);
+}
+
+__global__ __launch_bounds__(1024) void fits_tiles_zscale_chain_kernel(const mrcnn_fits_tile* __restrict__ tiles, const float* __restrict__ vals,
+                                                                       const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
+                                                                       const FitsChainDev d, FitsParams* __restrict__ params) {
+    const mrcnn_fits_tile t = tiles[blockIdx.x];
+    const long long n = (long long)t.w * t.h;
+    fits_zscale_body(vals + t.pixel_offset, n, (int)fits_tile_chunks(n), chunks + t.chunk_offset, c0, c1, c2, params + blockIdx.x);
+    if (threadIdx.x == 0) fits_chain_finish(params + blockIdx.x, d);
+}
+
+typedef float fits_f32x4 __attribute__((ext_vector_type(4)));          // a native vector: stored as one dwordx4
+
+// one pixel's channels after the whole chain (uint8 output: the rounded grey levels, still float); gray: o[0] alone
+template <int OUT>
+__device__ __forceinline__ void fits_image_pixel(float x, const FitsParams& p, const FitsChainDev& d, float* o) {
+    if (x != x) x = p.fill;
+#pragma unroll
+    for (int c = 0; c < (OUT == 2 ? 1 : 3); ++c) {
+        float r;
+        if (p.all_nan) {
+            r = NAN;                                     // (uint8: byte 0, as mrcnn_fits_to_rgb)
+        } else if (d.src[c] == c) {
+            r = fits_chain_value(x, p.ch[c], d);
+            if (d.divide) r = r / p.ch[c].cmax;          // normalize_img (float32)
+            if (OUT == 0) r = rintf(r * 255.f);          // gray2rgb: (c * 255).round()
+            if (OUT == 1) r = r * 255.f;
+        } else {
+            r = d.src[c] == 0 ? o[0] : o[1];
+        }
+        o[c] = r;
+    }
+}
+
+__device__ __forceinline__ unsigned fits_image_byte(float q) {
+    return (q >= 0.f && q <= 255.f) ? (unsigned)q : 0u;                     // 0 / 0 (constant tile): NaN -> 0
+}
+
+// Pixels of one tile, four per thread.  vals / out: the POOLS; off: where the tile starts in them (in pixels).
+// OUT: mrcnn_fits_chain.out_kind.
+template <int OUT>
+__device__ __forceinline__ void fits_image_body(const float* __restrict__ vals, long long off, long long n, const FitsParams& p,
+                                                const FitsChainDev& d, void* __restrict__ out, long long group) {
+    const long long g0 = (off & ~3ll) + group * 4;        // first pool pixel of this thread's group
+    const long long lo = g0 > off ? g0 : off, hi = g0 + 4 < off + n ? g0 + 4 : off + n;
+    if (lo >= hi) return;
+    if (d.vec && hi - lo == 4) {
+        const float4 q = *(const float4*)(vals + g0);
+        float o[4][3];
+        fits_image_pixel<OUT>(q.x, p, d, o[0]); fits_image_pixel<OUT>(q.y, p, d, o[1]);
+        fits_image_pixel<OUT>(q.z, p, d, o[2]); fits_image_pixel<OUT>(q.w, p, d, o[3]);
+        if (OUT == 0) {
+            unsigned b[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) b[k] = fits_image_byte(o[k / 3][k % 3]);
+            uint3 w;
+            w.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+            w.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+            w.z = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+            *(uint3*)((unsigned char*)out + 3 * g0) = w;
+        } else if (OUT == 1) {
+            fits_f32x4* d4 = (fits_f32x4*)((float*)out + 3 * g0);         // 48 bytes: three 16-byte stores
+            d4[0] = fits_f32x4{o[0][0], o[0][1], o[0][2], o[1][0]};
+            d4[1] = fits_f32x4{o[1][1], o[1][2], o[2][0], o[2][1]};
+            d4[2] = fits_f32x4{o[2][2], o[3][0], o[3][1], o[3][2]};
+        } else {
+            *(fits_f32x4*)((float*)out + g0) = fits_f32x4{o[0][0], o[1][0], o[2][0], o[3][0]};
+        }
+        return;
+    }
+    // the partial groups at a tile's two ends (every group of pools that are not 16-byte aligned): pixel by pixel
+#pragma nounroll
+    for (long long i = lo; i < hi; ++i) {
+        float o[3];
+        fits_image_pixel<OUT>(vals[i], p, d, o);
+        if (OUT == 0) {
+            unsigned char* dst = (unsigned char*)out + 3 * i;
+            dst[0] = (unsigned char)fits_image_byte(o[0]); dst[1] = (unsigned char)fits_image_byte(o[1]);
+            dst[2] = (unsigned char)fits_image_byte(o[2]);
+        } else if (OUT == 1) {
+            float* dst = (float*)out + 3 * i;
+            dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+        } else {
+            ((float*)out)[i] = o[0];
+        }
+    }
+}
+
+template <int OUT>
+__global__ __launch_bounds__(256) void fits_image_kernel(const float* __restrict__ vals, long long n, const FitsParams* __restrict__ params,
+                                                         const FitsChainDev d, void* __restrict__ out) {
+    const FitsParams p = *params;                        // once, into registers: the stores below could alias *params
+    fits_image_body<OUT>(vals, 0, n, p, d, out, (long long)blockIdx.x * 256 + threadIdx.x);
+}
+
+template <int OUT>
+__global__ __launch_bounds__(256) void fits_tiles_image_kernel(const mrcnn_fits_tile* __restrict__ tiles, const float* __restrict__ vals,
+                                                               const FitsParams* __restrict__ params, const FitsChainDev d,
+                                                               void* __restrict__ out) {
+    const mrcnn_fits_tile t = tiles[blockIdx.y];
+    const FitsParams p = params[blockIdx.y];
+    fits_image_body<OUT>(vals, t.pixel_offset, (long long)t.w * t.h, p, d, out, (long long)blockIdx.x * 256 + threadIdx.x);
+}
+
+// the descriptor as the kernels take it; the refusals of include/mrcnn_hip.h
+static int fits_chain_dev(const mrcnn_fits_chain* c, FitsChainDev* d) {
+    if (!c || c->out_kind < 0 || c->out_kind > 2) return MRCNN_ERR_ARG;
+    if (c->out_kind == 0 && !c->zscale && !c->biascontrast) return MRCNN_ERR_UNSUPPORTED;      // nothing clips to [0, 1]: uint8 of any float
+    d->zscale = c->zscale != 0;
+    d->biascontrast = c->biascontrast != 0;
+    d->divide = c->normalize != 0 || c->out_kind != 2;
+    d->out_kind = c->out_kind;
+    for (int k = 0; k < 3; ++k) {
+        d->src[k] = k;
+        for (int j = k - 1; j >= 0; --j)
+            if (!d->zscale || c->zscale_contrasts[j] == c->zscale_contrasts[k]) d->src[k] = j;
+    }
+    d->vec = 0;
+    d->bias = c->bias;
+    d->contrast = c->contrast;
+    return MRCNN_OK;
+}
+
+static size_t fits_image_pixel_bytes(int out_kind) { return out_kind == 0 ? 3 : out_kind == 1 ? 12 : 4; }
+
+extern "C" int mrcnn_fits_image_check(const mrcnn_fits_chain* chain, int H, int W) {
+    FitsChainDev d;
+    const int rc = fits_chain_dev(chain, &d);
+    if (rc != MRCNN_OK) return rc;
+    if (H <= 0 || W <= 0) return MRCNN_ERR_ARG;
+    if (((long long)H * W + FITS_CHUNK - 1) / FITS_CHUNK > FITS_MAX_CHUNKS) return MRCNN_ERR_UNSUPPORTED;
+    return MRCNN_OK;
+}
+
+template <int OUT>
+static void fits_image_launch(hipStream_t s, const float* vals, long long n, const FitsParams* params, const FitsChainDev& d, void* out) {
+    hipLaunchKernelGGL(fits_image_kernel<OUT>, dim3((unsigned)cdiv64(cdiv64(n, 4), 256)), dim3(256), 0, s, vals, n, params, d, out);
+}
+
+template <int OUT>
+static void fits_tiles_image_launch(hipStream_t s, const mrcnn_fits_tile* tiles, int T, long long max_pixels, const float* vals,
+                                    const FitsParams* params, const FitsChainDev& d, void* out) {
+    // a tile that starts 3 pixels into a group of four has ceil((n + 3) / 4) groups
+    hipLaunchKernelGGL(fits_tiles_image_kernel<OUT>, dim3((unsigned)cdiv64(cdiv64(max_pixels + 3, 4), 256), (unsigned)T), dim3(256), 0, s,
+                       tiles, vals, params, d, out);
+}
+
+extern "C" int mrcnn_fits_to_image(const void* raw, int big_endian, int H, int W, const mrcnn_fits_chain* chain, void* out, size_t out_bytes,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    FitsChainDev d;
+    const int rc = mrcnn_fits_image_check(chain, H, W);
+    if (rc != MRCNN_OK) return rc;
+    fits_chain_dev(chain, &d);
+    if (!raw || !out) return MRCNN_ERR_ARG;
+    const long long n = (long long)H * W;
+    const long long chunks = (n + FITS_CHUNK - 1) / FITS_CHUNK;
+    if (out_bytes < (size_t)n * fits_image_pixel_bytes(d.out_kind)) return MRCNN_ERR_ARG;
+    if (!workspace || workspace_bytes < mrcnn_fits_workspace(H, W)) return MRCNN_ERR_WORKSPACE;
+    float* vals = (float*)workspace;
+    FitsChunk* ch = (FitsChunk*)(vals + n);
+    FitsParams* params = (FitsParams*)(((uintptr_t)(ch + chunks) + 63) & ~(uintptr_t)63);
+    d.vec = (((uintptr_t)workspace | (uintptr_t)out) & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(fits_stats_kernel, dim3((unsigned)chunks), dim3(256), 0, s, (const unsigned*)raw, vals, n, big_endian, ch);
+    if (d.zscale)
+        hipLaunchKernelGGL(fits_zscale_chain_kernel, dim3(1), dim3(1024), 0, s, (const float*)vals, n, (int)chunks, (const FitsChunk*)ch,
+                           chain->zscale_contrasts[0], chain->zscale_contrasts[1], chain->zscale_contrasts[2], d, params);
+    else
+        hipLaunchKernelGGL(fits_minmax_kernel, dim3(1), dim3(256), 0, s, n, (int)chunks, (const FitsChunk*)ch, d, params);
+    if (d.out_kind == 0) fits_image_launch<0>(s, vals, n, params, d, out);
+    else if (d.out_kind == 1) fits_image_launch<1>(s, vals, n, params, d, out);
+    else fits_image_launch<2>(s, vals, n, params, d, out);
+    return mrcnn_launch_status();
+}
+
+extern "C" int mrcnn_fits_tiles_to_image(const void* plane, int big_endian, int NY, int NX, const mrcnn_fits_tile* tiles_host,
+                                         const mrcnn_fits_tile* tiles_dev, int T, const mrcnn_fits_chain* chain, void* out,
+                                         size_t out_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    FitsChainDev d;
+    int rc = fits_chain_dev(chain, &d);
+    if (rc != MRCNN_OK) return rc;
+    if (!plane || !out || !tiles_dev) return MRCNN_ERR_ARG;
+    FitsTilesLayout l;
+    rc = fits_tiles_layout(tiles_host, T, NY, NX, &l);
+    if (rc != MRCNN_OK) return rc;
+    if (out_bytes < (size_t)l.pixels * fits_image_pixel_bytes(d.out_kind)) return MRCNN_ERR_ARG;
+    if (!workspace || workspace_bytes < mrcnn_fits_tiles_workspace(tiles_host, T, NY, NX)) return MRCNN_ERR_WORKSPACE;
+    float* vals = (float*)workspace;
+    FitsChunk* ch = (FitsChunk*)(vals + l.pixels);
+    FitsParams* params = (FitsParams*)(((uintptr_t)(ch + l.chunks) + 63) & ~(uintptr_t)63);
+    d.vec = (((uintptr_t)workspace | (uintptr_t)out) & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(fits_tiles_stats_kernel, dim3((unsigned)l.max_chunks, (unsigned)T), dim3(256), 0, s, (const unsigned*)plane,
+                       (long long)NX, big_endian, tiles_dev, vals, ch);
+    if (d.zscale)
+        hipLaunchKernelGGL(fits_tiles_zscale_chain_kernel, dim3((unsigned)T), dim3(1024), 0, s, tiles_dev, (const float*)vals,
+                           (const FitsChunk*)ch, chain->zscale_contrasts[0], chain->zscale_contrasts[1], chain->zscale_contrasts[2], d, params);
+    else
+        hipLaunchKernelGGL(fits_tiles_minmax_kernel, dim3((unsigned)T), dim3(256), 0, s, tiles_dev, (const FitsChunk*)ch, d, params);
+    if (d.out_kind == 0) fits_tiles_image_launch<0>(s, tiles_dev, T, l.max_pixels, vals, params, d, out);
+    else if (d.out_kind == 1) fits_tiles_image_launch<1>(s, tiles_dev, T, l.max_pixels, vals, params, d, out);
+    else fits_tiles_image_launch<2>(s, tiles_dev, T, l.max_pixels, vals, params, d, out);
+    return mrcnn_launch_status();
+}
+
 // ---- the overview of a whole mosaic (include/mrcnn_hip.h: mrcnn_mosaic_overview) -----------------------------------------------
 // G = one channel of the chain above on the WHOLE plane [ny, nx] with one contrast; O[Y, X] = max of G over the k x k block
 // (partial at the right and lower edge); out = O in three channels.  Four launches, the plane read twice where it lies:

@@ -9,6 +9,7 @@ astropy is not available on the target image, so this module carries
     astropy itself cannot run here -- the algorithm follows the published astropy 2.x implementation,
     SURVEY App. C-6].
 """
+import collections
 import logging
 
 import numpy as np
@@ -16,6 +17,9 @@ import numpy as np
 logger = logging.getLogger("mrcnn")
 
 DEVICE_TILE_MAX_PIXELS = 4096 * 1024      # the size limit of the device chain (csrc/fits.hip: 4096 chunks of 1024 pixels)
+# Chains without zscale that end in a gray image or skip the bias / contrast stretch too: on the device only from the size at
+# which read_fits was measured ahead there (2048 x 2048; at 256 x 256 the host was level or ahead, no size between was measured)
+DEVICE_LIGHT_CHAIN_MIN_PIXELS = 2048 * 2048
 
 _BITPIX = {8: ">u1", 16: ">i2", 32: ">i4", 64: ">i8", -32: ">f4", -64: ">f8"}
 
@@ -205,20 +209,58 @@ def gray2rgb(data_float, to_uint8=True):
     return np.stack(chans, axis=-1)
 
 
+DeviceChain = collections.namedtuple("DeviceChain", "zscale biascontrast normalize out_kind zscale_contrasts bias contrast default")
+DeviceChain.__doc__ = """read_fits flags as the device chain takes them (mrcnn_fits_chain, include/mrcnn_hip.h).  out_kind: 0 uint8
+[H, W, 3], 1 float32 [H, W, 3], 2 float32 [H, W]; default: the run.py flags, computed by the older entries mrcnn_fits_to_rgb /
+mrcnn_fits_tiles_to_rgb."""
+
+
+def device_chain(stretch, normalize, convertToRGB, to_uint8, stretch_biascontrast, zscale_contrasts, contrast, bias, pixels=None):
+    """Whether the device chain (csrc/fits.hip) computes read_fits with these flags: (DeviceChain, None), or (None, why) when the
+    host path must run.  The only place that decides it -- read_fits(device=) and SFinder's batched front end both ask here.
+    Refused: uint8 output with neither stretch.  Nothing then clips the channel to [0, 1] (radio maps are negative in half their
+    pixels), the host casts out-of-range floats to uint8, and NumPy leaves that cast to the platform.  With either stretch on
+    every value is in [0, 1] before the division; the float outputs are IEEE arithmetic whatever the values.
+    pixels: the tile's size when the caller knows it.  Without zscale, a gray image or one without the bias / contrast stretch
+    is a few host operations per pixel, and the device branch pays an upload and a download for them: measured behind or level
+    with the host on a 256 x 256 tile and ahead on a 2048 x 2048 one, so these are refused below
+    DEVICE_LIGHT_CHAIN_MIN_PIXELS."""
+    if len(zscale_contrasts) != 3:
+        zscale_contrasts = [0.25, 0.25, 0.25]                       # as read_fits: any other length is ignored
+    try:
+        zc = tuple(float(v) for v in zscale_contrasts)
+        bias, contrast = float(bias), float(contrast)
+    except (TypeError, ValueError):
+        return None, "zscale contrasts, bias and contrast must be real numbers"
+    stretch, normalize, stretch_biascontrast = bool(stretch), bool(normalize), bool(stretch_biascontrast)
+    out_kind = (0 if to_uint8 else 1) if convertToRGB else 2        # without the RGB conversion to_uint8 is not looked at
+    if out_kind == 0 and not stretch and not stretch_biascontrast:
+        return None, "uint8 output with neither zscale nor the bias / contrast stretch: the cast of unclipped floats is platform-defined"
+    if pixels is not None and pixels < DEVICE_LIGHT_CHAIN_MIN_PIXELS and not stretch and (out_kind == 2 or not stretch_biascontrast):
+        return None, "no zscale and %s: the host is level or ahead below %d pixels" % (
+            "a gray image" if out_kind == 2 else "no bias / contrast stretch", DEVICE_LIGHT_CHAIN_MIN_PIXELS)
+    default = stretch and normalize and out_kind == 0 and not stretch_biascontrast
+    return DeviceChain(stretch, stretch_biascontrast, normalize, out_kind, zc, bias, contrast, default), None
+
+
 def read_fits(filename, xmin=-1, xmax=-1, ymin=-1, ymax=-1, stretch=True, normalize=True, convertToRGB=True,
               zscale_contrasts=[0.25, 0.25, 0.25], to_uint8=True, stretch_biascontrast=False, contrast=1, bias=0.5, device=None,
               device_out=False):
     """Tile of a FITS image as the network's input image (utils.py:1033-1163): NaN -> min, per-channel
     zscale, normalise by the channel maximum, uint8 RGB.  Returns (image, header) or None on error.
-    device: a torch GPU device -- the numeric part (everything after the header parse and the tile cut) runs there
-    (mrcnn_fits_to_rgb; the file's big-endian floats cross PCIe as they are) when the flags are the run.py ones (stretch,
-    normalize, convertToRGB, to_uint8, no bias / contrast stretch); the uint8 image comes back to the host, identical to the
-    host path's.  device_out: the image of that device branch stays there, as a uint8 [H, W, 3] torch tensor (the device sample
-    path of datagen.data_generator); a call that does not take the branch returns the host array as ever."""
+    device: a torch GPU device -- the numeric part (everything after the header parse and the tile cut) runs there (the file's
+    big-endian floats cross PCIe as they are) for every flag combination device_chain() accepts: mrcnn_fits_to_rgb for the
+    run.py flags (stretch, normalize, convertToRGB, to_uint8, no bias / contrast stretch), mrcnn_fits_to_image for the others;
+    the image comes back to the host, identical to the host path's (uint8 byte for byte, float32 bit for bit).  device_out: a
+    uint8 RGB image of that device branch stays there, as a uint8 [H, W, 3] torch tensor (the device sample path of
+    datagen.data_generator); any other call returns the host array as ever."""
     if len(zscale_contrasts) != 3:
         logger.warning("Size of input zscale_contrasts is !=3, ignoring inputs and using default (0.25,0.25,0.25)...")
         zscale_contrasts = [0.25, 0.25, 0.25]
-    on_device = device is not None and stretch and normalize and convertToRGB and to_uint8 and not stretch_biascontrast
+    chain = None
+    if device is not None:
+        chain, _ = device_chain(stretch, normalize, convertToRGB, to_uint8, stretch_biascontrast, zscale_contrasts, contrast, bias)
+    on_device = chain is not None
     try:
         data, header = read_primary_hdu(filename, native=not on_device)
     except Exception:
@@ -240,7 +282,10 @@ def read_fits(filename, xmin=-1, xmax=-1, ymin=-1, ymax=-1, stretch=True, normal
         logger.error('ERROR: Invalid/unsupported number of channels found in file %s (nchan=%d)!' % (filename, data.ndim))
         return None
     if on_device and out.size and out.shape[0] * out.shape[1] <= DEVICE_TILE_MAX_PIXELS:
-        return _read_fits_device(out, zscale_contrasts, device, device_out), header
+        chain, _ = device_chain(stretch, normalize, convertToRGB, to_uint8, stretch_biascontrast, zscale_contrasts, contrast, bias,
+                                pixels=out.shape[0] * out.shape[1])
+        if chain is not None:
+            return _read_fits_device(out, chain, device, device_out), header
     out = out.astype(np.float32)
     out[np.isnan(out)] = np.nanmin(out)
     # The reference runs the whole per-channel chain three times (utils.py:1101-1157); the channels differ only in their
@@ -300,9 +345,10 @@ def mosaic_overview_host(plane, shrink, contrast=0.25):
     return np.repeat(O[:, :, None], 3, axis=2)
 
 
-def _read_fits_device(tile, zscale_contrasts, device, device_out=False):
-    """The cut tile (still in the file's dtype / byte order) -> uint8 [H, W, 3] through ops.fits_to_rgb; returns a host array
-    (device_out: the device tensor, allocated on the loader stream, where its consumers run too).
+def _read_fits_device(tile, chain, device, device_out=False):
+    """The cut tile (still in the file's dtype / byte order) -> the image of `chain` (a DeviceChain) through ops.fits_to_rgb
+    (the run.py flags) or ops.fits_to_image (any other accepted combination); returns a host array of the host path's shape
+    and dtype (device_out and a uint8 RGB image: the device tensor, allocated on the loader stream, where its consumers run too).
     Called from loader threads while the main thread issues training steps: the three launches go to ONE side stream shared
     by all loader threads (its own hardware queue beside the step's three; a stream per thread would wrap onto the step's
     queues and wait behind a whole step) under a lock (the stream's scratch buffer is shared), and only that stream is
@@ -316,14 +362,18 @@ def _read_fits_device(tile, zscale_contrasts, device, device_out=False):
         tile = tile.astype(np.float32)                              # integer / float64 images: converted on the host as the host path does
     raw = torch.from_numpy(np.array(tile, order="C", copy=True).view(np.uint8).reshape(-1))   # (a writable copy: the file view is read-only)
     device = torch.device(device)
+    device_out = device_out and chain.out_kind == 0
     with loader_stream(device) as st:
         with torch.cuda.stream(st):
-            rgb = ops.fits_to_rgb(raw.to(device, non_blocking=True), H, W, zscale_contrasts, big_endian=big)
+            if chain.default:
+                img = ops.fits_to_rgb(raw.to(device, non_blocking=True), H, W, chain.zscale_contrasts, big_endian=big)
+            else:
+                img = ops.fits_to_image(raw.to(device, non_blocking=True), H, W, chain, big_endian=big)
             if not device_out:
-                host = torch.empty((H, W, 3), dtype=torch.uint8, pin_memory=True)
-                host.copy_(rgb, non_blocking=True)
+                host = torch.empty(tuple(img.shape), dtype=img.dtype, pin_memory=True)
+                host.copy_(img, non_blocking=True)
         st.synchronize()                                            # (device_out too: `raw` is pageable and freed on return)
-    return rgb if device_out else host.numpy().copy()
+    return img if device_out else host.numpy().copy()
 
 
 def read_table(filename):

@@ -804,6 +804,89 @@ def fits_tiles_to_rgb(plane, tiles, zscale_contrasts=(0.25, 0.25, 0.25), big_end
     return out
 
 
+# ---- every read_fits flag combination (csrc/fits.hip: mrcnn_fits_to_image / mrcnn_fits_tiles_to_image) ----------------------------
+FITS_OUT_UINT8_RGB, FITS_OUT_FLOAT_RGB, FITS_OUT_GRAY = 0, 1, 2
+
+
+class FitsChainUnsupported(_hip.HipPathError):
+    """A flag combination the device chain refuses: uint8 output with neither stretch (nothing clips the channel to [0, 1] and
+    the host's cast of out-of-range floats to uint8 is platform-defined).  Nothing was launched: the caller takes the host path."""
+
+
+def _fits_chain(chain):
+    """(mrcnn_fits_chain, dtype, trailing shape) of a chain description: an object with the fields of fits.DeviceChain."""
+    zc = [float(v) for v in chain.zscale_contrasts]
+    assert len(zc) == 3, "zscale_contrasts must hold three values"
+    c = _hip.FitsChain(1 if chain.zscale else 0, 1 if chain.biascontrast else 0, 1 if chain.normalize else 0, int(chain.out_kind),
+                       (C.c_double * 3)(*zc), float(chain.bias), float(chain.contrast))
+    if c.out_kind not in (FITS_OUT_UINT8_RGB, FITS_OUT_FLOAT_RGB, FITS_OUT_GRAY):
+        raise ValueError("out_kind must be 0 (uint8 RGB), 1 (float32 RGB) or 2 (float32 gray), got %r" % (chain.out_kind,))
+    if _hip.lib().mrcnn_fits_image_check(C.byref(c), 1, 1) == ERR_UNSUPPORTED:
+        raise FitsChainUnsupported("the device chain does not take uint8 output with neither zscale nor the bias / contrast stretch")
+    dtype = torch.uint8 if c.out_kind == FITS_OUT_UINT8_RGB else torch.float32
+    return c, dtype, (() if c.out_kind == FITS_OUT_GRAY else (3,))
+
+
+def fits_to_image(raw, H, W, chain, big_endian=False, out=None):
+    """fits_to_rgb for any flag combination of fits.read_fits (mrcnn_fits_to_image): raw as there; chain: what
+    fits.device_chain returns.  -> uint8 [H, W, 3], float32 [H, W, 3] or float32 [H, W] device tensor by chain.out_kind, equal
+    bit for bit to the host branch of fits.read_fits on the same tile.  FitsChainUnsupported for the one combination the chain
+    refuses, FitsTileUnsupported for a tile above 2048 x 2048 pixels; neither launches or allocates anything."""
+    _need_cuda(raw, out)
+    assert raw.is_contiguous() and raw.numel() * raw.element_size() == 4 * H * W, "raw must hold H * W float32 values"
+    c, dtype, tail = _fits_chain(chain)
+    L = _hip.lib()
+    rc = L.mrcnn_fits_image_check(C.byref(c), H, W)
+    if rc == ERR_UNSUPPORTED:
+        raise FitsTileUnsupported("mrcnn_fits_to_image: a %d x %d tile is above the kernel's size limit (2048 x 2048 pixels)" % (H, W))
+    check(rc, "mrcnn_fits_image_check")
+    shape = (H, W) + tail
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=raw.device)
+    assert tuple(out.shape) == shape and out.dtype == dtype and out.is_contiguous()
+    nbytes = L.mrcnn_fits_workspace(H, W)
+    ws = workspace(nbytes, raw.device, "fits")
+    check(L.mrcnn_fits_to_image(ptr(raw), 1 if big_endian else 0, H, W, C.byref(c), ptr(out), out.numel() * out.element_size(), ptr(ws),
+                                ws.numel(), current_stream()), "mrcnn_fits_to_image")
+    return out
+
+
+def fits_tiles_to_image(plane, tiles, chain, big_endian=False):
+    """fits_tiles_to_rgb for any flag combination (mrcnn_fits_tiles_to_image): plane and tiles as there, chain as for
+    fits_to_image.  Returns a list of T device tensors, views into one pool, each equal to fits_to_image of that cut.  The same
+    refusals as fits_tiles_to_rgb, and FitsChainUnsupported."""
+    import numpy as np
+    _need_cuda(plane)
+    if plane.dim() < 2 or plane.numel() * plane.element_size() != 4 * plane.shape[0] * plane.shape[1]:
+        raise ValueError("plane must hold NY x NX float32 values (got shape %r, dtype %s)" % (tuple(plane.shape), plane.dtype))
+    NY, NX = int(plane.shape[0]), int(plane.shape[1])
+    c, dtype, tail = _fits_chain(chain)
+    table = fits_tile_table(tiles)
+    T = int(table.shape[0])
+    L = _hip.lib()
+    host = table.ctypes.data_as(C.c_void_p)
+    stream = current_stream()
+    rc = L.mrcnn_fits_tiles_check(host, T, NY, NX)
+    if rc == ERR_UNSUPPORTED:
+        raise FitsTileUnsupported("mrcnn_fits_tiles_to_image: a tile above the kernel's size limit (2048 x 2048 pixels)")
+    if rc:
+        raise ValueError("mrcnn_fits_tiles_to_image refuses the tiles (status %d): no tile, an empty rectangle or one outside the "
+                         "%d x %d plane" % (rc, NY, NX))
+    nbytes = L.mrcnn_fits_tiles_workspace(host, T, NY, NX)
+    ws = workspace(nbytes, plane.device, "fits_tiles")
+    total = int(table["pixel_offset"][-1]) + int(table["w"][-1]) * int(table["h"][-1])
+    per = 3 if tail else 1
+    pool = torch.empty(per * total, dtype=dtype, device=plane.device)
+    table_dev = torch.from_numpy(table.view(np.uint8)).to(plane.device)
+    check(L.mrcnn_fits_tiles_to_image(ptr(plane), 1 if big_endian else 0, NY, NX, host, ptr(table_dev), T, C.byref(c), ptr(pool),
+                                      pool.numel() * pool.element_size(), ptr(ws), ws.numel(), stream), "mrcnn_fits_tiles_to_image")
+    out = []
+    for r in table:
+        o, h, w = per * int(r["pixel_offset"]), int(r["h"]), int(r["w"])
+        out.append(pool[o:o + per * h * w].view((h, w) + tail))
+    return out
+
+
 # ---- the overview picture of a mosaic (csrc/fits.hip: mrcnn_mosaic_overview; csrc/maskgraph.hip: mrcnn_sources_to_planes) --------
 class MosaicUnsupported(_hip.HipPathError):
     """A mosaic past a cap of mrcnn_mosaic_overview (more than 2^31 - 1 pixels) or of mrcnn_sources_to_planes (planes of more

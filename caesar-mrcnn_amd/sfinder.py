@@ -301,7 +301,8 @@ class SFinder(object):
         self._plane = None                # (image plane as stored, path, header) while tiles / compute_sources_params need it
         self._plane_dev = None            # (its device copy, big-endian bytes?, path): uploaded once, shared by both
         # Tiles per model.detect call of run_parallel.  0: the reference's loop, one file read / host stretch / detect per tile.
-        # N >= 1: the batched, device-resident front end (needs the run.py read_fits flags and a model built for batches of N).
+        # N >= 1: the batched, device-resident front end (needs read_fits flags that end in a uint8 RGB image on the device, see
+        # _tiles_batched(), and a model built for batches of N).
         self.tile_batch = 0
         self._wcs_warned = False
         # The overview picture of the mosaic with the merged catalogue on it: off by default.
@@ -370,12 +371,20 @@ class SFinder(object):
             self._drop_plane()
         return 0
 
-    def _tiles_batched(self):
-        """True when run_parallel takes the batched front end: tile_batch set and the read_fits flags those of run.py (stretch,
-        normalize, RGB, uint8, no bias / contrast stretch -- what the device chain computes; fits.read_fits(device=) asks the same)."""
+    def _tiles_chain(self):
+        """(DeviceChain, None) of this run's read_fits flags, or (None, why): fits.device_chain decides, as for read_fits(device=)."""
         cfg = self.config
-        return bool(self.tile_batch >= 1 and cfg.ZSCALE_STRETCH and cfg.NORMALIZE_IMG and cfg.IMG_TO_RGB and cfg.IMG_TO_UINT8 and
-                    not cfg.BIAS_CONTRAST_STRETCH)
+        return fits.device_chain(cfg.ZSCALE_STRETCH, cfg.NORMALIZE_IMG, cfg.IMG_TO_RGB, cfg.IMG_TO_UINT8, cfg.BIAS_CONTRAST_STRETCH,
+                                 cfg.ZSCALE_CONTRASTS, cfg.IMG_CONTRAST, cfg.IMG_BIAS)
+
+    def _tiles_batched(self):
+        """True when run_parallel takes the batched front end: tile_batch set and read_fits flags the device chain computes and
+        that end in a uint8 RGB image (RGB, uint8, zscale or the bias / contrast stretch; NORMALIZE_IMG either way -- the RGB
+        conversion normalises anyway).  detect()'s device molding takes uint8 only: gray or float32 tiles keep the loop."""
+        if self.tile_batch < 1:
+            return False
+        chain, _ = self._tiles_chain()
+        return chain is not None and chain.out_kind == 0
 
     def _read_header(self):
         """The header of the image; on the batched path from the ONE read of the file that also gives the plane."""
@@ -464,8 +473,9 @@ class SFinder(object):
                 status = self._run_tasks_batched(tasks)
             else:
                 if self.tile_batch >= 1:
-                    logger.info("[PROC %d] tile_batch = %d ignored: the read_fits flags are not the run.py ones (stretch, normalize, RGB, "
-                                "uint8, no bias/contrast stretch); tiles are read and detected one at a time" % (self.procId, self.tile_batch))
+                    logger.info("[PROC %d] tile_batch = %d ignored: the read_fits flags do not end in a uint8 RGB image the device chain "
+                                "computes (%s); tiles are read and detected one at a time" % (
+                                    self.procId, self.tile_batch, self._tiles_chain()[1] or "gray or float32 tiles"))
                 for j, task in enumerate(tasks):
                     logger.info("[PROC %d] Start processing of task id %d (%d/%d) ..." % (self.procId, task.tid, j + 1, len(tasks)))
                     if self._run_task(j, task, task.find_sources) < 0:
@@ -550,8 +560,9 @@ class SFinder(object):
 
     def prepare_tile_images(self, tasks):
         """The network input images of `tasks`' tiles, in order: uint8 [h, w, 3] device tensors, cut from the resident plane (as
-        NumPy slicing cuts: clipped to the plane), NaN-filled, zscaled, normalised and converted in one ops.fits_tiles_to_rgb call --
-        byte for byte what fits.read_fits gives per tile."""
+        NumPy slicing cuts: clipped to the plane), NaN-filled, stretched, normalised and converted in one ops.fits_tiles_to_rgb
+        call (the run.py flags) or one ops.fits_tiles_to_image call (any other combination _tiles_batched() accepts) -- byte for
+        byte what fits.read_fits gives per tile."""
         from . import ops
         plane_t, big = self._plane_device()
         ny, nx = int(plane_t.shape[0]), int(plane_t.shape[1])
@@ -559,7 +570,12 @@ class SFinder(object):
         for t in tasks:
             x0, x1, y0, y1 = min(t.ix_min, nx), min(t.ix_max, nx), min(t.iy_min, ny), min(t.iy_max, ny)
             rects.append((x0, y0, x1 - x0, y1 - y0))
-        return ops.fits_tiles_to_rgb(plane_t, rects, self._zscale_contrasts(), big_endian=big)
+        chain, why = self._tiles_chain()
+        if chain is None or chain.out_kind != 0:
+            raise RuntimeError("prepare_tile_images: the read_fits flags are not the device chain's (%s)" % (why or "no uint8 RGB image"))
+        if chain.default:
+            return ops.fits_tiles_to_rgb(plane_t, rects, self._zscale_contrasts(), big_endian=big)
+        return ops.fits_tiles_to_image(plane_t, rects, chain, big_endian=big)
 
     def _zscale_contrasts(self):
         zc = self.config.ZSCALE_CONTRASTS

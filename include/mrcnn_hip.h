@@ -661,6 +661,36 @@ int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY, int NX, c
                             const mrcnn_fits_tile* tiles_dev, int T, const double* zscale_contrasts, void* rgb, size_t rgb_bytes,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same two entries for every flag combination of utils.read_fits (stretch, stretch_biascontrast, normalize, convertToRGB,
+ * to_uint8; the host statement is caesar-mrcnn_amd/fits.py:read_fits, held bit for bit).  Per channel c of zscale contrast zc:
+ *   zscale        c = float32(ZScaleInterval(zc)(c))                        (as mrcnn_fits_to_rgb)
+ *   biascontrast  c = float32(clip((float64(c) - bias) * contrast + 0.5, 0, 1))    three separately rounded operations
+ *   normalize, or out_kind 0 / 1:  c = c / max(c)                           float32
+ *   out_kind 0: uint8 [H, W, 3] = round(255 c)   1: float32 [H, W, 3] = c * 255   2: float32 [H, W] = channel 0 as it is
+ * Without zscale the sampling / sort / fit workgroup is not launched: a reduction of the statistics table gives the minimum
+ * (the NaN fill) and the maximum.
+ * MRCNN_ERR_UNSUPPORTED: out_kind 0 with neither stretch (nothing clips the channel to [0, 1]; the host casts out-of-range
+ * floats to uint8, which is platform-defined) and a tile above 2048 x 2048 pixels; MRCNN_ERR_ARG: out_kind outside 0 .. 2.
+ * A tile without a finite pixel under zscale, or of NaNs alone: zeros for out_kind 0, NaN for the float outputs (the host
+ * raises under zscale).  out: out_bytes >= 3 / 12 / 4 bytes per pixel; for the tiled entry a pool with tile t at
+ * pixel_offset[t] times that.  workspace: mrcnn_fits_workspace / mrcnn_fits_tiles_workspace; the tile table and its check are
+ * those of mrcnn_fits_tiles_to_rgb.  mrcnn_fits_image_check: the status mrcnn_fits_to_image would return for that descriptor
+ * and size (host-side alone; launches nothing).  16-byte aligned out and workspace take the vector stores.                    */
+typedef struct mrcnn_fits_chain {
+    int32_t zscale;        /* stretch_img per channel */
+    int32_t biascontrast;  /* stretch_img_biasconstrast after it */
+    int32_t normalize;     /* normalize_img */
+    int32_t out_kind;
+    double zscale_contrasts[3];
+    double bias, contrast;
+} mrcnn_fits_chain;
+int mrcnn_fits_image_check(const mrcnn_fits_chain* chain, int H, int W);
+int mrcnn_fits_to_image(const void* raw, int big_endian, int H, int W, const mrcnn_fits_chain* chain, void* out, size_t out_bytes,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int mrcnn_fits_tiles_to_image(const void* plane, int big_endian, int NY, int NX, const mrcnn_fits_tile* tiles_host,
+                              const mrcnn_fits_tile* tiles_dev, int T, const mrcnn_fits_chain* chain, void* out, size_t out_bytes,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* The overview frame of a whole mosaic (the host statement is fits.mosaic_overview_host): the chain of
  * mrcnn_fits_to_rgb on the WHOLE plane with one zscale contrast, then shrunk by block maxima:
  *   plane   [ny, nx] float32 where it lies, native or (big_endian != 0) in FITS byte order; 4-byte aligned (16-byte aligned
