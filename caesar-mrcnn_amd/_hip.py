@@ -231,6 +231,8 @@ _SIGNATURES = {
     "mrcnn_catalog_nan_fill": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "mrcnn_mold_image_u8": (C.c_int, [_P] + [C.c_int] * 9 + [C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
     "mrcnn_resize_image_u8": (C.c_int, [_P] + [C.c_int] * 9 + [_P, _P, C.c_size_t, _P]),
+    "mrcnn_mold_image_f32_workspace_bytes": (C.c_size_t, []),
+    "mrcnn_mold_image_f32": (C.c_int, [_P] + [C.c_int] * 9 + [C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
     "mrcnn_add_inplace": (C.c_int, [_P, _P, C.c_int64, _P]),
     "mrcnn_softmax_rows": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "mrcnn_roialign_fwd": (C.c_int, [C.POINTER(RoiAlignDesc)] + [_P] * 8),

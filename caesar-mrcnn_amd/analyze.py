@@ -1584,6 +1584,9 @@ class Analyzer(object):
             logger.error("The image of %s stayed on the device (only its shape is known here): nothing is drawn ..." % self.image_id)
             return None
         image = np.asarray(self.image)
+        shape_cfg = np.asarray(getattr(self.config, "IMAGE_SHAPE", (0, 0, 3))).reshape(-1)
+        if image.ndim == 3 and image.shape[2] == 1 and image.dtype == np.uint8 and shape_cfg.size >= 3 and int(shape_cfg[2]) == 1:
+            image = np.repeat(image, 3, axis=2)           # a gray-level configuration's uint8 frame: drawn as its three-fold copy
         if image.ndim != 3 or image.shape[2] != 3 or image.shape[0] == 0 or image.shape[1] == 0:
             logger.error("Cannot draw an image of shape %r (need [H, W, 3]): nothing is drawn ..." % (tuple(image.shape),))
             return None

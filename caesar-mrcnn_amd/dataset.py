@@ -205,6 +205,8 @@ class SourceDataset(Dataset):
                                   convertToRGB=self.convert_to_rgb, to_uint8=self.convert_to_uint8,
                                   stretch_biascontrast=self.apply_biascontrast, bias=self.bias, contrast=self.contrast,
                                   device=getattr(self, "device", None), device_out=device_out)
+        if image.ndim == 2:                 # convert_to_rgb False (run.py --grayimg): the model's gray image is [H, W, 1]
+            image = image[:, :, None]
         return image
 
     def image_uuid(self, image_id):

@@ -754,7 +754,11 @@ class MaskRCNNEngine(object):
             if name == "mrcnn_mask_deconv/kernel" and a.shape == (2, 2, shape[3], shape[0]):
                 a = deconv_keras_to_gemm(a)
             if a.size != n:
-                raise ValueError("shape mismatch for %s: %s vs %s" % (name, a.shape, shape))
+                hint = ""
+                if name == "conv1/kernel":      # weights of a model with another number of input channels (RGB <-> gray)
+                    hint = "; the first layer depends on the image's channels: load the rest with load_weights(..., exclude=\"conv1\") " \
+                           "(run.py --exclude_first_layer_weights)"
+                raise ValueError("shape mismatch for %s: %s vs %s%s" % (name, a.shape, shape, hint))
             self.params[off:off + n].copy_(torch.from_numpy(np.ascontiguousarray(a).reshape(-1)))
         for l in L.bn_layers:
             c0, c = L.bn_channel_offset[l.bn], l.shape[3]

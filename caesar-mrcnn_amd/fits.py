@@ -251,9 +251,11 @@ def read_fits(filename, xmin=-1, xmax=-1, ymin=-1, ymax=-1, stretch=True, normal
     device: a torch GPU device -- the numeric part (everything after the header parse and the tile cut) runs there (the file's
     big-endian floats cross PCIe as they are) for every flag combination device_chain() accepts: mrcnn_fits_to_rgb for the
     run.py flags (stretch, normalize, convertToRGB, to_uint8, no bias / contrast stretch), mrcnn_fits_to_image for the others;
-    the image comes back to the host, identical to the host path's (uint8 byte for byte, float32 bit for bit).  device_out: a
-    uint8 RGB image of that device branch stays there, as a uint8 [H, W, 3] torch tensor (the device sample path of
-    datagen.data_generator); any other call returns the host array as ever."""
+    the image comes back to the host, identical to the host path's (uint8 byte for byte, float32 bit for bit).  device_out:
+    True -- a uint8 RGB image of that device branch stays there, as a uint8 [H, W, 3] torch tensor (the device sample path of
+    datagen.data_generator), a float32 image still comes back to the host; "any" -- every image of the device branch stays
+    there, as a torch tensor of the host array's shape and dtype: uint8 [H, W, 3], float32 [H, W, 3] or, gray, float32 [H, W]
+    (MaskRCNN.detect molds all three where they are).  A call that takes the host branch returns the host array as ever."""
     if len(zscale_contrasts) != 3:
         logger.warning("Size of input zscale_contrasts is !=3, ignoring inputs and using default (0.25,0.25,0.25)...")
         zscale_contrasts = [0.25, 0.25, 0.25]
@@ -348,7 +350,8 @@ def mosaic_overview_host(plane, shrink, contrast=0.25):
 def _read_fits_device(tile, chain, device, device_out=False):
     """The cut tile (still in the file's dtype / byte order) -> the image of `chain` (a DeviceChain) through ops.fits_to_rgb
     (the run.py flags) or ops.fits_to_image (any other accepted combination); returns a host array of the host path's shape
-    and dtype (device_out and a uint8 RGB image: the device tensor, allocated on the loader stream, where its consumers run too).
+    and dtype (device_out True and a uint8 RGB image, or device_out "any": the device tensor, allocated on the loader stream, where
+    its consumers run too).
     Called from loader threads while the main thread issues training steps: the three launches go to ONE side stream shared
     by all loader threads (its own hardware queue beside the step's three; a stream per thread would wrap onto the step's
     queues and wait behind a whole step) under a lock (the stream's scratch buffer is shared), and only that stream is
@@ -362,7 +365,7 @@ def _read_fits_device(tile, chain, device, device_out=False):
         tile = tile.astype(np.float32)                              # integer / float64 images: converted on the host as the host path does
     raw = torch.from_numpy(np.array(tile, order="C", copy=True).view(np.uint8).reshape(-1))   # (a writable copy: the file view is read-only)
     device = torch.device(device)
-    device_out = device_out and chain.out_kind == 0
+    device_out = device_out == "any" or (bool(device_out) and chain.out_kind == 0)
     with loader_stream(device) as st:
         with torch.cuda.stream(st):
             if chain.default:

@@ -261,7 +261,7 @@ class DeviceSampler(object):
         with loader_stream(self.device) as st:
             with torch.cuda.stream(st):
                 ops.mask_bits_gather(sample.bits, sel, self.config.MAX_GT_INSTANCES, out=out_masks)
-                ops.mold_image_u8(sample.img, (OH, OW), (0, 0), (OH, OW), self.config.MEAN_PIXEL, out=out_image)
+                ops.mold_image_u8(sample.img, (OH, OW), (0, 0), (OH, OW), utils.mean_pixel(self.config, sample.shape[2]), out=out_image)
         _count("device")
         if sample.scaled:
             _count("scaled")

@@ -19,6 +19,11 @@ from .datagen import data_generator
 
 logger = logging.getLogger("mrcnn")
 
+# float32 HOST images with fewer pixels (h * w) keep the host molding; device tensors are always molded where they are.  The
+# smallest size at which tools/mold_bench.py measured the device path ahead (it is ahead in every row of
+# profiles/gray_float_bench.json: 1.32 x at 256 x 256 gray unscaled, the closest); smaller sizes were not measured.
+DEVICE_MOLD_F32_MIN_PIXELS = 256 * 256
+
 
 def log(text, array=None):
     if array is not None:
@@ -72,6 +77,8 @@ class MaskRCNN(object):
     def build(self, mode, config, device=None, weights=None, seed=0):
         assert mode in ['training', 'inference']
         h, w = config.IMAGE_SHAPE[:2]
+        utils.image_channels(config)                  # ValueError unless 1 (gray) or 3 (RGB)
+        utils.mean_pixel(config)                      # ValueError unless a scalar or one value per channel
         if h / 2 ** 6 != int(h / 2 ** 6) or w / 2 ** 6 != int(w / 2 ** 6):
             raise Exception("Image size must be dividable by 2 at least 6 times "
                             "to avoid fractions when downscaling and upscaling."
@@ -265,6 +272,9 @@ class MaskRCNN(object):
         """Forward + backward + (all-reduce) + SGD step on one generator batch.  Returns the five
         losses (host array, this rank's batch means)."""
         eng = self.engine
+        C_ = utils.image_channels(self.config)
+        if len(inputs[0].shape) != 4 or inputs[0].shape[3] != C_:
+            raise ValueError("train_on_batch: images of shape %r given to a model of %d input channel(s)" % (tuple(inputs[0].shape), C_))
         dev_inputs = self._to_device(inputs, rand_keys)
         eng.grad_ready = reducer.ready if reducer is not None else None
         if apply and reducer is None and world_size == 1 and not keep_outputs and getattr(self.config, "TRAIN_HIP_GRAPH", False):
@@ -373,13 +383,14 @@ class MaskRCNN(object):
         return np.stack(molded_images), np.stack(image_metas), np.stack(windows)
 
     def _mold_inputs_device(self, images):
-        """mold_inputs for uint8 images with the pixel work on the GPU (ops.mold_image_u8): each image crosses PCIe as its
-        uint8 bytes and is scaled, padded and mean-subtracted there.  An image may also be a uint8 [h, w, C] torch tensor that is
-        already on the engine's device (the tiled source finder's tiles): it is molded where it is.  Returns the molded batch as a
-        device tensor [B, H, W, C] float32, image_metas and windows as mold_inputs does -- or None when a host image is not uint8
-        HxWxC or the resize mode draws random numbers ("crop"): the caller then takes the host path.  A tensor that cannot be
-        molded here (another device, another dtype or shape, a resize mode of the host path) raises ValueError: it never goes to
-        the host path."""
+        """mold_inputs with the pixel work on the GPU (ops.mold_image_u8 / ops.mold_image_f32): a uint8 or float32 [h, w, C] host
+        array crosses PCIe as it is and is scaled, padded and mean-subtracted there.  An image may also be a uint8 or float32
+        [h, w, C] torch tensor that is already on the engine's device (the tiled source finder's tiles): it is molded where it
+        is.  Returns the molded batch as a device tensor [B, H, W, C] float32, image_metas and windows as mold_inputs does -- or
+        None when a host image is neither (float64 included), when a float32 host image has fewer than
+        DEVICE_MOLD_F32_MIN_PIXELS pixels or the resize mode draws random numbers ("crop"): the caller then
+        takes the host path.  A tensor that cannot be molded here (another device, another dtype or shape, a resize mode of the
+        host path) raises ValueError: it never goes to the host path; so does a batch that holds tensors and mixes dtypes."""
         import torch
         from . import ops
         cfg = self.config
@@ -395,17 +406,25 @@ class MaskRCNN(object):
             return host_path("device images need IMAGE_RESIZE_MODE square, pad64 or none (got %r)" % cfg.IMAGE_RESIZE_MODE)
         plans = []
         for image in images:
-            if not torch.is_tensor(image) and not (isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and
-                                                   image.shape[2] <= 4):
-                return host_path("device images cannot share a batch with host images the GPU molding does not take")
+            if not torch.is_tensor(image):
+                if not (isinstance(image, np.ndarray) and image.dtype in (np.uint8, np.float32) and image.ndim == 3 and
+                        1 <= image.shape[2] <= 4):
+                    return host_path("device images cannot share a batch with host images the GPU molding does not take")
+                if image.dtype == np.float32 and not on_device and image.shape[0] * image.shape[1] < DEVICE_MOLD_F32_MIN_PIXELS:
+                    return None
             scale, (oh, ow), padding, window = utils.resize_plan(tuple(image.shape), cfg.IMAGE_MIN_DIM, cfg.IMAGE_MAX_DIM, cfg.IMAGE_MIN_SCALE,
                                                                  cfg.IMAGE_RESIZE_MODE)
             canvas = (oh + padding[0][0] + padding[0][1], ow + padding[1][0] + padding[1][1])
             plans.append((scale, (oh, ow), padding, window, canvas))
         if any(p[4] != plans[0][4] for p in plans) or any(im.shape[2] != images[0].shape[2] for im in images):
             return host_path("after resizing, all images must have the same size")     # (the host path raises the reference's assertion)
+        if on_device and len({str(im.dtype).replace("torch.", "") for im in images}) > 1:
+            # a batch's images come out of one read_fits chain: uint8 beside float32 is a caller's mistake, not a batch
+            raise ValueError("detect: a batch that holds device images must have one dtype (got %s)" % sorted(
+                {str(im.dtype).replace("torch.", "") for im in images}))
         OH, OW = plans[0][4]
         C_ = images[0].shape[2]
+        mean = utils.mean_pixel(cfg, C_)
         batch = torch.empty((len(images), OH, OW, C_), dtype=torch.float32, device=dev)
         metas, windows = [], []
         for i, (image, (scale, out_hw, padding, window, canvas)) in enumerate(zip(images, plans)):
@@ -413,14 +432,16 @@ class MaskRCNN(object):
                 src = image.contiguous()
             else:
                 src = torch.from_numpy(np.ascontiguousarray(image)).to(dev, non_blocking=True)
-            ops.mold_image_u8(src, out_hw, (padding[0][0], padding[1][0]), canvas, cfg.MEAN_PIXEL, out=batch[i])
+            mold = ops.mold_image_u8 if src.dtype == torch.uint8 else ops.mold_image_f32
+            mold(src, out_hw, (padding[0][0], padding[1][0]), canvas, mean, out=batch[i])
             metas.append(utils.compose_image_meta(0, tuple(image.shape), (OH, OW, C_), window, scale,
                                                   np.zeros([cfg.NUM_CLASSES], dtype=np.int32)))
             windows.append(window)
         return batch, np.stack(metas), np.stack(windows)
 
     def _check_device_images(self, images):
-        """True when `images` holds torch tensors; ValueError for one that is not a uint8 [h, w, C <= 4] tensor on the engine's device."""
+        """True when `images` holds torch tensors; ValueError for one that is not a uint8 or float32 [h, w, C <= 4] tensor on the
+        engine's device."""
         import torch
         d = torch.device(self.engine.dev)
         found = False
@@ -430,9 +451,24 @@ class MaskRCNN(object):
             found = True
             if not image.is_cuda or image.device.index != (torch.cuda.current_device() if d.index is None else d.index):
                 raise ValueError("detect: image tensor on %s, the model runs on %s (host images go in as NumPy arrays)" % (image.device, d))
-            if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] > 4:
-                raise ValueError("detect: device images must be uint8 [h, w, C <= 4] (got %s %r)" % (image.dtype, tuple(image.shape)))
+            if image.dtype not in (torch.uint8, torch.float32) or image.dim() != 3 or not 1 <= image.shape[2] <= 4:
+                raise ValueError("detect: device images must be uint8 or float32 [h, w, C <= 4] (got %s %r)" % (image.dtype, tuple(image.shape)))
         return found
+
+    def _model_images(self, images, what):
+        """`images` as the model takes them: a 2-D image is [H, W, 1] to a 1-channel model (and to no other); ValueError for an
+        image whose channel count is not the model's -- the stem would read it with the wrong stride."""
+        C_ = utils.image_channels(self.config)
+        out = []
+        for image in images:
+            shape = tuple(image.shape)
+            if len(shape) == 2 and C_ == 1:
+                image = image[:, :, None]
+            elif len(shape) != 3 or shape[2] != C_:
+                raise ValueError("%s: image of shape %r given to a model of %d input channel(s) (IMAGE_SHAPE %r)" % (
+                    what, shape, C_, tuple(int(v) for v in self.config.IMAGE_SHAPE)))
+            out.append(image)
+        return out
 
     def _unmold_boxes(self, detections, original_image_shape, image_shape, window):
         """Host half of unmold_detections (mrcnn/model.py:2578-2605): the rows before the first class id 0, boxes from
@@ -564,7 +600,8 @@ class MaskRCNN(object):
         if timing is not None:
             import time
             timing["start"] = time.perf_counter()
-        molded = self._mold_inputs_device(images)                  # uint8 images: scaled / padded / mean-subtracted on the GPU
+        images = self._model_images(images, "detect")
+        molded = self._mold_inputs_device(images)                  # uint8 / float32 images: scaled / padded / mean-subtracted on the GPU
         if molded is None:
             molded = self.mold_inputs(images)
         molded_images, image_metas, windows = molded
@@ -590,6 +627,9 @@ class MaskRCNN(object):
         image_shape = molded_images[0].shape
         for g in molded_images[1:]:
             assert g.shape == image_shape, "Images must have the same size"
+        C_ = utils.image_channels(self.config)
+        if len(image_shape) != 3 or image_shape[2] != C_:
+            raise ValueError("detect_molded: molded images of shape %r given to a model of %d input channel(s)" % (tuple(image_shape), C_))
         out = self._run_graph(np.asarray(molded_images), image_metas)
         shapes = [im.shape for im in molded_images]
         return self._detect_results(out, shapes, shapes, [[0, 0, s[0], s[1]] for s in shapes])

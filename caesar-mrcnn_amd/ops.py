@@ -1085,6 +1085,42 @@ def mold_image_u8(src, out_hw, pad_tl, canvas_hw, mean_pixel, out=None):
     return out
 
 
+def mold_image_f32(src, out_hw, pad_tl, canvas_hw, mean_pixel, out=None):
+    """mold_image_u8's float32 twin (mrcnn_mold_image_f32): src [h, w, C] float32 device (C <= 4) -> float32 [OH, OW, C]: the image
+    scaled to out_hw (bilinear in float64, np.clip to the image's minimum / maximum, rounded to float32 as resize_image's
+    astype(dtype) does; a copy when out_hw == (h, w)) at pad_tl inside a zero canvas, minus mean_pixel (float64), rounded to
+    float32 -- MaskRCNN.mold_inputs followed by the graph's float32 cast, bit for bit apart from the payload of a NaN.  A NaN in
+    an image that is scaled makes the scaled image NaN throughout, as np.clip with NaN bounds does.  ValueError for malformed
+    input; it allocates, launches and writes nothing then."""
+    import numpy as np
+    if not torch.is_tensor(src) or src.dtype != torch.float32 or src.dim() != 3 or not src.is_contiguous():
+        raise ValueError("mold_image_f32: src must be a contiguous float32 [h, w, C] tensor")
+    h, w, C_ = (int(v) for v in src.shape)
+    if h < 1 or w < 1 or not 1 <= C_ <= 4:
+        raise ValueError("mold_image_f32: src %r must be non-empty with 1 to 4 channels" % ((h, w, C_),))
+    try:
+        (oh, ow), (top, left), (OH, OW) = (int(v) for v in out_hw), (int(v) for v in pad_tl), (int(v) for v in canvas_hw)
+    except (TypeError, ValueError):
+        raise ValueError("mold_image_f32: out_hw, pad_tl and canvas_hw must be pairs of integers")
+    if oh < 1 or ow < 1 or top < 0 or left < 0 or top + oh > OH or left + ow > OW or max(OH, OW, h, w) >= 2 ** 31:
+        raise ValueError("mold_image_f32: a %d x %d image at %r does not fit the %d x %d canvas" % (oh, ow, (top, left), OH, OW))
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (OH, OW, C_)
+                            or not out.is_contiguous() or out.device != src.device or out.data_ptr() == src.data_ptr()):
+        raise ValueError("mold_image_f32: out must be a contiguous float32 [%d, %d, %d] tensor on src's device, not src itself"
+                         % (OH, OW, C_))
+    m = np.asarray(mean_pixel, np.float64).reshape(-1)
+    if m.size not in (1, C_):
+        raise ValueError("mold_image_f32: mean_pixel %r does not fit %d channel(s)" % (mean_pixel, C_))
+    _need_cuda(src)
+    if out is None:
+        out = torch.empty((OH, OW, C_), dtype=torch.float32, device=src.device)
+    ws = workspace(int(_hip.lib().mrcnn_mold_image_f32_workspace_bytes()), src.device, "mold_f32")
+    mean = (C.c_double * C_)(*[float(v) for v in np.broadcast_to(m, (C_,))])
+    check(_hip.lib().mrcnn_mold_image_f32(ptr(src), h, w, C_, oh, ow, top, left, OH, OW, mean, ptr(out), ptr(ws), ws.numel(),
+                                          current_stream()), "mrcnn_mold_image_f32")
+    return out
+
+
 def _augment_matrix(m):
     import numpy as np
     m = np.asarray(m, dtype=np.float64).reshape(-1)

@@ -24,8 +24,9 @@ class LayerSpec(object):
         self.stride, self.padding, self.group = stride, padding, group
 
 
-def backbone_layers(arch):
-    """Conv layers of resnet_graph / custom_backbone (model.py:175-244) in forward order."""
+def backbone_layers(arch, in_channels=3):
+    """Conv layers of resnet_graph / custom_backbone (model.py:175-244) in forward order.  in_channels: the stem's input
+    channels (config.IMAGE_SHAPE[2]: 3, or 1 for a gray-level model)."""
     if arch == "custom":
         stem, stages = 16, [(2, [16, 16, 64], "abc"), (3, [32, 32, 128], "abcd"), (4, [64, 64, 256], "ab"),
                             (5, [128, 128, 512], "abc")]
@@ -34,7 +35,7 @@ def backbone_layers(arch):
         stem, stages = 64, [(2, [64, 64, 256], "abc"), (3, [128, 128, 512], "abcd"),
                             (4, [256, 256, 1024], "a" + "".join(chr(98 + i) for i in range(n4))),
                             (5, [512, 512, 2048], "abc")]
-    L = [LayerSpec("conv1", "conv", (7, 7, 3, stem), bn="bn_conv1", stride=2, padding=(3, 3))]
+    L = [LayerSpec("conv1", "conv", (7, 7, in_channels, stem), bn="bn_conv1", stride=2, padding=(3, 3))]
     cin = stem
     for stage, (f1, f2, f3), blocks in stages:
         for bi, b in enumerate(blocks):
@@ -53,7 +54,8 @@ def model_layers(config):
     arch = config.BACKBONE
     if callable(arch):
         raise NotImplementedError("callable BACKBONE is a TF-graph hook and has no meaning here")
-    L, (c2, c3, c4, c5) = backbone_layers(arch)
+    from .utils import image_channels
+    L, (c2, c3, c4, c5) = backbone_layers(arch, image_channels(config))
     P = config.TOP_DOWN_PYRAMID_SIZE
     C = config.NUM_CLASSES
     na = len(config.RPN_ANCHOR_RATIOS)

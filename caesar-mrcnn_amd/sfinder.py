@@ -378,13 +378,24 @@ class SFinder(object):
                                  cfg.ZSCALE_CONTRASTS, cfg.IMG_CONTRAST, cfg.IMG_BIAS)
 
     def _tiles_batched(self):
-        """True when run_parallel takes the batched front end: tile_batch set and read_fits flags the device chain computes and
-        that end in a uint8 RGB image (RGB, uint8, zscale or the bias / contrast stretch; NORMALIZE_IMG either way -- the RGB
-        conversion normalises anyway).  detect()'s device molding takes uint8 only: gray or float32 tiles keep the loop."""
+        """True when run_parallel takes the batched front end: tile_batch set and read_fits flags the device chain computes
+        (fits.device_chain: uint8 RGB, float32 RGB or float32 gray tiles).  A chain whose image does not have the model's input
+        channels -- gray tiles for an RGB model or the reverse -- is a configuration error: ValueError, no fallback.  The channels
+        are those of the MaskRCNN's stem; an object without an engine (a test's stand-in for the model) is handed uint8 RGB tiles
+        only, as before."""
         if self.tile_batch < 1:
             return False
         chain, _ = self._tiles_chain()
-        return chain is not None and chain.out_kind == 0
+        if chain is None:
+            return False
+        layout = getattr(getattr(self.model, "engine", None), "layout", None)
+        if layout is None:                       # not a MaskRCNN (stand-in models of the tests): uint8 RGB tiles, what it always got
+            return chain.out_kind == 0
+        model_c = int(layout.by_name["conv1"].shape[2])
+        if (1 if chain.out_kind == 2 else 3) != model_c:
+            raise ValueError("tile_batch: the read_fits flags give %s tiles, the model's first layer takes %d channel(s) (IMG_TO_RGB %r)"
+                             % ("gray" if chain.out_kind == 2 else "RGB", model_c, self.config.IMG_TO_RGB))
+        return True
 
     def _read_header(self):
         """The header of the image; on the batched path from the ONE read of the file that also gives the plane."""
@@ -473,9 +484,9 @@ class SFinder(object):
                 status = self._run_tasks_batched(tasks)
             else:
                 if self.tile_batch >= 1:
-                    logger.info("[PROC %d] tile_batch = %d ignored: the read_fits flags do not end in a uint8 RGB image the device chain "
-                                "computes (%s); tiles are read and detected one at a time" % (
-                                    self.procId, self.tile_batch, self._tiles_chain()[1] or "gray or float32 tiles"))
+                    logger.info("[PROC %d] tile_batch = %d ignored: %s; tiles are read and detected one at a time" % (
+                        self.procId, self.tile_batch, self._tiles_chain()[1] or "the model has no engine to read its input channels "
+                        "from, and the tiles are not uint8 RGB"))
                 for j, task in enumerate(tasks):
                     logger.info("[PROC %d] Start processing of task id %d (%d/%d) ..." % (self.procId, task.tid, j + 1, len(tasks)))
                     if self._run_task(j, task, task.find_sources) < 0:
@@ -559,10 +570,10 @@ class SFinder(object):
             (task.ix_max - task.ix_min) * (task.iy_max - task.iy_min) <= fits.DEVICE_TILE_MAX_PIXELS
 
     def prepare_tile_images(self, tasks):
-        """The network input images of `tasks`' tiles, in order: uint8 [h, w, 3] device tensors, cut from the resident plane (as
-        NumPy slicing cuts: clipped to the plane), NaN-filled, stretched, normalised and converted in one ops.fits_tiles_to_rgb
-        call (the run.py flags) or one ops.fits_tiles_to_image call (any other combination _tiles_batched() accepts) -- byte for
-        byte what fits.read_fits gives per tile."""
+        """The network input images of `tasks`' tiles, in order: device tensors -- uint8 [h, w, 3], float32 [h, w, 3] or, gray,
+        float32 [h, w, 1] -- cut from the resident plane (as NumPy slicing cuts: clipped to the plane), NaN-filled, stretched,
+        normalised and converted in one ops.fits_tiles_to_rgb call (the run.py flags) or one ops.fits_tiles_to_image call (any
+        other combination _tiles_batched() accepts) -- value for value what fits.read_fits gives per tile."""
         from . import ops
         plane_t, big = self._plane_device()
         ny, nx = int(plane_t.shape[0]), int(plane_t.shape[1])
@@ -571,11 +582,14 @@ class SFinder(object):
             x0, x1, y0, y1 = min(t.ix_min, nx), min(t.ix_max, nx), min(t.iy_min, ny), min(t.iy_max, ny)
             rects.append((x0, y0, x1 - x0, y1 - y0))
         chain, why = self._tiles_chain()
-        if chain is None or chain.out_kind != 0:
-            raise RuntimeError("prepare_tile_images: the read_fits flags are not the device chain's (%s)" % (why or "no uint8 RGB image"))
+        if chain is None:
+            raise RuntimeError("prepare_tile_images: the read_fits flags are not the device chain's (%s)" % why)
         if chain.default:
             return ops.fits_tiles_to_rgb(plane_t, rects, self._zscale_contrasts(), big_endian=big)
-        return ops.fits_tiles_to_image(plane_t, rects, chain, big_endian=big)
+        images = ops.fits_tiles_to_image(plane_t, rects, chain, big_endian=big)
+        if chain.out_kind == 2:
+            images = [im.view(im.shape[0], im.shape[1], 1) for im in images]      # the model's gray image is [h, w, 1]
+        return images
 
     def _zscale_contrasts(self):
         zc = self.config.ZSCALE_CONTRASTS

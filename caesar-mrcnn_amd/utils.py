@@ -288,12 +288,33 @@ def parse_image_meta(meta):
             "scale": meta[:, 11].astype(np.float32), "active_class_ids": meta[:, 12:].astype(np.int32)}
 
 
+def image_channels(config):
+    """Channels of the model's input image: config.IMAGE_SHAPE[2].  The stem convolution exists for 3 (RGB) and 1 (gray:
+    run.py --grayimg, an image is [H, W, 1]); anything else is a ValueError here, not a shape error three layers down."""
+    c = int(np.asarray(config.IMAGE_SHAPE).reshape(-1)[2])
+    if c not in (1, 3):
+        raise ValueError("IMAGE_SHAPE %r: the model takes images of 1 (gray) or 3 (RGB) channels, not %d" % (
+            tuple(int(v) for v in np.asarray(config.IMAGE_SHAPE).reshape(-1)), c))
+    return c
+
+
+def mean_pixel(config, channels=None):
+    """config.MEAN_PIXEL as every consumer reads it: a float64 vector of `channels` values (default: the model's).  The
+    reference's gray-level setting is the scalar 0 (scripts/run.py:898); a scalar or a length-1 sequence stands for every
+    channel, any other length must be `channels`."""
+    c = image_channels(config) if channels is None else int(channels)
+    m = np.asarray(config.MEAN_PIXEL, dtype=np.float64).reshape(-1)
+    if m.size not in (1, c):
+        raise ValueError("MEAN_PIXEL %r does not fit images of %d channel(s)" % (config.MEAN_PIXEL, c))
+    return np.ascontiguousarray(np.broadcast_to(m, (c,)))
+
+
 def mold_image(images, config):
-    return images.astype(np.float32) - config.MEAN_PIXEL
+    return images.astype(np.float32) - mean_pixel(config, images.shape[-1])
 
 
 def unmold_image(normalized_images, config):
-    return (normalized_images + config.MEAN_PIXEL).astype(np.uint8)
+    return (normalized_images + mean_pixel(config, normalized_images.shape[-1])).astype(np.uint8)
 
 
 # ---- evaluation helpers used by the test driver (mrcnn/utils.py:725-862) ---------------------------

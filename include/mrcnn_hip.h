@@ -723,6 +723,18 @@ int mrcnn_mold_image_u8(const void* src, int h, int w, int C, int oh, int ow, in
  * min / max and truncation per value, zero padding.  Same arguments, refusals and workspace.                              */
 int mrcnn_resize_image_u8(const void* src, int h, int w, int C, int oh, int ow, int top, int left, int OH, int OW, void* out,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* The float32 twin of mrcnn_mold_image_u8, for read_fits' float32 RGB and gray images: src [h, w, C] float32 (C <= 4), same
+ * scalar arguments.  resize_image keeps the image's dtype: utils.resize's float64 bilinear in its order, np.clip to the source's
+ * minimum / maximum as NumPy evaluates it, rounded to float32, zero padding, minus mean_pixel in float64, rounded to float32 --
+ * MaskRCNN.mold_inputs followed by the float32 cast of the graph's input, bit for bit wherever the value is not NaN, NaN in the
+ * same places.  A NaN in a source that is scaled makes the bounds NaN and the scaled image NaN throughout (np.clip); unscaled,
+ * nothing is clipped and a NaN stays where it was.  The min / max pass runs only when (oh, ow) != (h, w): up to 1024 workgroups
+ * write one record each, a one-workgroup second stage reduces them (no atomics, bitwise reproducible; -0.0 orders below +0.0).
+ * workspace: mrcnn_mold_image_f32_workspace_bytes() bytes, 16-byte aligned (MRCNN_ERR_WORKSPACE otherwise); src / out not
+ * 4-byte aligned: MRCNN_ERR_ARG.  At most three launches on `stream`, nothing allocated or synchronised.                    */
+size_t mrcnn_mold_image_f32_workspace_bytes(void);
+int mrcnn_mold_image_f32(const void* src, int h, int w, int C, int oh, int ow, int top, int left, int OH, int OW,
+                         const double* mean_pixel, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Elementwise helpers on flat buffers. */
 int mrcnn_add_inplace(float* dst, const float* src, int64_t n, void* stream);

@@ -212,6 +212,10 @@ def build_config(args, class_dict_model):
     cfg.TRAIN_ROIS_PER_IMAGE = args.train_rois_per_image
     cfg.RPN_ANCHOR_RATIOS = [float(v) for v in args.rpn_anchor_ratios.split(",")]
     cfg.IMAGE_MIN_DIM = cfg.IMAGE_MAX_DIM = args.imgsize
+    if args.grayimg:                       # scripts/run.py:897-900 / 1686-1689: one channel, nothing subtracted, no RGB conversion
+        cfg.IMAGE_CHANNEL_COUNT = 1
+        cfg.MEAN_PIXEL = np.zeros(1)
+        cfg.IMG_TO_RGB = False
     cfg.IMAGE_SHAPE = np.array([args.imgsize, args.imgsize, cfg.IMAGE_CHANNEL_COUNT])
     cfg.ZSCALE_STRETCH, cfg.IMG_TO_UINT8, cfg.NORMALIZE_IMG = args.zscale, args.to_uint8, args.norm_img
     cfg.ZSCALE_CONTRASTS = [float(v) for v in args.zscale_contrasts.split(",")]
@@ -235,6 +239,7 @@ def make_dataset(args, path):
     if ds.set_class_dict(args.classdict) < 0:
         return None
     ds.apply_zscale, ds.convert_to_uint8 = args.zscale, args.to_uint8
+    ds.convert_to_rgb = not args.grayimg              # gray: load_image returns float32 [H, W, 1]
     ds.zscale_contrasts = [float(v) for v in args.zscale_contrasts.split(",")]
     ds.apply_biascontrast, ds.bias, ds.contrast = args.biascontrast, args.bias, args.contrast
     if args.dataloader == 'datalist':
@@ -421,12 +426,14 @@ def detect(args, model, cfg):
         if t % world != rank:            # tiles are independent: replicas only (sfinder.py:1235-1251 round-robin)
             continue
         res = fits.read_fits(args.image, xmin, xmax, ymin, ymax, stretch=cfg.ZSCALE_STRETCH,
-                             zscale_contrasts=cfg.ZSCALE_CONTRASTS, normalize=cfg.NORMALIZE_IMG, convertToRGB=True,
+                             zscale_contrasts=cfg.ZSCALE_CONTRASTS, normalize=cfg.NORMALIZE_IMG, convertToRGB=cfg.IMG_TO_RGB,
                              to_uint8=cfg.IMG_TO_UINT8, stretch_biascontrast=cfg.BIAS_CONTRAST_STRETCH, bias=cfg.IMG_BIAS,
                              contrast=cfg.IMG_CONTRAST)
         if res is None:
             return -1
         image, header = res
+        if image.ndim == 2:                  # --grayimg: the model's gray image is [H, W, 1]
+            image = image[:, :, None]
         analyzer.obj_name_tag = "t%d" % t if len(tiles) > 1 else ""
         if analyzer.predict(image, image_id=base, header=header, xmin=max(xmin, 0), ymin=max(ymin, 0)) < 0:
             logger.error("Failed to run model prediction on image %s!" % args.image)

@@ -4,7 +4,7 @@ leaves untouched -- against the batched, device-resident front end at tile_batch
 Prints one JSON object and writes it with --out (default profiles/sfinder_tiles_bench.json).
 
     python tools/sfinder_tiles_bench.py [--sizes 2304[,4352]] [--max-instances 10] [--tile 512] [--step 0.5] [--backbone resnet101] [--imgsize 256]
-                                        [--reps 3] [--batches 1,4,8] [--bias-contrast BIAS,CONTRAST] [--out FILE]
+                                        [--reps 3] [--batches 1,4,8] [--bias-contrast BIAS,CONTRAST] [--no-uint8 | --gray] [--out FILE]
 
 One process, one GPU, one set of seeded weights: a model per batch size (1 serves the loop and tile_batch = 1), every model
 warmed on a few tiles first (library load, graph capture, allocator).  Per mosaic size:
@@ -91,6 +91,9 @@ def main():
     ap.add_argument("--bias-contrast", default=None,
                     help="BIAS,CONTRAST: BIAS_CONTRAST_STRETCH on (after zscale) with these values in every variant; the batched front end "
                          "then runs ops.fits_tiles_to_image")
+    ap.add_argument("--no-uint8", action="store_true", help="IMG_TO_UINT8 off in every variant: float32 RGB tiles (run.py --no_uint8)")
+    ap.add_argument("--gray", action="store_true",
+                    help="a gray-level model and gray tiles in every variant (run.py --grayimg): one input channel, IMG_TO_RGB off")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sfinder_tiles_bench.json"))
     args = ap.parse_args()
     import torch
@@ -122,6 +125,11 @@ def main():
         cfg.TILE_XSTEP = cfg.TILE_YSTEP = args.step
         cfg.MAX_NTASKS_PER_WORKER = 1 << 30
         cfg.IMG_XMIN = cfg.IMG_XMAX = cfg.IMG_YMIN = cfg.IMG_YMAX = -1
+        if args.no_uint8:
+            cfg.IMG_TO_UINT8 = False
+        if args.gray:
+            cfg.IMAGE_CHANNEL_COUNT, cfg.MEAN_PIXEL, cfg.IMG_TO_RGB = 1, 0, False
+            cfg.IMAGE_SHAPE = np.array([args.imgsize, args.imgsize, 1])
         if args.bias_contrast:
             cfg.BIAS_CONTRAST_STRETCH = True
             cfg.IMG_BIAS, cfg.IMG_CONTRAST = [float(v) for v in args.bias_contrast.split(",")]
@@ -175,7 +183,8 @@ def main():
 
     res = {"device": torch.cuda.get_device_name(0), "backbone": args.backbone, "imgsize": args.imgsize, "tile": args.tile, "step": args.step,
            "reps": args.reps, "weights": "random, seed %d" % args.seed, "detection_max_instances": args.max_instances, "hip_graph": True,
-           "bias_contrast": [float(v) for v in args.bias_contrast.split(",")] if args.bias_contrast else None, "mosaics": []}
+           "bias_contrast": [float(v) for v in args.bias_contrast.split(",")] if args.bias_contrast else None,
+           "tiles_kind": "float32 gray" if args.gray else ("float32 RGB" if args.no_uint8 else "uint8 RGB"), "mosaics": []}
     variants = [0] + batches
     for size in [int(v) for v in args.sizes.split(",")]:
         path = os.path.join(tmp, "mosaic_%d.fits" % size)
