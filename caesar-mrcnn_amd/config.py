@@ -75,8 +75,8 @@ class Config(object):
     # MRCNN_TRAIN_TAPE=0 switches it off.  Data-parallel runs keep eager launches (gradient hooks are not recorded).
     TRAIN_LAUNCH_TAPE = os.environ.get("MRCNN_TRAIN_TAPE", "1") != "0"
     # FITS tiles of the training / validation datasets: NaN fill, zscale, normalisation and the uint8 RGB conversion of
-    # utils.read_fits (mrcnn/utils.py:1088-1157) on the GPU (mrcnn_fits_to_rgb; byte-identical images), from the loader threads;
-    # with other stretch flags (bias / contrast stretch, no zscale, float32 or gray images) mrcnn_fits_to_image, for every
+    # utils.read_fits (mrcnn/utils.py:1088-1157) on the GPU (mrcnn_fits_to_image; byte-identical images), from the loader threads;
+    # the same chain with other stretch flags (bias / contrast stretch, no zscale, float32 or gray images), for every
     # combination fits.device_chain accepts
     DEVICE_FITS = os.environ.get("MRCNN_DEVICE_FITS", "1") != "0"
     # extension: MaskRCNN.train's generators assemble every training sample on the GPU (gtprep.py, csrc/gtprep.hip): the image

@@ -1,26 +1,28 @@
-// FITS tile -> network input image on the device: the numeric part of utils.read_fits (mrcnn/utils.py:1033-1163) as the
-// run.py path calls it (stretch = normalize = convertToRGB = to_uint8 = True, no bias / contrast stretch):
+// FITS tile -> network input image on the device: the numeric part of utils.read_fits (mrcnn/utils.py:1033-1163).  As the run.py
+// path calls it (stretch = normalize = convertToRGB = to_uint8 = True, no bias / contrast stretch):
 //   out = data.astype(float32); out[isnan(out)] = nanmin(out)                                   (:1088-1091)
 //   per channel c (zscale contrast zc):  ZScaleInterval(contrast=zc)(out)  -> [0, 1]            (:1101-1111, stretch_img :1166-1172)
 //                                        / max                                                  (normalize_img :1182-1188)
 //   uint8 RGB = round(255 * channel)                                                            (gray2rgb :1190-1208)
+// and every other flag combination through the same three launches (the descriptor mrcnn_fits_chain; the second part of this file).
 // astropy's ZScaleInterval [3P, SURVEY App. C-6] is the restatement of caesar-mrcnn_amd/fits.py:zscale_limits (<= 1000 strided
 // samples of the finite values, sorted; <= 5 rounds of a straight-line fit with 2.5 sigma rejection grown by 1 % of the samples;
 // limits = median -/+ slope / contrast, clamped to the sample range).  Three launches: per-chunk statistics (+ byte swap of the
-// big-endian FITS floats), ONE workgroup for sampling / sort / fit, one pass that writes the bytes.  The per-pixel arithmetic is
+// big-endian FITS floats), ONE workgroup for sampling / sort / fit, one pass that writes the image.  The per-pixel arithmetic is
 // the host's, type for type (float32 subtraction, float64 division and clip, float32 normalisation, round-half-even), so the
-// uint8 image is identical to fits.read_fits's; the fit uses the closed form of the weighted least-squares line where the host
+// image is identical to fits.read_fits's; the fit uses the closed form of the weighted least-squares line where the host
 // goes through numpy.polyfit's SVD (agreement ~1e-15 relative in the limits: far below half a grey level).
 //
-// mrcnn_fits_tiles_to_rgb runs the same three stages over T tiles of ONE resident plane (the mosaic of the tiled source finder)
+// mrcnn_fits_tiles_to_image runs the same three stages over T tiles of ONE resident plane (the mosaic of the tiled source finder)
 // with the tile as a grid dimension: the statistics pass reads every tile row as a strided segment of the plane (consecutive
 // lanes = consecutive pixels of a row: a wavefront's loads stay in one row segment, two at a row end) and leaves the tile's
 // native-endian values row-major and contiguous in the workspace, so the sampling and the pixel pass address a tile exactly as
-// the single-tile path does -- the bodies below are shared, not copied.
+// the single-tile path does -- the bodies below are shared, not copied.  mrcnn_fits_to_rgb / mrcnn_fits_tiles_to_rgb are these
+// entries with the run.py descriptor.
 //
 // mrcnn_mosaic_overview (at the end of this file) stretches a WHOLE plane of any size up to 2^31 - 1 pixels and shrinks it by
 // block maxima: the same statistics per 1024-pixel chunk, a two-level scan of the chunks' finite counts instead of the one LDS
-// table, the sampling from the plane where it lies (no native-endian copy), then fits_zscale_fit and fits_byte as above.
+// table, the sampling from the plane where it lies (no native-endian copy), then fits_zscale_fit and fits_byte.
 #include "common.h"
 #include <math.h>
 
@@ -281,37 +283,11 @@ __device__ __forceinline__ void fits_zscale_body(const float* __restrict__ vals,
     fits_zscale_fit(s_samp, s_red, npix, fill, dmax, c0, c1, c2, params);
 }
 
-__global__ __launch_bounds__(1024) void fits_zscale_kernel(const float* __restrict__ vals, long long n, int nchunks,
-                                                           const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
-                                                           FitsParams* __restrict__ params) {
-    fits_zscale_body(vals, n, nchunks, chunks, c0, c1, c2, params);
-}
-
-// one channel's byte of a (NaN-filled) pixel value
+// one channel's byte of a (NaN-filled) pixel value on the run.py path (the mosaic overview's pixel pass)
 __device__ __forceinline__ unsigned char fits_byte(float v, const FitsChannel& c) {
     const float s = fits_stretch(v, c);
     const float q = rintf((s / c.cmax) * 255.f);                         // normalize_img (float32), gray2rgb: (c * 255).round()
     return (q >= 0.f && q <= 255.f) ? (unsigned char)q : (unsigned char)0;             // 0 / 0 (constant tile): NaN -> 0
-}
-
-// pixel i of a tile: its three bytes
-__device__ __forceinline__ void fits_rgb_pixel(const float* __restrict__ vals, long long i, const FitsParams& p,
-                                               unsigned char* __restrict__ rgb) {
-    unsigned char o[3] = {0, 0, 0};
-    if (!p.all_nan) {
-        float v = vals[i];
-        if (v != v) v = p.fill;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[c] = fits_byte(v, p.ch[c]);
-    }
-    rgb[i * 3 + 0] = o[0]; rgb[i * 3 + 1] = o[1]; rgb[i * 3 + 2] = o[2];
-}
-
-__global__ __launch_bounds__(256) void fits_rgb_kernel(const float* __restrict__ vals, long long n, const FitsParams* __restrict__ params,
-                                                       unsigned char* __restrict__ rgb) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    fits_rgb_pixel(vals, i, *params, rgb);
 }
 
 // ---- T tiles of one plane: the tile is grid dimension y (stats, pixels) or x (zscale) ------------------------------------------
@@ -328,45 +304,11 @@ __global__ __launch_bounds__(256) void fits_tiles_stats_kernel(const unsigned* _
     fits_stats_body(plane, addr, vals + t.pixel_offset, n, big_endian, (int)blockIdx.x, chunks + t.chunk_offset);
 }
 
-__global__ __launch_bounds__(1024) void fits_tiles_zscale_kernel(const mrcnn_fits_tile* __restrict__ tiles, const float* __restrict__ vals,
-                                                                 const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
-                                                                 FitsParams* __restrict__ params) {
-    const mrcnn_fits_tile t = tiles[blockIdx.x];
-    const long long n = (long long)t.w * t.h;
-    fits_zscale_body(vals + t.pixel_offset, n, (int)fits_tile_chunks(n), chunks + t.chunk_offset, c0, c1, c2, params + blockIdx.x);
-}
-
-__global__ __launch_bounds__(256) void fits_tiles_rgb_kernel(const mrcnn_fits_tile* __restrict__ tiles, const float* __restrict__ vals,
-                                                             const FitsParams* __restrict__ params, unsigned char* __restrict__ rgb) {
-    const mrcnn_fits_tile t = tiles[blockIdx.y];
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)t.w * t.h) return;
-    fits_rgb_pixel(vals + t.pixel_offset, i, params[blockIdx.y], rgb + 3 * t.pixel_offset);
-}
-
 extern "C" size_t mrcnn_fits_workspace(int H, int W) {
     if (H <= 0 || W <= 0) return 0;
     const long long n = (long long)H * W;
     const long long chunks = (n + FITS_CHUNK - 1) / FITS_CHUNK;
     return (size_t)n * sizeof(float) + (size_t)chunks * sizeof(FitsChunk) + 256;
-}
-
-extern "C" int mrcnn_fits_to_rgb(const void* raw, int big_endian, int H, int W, const double* zscale_contrasts, void* rgb, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-    if (!raw || !rgb || !zscale_contrasts || H <= 0 || W <= 0) return MRCNN_ERR_ARG;
-    const long long n = (long long)H * W;
-    const long long chunks = (n + FITS_CHUNK - 1) / FITS_CHUNK;
-    if (chunks > FITS_MAX_CHUNKS) return MRCNN_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < mrcnn_fits_workspace(H, W)) return MRCNN_ERR_WORKSPACE;
-    float* vals = (float*)workspace;
-    FitsChunk* ch = (FitsChunk*)(vals + n);
-    FitsParams* params = (FitsParams*)(((uintptr_t)(ch + chunks) + 63) & ~(uintptr_t)63);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(fits_stats_kernel, dim3((unsigned)chunks), dim3(256), 0, s, (const unsigned*)raw, vals, n, big_endian, ch);
-    hipLaunchKernelGGL(fits_zscale_kernel, dim3(1), dim3(1024), 0, s, vals, n, (int)chunks, ch, zscale_contrasts[0], zscale_contrasts[1],
-                       zscale_contrasts[2], params);
-    hipLaunchKernelGGL(fits_rgb_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, vals, n, params, (unsigned char*)rgb);
-    return mrcnn_launch_status();
 }
 
 // Host-side check of a tile table: every rectangle inside the plane and within the chunk limit, the pools laid out back to back
@@ -404,29 +346,18 @@ extern "C" size_t mrcnn_fits_tiles_workspace(const mrcnn_fits_tile* tiles, int T
     return (size_t)l.pixels * sizeof(float) + (size_t)l.chunks * sizeof(FitsChunk) + (size_t)T * sizeof(FitsParams) + 256;
 }
 
-extern "C" int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY, int NX, const mrcnn_fits_tile* tiles_host,
-                                       const mrcnn_fits_tile* tiles_dev, int T, const double* zscale_contrasts, void* rgb, size_t rgb_bytes,
-                                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (!plane || !rgb || !zscale_contrasts || !tiles_dev) return MRCNN_ERR_ARG;
-    FitsTilesLayout l;
-    const int rc = fits_tiles_layout(tiles_host, T, NY, NX, &l);
-    if (rc != MRCNN_OK) return rc;
-    if (rgb_bytes < (size_t)l.pixels * 3) return MRCNN_ERR_ARG;
-    if (!workspace || workspace_bytes < mrcnn_fits_tiles_workspace(tiles_host, T, NY, NX)) return MRCNN_ERR_WORKSPACE;
-    float* vals = (float*)workspace;
-    FitsChunk* ch = (FitsChunk*)(vals + l.pixels);
-    FitsParams* params = (FitsParams*)(((uintptr_t)(ch + l.chunks) + 63) & ~(uintptr_t)63);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(fits_tiles_stats_kernel, dim3((unsigned)l.max_chunks, (unsigned)T), dim3(256), 0, s, (const unsigned*)plane,
-                       (long long)NX, big_endian, tiles_dev, vals, ch);
-    hipLaunchKernelGGL(fits_tiles_zscale_kernel, dim3((unsigned)T), dim3(1024), 0, s, tiles_dev, (const float*)vals, (const FitsChunk*)ch,
-                       zscale_contrasts[0], zscale_contrasts[1], zscale_contrasts[2], params);
-    hipLaunchKernelGGL(fits_tiles_rgb_kernel, dim3((unsigned)cdiv64(l.max_pixels, 256), (unsigned)T), dim3(256), 0, s, tiles_dev,
-                       (const float*)vals, (const FitsParams*)params, (unsigned char*)rgb);
-    return mrcnn_launch_status();
+// a workspace of either size above: the native-endian values, the chunk table, the tiles' parameters (64-byte aligned)
+struct FitsWorkspace { float* vals; FitsChunk* ch; FitsParams* params; };
+
+static FitsWorkspace fits_carve(void* workspace, long long pixels, long long chunks) {
+    FitsWorkspace w;
+    w.vals = (float*)workspace;
+    w.ch = (FitsChunk*)(w.vals + pixels);
+    w.params = (FitsParams*)(((uintptr_t)(w.ch + chunks) + 63) & ~(uintptr_t)63);
+    return w;
 }
 
-// ---- every flag combination of read_fits: mrcnn_fits_to_image / mrcnn_fits_tiles_to_image (include/mrcnn_hip.h) -----------------
+// ---- the chain and its entries: mrcnn_fits_to_image / mrcnn_fits_tiles_to_image (include/mrcnn_hip.h) -------------------------
 // The host statement, per channel c of zscale contrast zc (caesar-mrcnn_amd/fits.py:read_fits):
 //   c = out (float32, NaN-filled)
 //   zscale:        c = float32(stretch_img(c, zc))                                   fits_zscale_* and fits_stretch above
@@ -527,17 +458,17 @@ __global__ __launch_bounds__(256) void fits_tiles_minmax_kernel(const mrcnn_fits
     fits_minmax_body(n, (int)fits_tile_chunks(n), chunks + t.chunk_offset, d, params + blockIdx.x);
 }
 
-// the zscale workgroup of the older entries, then the maxima of the whole chain (thread 0 wrote the parameters it now reads)
-__global__ __launch_bounds__(1024) void fits_zscale_chain_kernel(const float* __restrict__ vals, long long n, int nchunks,
-                                                                 const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
-                                                                 const FitsChainDev d, FitsParams* __restrict__ params) {
+// the zscale workgroup, then the maxima of the whole chain (thread 0 wrote the parameters it now reads)
+__global__ __launch_bounds__(1024) void fits_zscale_kernel(const float* __restrict__ vals, long long n, int nchunks,
+                                                           const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
+                                                           const FitsChainDev d, FitsParams* __restrict__ params) {
     fits_zscale_body(vals, n, nchunks, chunks, c0, c1, c2, params);
     if (threadIdx.x == 0) fits_chain_finish(params, d);
 }
 
-__global__ __launch_bounds__(1024) void fits_tiles_zscale_chain_kernel(const mrcnn_fits_tile* __restrict__ tiles, const float* __restrict__ vals,
-                                                                       const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
-                                                                       const FitsChainDev d, FitsParams* __restrict__ params) {
+__global__ __launch_bounds__(1024) void fits_tiles_zscale_kernel(const mrcnn_fits_tile* __restrict__ tiles, const float* __restrict__ vals,
+                                                                 const FitsChunk* __restrict__ chunks, double c0, double c1, double c2,
+                                                                 const FitsChainDev d, FitsParams* __restrict__ params) {
     const mrcnn_fits_tile t = tiles[blockIdx.x];
     const long long n = (long long)t.w * t.h;
     fits_zscale_body(vals + t.pixel_offset, n, (int)fits_tile_chunks(n), chunks + t.chunk_offset, c0, c1, c2, params + blockIdx.x);
@@ -691,20 +622,18 @@ extern "C" int mrcnn_fits_to_image(const void* raw, int big_endian, int H, int W
     const long long chunks = (n + FITS_CHUNK - 1) / FITS_CHUNK;
     if (out_bytes < (size_t)n * fits_image_pixel_bytes(d.out_kind)) return MRCNN_ERR_ARG;
     if (!workspace || workspace_bytes < mrcnn_fits_workspace(H, W)) return MRCNN_ERR_WORKSPACE;
-    float* vals = (float*)workspace;
-    FitsChunk* ch = (FitsChunk*)(vals + n);
-    FitsParams* params = (FitsParams*)(((uintptr_t)(ch + chunks) + 63) & ~(uintptr_t)63);
+    const FitsWorkspace w = fits_carve(workspace, n, chunks);
     d.vec = (((uintptr_t)workspace | (uintptr_t)out) & 15) == 0;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(fits_stats_kernel, dim3((unsigned)chunks), dim3(256), 0, s, (const unsigned*)raw, vals, n, big_endian, ch);
+    hipLaunchKernelGGL(fits_stats_kernel, dim3((unsigned)chunks), dim3(256), 0, s, (const unsigned*)raw, w.vals, n, big_endian, w.ch);
     if (d.zscale)
-        hipLaunchKernelGGL(fits_zscale_chain_kernel, dim3(1), dim3(1024), 0, s, (const float*)vals, n, (int)chunks, (const FitsChunk*)ch,
-                           chain->zscale_contrasts[0], chain->zscale_contrasts[1], chain->zscale_contrasts[2], d, params);
+        hipLaunchKernelGGL(fits_zscale_kernel, dim3(1), dim3(1024), 0, s, (const float*)w.vals, n, (int)chunks, (const FitsChunk*)w.ch,
+                           chain->zscale_contrasts[0], chain->zscale_contrasts[1], chain->zscale_contrasts[2], d, w.params);
     else
-        hipLaunchKernelGGL(fits_minmax_kernel, dim3(1), dim3(256), 0, s, n, (int)chunks, (const FitsChunk*)ch, d, params);
-    if (d.out_kind == 0) fits_image_launch<0>(s, vals, n, params, d, out);
-    else if (d.out_kind == 1) fits_image_launch<1>(s, vals, n, params, d, out);
-    else fits_image_launch<2>(s, vals, n, params, d, out);
+        hipLaunchKernelGGL(fits_minmax_kernel, dim3(1), dim3(256), 0, s, n, (int)chunks, (const FitsChunk*)w.ch, d, w.params);
+    if (d.out_kind == 0) fits_image_launch<0>(s, w.vals, n, w.params, d, out);
+    else if (d.out_kind == 1) fits_image_launch<1>(s, w.vals, n, w.params, d, out);
+    else fits_image_launch<2>(s, w.vals, n, w.params, d, out);
     return mrcnn_launch_status();
 }
 
@@ -720,22 +649,43 @@ extern "C" int mrcnn_fits_tiles_to_image(const void* plane, int big_endian, int 
     if (rc != MRCNN_OK) return rc;
     if (out_bytes < (size_t)l.pixels * fits_image_pixel_bytes(d.out_kind)) return MRCNN_ERR_ARG;
     if (!workspace || workspace_bytes < mrcnn_fits_tiles_workspace(tiles_host, T, NY, NX)) return MRCNN_ERR_WORKSPACE;
-    float* vals = (float*)workspace;
-    FitsChunk* ch = (FitsChunk*)(vals + l.pixels);
-    FitsParams* params = (FitsParams*)(((uintptr_t)(ch + l.chunks) + 63) & ~(uintptr_t)63);
+    const FitsWorkspace w = fits_carve(workspace, l.pixels, l.chunks);
     d.vec = (((uintptr_t)workspace | (uintptr_t)out) & 15) == 0;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(fits_tiles_stats_kernel, dim3((unsigned)l.max_chunks, (unsigned)T), dim3(256), 0, s, (const unsigned*)plane,
-                       (long long)NX, big_endian, tiles_dev, vals, ch);
+                       (long long)NX, big_endian, tiles_dev, w.vals, w.ch);
     if (d.zscale)
-        hipLaunchKernelGGL(fits_tiles_zscale_chain_kernel, dim3((unsigned)T), dim3(1024), 0, s, tiles_dev, (const float*)vals,
-                           (const FitsChunk*)ch, chain->zscale_contrasts[0], chain->zscale_contrasts[1], chain->zscale_contrasts[2], d, params);
+        hipLaunchKernelGGL(fits_tiles_zscale_kernel, dim3((unsigned)T), dim3(1024), 0, s, tiles_dev, (const float*)w.vals,
+                           (const FitsChunk*)w.ch, chain->zscale_contrasts[0], chain->zscale_contrasts[1], chain->zscale_contrasts[2], d,
+                           w.params);
     else
-        hipLaunchKernelGGL(fits_tiles_minmax_kernel, dim3((unsigned)T), dim3(256), 0, s, tiles_dev, (const FitsChunk*)ch, d, params);
-    if (d.out_kind == 0) fits_tiles_image_launch<0>(s, tiles_dev, T, l.max_pixels, vals, params, d, out);
-    else if (d.out_kind == 1) fits_tiles_image_launch<1>(s, tiles_dev, T, l.max_pixels, vals, params, d, out);
-    else fits_tiles_image_launch<2>(s, tiles_dev, T, l.max_pixels, vals, params, d, out);
+        hipLaunchKernelGGL(fits_tiles_minmax_kernel, dim3((unsigned)T), dim3(256), 0, s, tiles_dev, (const FitsChunk*)w.ch, d, w.params);
+    if (d.out_kind == 0) fits_tiles_image_launch<0>(s, tiles_dev, T, l.max_pixels, w.vals, w.params, d, out);
+    else if (d.out_kind == 1) fits_tiles_image_launch<1>(s, tiles_dev, T, l.max_pixels, w.vals, w.params, d, out);
+    else fits_tiles_image_launch<2>(s, tiles_dev, T, l.max_pixels, w.vals, w.params, d, out);
     return mrcnn_launch_status();
+}
+
+// The run.py flags (zscale, / max, uint8 RGB) under their own names: the descriptor of that chain, then the entries above.
+static mrcnn_fits_chain fits_rgb_chain(const double* zc) {
+    return {1, 0, 1, 0, {zc[0], zc[1], zc[2]}, 0.5, 1.0};
+}
+
+extern "C" int mrcnn_fits_to_rgb(const void* raw, int big_endian, int H, int W, const double* zscale_contrasts, void* rgb, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    if (!zscale_contrasts) return MRCNN_ERR_ARG;
+    const mrcnn_fits_chain chain = fits_rgb_chain(zscale_contrasts);
+    const size_t rgb_bytes = H > 0 && W > 0 ? (size_t)H * W * 3 : 0;
+    return mrcnn_fits_to_image(raw, big_endian, H, W, &chain, rgb, rgb_bytes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY, int NX, const mrcnn_fits_tile* tiles_host,
+                                       const mrcnn_fits_tile* tiles_dev, int T, const double* zscale_contrasts, void* rgb, size_t rgb_bytes,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!zscale_contrasts) return MRCNN_ERR_ARG;
+    const mrcnn_fits_chain chain = fits_rgb_chain(zscale_contrasts);
+    return mrcnn_fits_tiles_to_image(plane, big_endian, NY, NX, tiles_host, tiles_dev, T, &chain, rgb, rgb_bytes, workspace, workspace_bytes,
+                                     stream);
 }
 
 // ---- the overview of a whole mosaic (include/mrcnn_hip.h: mrcnn_mosaic_overview) -----------------------------------------------

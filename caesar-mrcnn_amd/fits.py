@@ -209,10 +209,9 @@ def gray2rgb(data_float, to_uint8=True):
     return np.stack(chans, axis=-1)
 
 
-DeviceChain = collections.namedtuple("DeviceChain", "zscale biascontrast normalize out_kind zscale_contrasts bias contrast default")
+DeviceChain = collections.namedtuple("DeviceChain", "zscale biascontrast normalize out_kind zscale_contrasts bias contrast")
 DeviceChain.__doc__ = """read_fits flags as the device chain takes them (mrcnn_fits_chain, include/mrcnn_hip.h).  out_kind: 0 uint8
-[H, W, 3], 1 float32 [H, W, 3], 2 float32 [H, W]; default: the run.py flags, computed by the older entries mrcnn_fits_to_rgb /
-mrcnn_fits_tiles_to_rgb."""
+[H, W, 3], 1 float32 [H, W, 3], 2 float32 [H, W]."""
 
 
 def device_chain(stretch, normalize, convertToRGB, to_uint8, stretch_biascontrast, zscale_contrasts, contrast, bias, pixels=None):
@@ -239,8 +238,7 @@ def device_chain(stretch, normalize, convertToRGB, to_uint8, stretch_biascontras
     if pixels is not None and pixels < DEVICE_LIGHT_CHAIN_MIN_PIXELS and not stretch and (out_kind == 2 or not stretch_biascontrast):
         return None, "no zscale and %s: the host is level or ahead below %d pixels" % (
             "a gray image" if out_kind == 2 else "no bias / contrast stretch", DEVICE_LIGHT_CHAIN_MIN_PIXELS)
-    default = stretch and normalize and out_kind == 0 and not stretch_biascontrast
-    return DeviceChain(stretch, stretch_biascontrast, normalize, out_kind, zc, bias, contrast, default), None
+    return DeviceChain(stretch, stretch_biascontrast, normalize, out_kind, zc, bias, contrast), None
 
 
 def read_fits(filename, xmin=-1, xmax=-1, ymin=-1, ymax=-1, stretch=True, normalize=True, convertToRGB=True,
@@ -249,9 +247,8 @@ def read_fits(filename, xmin=-1, xmax=-1, ymin=-1, ymax=-1, stretch=True, normal
     """Tile of a FITS image as the network's input image (utils.py:1033-1163): NaN -> min, per-channel
     zscale, normalise by the channel maximum, uint8 RGB.  Returns (image, header) or None on error.
     device: a torch GPU device -- the numeric part (everything after the header parse and the tile cut) runs there (the file's
-    big-endian floats cross PCIe as they are) for every flag combination device_chain() accepts: mrcnn_fits_to_rgb for the
-    run.py flags (stretch, normalize, convertToRGB, to_uint8, no bias / contrast stretch), mrcnn_fits_to_image for the others;
-    the image comes back to the host, identical to the host path's (uint8 byte for byte, float32 bit for bit).  device_out:
+    big-endian floats cross PCIe as they are) for every flag combination device_chain() accepts (mrcnn_fits_to_image); the
+    image comes back to the host, identical to the host path's (uint8 byte for byte, float32 bit for bit).  device_out:
     True -- a uint8 RGB image of that device branch stays there, as a uint8 [H, W, 3] torch tensor (the device sample path of
     datagen.data_generator), a float32 image still comes back to the host; "any" -- every image of the device branch stays
     there, as a torch tensor of the host array's shape and dtype: uint8 [H, W, 3], float32 [H, W, 3] or, gray, float32 [H, W]
@@ -348,10 +345,9 @@ def mosaic_overview_host(plane, shrink, contrast=0.25):
 
 
 def _read_fits_device(tile, chain, device, device_out=False):
-    """The cut tile (still in the file's dtype / byte order) -> the image of `chain` (a DeviceChain) through ops.fits_to_rgb
-    (the run.py flags) or ops.fits_to_image (any other accepted combination); returns a host array of the host path's shape
-    and dtype (device_out True and a uint8 RGB image, or device_out "any": the device tensor, allocated on the loader stream, where
-    its consumers run too).
+    """The cut tile (still in the file's dtype / byte order) -> the image of `chain` (a DeviceChain) through ops.fits_to_image;
+    returns a host array of the host path's shape and dtype (device_out True and a uint8 RGB image, or device_out "any": the
+    device tensor, allocated on the loader stream, where its consumers run too).
     Called from loader threads while the main thread issues training steps: the three launches go to ONE side stream shared
     by all loader threads (its own hardware queue beside the step's three; a stream per thread would wrap onto the step's
     queues and wait behind a whole step) under a lock (the stream's scratch buffer is shared), and only that stream is
@@ -368,10 +364,7 @@ def _read_fits_device(tile, chain, device, device_out=False):
     device_out = device_out == "any" or (bool(device_out) and chain.out_kind == 0)
     with loader_stream(device) as st:
         with torch.cuda.stream(st):
-            if chain.default:
-                img = ops.fits_to_rgb(raw.to(device, non_blocking=True), H, W, chain.zscale_contrasts, big_endian=big)
-            else:
-                img = ops.fits_to_image(raw.to(device, non_blocking=True), H, W, chain, big_endian=big)
+            img = ops.fits_to_image(raw.to(device, non_blocking=True), H, W, chain, big_endian=big)
             if not device_out:
                 host = torch.empty(tuple(img.shape), dtype=img.dtype, pin_memory=True)
                 host.copy_(img, non_blocking=True)

@@ -725,23 +725,6 @@ def unmold_masks(mrcnn_mask, dets, image_hw, packed=False, out=None):
     return out
 
 
-def fits_to_rgb(raw, H, W, zscale_contrasts=(0.25, 0.25, 0.25), big_endian=False, out=None):
-    """utils.read_fits's numeric part on the device (mrcnn/utils.py:1088-1157): raw = the tile's H * W float32 values as a
-    device tensor (any dtype of 4 * H * W bytes: float32, or the file's big-endian bytes as uint8 with big_endian=True) ->
-    uint8 [H, W, 3] (NaN -> min, per-channel zscale, / max, round(255 x))."""
-    _need_cuda(raw, out)
-    assert raw.is_contiguous() and raw.numel() * raw.element_size() == 4 * H * W, "raw must hold H * W float32 values"
-    if out is None:
-        out = torch.empty((H, W, 3), dtype=torch.uint8, device=raw.device)
-    L = _hip.lib()
-    nbytes = L.mrcnn_fits_workspace(H, W)
-    ws = workspace(nbytes, raw.device, "fits")
-    zc = (C.c_double * 3)(*[float(v) for v in zscale_contrasts])
-    check(L.mrcnn_fits_to_rgb(ptr(raw), 1 if big_endian else 0, H, W, zc, ptr(out), ptr(ws), ws.numel(), current_stream()),
-          "mrcnn_fits_to_rgb")
-    return out
-
-
 FITS_TILE_DTYPE = [("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("pixel_offset", "<i8"), ("chunk_offset", "<i8")]
 FITS_TILE_CHUNK = 1024                   # pixels per statistics chunk (csrc/fits.hip)
 
@@ -752,7 +735,7 @@ class FitsTileUnsupported(_hip.HipPathError):
 
 def fits_tile_table(tiles):
     """mrcnn_fits_tile records (include/mrcnn_hip.h) of rectangles [(x0, y0, w, h), ...]: the pools laid out back to back in
-    table order.  Host array; nothing is checked here -- mrcnn_fits_tiles_to_rgb does that before it launches."""
+    table order.  Host array; nothing is checked here -- mrcnn_fits_tiles_to_image does that before it launches."""
     import numpy as np
     r = np.asarray(tiles, dtype=np.int64).reshape(-1, 4)
     table = np.zeros(r.shape[0], dtype=FITS_TILE_DTYPE)
@@ -766,45 +749,7 @@ def fits_tile_table(tiles):
     return table
 
 
-def fits_tiles_to_rgb(plane, tiles, zscale_contrasts=(0.25, 0.25, 0.25), big_endian=False):
-    """fits_to_rgb for T tiles of one plane that is already on the device, every stage one launch over all tiles
-    (mrcnn_fits_tiles_to_rgb).  plane: [NY, NX] float32 device tensor, or with big_endian=True the file's bytes as uint8
-    [NY, NX, 4]; tiles: T rectangles (x0, y0, w, h) in plane pixels -- sizes may differ, rectangles may overlap.  Returns a list
-    of T uint8 [h, w, 3] device tensors, views into one pool, each byte-identical to fits.read_fits of that cut.  Runs on the
-    current stream.  ValueError for a malformed table (no tile, w or h <= 0, a rectangle that leaves the plane),
-    FitsTileUnsupported for a tile above 2048 x 2048 pixels; neither launches or writes anything."""
-    import numpy as np
-    _need_cuda(plane)
-    if plane.dim() < 2 or plane.numel() * plane.element_size() != 4 * plane.shape[0] * plane.shape[1]:
-        raise ValueError("plane must hold NY x NX float32 values (got shape %r, dtype %s)" % (tuple(plane.shape), plane.dtype))
-    NY, NX = int(plane.shape[0]), int(plane.shape[1])
-    table = fits_tile_table(tiles)
-    T = int(table.shape[0])
-    L = _hip.lib()
-    host = table.ctypes.data_as(C.c_void_p)
-    zc = (C.c_double * 3)(*[float(v) for v in zscale_contrasts])
-    stream = current_stream()
-    rc = L.mrcnn_fits_tiles_check(host, T, NY, NX)          # the call's own host-side check: nothing is allocated for a refused table
-    if rc == ERR_UNSUPPORTED:
-        raise FitsTileUnsupported("mrcnn_fits_tiles_to_rgb: a tile above the kernel's size limit (2048 x 2048 pixels)")
-    if rc:
-        raise ValueError("mrcnn_fits_tiles_to_rgb refuses the tiles (status %d): no tile, an empty rectangle or one outside the "
-                         "%d x %d plane" % (rc, NY, NX))
-    nbytes = L.mrcnn_fits_tiles_workspace(host, T, NY, NX)
-    ws = workspace(nbytes, plane.device, "fits_tiles")
-    total = int(table["pixel_offset"][-1]) + int(table["w"][-1]) * int(table["h"][-1])
-    pool = torch.empty(3 * total, dtype=torch.uint8, device=plane.device)
-    table_dev = torch.from_numpy(table.view(np.uint8)).to(plane.device)
-    check(L.mrcnn_fits_tiles_to_rgb(ptr(plane), 1 if big_endian else 0, NY, NX, host, ptr(table_dev), T, zc, ptr(pool), pool.numel(),
-                                    ptr(ws), ws.numel(), stream), "mrcnn_fits_tiles_to_rgb")
-    out = []
-    for r in table:
-        o, h, w = 3 * int(r["pixel_offset"]), int(r["h"]), int(r["w"])
-        out.append(pool[o:o + 3 * h * w].view(h, w, 3))
-    return out
-
-
-# ---- every read_fits flag combination (csrc/fits.hip: mrcnn_fits_to_image / mrcnn_fits_tiles_to_image) ----------------------------
+# ---- read_fits on the device, every flag combination (csrc/fits.hip: mrcnn_fits_to_image / mrcnn_fits_tiles_to_image) -------------
 FITS_OUT_UINT8_RGB, FITS_OUT_FLOAT_RGB, FITS_OUT_GRAY = 0, 1, 2
 
 
@@ -813,33 +758,42 @@ class FitsChainUnsupported(_hip.HipPathError):
     the host's cast of out-of-range floats to uint8 is platform-defined).  Nothing was launched: the caller takes the host path."""
 
 
-def _fits_chain(chain):
-    """(mrcnn_fits_chain, dtype, trailing shape) of a chain description: an object with the fields of fits.DeviceChain."""
+def _fits_rgb_chain(zscale_contrasts):
+    """The run.py flags (zscale, / max, uint8 RGB; no bias / contrast stretch) with these three contrasts."""
+    from .fits import DeviceChain
+    return DeviceChain(True, False, True, FITS_OUT_UINT8_RGB, tuple(zscale_contrasts), 0.5, 1.0)
+
+
+def _fits_chain(chain, H=1, W=1):
+    """(mrcnn_fits_chain, dtype, trailing shape) of a chain description: an object with the fields of fits.DeviceChain, checked
+    for an H x W tile (mrcnn_fits_image_check: the refusals of fits_to_image, before anything is allocated)."""
     zc = [float(v) for v in chain.zscale_contrasts]
     assert len(zc) == 3, "zscale_contrasts must hold three values"
     c = _hip.FitsChain(1 if chain.zscale else 0, 1 if chain.biascontrast else 0, 1 if chain.normalize else 0, int(chain.out_kind),
                        (C.c_double * 3)(*zc), float(chain.bias), float(chain.contrast))
     if c.out_kind not in (FITS_OUT_UINT8_RGB, FITS_OUT_FLOAT_RGB, FITS_OUT_GRAY):
         raise ValueError("out_kind must be 0 (uint8 RGB), 1 (float32 RGB) or 2 (float32 gray), got %r" % (chain.out_kind,))
-    if _hip.lib().mrcnn_fits_image_check(C.byref(c), 1, 1) == ERR_UNSUPPORTED:
-        raise FitsChainUnsupported("the device chain does not take uint8 output with neither zscale nor the bias / contrast stretch")
+    rc = _hip.lib().mrcnn_fits_image_check(C.byref(c), H, W)
+    if rc == ERR_UNSUPPORTED:
+        if (H, W) == (1, 1) or _hip.lib().mrcnn_fits_image_check(C.byref(c), 1, 1) == ERR_UNSUPPORTED:
+            raise FitsChainUnsupported("the device chain does not take uint8 output with neither zscale nor the bias / contrast stretch")
+        raise FitsTileUnsupported("mrcnn_fits_to_image: a %d x %d tile is above the kernel's size limit (2048 x 2048 pixels)" % (H, W))
+    check(rc, "mrcnn_fits_image_check")
     dtype = torch.uint8 if c.out_kind == FITS_OUT_UINT8_RGB else torch.float32
     return c, dtype, (() if c.out_kind == FITS_OUT_GRAY else (3,))
 
 
 def fits_to_image(raw, H, W, chain, big_endian=False, out=None):
-    """fits_to_rgb for any flag combination of fits.read_fits (mrcnn_fits_to_image): raw as there; chain: what
-    fits.device_chain returns.  -> uint8 [H, W, 3], float32 [H, W, 3] or float32 [H, W] device tensor by chain.out_kind, equal
-    bit for bit to the host branch of fits.read_fits on the same tile.  FitsChainUnsupported for the one combination the chain
-    refuses, FitsTileUnsupported for a tile above 2048 x 2048 pixels; neither launches or allocates anything."""
+    """utils.read_fits's numeric part on the device (mrcnn/utils.py:1088-1157; mrcnn_fits_to_image) for any flag combination of
+    fits.read_fits: raw = the tile's H * W float32 values as a device tensor (any dtype of 4 * H * W bytes: float32, or the
+    file's big-endian bytes as uint8 with big_endian=True); chain: what fits.device_chain returns.  -> uint8 [H, W, 3], float32
+    [H, W, 3] or float32 [H, W] device tensor by chain.out_kind, equal bit for bit to the host branch of fits.read_fits on the
+    same tile.  FitsChainUnsupported for the one combination the chain refuses, FitsTileUnsupported for a tile above 2048 x 2048
+    pixels; neither launches or allocates anything."""
     _need_cuda(raw, out)
     assert raw.is_contiguous() and raw.numel() * raw.element_size() == 4 * H * W, "raw must hold H * W float32 values"
-    c, dtype, tail = _fits_chain(chain)
+    c, dtype, tail = _fits_chain(chain, H, W)
     L = _hip.lib()
-    rc = L.mrcnn_fits_image_check(C.byref(c), H, W)
-    if rc == ERR_UNSUPPORTED:
-        raise FitsTileUnsupported("mrcnn_fits_to_image: a %d x %d tile is above the kernel's size limit (2048 x 2048 pixels)" % (H, W))
-    check(rc, "mrcnn_fits_image_check")
     shape = (H, W) + tail
     if out is None:
         out = torch.empty(shape, dtype=dtype, device=raw.device)
@@ -851,10 +805,19 @@ def fits_to_image(raw, H, W, chain, big_endian=False, out=None):
     return out
 
 
+def fits_to_rgb(raw, H, W, zscale_contrasts=(0.25, 0.25, 0.25), big_endian=False, out=None):
+    """fits_to_image with the run.py flags: -> uint8 [H, W, 3] (NaN -> min, per-channel zscale, / max, round(255 x))."""
+    return fits_to_image(raw, H, W, _fits_rgb_chain(zscale_contrasts), big_endian=big_endian, out=out)
+
+
 def fits_tiles_to_image(plane, tiles, chain, big_endian=False):
-    """fits_tiles_to_rgb for any flag combination (mrcnn_fits_tiles_to_image): plane and tiles as there, chain as for
-    fits_to_image.  Returns a list of T device tensors, views into one pool, each equal to fits_to_image of that cut.  The same
-    refusals as fits_tiles_to_rgb, and FitsChainUnsupported."""
+    """fits_to_image for T tiles of one plane that is already on the device, every stage one launch over all tiles
+    (mrcnn_fits_tiles_to_image).  plane: [NY, NX] float32 device tensor, or with big_endian=True the file's bytes as uint8
+    [NY, NX, 4]; tiles: T rectangles (x0, y0, w, h) in plane pixels -- sizes may differ, rectangles may overlap; chain as for
+    fits_to_image.  Returns a list of T device tensors, views into one pool, each equal to fits_to_image of that cut (so to
+    fits.read_fits of it).  Runs on the current stream.  ValueError for a malformed table (no tile, w or h <= 0, a rectangle
+    that leaves the plane), FitsTileUnsupported for a tile above 2048 x 2048 pixels, FitsChainUnsupported; none launches or
+    writes anything."""
     import numpy as np
     _need_cuda(plane)
     if plane.dim() < 2 or plane.numel() * plane.element_size() != 4 * plane.shape[0] * plane.shape[1]:
@@ -866,7 +829,7 @@ def fits_tiles_to_image(plane, tiles, chain, big_endian=False):
     L = _hip.lib()
     host = table.ctypes.data_as(C.c_void_p)
     stream = current_stream()
-    rc = L.mrcnn_fits_tiles_check(host, T, NY, NX)
+    rc = L.mrcnn_fits_tiles_check(host, T, NY, NX)          # the call's own host-side check: nothing is allocated for a refused table
     if rc == ERR_UNSUPPORTED:
         raise FitsTileUnsupported("mrcnn_fits_tiles_to_image: a tile above the kernel's size limit (2048 x 2048 pixels)")
     if rc:
@@ -885,6 +848,11 @@ def fits_tiles_to_image(plane, tiles, chain, big_endian=False):
         o, h, w = per * int(r["pixel_offset"]), int(r["h"]), int(r["w"])
         out.append(pool[o:o + per * h * w].view((h, w) + tail))
     return out
+
+
+def fits_tiles_to_rgb(plane, tiles, zscale_contrasts=(0.25, 0.25, 0.25), big_endian=False):
+    """fits_tiles_to_image with the run.py flags: a list of T uint8 [h, w, 3] device tensors."""
+    return fits_tiles_to_image(plane, tiles, _fits_rgb_chain(zscale_contrasts), big_endian=big_endian)
 
 
 # ---- the overview picture of a mosaic (csrc/fits.hip: mrcnn_mosaic_overview; csrc/maskgraph.hip: mrcnn_sources_to_planes) --------

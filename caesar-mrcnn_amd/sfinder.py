@@ -24,7 +24,7 @@ it).  It has two implementations as well, behind ``SFinder.params_device``:
 
 The front of a tiled run -- read the tile, stretch it, detect -- has a batched form behind ``SFinder.tile_batch`` (default 0:
 the per-tile loop of the reference; run.py --tile_batch N): the mosaic plane is read and uploaded once, the tiles of a group of
-N are cut and stretched on the GPU in one ops.fits_tiles_to_rgb call and go to ONE model.detect call as device tensors
+N are cut and stretched on the GPU in one ops.fits_tiles_to_image call and go to ONE model.detect call as device tensors
 (``prepare_tile_images`` / ``_detect_images``); every tile's Analyzer then takes its own result (TileTask.accept_detection).
 
 astropy.stats.sigma_clipped_stats and astropy.wcs.WCS are restated in fits.py (sigma_clipped_stats, SimpleWCS), unpinned;
@@ -572,8 +572,8 @@ class SFinder(object):
     def prepare_tile_images(self, tasks):
         """The network input images of `tasks`' tiles, in order: device tensors -- uint8 [h, w, 3], float32 [h, w, 3] or, gray,
         float32 [h, w, 1] -- cut from the resident plane (as NumPy slicing cuts: clipped to the plane), NaN-filled, stretched,
-        normalised and converted in one ops.fits_tiles_to_rgb call (the run.py flags) or one ops.fits_tiles_to_image call (any
-        other combination _tiles_batched() accepts) -- value for value what fits.read_fits gives per tile."""
+        normalised and converted in one ops.fits_tiles_to_image call (any combination _tiles_batched() accepts) -- value for value
+        what fits.read_fits gives per tile."""
         from . import ops
         plane_t, big = self._plane_device()
         ny, nx = int(plane_t.shape[0]), int(plane_t.shape[1])
@@ -584,16 +584,10 @@ class SFinder(object):
         chain, why = self._tiles_chain()
         if chain is None:
             raise RuntimeError("prepare_tile_images: the read_fits flags are not the device chain's (%s)" % why)
-        if chain.default:
-            return ops.fits_tiles_to_rgb(plane_t, rects, self._zscale_contrasts(), big_endian=big)
         images = ops.fits_tiles_to_image(plane_t, rects, chain, big_endian=big)
         if chain.out_kind == 2:
             images = [im.view(im.shape[0], im.shape[1], 1) for im in images]      # the model's gray image is [h, w, 1]
         return images
-
-    def _zscale_contrasts(self):
-        zc = self.config.ZSCALE_CONTRASTS
-        return zc if len(zc) == 3 else [0.25, 0.25, 0.25]                 # read_fits: any other length is ignored
 
     def _detect_images(self, images):
         """One model.detect call on a group of tile images (host arrays or device tensors).  The model takes exactly tile_batch

@@ -632,7 +632,10 @@ int mrcnn_unmold_masks(const float* mrcnn_mask, int n_rows, int MH, int MW, int 
  *         parsed the header and cut the tile; NaN pixels are replaced by the minimum of the others (:1090-1091);
  *   zscale_contrasts  3 doubles (HOST pointer, read at call time);
  *   rgb   [H, W, 3] uint8, byte-identical to the host statement caesar-mrcnn_amd/fits.py:read_fits.
- * Tiles up to 4096 x 1024 pixels (else MRCNN_ERR_UNSUPPORTED: use the host path).  workspace: mrcnn_fits_workspace(H, W).  */
+ * Tiles up to 4096 x 1024 pixels (else MRCNN_ERR_UNSUPPORTED: use the host path).  workspace: mrcnn_fits_workspace(H, W).
+ * The call IS mrcnn_fits_to_image (below) with the descriptor {zscale 1, biascontrast 0, normalize 1, out_kind 0, these
+ * contrasts, bias 0.5, contrast 1} and out_bytes = 3 * H * W: the same launches, the same statuses in the same order, after
+ * MRCNN_ERR_ARG for a null zscale_contrasts.                                                                                */
 size_t mrcnn_fits_workspace(int H, int W);
 int mrcnn_fits_to_rgb(const void* raw, int big_endian, int H, int W, const double* zscale_contrasts, void* rgb, void* workspace,
                       size_t workspace_bytes, void* stream);
@@ -646,8 +649,10 @@ int mrcnn_fits_to_rgb(const void* raw, int big_endian, int H, int W, const doubl
  *               leaves the plane or offsets other than these: MRCNN_ERR_ARG; a tile of more than 2048 x 2048 pixels (or
  *               T > 65535): MRCNN_ERR_UNSUPPORTED -- nothing launched, nothing written;
  *   tiles_dev   the same table on the device;
- *   rgb         pool of rgb_bytes >= 3 * sum(w * h) bytes: tile t is the [h, w, 3] uint8 image at byte 3 * pixel_offset[t], each
- *               byte-identical to mrcnn_fits_to_rgb of that cut (pixels enumerated row-major within the tile).
+ *   rgb         pool of rgb_bytes >= 3 * sum(w * h) bytes (else MRCNN_ERR_ARG): tile t is the [h, w, 3] uint8 image at byte
+ *               3 * pixel_offset[t], each byte-identical to mrcnn_fits_to_rgb of that cut (pixels enumerated row-major within the
+ *               tile).
+ * The call IS mrcnn_fits_tiles_to_image (below) with the descriptor of mrcnn_fits_to_rgb.
  * workspace: mrcnn_fits_tiles_workspace(tiles_host, T, NY, NX) bytes (0 for a table the call would refuse);
  * mrcnn_fits_tiles_check: the status the call would return for that table (the host-side check alone; launches nothing).     */
 typedef struct mrcnn_fits_tile {
@@ -661,9 +666,9 @@ int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY, int NX, c
                             const mrcnn_fits_tile* tiles_dev, int T, const double* zscale_contrasts, void* rgb, size_t rgb_bytes,
                             void* workspace, size_t workspace_bytes, void* stream);
 
-/* The same two entries for every flag combination of utils.read_fits (stretch, stretch_biascontrast, normalize, convertToRGB,
+/* The chain itself, for every flag combination of utils.read_fits (stretch, stretch_biascontrast, normalize, convertToRGB,
  * to_uint8; the host statement is caesar-mrcnn_amd/fits.py:read_fits, held bit for bit).  Per channel c of zscale contrast zc:
- *   zscale        c = float32(ZScaleInterval(zc)(c))                        (as mrcnn_fits_to_rgb)
+ *   zscale        c = float32(ZScaleInterval(zc)(c))
  *   biascontrast  c = float32(clip((float64(c) - bias) * contrast + 0.5, 0, 1))    three separately rounded operations
  *   normalize, or out_kind 0 / 1:  c = c / max(c)                           float32
  *   out_kind 0: uint8 [H, W, 3] = round(255 c)   1: float32 [H, W, 3] = c * 255   2: float32 [H, W] = channel 0 as it is
@@ -674,8 +679,15 @@ int mrcnn_fits_tiles_to_rgb(const void* plane, int big_endian, int NY, int NX, c
  * A tile without a finite pixel under zscale, or of NaNs alone: zeros for out_kind 0, NaN for the float outputs (the host
  * raises under zscale).  out: out_bytes >= 3 / 12 / 4 bytes per pixel; for the tiled entry a pool with tile t at
  * pixel_offset[t] times that.  workspace: mrcnn_fits_workspace / mrcnn_fits_tiles_workspace; the tile table and its check are
- * those of mrcnn_fits_tiles_to_rgb.  mrcnn_fits_image_check: the status mrcnn_fits_to_image would return for that descriptor
- * and size (host-side alone; launches nothing).  16-byte aligned out and workspace take the vector stores.                    */
+ * those described above.  mrcnn_fits_image_check: the status mrcnn_fits_to_image would return for that descriptor and size
+ * (host-side alone; launches nothing).  16-byte aligned out and workspace take the vector stores; any other alignment (of the
+ * element type) stores pixel by pixel, to the same values.
+ * A call that is faulty in more than one way reports the first of, for mrcnn_fits_to_image: the descriptor (null or out_kind:
+ * MRCNN_ERR_ARG; the refused combination: MRCNN_ERR_UNSUPPORTED), H or W <= 0 (MRCNN_ERR_ARG), the tile's size
+ * (MRCNN_ERR_UNSUPPORTED), a null raw or out, out_bytes (MRCNN_ERR_ARG), the workspace (MRCNN_ERR_WORKSPACE) -- so a null
+ * pointer WITH an oversize tile is MRCNN_ERR_UNSUPPORTED; for mrcnn_fits_tiles_to_image: the descriptor, a null plane, out or
+ * tiles_dev (MRCNN_ERR_ARG), the tile table (MRCNN_ERR_ARG or MRCNN_ERR_UNSUPPORTED, as above), out_bytes, the workspace -- so
+ * there a null pointer with an oversize tile is MRCNN_ERR_ARG.  Nothing is launched or written on any of them.                */
 typedef struct mrcnn_fits_chain {
     int32_t zscale;        /* stretch_img per channel */
     int32_t biascontrast;  /* stretch_img_biasconstrast after it */

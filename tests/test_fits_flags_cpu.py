@@ -18,7 +18,7 @@ BIAS_CONTRAST = [(0.5, 1), (0.2, 3.5), (-1, 0.5), (2, 1), (0.5, 0), (0.5, -2)]
 def test_device_chain_over_all_flag_combinations():
     """All 32 combinations of (stretch, normalize, convertToRGB, to_uint8, stretch_biascontrast): refused exactly when the output
     is uint8 RGB and neither stretch is on; out_kind 0 / 1 / 2 = uint8 RGB / float32 RGB / gray (to_uint8 is not looked at
-    without the RGB conversion, as in read_fits); `default` marks the run.py flags alone."""
+    without the RGB conversion, as in read_fits); the descriptor carries the flags and nothing else."""
     from caesar_mrcnn_amd import fits
     n_ok = 0
     for stretch, normalize, rgb, u8, bc in itertools.product((False, True), repeat=5):
@@ -33,7 +33,7 @@ def test_device_chain_over_all_flag_combinations():
         assert chain.out_kind == ((0 if u8 else 1) if rgb else 2)
         assert (chain.zscale, chain.biascontrast, chain.normalize) == (stretch, bc, normalize)
         assert chain.zscale_contrasts == (0.1, 0.25, 0.6) and (chain.bias, chain.contrast) == (0.2, 3.5)
-        assert chain.default == (stretch and normalize and rgb and u8 and not bc)
+        assert chain._fields == ("zscale", "biascontrast", "normalize", "out_kind", "zscale_contrasts", "bias", "contrast")
     assert n_ok == 30
 
 
@@ -63,7 +63,8 @@ def test_device_chain_replaces_a_contrast_list_of_the_wrong_length():
     from caesar_mrcnn_amd import fits
     for zc in ([], [0.3], [0.3, 0.4], [0.1, 0.2, 0.3, 0.4]):
         chain, why = fits.device_chain(True, True, True, True, False, zc, 1, 0.5)
-        assert why is None and chain.zscale_contrasts == (0.25, 0.25, 0.25) and chain.default
+        assert why is None and chain.zscale_contrasts == (0.25, 0.25, 0.25)
+        assert (chain.zscale, chain.biascontrast, chain.normalize, chain.out_kind) == (True, False, True, 0)
     chain, _ = fits.device_chain(True, True, True, True, False, (0.3, 0.4, 0.5), 1, 0.5)
     assert chain.zscale_contrasts == (0.3, 0.4, 0.5)
     assert fits.device_chain(True, True, True, True, True, [0.25] * 3, "x", 0.5)[0] is None

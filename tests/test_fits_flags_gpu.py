@@ -54,7 +54,7 @@ def _chain(zscale, bc, normalize, out_kind, zc, bias, contrast):
     """The descriptor itself: what the kernels compute is tested here for every combination they take, whichever of them
     fits.device_chain sends to the device."""
     from caesar_mrcnn_amd import fits
-    return fits.DeviceChain(zscale, bc, normalize, out_kind, tuple(zc), float(bias), float(contrast), False)
+    return fits.DeviceChain(zscale, bc, normalize, out_kind, tuple(zc), float(bias), float(contrast))
 
 
 def _host(path, zscale, bc, normalize, out_kind, zc, bias, contrast, **cut):
@@ -163,6 +163,72 @@ def test_tiled_entry_equals_the_single_tile_entry(dev):
                 assert o.is_cuda and _same(o.cpu().numpy(), single), (cfg, big, (x0, y0, w, h))
 
 
+def test_unaligned_output_takes_the_scalar_path_to_the_same_bytes(dev, tile_files):
+    """out= a contiguous view one element (1 byte for uint8, 4 bytes for float32) into a sentinel-filled buffer: its base is not
+    16-byte aligned, so every group of the pixel pass stores pixel by pixel.  The run.py stretch flags, both contrast triples, the
+    three output kinds, tiles of 7, 1025 and 4160 pixels: the image equals the aligned call bit for bit and the host read_fits, and
+    the sentinel elements on either side of the view keep their value."""
+    import torch
+    from caesar_mrcnn_amd import ops
+    picked = [tile_files[k] for k in (1, 4, 5)]
+    assert [im.shape for _, im, _ in picked] == [(1, 7), (25, 41), (64, 65)]
+    n = 0
+    for name, img, path in picked:
+        h, w = img.shape
+        raw = _raw(img, False, dev)
+        for zc, out_kind in itertools.product(CONTRASTS, (0, 1, 2)):
+            chain = _chain(True, False, True, out_kind, zc, 0.5, 1)
+            dtype, sentinel = (torch.uint8, 0xA5) if out_kind == 0 else (torch.float32, -12345.5)
+            shape = (h, w) if out_kind == 2 else (h, w, 3)
+            count = int(np.prod(shape))
+            buf = torch.full((count + 2,), sentinel, dtype=dtype, device=dev)
+            view = buf[1:1 + count].view(shape)
+            assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 != 0 and view.is_contiguous()
+            got = ops.fits_to_image(raw, h, w, chain, out=view)
+            assert got is view
+            aligned = ops.fits_to_image(raw, h, w, chain)
+            assert aligned.data_ptr() % 16 == 0
+            tag = "%s %r out_kind=%d" % (name, zc, out_kind)
+            assert _same(got.cpu().numpy(), aligned.cpu().numpy()), tag
+            assert _same(got.cpu().numpy(), _host(path, True, False, True, out_kind, zc, 0.5, 1)), tag
+            ends = buf[[0, count + 1]].cpu().numpy()
+            assert ends[0] == sentinel and ends[1] == sentinel, tag
+            n += 1
+    assert n == 3 * 2 * 3
+
+
+def test_unaligned_pool_through_the_rgb_entry_takes_the_scalar_path_to_the_same_bytes(dev):
+    """The C entry mrcnn_fits_tiles_to_rgb with `rgb` one byte into a sentinel pool, the five rectangles of the 96 x 130 plane, both
+    contrast triples: every tile equals ops.fits_tiles_to_rgb of the same rectangles (an aligned pool), the byte before the pool
+    and the bytes after it stay sentinel."""
+    import ctypes as C
+    import torch
+    from caesar_mrcnn_amd import _hip, ops
+    ny, nx = TILED_PLANE
+    plane = torch.from_numpy(_noise_tile(ny, nx, 7)).to(dev)
+    table = ops.fits_tile_table(TILED_RECTS)
+    host = table.ctypes.data_as(C.c_void_p)
+    table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+    total = sum(w * h for _, _, w, h in TILED_RECTS)
+    L = _hip.lib()
+    nbytes = L.mrcnn_fits_tiles_workspace(host, len(TILED_RECTS), ny, nx)
+    assert nbytes > 0
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    for zc in CONTRASTS:
+        want = ops.fits_tiles_to_rgb(plane, TILED_RECTS, zc)
+        pool = torch.full((1 + 3 * total + 16,), 0xA5, dtype=torch.uint8, device=dev)
+        assert pool.data_ptr() % 16 == 0 and ws.data_ptr() % 16 == 0
+        rc = L.mrcnn_fits_tiles_to_rgb(_hip.ptr(plane), 0, ny, nx, host, _hip.ptr(table_dev), len(TILED_RECTS), (C.c_double * 3)(*zc),
+                                       C.c_void_p(pool.data_ptr() + 1), 3 * total, _hip.ptr(ws), ws.numel(), _hip.current_stream())
+        assert rc == 0
+        torch.cuda.synchronize()
+        got = pool.cpu().numpy()
+        assert got[0] == 0xA5 and (got[1 + 3 * total:] == 0xA5).all(), zc
+        for t, (o, (x0, y0, w, h)) in enumerate(zip(want, TILED_RECTS)):
+            at = 1 + 3 * int(table["pixel_offset"][t])
+            assert np.array_equal(got[at:at + 3 * w * h].reshape(h, w, 3), o.cpu().numpy()), (zc, (x0, y0, w, h))
+
+
 def _spy(real, log):
     def f(*a, **k):
         log.append(a)
@@ -172,8 +238,8 @@ def _spy(real, log):
 
 def test_read_fits_takes_the_device_for_other_flags(dev, tile_files, monkeypatch):
     """read_fits(device=) with stretch_biascontrast=True, and with to_uint8=False: the host path's array, and ops.fits_to_image
-    ran (before this entry existed the call took the host branch without a word).  With the run.py flags the older entry
-    ops.fits_to_rgb runs and fits_to_image does not; device_out keeps a device tensor for the uint8 RGB image alone."""
+    ran (before this entry existed the call took the host branch without a word).  With the run.py flags the same entry runs,
+    once, with that chain, and not through ops.fits_to_rgb; device_out keeps a device tensor for the uint8 RGB image alone."""
     import torch
     from caesar_mrcnn_amd import fits, ops
     name, img, path = tile_files[5]
@@ -202,11 +268,13 @@ def test_read_fits_takes_the_device_for_other_flags(dev, tile_files, monkeypatch
     want = fits.read_fits(path, stretch_biascontrast=True, **cut)[0]
     got = fits.read_fits(path, stretch_biascontrast=True, device=dev, **cut)[0]
     assert len(new) == 1 and got.shape == (31, 47, 3) and _same(got, want)
-    # the run.py flags: the older entry, untouched
+    # the run.py flags: the same entry, with their chain
     del new[:], old[:]
     want = fits.read_fits(path)[0]
     got = fits.read_fits(path, device=dev)[0]
-    assert new == [] and len(old) == 1 and _same(got, want)
+    assert len(new) == 1 and old == [] and _same(got, want)
+    chain = new[0][3]
+    assert (bool(chain.zscale), bool(chain.biascontrast), bool(chain.normalize), chain.out_kind) == (True, False, True, 0)
     # the refused combination stays on the host
     del new[:], old[:]
     with warnings.catch_warnings(), np.errstate(all="ignore"):
@@ -273,7 +341,7 @@ def test_refusals_launch_nothing(dev):
     import ctypes as C
     import torch
     from caesar_mrcnn_amd import _hip, fits, ops
-    bad = fits.DeviceChain(False, False, True, 0, (0.25, 0.25, 0.25), 0.5, 1.0, False)
+    bad = fits.DeviceChain(False, False, True, 0, (0.25, 0.25, 0.25), 0.5, 1.0)
     raw = torch.zeros(16, dtype=torch.float32, device=dev)
     out = torch.full((4, 4, 3), 0xA5, dtype=torch.uint8, device=dev)
     with pytest.raises(ops.FitsChainUnsupported):

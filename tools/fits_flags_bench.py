@@ -8,11 +8,12 @@ pixel kernels of csrc/fits.hip per output kind.  Writes one JSON object with --o
   read_fits   end to end (file read, header parse, cut, numeric chain; the device branch with its upload and download), per
               (stretch, stretch_biascontrast, normalize, output) and tile size: perf_counter with the device synchronised before
               and after, host and device alternating within every repetition, median of --reps.  Equal contrasts (0.25), bias
-              0.5, contrast 1.  `host_over_device` > 1: the device branch is ahead.
-  kernels     --kernels-only issues, on one 2048 x 2048 tile, groups of launches of the older entry (fits_rgb_kernel) and of
-              mrcnn_fits_to_image per output kind; under rocprofv3 the trace holds every launch, and --kernel-trace reads the
-              pixel kernels' rows back in issue order: median duration of the timed launches of each group, bytes moved (4 read
-              + 3 / 12 / 4 written per pixel) per second and its fraction of the 6.3 TB/s copy rate of the card.
+              0.5, contrast 1; the run.py flags once more with three distinct contrasts (0.1, 0.25, 0.6).  `host_over_device`
+              > 1: the device branch is ahead.
+  kernels     --kernels-only issues, on one 2048 x 2048 tile, groups of launches of mrcnn_fits_to_image per output kind; under
+              rocprofv3 the trace holds every launch, and --kernel-trace reads the pixel kernels' rows back in issue order:
+              median duration of the timed launches of each group, bytes moved (4 read + 3 / 12 / 4 written per pixel) per
+              second and its fraction of the 6.3 TB/s copy rate of the card.
   --sfinder-tiles   the JSON of `tools/sfinder_tiles_bench.py --bias-contrast ...`, stored under "sfinder_tiles_bias_contrast".
 The second and third form add to the file the first one wrote."""
 import argparse
@@ -33,10 +34,9 @@ HBM_COPY_RATE = 6.3e12                    # bytes / s, the copy rate the other s
 KERNEL_SIZE = 2048
 KERNEL_WARM, KERNEL_TIMED = 3, 10
 OUT_BYTES = {0: 3, 1: 12, 2: 4}
-# (label, zscale, biascontrast, normalize, out_kind, contrasts); out_kind None: the older entry, ops.fits_to_rgb
+EQUAL_CONTRASTS, DISTINCT_CONTRASTS = (0.25, 0.25, 0.25), (0.1, 0.25, 0.6)
+# (label, zscale, biascontrast, normalize, out_kind, contrasts)
 KERNEL_GROUPS = [
-    ("fits_rgb_kernel, equal contrasts", True, False, True, None, (0.25, 0.25, 0.25)),
-    ("fits_rgb_kernel, three contrasts", True, False, True, None, (0.1, 0.25, 0.6)),
     ("uint8 RGB, zscale, equal contrasts", True, False, True, 0, (0.25, 0.25, 0.25)),
     ("uint8 RGB, zscale, three contrasts", True, False, True, 0, (0.1, 0.25, 0.6)),
     ("uint8 RGB, zscale + bias/contrast, three contrasts", True, True, True, 0, (0.1, 0.25, 0.6)),
@@ -77,11 +77,13 @@ def bench_read_fits(args, res):
     for size in [int(v) for v in args.sizes.split(",")]:
         path = os.path.join(tmp, "tile_%d.fits" % size)
         fits.write_fits(path, synth_tile(size))
-        for stretch, bc, normalize, out_kind in itertools.product((False, True), (False, True), (False, True), (0, 1, 2)):
-            kw = flag_kwargs(stretch, bc, normalize, out_kind)
-            chain, why = fits.device_chain(stretch, normalize, kw["convertToRGB"], kw["to_uint8"], bc, [0.25] * 3, 1, 0.5)
+        combos = [c + (EQUAL_CONTRASTS,) for c in itertools.product((False, True), (False, True), (False, True), (0, 1, 2))]
+        combos.append((True, False, True, 0, DISTINCT_CONTRASTS))      # the run.py flags, no channel shared
+        for stretch, bc, normalize, out_kind, zc in combos:
+            kw = dict(flag_kwargs(stretch, bc, normalize, out_kind), zscale_contrasts=list(zc))
+            chain, why = fits.device_chain(stretch, normalize, kw["convertToRGB"], kw["to_uint8"], bc, zc, 1, 0.5)
             row = {"size": size, "stretch": stretch, "stretch_biascontrast": bc, "normalize": normalize,
-                   "output": ("uint8_rgb", "float32_rgb", "float32_gray")[out_kind]}
+                   "output": ("uint8_rgb", "float32_rgb", "float32_gray")[out_kind], "zscale_contrasts": list(zc)}
             if chain is None:
                 row["refused"] = why
                 rows.append(row)
@@ -98,12 +100,11 @@ def bench_read_fits(args, res):
                         if rep:
                             t[which].append(time.perf_counter() - t0)
             h, d = float(np.median(t["host"])), float(np.median(t["device"]))
-            row.update(host_ms=round(1e3 * h, 3), device_ms=round(1e3 * d, 3), host_over_device=round(h / d, 2),
-                       entry="mrcnn_fits_to_rgb" if chain.default else "mrcnn_fits_to_image")
+            row.update(host_ms=round(1e3 * h, 3), device_ms=round(1e3 * d, 3), host_over_device=round(h / d, 2))
             rows.append(row)
             sys.stderr.write("%s\n" % json.dumps(row))
         os.remove(path)
-    res["read_fits"] = {"reps": args.reps, "contrasts": [0.25] * 3, "bias": 0.5, "contrast": 1, "rows": rows}
+    res["read_fits"] = {"reps": args.reps, "bias": 0.5, "contrast": 1, "rows": rows}
 
 
 def kernels_only():
@@ -113,17 +114,13 @@ def kernels_only():
     raw = torch.from_numpy(synth_tile(KERNEL_SIZE)).to(dev)
     for _, zscale, bc, normalize, out_kind, zc in KERNEL_GROUPS:
         for _ in range(KERNEL_WARM + KERNEL_TIMED):
-            if out_kind is None:
-                ops.fits_to_rgb(raw, KERNEL_SIZE, KERNEL_SIZE, zc)
-            else:
-                chain = fits.DeviceChain(zscale, bc, normalize, out_kind, zc, 0.5, 1.0, False)
-                ops.fits_to_image(raw, KERNEL_SIZE, KERNEL_SIZE, chain)
+            ops.fits_to_image(raw, KERNEL_SIZE, KERNEL_SIZE, fits.DeviceChain(zscale, bc, normalize, out_kind, zc, 0.5, 1.0))
             torch.cuda.synchronize()
 
 
 def read_kernel_trace(path, res):
     with open(path) as f:
-        rows = [r for r in csv.DictReader(f) if "fits_rgb_kernel" in r["Kernel_Name"] or "fits_image_kernel" in r["Kernel_Name"]]
+        rows = [r for r in csv.DictReader(f) if "fits_image_kernel" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     per = KERNEL_WARM + KERNEL_TIMED
     assert len(rows) == per * len(KERNEL_GROUPS), "%d pixel-kernel launches in the trace, %d expected" % (len(rows), per * len(KERNEL_GROUPS))
@@ -132,9 +129,9 @@ def read_kernel_trace(path, res):
     for k, (label, zscale, bc, normalize, out_kind, zc) in enumerate(KERNEL_GROUPS):
         group = rows[k * per + KERNEL_WARM:(k + 1) * per]
         names = set(r["Kernel_Name"] for r in group)
-        assert len(names) == 1 and (("fits_rgb_kernel" in list(names)[0]) == (out_kind is None)), (label, names)
+        assert len(names) == 1, (label, names)
         us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in group]
-        nbytes = n * (4 + OUT_BYTES[0 if out_kind is None else out_kind])
+        nbytes = n * (4 + OUT_BYTES[out_kind])
         med = float(np.median(us))
         out.append({"group": label, "kernel": list(names)[0].split("(")[0], "launches": len(us), "median_us": round(med, 2),
                     "min_us": round(min(us), 2), "max_us": round(max(us), 2), "bytes": nbytes,

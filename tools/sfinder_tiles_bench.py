@@ -13,7 +13,7 @@ warmed on a few tiles first (library load, graph capture, allocator).  Per mosai
            alternating within every repetition; median of --reps;
   stages   from ONE further run per variant that synchronises after every stage (so its sum is not the wall time):
            read_cut  (loop: fits.read_primary_hdu per tile + the cut; batched: the one read + upload of the plane),
-           stretch   (loop: the rest of fits.read_fits on the host; batched: ops.fits_tiles_to_rgb),
+           stretch   (loop: the rest of fits.read_fits on the host; batched: ops.fits_tiles_to_image),
            mold_graph (MaskRCNN.detect up to the end of the inference graph), unmold (the rest of detect),
            analyzer  (Analyzer.accept_detection: mask selection, JSON, regions), edge (find_sources_at_edge);
   equal    the tile_batch = 1 catalogue of tile results equals the loop's (same model, same bytes); larger batches are not
