@@ -598,7 +598,7 @@ class MaskRCNNEngine(object):
         context keeps the input transform V: the layer's weight gradient contracts it with the transformed dz."""
         out = ops.empty(tuple(x.shape[:3]) + (op.wshape[3],), torch.float32, x.device)
         z = ops.empty_like(out) if (train and op.bn) else None
-        V = ops.empty((ops.winograd_v_floats(tuple(x.shape)),), torch.float32, x.device) if (train and self.winograd_wgrad) else None
+        V = ops.winograd_v_empty(tuple(x.shape), x.device) if (train and self.winograd_wgrad) else None
         ops.conv2d_winograd(x, self._wino_U(op, 0, x.shape, train, infer_tile), op.b, op.scale, op.shift, act, out=out, z_out=z, keep_v=V)
         return out, (Ctx(x, z, out, act, WINO, V) if train else None)
 
@@ -609,7 +609,7 @@ class MaskRCNNEngine(object):
         tile = ops.winograd_tile(tuple(xshape))
         oshape = tuple(xshape[:3]) + (op.wshape[3],)
         return (self.winograd_chain and self.winograd_wgrad and self.fused_dgrad_epilogue and op.bn is not None and
-                tile == ops.TILE_MIXED and ops.winograd_chain_ok(tuple(xshape), op.wshape[3], tile) and
+                ops.winograd_chain_ok(tuple(xshape), op.wshape[3], tile) and
                 self._wino_ok(nxt, oshape) and ops.winograd_tile(oshape) == tile)
 
     def _wino_bwd_link_ok(self, ctx, below, bctx, shape, bshape):
@@ -620,7 +620,7 @@ class MaskRCNNEngine(object):
         tile = ops.winograd_tile(shape)
         return (self.winograd_bwd_chain and self.fused_dgrad_epilogue and ctx.path == WINO and bctx.path == WINO and
                 below.bn is not None and bctx.act == ACT_RELU and bctx.z is not None and bctx.V is not None and
-                tile == ops.TILE_MIXED and ops.winograd_tile(bshape) == tile and ops.winograd_chain_ok(shape, bshape[3], tile))
+                ops.winograd_tile(bshape) == tile and ops.winograd_chain_ok(shape, bshape[3], tile))
 
     def _wino_chained_fwd(self, layers, x, act):
         """Training forward of consecutive 3 x 3 layers, [(x, ctx) = _wino_fwd(op, x, act, True) or op.forward(...)] with the layers
@@ -640,9 +640,9 @@ class MaskRCNNEngine(object):
             U = self._wino_U(op, 0, shape)
             z = ops.empty(oshape, torch.float32, self.dev) if op.bn else None
             if not ready and self.winograd_wgrad:
-                V = ops.empty((ops.winograd_v_floats(shape),), torch.float32, self.dev)
+                V = ops.winograd_v_empty(shape, self.dev)
             if nxt is not None and self._wino_link_ok(op, nxt, shape):
-                Vn = ops.empty((ops.winograd_v_floats(oshape),), torch.float32, self.dev)
+                Vn = ops.winograd_v_empty(oshape, self.dev)
                 out = ops.conv2d_winograd_chain(shape if ready else x, U, Vn, op.b, op.scale, op.shift, act, z_out=z, keep_v=V, v_ready=ready)
             else:
                 Vn = None
@@ -1241,8 +1241,7 @@ class MaskRCNNEngine(object):
                     if wino and self.fused_dgrad_epilogue and below.bn is not None:
                         Vn = dMn = None
                         if self._wino_bwd_link_ok(c, below, bctx, shape, bshape):
-                            nv = ops.winograd_v_floats(bshape)
-                            Vn, dMn = ops.empty((nv,), torch.float32, self.dev), ops.empty((nv,), torch.float32, self.dev)
+                            Vn, dMn = ops.winograd_v_empty(bshape, self.dev), ops.winograd_v_empty(bshape, self.dev)
                         dz = ops.conv2d_dgrad_ep_winograd(src, self._wino_U(op, 1, shape), bctx.out if bctx.act != ACT_NONE else None,
                                                           bctx.z, below.scale, below.mean, below.rstd, below.dgamma, below.dbeta,
                                                           below.db, bctx.act, fwd_shift=below.shift, next_v=Vn, next_dm=dMn,

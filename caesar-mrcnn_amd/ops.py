@@ -4,6 +4,7 @@ Every function takes/returns torch CUDA tensors that only serve as device-memory
 arithmetic happens in libmrcnn_hip.so.  Shapes follow the reference graph (NHWC float32).
 """
 import ctypes as C
+import functools
 import math
 import os
 
@@ -2032,17 +2033,55 @@ def winograd_groups(H, W, tile):
     return [G(4, 4, H // 4, W // 4, 0, 0), G(4, 2, H // 4, 1, 0, W - 2), G(2, 4, 1, W // 4, H - 2, 0), G(2, 2, 1, 1, H - 2, W - 2)]
 
 
-def _wino_nb(g):
-    return (g.oth + 2) * (g.otw + 2)
+class _WinoLayout(object):
+    """The tile layout of N maps of H x W under a tiling, made once per (N, H, W, tile) by _wino_layout and only read afterwards:
+    the groups, the transform-domain matrices nb of each, and per channel count -- asked of the library once -- the floats of each
+    group's transform (V, Mt and dM alike: nb matrices of whole row tiles) and the rows of channel-sum partials each group's
+    backward output transform writes, both with their prefix sums: a buffer of all groups end to end has group gi at offs[gi] and
+    offs[-1] elements."""
+
+    def __init__(self, N, H, W, tile):
+        self.N, self.H, self.W, self.tile = N, H, W, tile
+        self.groups = tuple(winograd_groups(H, W, tile))
+        self.nbs = tuple((g.oth + 2) * (g.otw + 2) for g in self.groups)
+        self.all = range(len(self.groups))
+        self._floats, self._rows = {}, {}
+
+    def _per_group(self, memo, entry, C_):
+        if C_ not in memo:
+            query = getattr(_hip.lib(), entry)
+            ns = tuple(query(C.byref(g), self.N, C_) for g in self.groups)
+            memo[C_] = (ns, tuple(sum(ns[:i]) for i in range(len(ns) + 1)))
+        return memo[C_]
+
+    def floats(self, C_):
+        """(floats of each group's transform of C_ channels, their prefix sums)"""
+        return self._per_group(self._floats, "mrcnn_winograd_group_floats", C_)
+
+    def sum_rows(self, C_):
+        """(rows of partials [3][C_] of each group, their prefix sums)"""
+        return self._per_group(self._rows, "mrcnn_winograd_output_bwd_rows", C_)
 
 
-def _wino_tile_of(U):
+_wino_layout = functools.lru_cache(maxsize=256)(_WinoLayout)
+
+
+def _wino_weights_of(U):
+    """U as winograd_weights made it, a tensor or -- the mixed tiling -- a list of four -> (tile, [U of each group], Cout)."""
     if isinstance(U, (list, tuple)):
         assert [u.shape[0] for u in U] == [36, 24, 24, 16], "U is not a mixed Winograd weight transform"
-        return TILE_MIXED
-    nb = U.shape[0]
-    assert nb in (16, 36), "U is not a Winograd weight transform"
-    return 2 if nb == 16 else 4
+        return TILE_MIXED, U, U[0].shape[2]
+    assert U.shape[0] in (16, 36), "U is not a Winograd weight transform"
+    return (2 if U.shape[0] == 16 else 4), [U], U.shape[2]
+
+
+def _wino_arg(t, ready):
+    """The public 'a tensor, or -- where the caller holds its transform (v_ready / dm_ready / mt_ready) -- its SHAPE' argument ->
+    (the tensor, None where it is not to be read; its shape)."""
+    if isinstance(t, (tuple, list)):
+        assert ready, "a shape stands for a tensor only where its transform is ready"
+        return None, tuple(t)
+    return (None if ready else t), tuple(t.shape)
 
 
 def winograd_ok(xshape, wshape, stride=1, padding="same", min_rows=None):
@@ -2079,72 +2118,102 @@ def winograd_weights(w, out=None, tile=2):
     return out
 
 
-def _winograd_run(x, U, finish, keep_v=None, after_input=None, v_ready=False, finish_all=None):
-    """Per tile group: input transform, the group's transform-domain GEMMs, then finish(group, Mt) -- the output transform the caller
-    wants.  V of all groups lives in one flat buffer (keep_v: kept for the weight gradient), Mt is a per-stream scratch buffer
-    reused group after group (stream order).
-    v_ready: keep_v already holds the input transform (the layer below wrote it, conv2d_winograd_chain) and x is the input's SHAPE.
-    finish_all: the groups' GEMMs run first, each into its own part of an Mt that holds all groups end to end (as V does), then
-    finish_all(Mt) once; finish is not called."""
-    N, H, W, Cin = x if v_ready else x.shape
-    assert not v_ready or keep_v is not None
-    tile = _wino_tile_of(U)
-    Us = U if isinstance(U, (list, tuple)) else [U]
-    cout = Us[0].shape[2]
-    groups = winograd_groups(H, W, tile)
-    lib = _hip.lib()
-    nvs = [lib.mrcnn_winograd_group_floats(C.byref(g), N, Cin) for g in groups]
-    nms = [lib.mrcnn_winograd_group_floats(C.byref(g), N, cout) for g in groups]
-    nv = sum(nvs)
-    dev = Us[0].device
+# The stages, each one loop over the groups `gis` of a layout (default: all).  A transform of all groups lies end to end in one flat
+# buffer (V, next_v, next_dm, a stacked Mt): group gi at the layout's prefix sum.  Where the public functions run the stages group
+# by group (input transform, GEMM, output transform, then the next group), Mt and dM are per-stream scratch buffers of the largest
+# group's size, reused group after group in stream order (stacked=False: every group at the buffer's start).
+def _wino_input(lay, x, C_, V, gis=None):
+    """B^T x B of x [N, H, W, C_] into the flat V."""
+    lib, offs = _hip.lib(), lay.floats(C_)[1]
+    for gi in lay.all if gis is None else gis:
+        check(lib.mrcnn_winograd_input_g(ptr(x), ptr(V) + offs[gi] * 4, lay.N, lay.H, lay.W, C_, C.byref(lay.groups[gi]), current_stream()),
+              "mrcnn_winograd_input_g")
+
+
+def _wino_dy(lay, dz, C_, dM, stacked, gis=None):
+    """A dz A^T of dz [N, H, W, C_] into dM."""
+    lib, offs = _hip.lib(), lay.floats(C_)[1]
+    for gi in lay.all if gis is None else gis:
+        check(lib.mrcnn_winograd_dy_g(ptr(dz), ptr(dM) + (offs[gi] * 4 if stacked else 0), lay.N, lay.H, lay.W, C_, C.byref(lay.groups[gi]),
+                                      current_stream()), "mrcnn_winograd_dy_g")
+
+
+def _wino_product(lay, x, Us, Cin, V, Mt, stacked, gis=None):
+    """Per group the input transform of x into V (x None: V holds it already), then the group's transform-domain GEMMs
+    V [nb, rows, Cin] x U [nb, Cin, Cout] -> Mt [nb, rows, Cout]."""
+    lib, cout = _hip.lib(), Us[0].shape[2]
+    (nvs, voffs), moffs = lay.floats(Cin), lay.floats(cout)[1]
+    for gi in lay.all if gis is None else gis:
+        if x is not None:
+            _wino_input(lay, x, Cin, V, (gi,))
+        nb = lay.nbs[gi]
+        check(lib.mrcnn_winograd_gemm(ptr(V) + voffs[gi] * 4, ptr(Us[gi]), ptr(Mt) + (moffs[gi] * 4 if stacked else 0), nb, nvs[gi] // (nb * Cin),
+                                      Cin, cout, current_stream()), "mrcnn_winograd_gemm")
+
+
+def _wino_output(lay, Mt, stacked, out, z_out, bias, scale, shift, act, gis=None):
+    """Output transforms A^T Mt A with the forward epilogue into out (and z_out)."""
+    lib, cout = _hip.lib(), out.shape[3]
+    moffs = lay.floats(cout)[1]
+    for gi in lay.all if gis is None else gis:
+        check(lib.mrcnn_winograd_output_g(ptr(Mt) + (moffs[gi] * 4 if stacked else 0), ptr(out), ptr(z_out), ptr(bias), ptr(scale), ptr(shift),
+                                          lay.N, lay.H, lay.W, cout, act, C.byref(lay.groups[gi]), current_stream()), "mrcnn_winograd_output_g")
+
+
+def _wino_output_bwd(lay, Mt, stacked, out, below_out, below_z, scale, mean, rstd, zmask_shift, act, part, gis=None):
+    """Output transforms with the epilogue backward of the layer below into out; zmask_shift (the forward's shift, or None): the ReLU
+    mask is recomputed from z.  part (an address, or None): every group's workgroups write one row of channel-sum partials
+    [3][cout] each, group gi from row sum_rows' prefix sum on."""
+    lib, cout = _hip.lib(), out.shape[3]
+    moffs, roffs = lay.floats(cout)[1], lay.sum_rows(cout)[1]
+    for gi in lay.all if gis is None else gis:
+        m = ptr(Mt) + (moffs[gi] * 4 if stacked else 0)
+        p = None if part is None else part + roffs[gi] * 3 * cout * 4
+        dims = (lay.N, lay.H, lay.W, cout)
+        if zmask_shift is not None:
+            check(lib.mrcnn_winograd_output_bwd_zmask_g(m, ptr(out), ptr(below_z), ptr(scale), ptr(zmask_shift), ptr(mean), ptr(rstd), p, *dims,
+                                                        C.byref(lay.groups[gi]), current_stream()), "mrcnn_winograd_output_bwd_zmask_g")
+        else:
+            check(lib.mrcnn_winograd_output_bwd_g(m, ptr(out), ptr(below_out), ptr(below_z), ptr(scale), ptr(mean), ptr(rstd), p, *dims, act,
+                                                  C.byref(lay.groups[gi]), current_stream()), "mrcnn_winograd_output_bwd_g")
+
+
+def _wino_scratch(lay, Us, Cin, keep_v, stacked):
+    """(V, Mt) of a layer: V of all groups in one flat buffer (keep_v: the caller's, kept for the weight gradient or written by the
+    layer before), Mt for all groups end to end (stacked) or for the largest."""
+    nv, nms, dev = lay.floats(Cin)[1][-1], lay.floats(Us[0].shape[2])[0], Us[0].device
     V = keep_v if keep_v is not None else workspace(nv * 4, dev, "winograd_v")[:nv * 4].view(torch.float32)
     assert keep_v is None or (keep_v.numel() == nv and keep_v.dtype == torch.float32)
-    Mt = workspace((max(nms) if finish_all is None else sum(nms)) * 4, dev, "winograd_m")
-    off = moff = 0
-    for gi, (g, u) in enumerate(zip(groups, Us)):
-        Vg = V[off:off + nvs[gi]]
-        off += nvs[gi]
-        if not v_ready:
-            check(lib.mrcnn_winograd_input_g(ptr(x), ptr(Vg), N, H, W, Cin, C.byref(g), current_stream()), "mrcnn_winograd_input_g")
-        if gi == 0 and after_input is not None:
-            after_input()                # e.g. an event: a second chain on another stream starts one transform behind this one
-        nb = _wino_nb(g)
-        rows = nvs[gi] // (nb * Cin)
-        check(lib.mrcnn_winograd_gemm(ptr(Vg), ptr(u), ptr(Mt) + moff * 4, nb, rows, Cin, cout, current_stream()), "mrcnn_winograd_gemm")
-        if finish_all is None:
-            finish(g, Mt)
-        else:
-            moff += nms[gi]
-    if finish_all is not None:
-        finish_all(Mt)
+    return V, workspace((sum(nms) if stacked else max(nms)) * 4, dev, "winograd_m")
 
 
 def winograd_v_floats(xshape, tile=None):
     N, H, W, Cin = xshape
-    if tile is None:
-        tile = winograd_tile(xshape)
-    lib = _hip.lib()
-    return sum(lib.mrcnn_winograd_group_floats(C.byref(g), N, Cin) for g in winograd_groups(H, W, tile))
+    return _wino_layout(N, H, W, winograd_tile(xshape) if tile is None else tile).floats(Cin)[1][-1]
 
 
-def conv2d_winograd(x, U, bias=None, scale=None, shift=None, act=ACT_NONE, out=None, z_out=None, keep_v=None, after_input=None,
-                    v_ready=False):
-    """3 x 3 'same' stride-1 convolution with its epilogue through the Winograd domain (U = winograd_weights(w, tile=...)).
+def winograd_v_empty(xshape, device, tile=None):
+    """A tensor for the input transform V of a layer of this input shape (or for A dz A^T of a dz of this shape)."""
+    return empty((winograd_v_floats(xshape, tile),), torch.float32, device)
+
+
+def conv2d_winograd(x, U, bias=None, scale=None, shift=None, act=ACT_NONE, out=None, z_out=None, keep_v=None, v_ready=False):
+    """3 x 3 'same' stride-1 convolution with its epilogue through the Winograd domain (U = winograd_weights(w, tile=...)): per tile
+    group the input transform, the group's transform-domain GEMMs and the output transform.  keep_v: V is written there (kept for
+    the weight gradient).
     v_ready: keep_v already holds the input transform (conv2d_winograd_chain of the layer below wrote it) and x is the input's
-    shape: no input transform runs."""
-    _need_cuda(None if v_ready else x, bias, scale, shift, out, z_out, keep_v)
-    N, H, W, _ = x if v_ready else x.shape
-    U0 = U[0] if isinstance(U, (list, tuple)) else U
-    cout = U0.shape[2]
+    SHAPE: no input transform runs."""
+    assert not v_ready or keep_v is not None
+    x, (N, H, W, Cin) = _wino_arg(x, v_ready)
+    _need_cuda(x, bias, scale, shift, out, z_out, keep_v)
+    tile, Us, cout = _wino_weights_of(U)
     if out is None:
-        out = empty((N, H, W, cout), torch.float32, U0.device)
-    lib = _hip.lib()
-
-    def finish(g, Mt):
-        check(lib.mrcnn_winograd_output_g(ptr(Mt), ptr(out), ptr(z_out), ptr(bias), ptr(scale), ptr(shift), N, H, W, cout, act, C.byref(g),
-                                          current_stream()), "mrcnn_winograd_output_g")
-
-    _winograd_run(x, U, finish, keep_v, after_input, v_ready)
+        out = empty((N, H, W, cout), torch.float32, Us[0].device)
+    lay = _wino_layout(N, H, W, tile)
+    V, Mt = _wino_scratch(lay, Us, Cin, keep_v, False)
+    for gi in lay.all:
+        _wino_product(lay, x, Us, Cin, V, Mt, False, (gi,))
+        _wino_output(lay, Mt, False, out, z_out, bias, scale, shift, act, (gi,))
     return out
 
 
@@ -2162,38 +2231,23 @@ def conv2d_winograd_chain(x, U, next_v, bias=None, scale=None, shift=None, act=A
     same bits as the separate launches; the activated output is not written.  The next layer runs as
     conv2d_winograd(shape, U2, ..., keep_v=next_v, v_ready=True).  Returns None, or -- where the one-launch kernel refuses the shape
     -- the activated output after the separate launches (output transforms, then the input transforms into next_v)."""
-    _need_cuda(None if v_ready else x, bias, scale, shift, z_out, keep_v, next_v)
-    N, H, W, _ = x if v_ready else x.shape
-    Us = U if isinstance(U, (list, tuple)) else [U]
-    cout = Us[0].shape[2]
-    tile = _wino_tile_of(U)
-    groups = winograd_groups(H, W, tile)
-    lib = _hip.lib()
-    nms = [lib.mrcnn_winograd_group_floats(C.byref(g), N, cout) for g in groups]
-    assert next_v.numel() == sum(nms) and next_v.dtype == torch.float32
-    res = []
-
-    def finish_all(Mt):
-        rc = lib.mrcnn_winograd_chain(ptr(Mt), ptr(z_out), ptr(bias), ptr(scale), ptr(shift), ptr(next_v), N, H, W, cout, act, tile,
-                                      current_stream())
-        if rc != ERR_UNSUPPORTED:
-            check(rc, "mrcnn_winograd_chain")
-            return
-        out = empty((N, H, W, cout), torch.float32, next_v.device)
-        off = 0
-        for g, nm in zip(groups, nms):
-            check(lib.mrcnn_winograd_output_g(ptr(Mt) + off * 4, ptr(out), ptr(z_out), ptr(bias), ptr(scale), ptr(shift), N, H, W, cout, act,
-                                              C.byref(g), current_stream()), "mrcnn_winograd_output_g")
-            off += nm
-        off = 0
-        for g, nm in zip(groups, nms):
-            check(lib.mrcnn_winograd_input_g(ptr(out), ptr(next_v) + off * 4, N, H, W, cout, C.byref(g), current_stream()),
-                  "mrcnn_winograd_input_g")
-            off += nm
-        res.append(out)
-
-    _winograd_run(x, U, None, keep_v, None, v_ready, finish_all)
-    return res[0] if res else None
+    assert not v_ready or keep_v is not None
+    x, (N, H, W, Cin) = _wino_arg(x, v_ready)
+    _need_cuda(x, bias, scale, shift, z_out, keep_v, next_v)
+    tile, Us, cout = _wino_weights_of(U)
+    lay = _wino_layout(N, H, W, tile)
+    assert next_v.numel() == lay.floats(cout)[1][-1] and next_v.dtype == torch.float32
+    V, Mt = _wino_scratch(lay, Us, Cin, keep_v, True)
+    _wino_product(lay, x, Us, Cin, V, Mt, True)
+    rc = _hip.lib().mrcnn_winograd_chain(ptr(Mt), ptr(z_out), ptr(bias), ptr(scale), ptr(shift), ptr(next_v), N, H, W, cout, act, tile,
+                                         current_stream())
+    if rc != ERR_UNSUPPORTED:
+        check(rc, "mrcnn_winograd_chain")
+        return None
+    out = empty((N, H, W, cout), torch.float32, next_v.device)
+    _wino_output(lay, Mt, True, out, z_out, bias, scale, shift, act)
+    _wino_input(lay, out, cout, next_v)
+    return out
 
 
 def conv2d_dgrad_ep_winograd(dz, Ut, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, act, fwd_shift=None,
@@ -2214,83 +2268,59 @@ def conv2d_dgrad_ep_winograd(dz, Ut, below_out, below_z, scale, mean, rstd, dgam
     mt_ready (chain form only): the transform-domain product Mt of all groups end to end, made by the caller -- no input transform
     and no GEMM runs, dz is a SHAPE and Ut only says the tiling and the channel count (the transforms take any channel count in
     whole 4s; the GEMM of this module wants whole 128s)."""
-    assert mt_ready is None or next_v is not None
-    v_ready = v_ready or mt_ready is not None
-    _need_cuda(mt_ready, None if v_ready else dz, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, fwd_shift, next_v, next_dm, dz_out, keep_v)
-    N, H, W, _ = dz if v_ready else dz.shape
-    U0 = Ut[0] if isinstance(Ut, (list, tuple)) else Ut
-    cout, dev = U0.shape[2], U0.device
-    tile = _wino_tile_of(Ut)
-    groups = winograd_groups(H, W, tile)
+    chain = next_v is not None
+    assert (mt_ready is None or chain) and (not v_ready or keep_v is not None)
+    dz, (N, H, W, Cin) = _wino_arg(dz, v_ready or mt_ready is not None)
+    _need_cuda(mt_ready, dz, below_out, below_z, scale, mean, rstd, dgamma, dbeta, dbias, fwd_shift, next_v, next_dm, dz_out, keep_v)
+    tile, Us, cout = _wino_weights_of(Ut)
+    dev = Us[0].device
+    lay = _wino_layout(N, H, W, tile)
     lib = _hip.lib()
     zmask = act == ACT_RELU and fwd_shift is not None and below_z is not None and scale is not None
     if dgamma is None:
         mean = rstd = None
     # channel sums: every group's workgroups write one row of partials [3][cout] each into one per-stream buffer, group after
-    # group (the chain form: one row per map); one launch after the last group adds the rows up (fixed order) onto dgamma /
+    # group (the one-launch kernel: one row per map); one launch after the last group adds the rows up (fixed order) onto dgamma /
     # dbeta / dbias
     want_sums = dgamma is not None or dbeta is not None or dbias is not None
-    rows = [lib.mrcnn_winograd_output_bwd_rows(C.byref(g), N, cout) for g in groups]
+    rows, roffs = lay.sum_rows(cout)
     assert min(rows) > 0, "channel count does not fit the Winograd data-gradient transform"
-    chain = next_v is not None
-    part = ptr(workspace(max(sum(rows), N if chain else 0) * 3 * cout * 4, dev, "winograd_bwd_sums")) if want_sums else None
-    done = []
-    res = []
-
-    def finish(g, Mt, out, moff=0):
-        p = None
-        if want_sums:
-            p = part + sum(done) * 3 * cout * 4
-            done.append(rows[len(done)])
-        if zmask:
-            check(lib.mrcnn_winograd_output_bwd_zmask_g(ptr(Mt) + moff * 4, ptr(out), ptr(below_z), ptr(scale), ptr(fwd_shift), ptr(mean),
-                                                        ptr(rstd), p, N, H, W, cout, C.byref(g), current_stream()),
-                  "mrcnn_winograd_output_bwd_zmask_g")
-            return
-        check(lib.mrcnn_winograd_output_bwd_g(ptr(Mt) + moff * 4, ptr(out), ptr(below_out), ptr(below_z), ptr(scale), ptr(mean), ptr(rstd),
-                                              p, N, H, W, cout, act, C.byref(g), current_stream()),
-              "mrcnn_winograd_output_bwd_g")
-
-    def finish_all(Mt):
-        nms = [lib.mrcnn_winograd_group_floats(C.byref(g), N, cout) for g in groups]
-        assert next_v.numel() == sum(nms) and next_v.dtype == torch.float32
-        assert next_dm is None or (next_dm.numel() == sum(nms) and next_dm.dtype == torch.float32)
+    part = ptr(workspace(max(roffs[-1], N if chain else 0) * 3 * cout * 4, dev, "winograd_bwd_sums")) if want_sums else None
+    epilogue = (below_out, below_z, scale, mean, rstd, fwd_shift if zmask else None, act, part)
+    n_rows = roffs[-1]
+    if not chain:
+        assert dz_out is None or tuple(dz_out.shape) == (N, H, W, cout)
+        out = dz_out if dz_out is not None else empty((N, H, W, cout), torch.float32, dev)
+        V, Mt = _wino_scratch(lay, Us, Cin, keep_v, False)
+        for gi in lay.all:
+            _wino_product(lay, dz, Us, Cin, V, Mt, False, (gi,))
+            _wino_output_bwd(lay, Mt, False, out, *epilogue, (gi,))
+    else:
+        nm = lay.floats(cout)[1][-1]
+        assert next_v.numel() == nm and next_v.dtype == torch.float32
+        assert next_dm is None or (next_dm.numel() == nm and next_dm.dtype == torch.float32)
+        Mt = mt_ready
+        if Mt is None:
+            V, Mt = _wino_scratch(lay, Us, Cin, keep_v, True)
+            _wino_product(lay, dz, Us, Cin, V, Mt, True)
         rc = ERR_UNSUPPORTED
         if zmask:
             rc = lib.mrcnn_winograd_bwd_chain(ptr(Mt), ptr(below_z), ptr(scale), ptr(fwd_shift), ptr(mean), ptr(rstd), part, ptr(next_v),
                                               ptr(next_dm), ptr(dz_out), N, H, W, cout, tile, current_stream())
         if rc != ERR_UNSUPPORTED:
             check(rc, "mrcnn_winograd_bwd_chain")
-            done.append(N)
-            res.append(dz_out)
-            return
-        out = dz_out if dz_out is not None else empty((N, H, W, cout), torch.float32, dev)
-        off = 0
-        for g, nm in zip(groups, nms):
-            finish(g, Mt, out, off)
-            off += nm
-        off = 0
-        for g, nm in zip(groups, nms):
-            check(lib.mrcnn_winograd_input_g(ptr(out), ptr(next_v) + off * 4, N, H, W, cout, C.byref(g), current_stream()),
-                  "mrcnn_winograd_input_g")
-            if next_dm is not None:
-                check(lib.mrcnn_winograd_dy_g(ptr(out), ptr(next_dm) + off * 4, N, H, W, cout, C.byref(g), current_stream()),
-                      "mrcnn_winograd_dy_g")
-            off += nm
-        res.append(out)
-
-    if mt_ready is not None:
-        finish_all(mt_ready)
-    elif chain:
-        _winograd_run(dz, Ut, None, keep_v, None, v_ready, finish_all)
-    else:
-        assert dz_out is None or tuple(dz_out.shape) == (N, H, W, cout)
-        res.append(dz_out if dz_out is not None else empty((N, H, W, cout), torch.float32, dev))
-        _winograd_run(dz, Ut, lambda g, Mt: finish(g, Mt, res[0]), keep_v, None, v_ready)
+            out, n_rows = dz_out, N
+        else:
+            out = dz_out if dz_out is not None else empty((N, H, W, cout), torch.float32, dev)
+            _wino_output_bwd(lay, Mt, True, out, *epilogue)
+            for gi in lay.all:
+                _wino_input(lay, out, cout, next_v, (gi,))
+                if next_dm is not None:
+                    _wino_dy(lay, out, cout, next_dm, True, (gi,))
     if want_sums:
-        check(lib.mrcnn_winograd_output_bwd_sums(part, sum(done), cout, ptr(dgamma), ptr(dbeta), ptr(dbias), current_stream()),
+        check(lib.mrcnn_winograd_output_bwd_sums(part, n_rows, cout, ptr(dgamma), ptr(dbeta), ptr(dbias), current_stream()),
               "mrcnn_winograd_output_bwd_sums")
-    return res[0]
+    return out
 
 
 def conv2d_wgrad_winograd(V, xshape, dz, dw, accumulate=False, tile=None, dm_ready=None):
@@ -2299,33 +2329,27 @@ def conv2d_wgrad_winograd(V, xshape, dz, dw, accumulate=False, tile=None, dm_rea
     winograd_tile(xshape), what the forward chose for this shape).
     dm_ready: A dz A^T of all groups end to end, as the chain form of conv2d_dgrad_ep_winograd wrote it (next_dm): no transform of
     dz runs, and dz may be its SHAPE."""
-    _need_cuda(V, None if dm_ready is not None else dz, dw, dm_ready)
+    stacked = dm_ready is not None
+    dz, dzshape = _wino_arg(dz, stacked)
+    _need_cuda(V, dz, dw, dm_ready)
     N, H, W, Cin = xshape
-    cout = (dz if isinstance(dz, (tuple, list)) else dz.shape)[3]
-    if tile is None:
-        tile = winograd_tile(xshape)
-    groups = winograd_groups(H, W, tile)
-    lib = _hip.lib()
-    nvs = [lib.mrcnn_winograd_group_floats(C.byref(g), N, Cin) for g in groups]
-    nms = [lib.mrcnn_winograd_group_floats(C.byref(g), N, cout) for g in groups]
-    assert V.numel() == sum(nvs), "V was made with another tiling"
-    assert dm_ready is None or (dm_ready.numel() == sum(nms) and dm_ready.dtype == torch.float32), "dM was made with another tiling"
-    dM_all = workspace(max(nms) * 4, V.device, "winograd_dm") if dm_ready is None else None
+    cout = dzshape[3]
+    lay = _wino_layout(N, H, W, winograd_tile(xshape) if tile is None else tile)
+    (nvs, voffs), (nms, moffs) = lay.floats(Cin), lay.floats(cout)
+    assert V.numel() == voffs[-1], "V was made with another tiling"
+    assert not stacked or (dm_ready.numel() == moffs[-1] and dm_ready.dtype == torch.float32), "dM was made with another tiling"
+    dM_all = dm_ready if stacked else workspace(max(nms) * 4, V.device, "winograd_dm")[:max(nms) * 4].view(torch.float32)
     dU_all = workspace(36 * Cin * cout * 4, V.device, "winograd_du")
-    off = moff = 0
-    for gi, g in enumerate(groups):
-        nb = _wino_nb(g)
+    for gi, g in enumerate(lay.groups):
+        nb = lay.nbs[gi]
         rows = nms[gi] // (nb * cout)
         T = N * g.th_n * g.tw_n
         dU = dU_all[:nb * Cin * cout * 4].view(torch.float32).view(nb, Cin, cout)
-        if dm_ready is None:
-            dM = dM_all[:nms[gi] * 4].view(torch.float32).view(nb, rows, cout)
-            check(lib.mrcnn_winograd_dy_g(ptr(dz), ptr(dM), N, H, W, cout, C.byref(g), current_stream()), "mrcnn_winograd_dy_g")
-        else:
-            dM = dm_ready[moff:moff + nms[gi]].view(nb, rows, cout)
-            moff += nms[gi]
-        Vv = V[off:off + nvs[gi]].view(nb, rows, Cin)
-        off += nvs[gi]
+        if not stacked:
+            _wino_dy(lay, dz, cout, dM_all, False, (gi,))
+        moff = moffs[gi] if stacked else 0
+        dM = dM_all[moff:moff + nms[gi]].view(nb, rows, cout)
+        Vv = V[voffs[gi]:voffs[gi] + nvs[gi]].view(nb, rows, Cin)
         items = [(Vv[k, :T].view(T, 1, 1, Cin), dM[k, :T].view(T, 1, 1, cout), (1, 1, Cin, cout), 1, "valid", dU[k].view(1, 1, Cin, cout), False)
                  for k in range(nb)]
         per = 16 if nb == 16 else 12                           # GEMMs per launch (+ one launch for their slab reductions): the argument block holds 16
@@ -2333,7 +2357,7 @@ def conv2d_wgrad_winograd(V, xshape, dz, dw, accumulate=False, tile=None, dm_rea
             if not conv2d_wgrad_multi(items[i:i + per]):
                 for x_, dy_, wshape, stride, padding, dw_, acc in items[i:i + per]:
                     conv2d_wgrad(x_, dy_, wshape, stride, padding, dw=dw_, accumulate=acc)
-        check(lib.mrcnn_winograd_dw_g(ptr(dU), ptr(dw), Cin, cout, 1 if (accumulate or gi > 0) else 0, g.oth, g.otw, current_stream()),
+        check(_hip.lib().mrcnn_winograd_dw_g(ptr(dU), ptr(dw), Cin, cout, 1 if (accumulate or gi > 0) else 0, g.oth, g.otw, current_stream()),
               "mrcnn_winograd_dw_g")
     return dw
 
