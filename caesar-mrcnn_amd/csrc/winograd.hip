@@ -868,10 +868,43 @@ struct GemmDeconvEp {
     FastDiv d_hw, d_w;
 };
 
-template <int TN, bool DECONV>      // TN 2: 128 x 128 tile (5 workgroups per CU); 4: 128 x 256 tile -- N = 256 whole: every V row block is fetched once
-__global__ __launch_bounds__(256, 2) void winograd_gemm_kernel(const float* __restrict__ V, const float* __restrict__ U, float* __restrict__ Mt,
+// MASK (with DECONV, TN = 4, Cd = 256: tile column block n0 / 256 is the tap, and a tile holds all 256 channels of its 128 output
+// pixels): the mask head's output layer in the same epilogue (mrcnn_deconv2x2_mask_gemm) --
+// m[img][2 h + a][2 w + b][k] = sigmoid(b_mask[k] + sum_co out[..][co] . w_mask[co][k]), k < C <= 16.  Mt may be null then (inference:
+// `out` itself is not stored).  The sum runs in a fixed order: in the lane over its four column groups, across the 32 lanes that
+// share a row by halving exchanges, then N-wave 0 + N-wave 1 through LDS.
+struct GemmMaskEp : GemmDeconvEp {
+    const float* w_mask;     // [Cd][C]
+    const float* b_mask;     // [C] or null
+    float* m;                // [N][2 H][2 W][C]
+    int C;
+};
+
+// the value of lane (l ^ X) within each half wave, X < 32: ds_swizzle in its bit-mask mode (and 0x1f, or 0, xor X) -- an LDS-pipe
+// instruction that touches no memory and, unlike ds_bpermute, takes no address register
+template <int X>
+__device__ __forceinline__ float wino_swz_xor(float v) {
+    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x1f | (X << 10)));
+}
+// one halving exchange over lane bit HS: s[0 .. 2 HS) on every lane -> s[0 .. HS), each the sum of the two partner lanes' values of
+// row i (lanes with the bit clear) or row i + HS (bit set)
+template <int HS>
+__device__ __forceinline__ void wino_halve(float* s, int li) {
+    const bool hi = li & HS;
+#pragma unroll
+    for (int i = 0; i < HS; ++i) {
+        const float lo_v = s[i], hi_v = s[i + HS];         // values, not lvalues: a conditional over array elements becomes a
+        const float keep = hi ? hi_v : lo_v;               // dynamic index into registers
+        const float send = hi ? lo_v : hi_v;
+        s[i] = keep + wino_swz_xor<HS>(send);
+    }
+}
+
+template <int TN, bool DECONV, bool MASK = false>   // TN 2: 128 x 128 tile (5 workgroups per CU); 4: 128 x 256 tile -- N = 256 whole: every V row block is fetched once
+__global__ __launch_bounds__(256, MASK ? 3 : 2) void winograd_gemm_kernel(const float* __restrict__ V, const float* __restrict__ U, float* __restrict__ Mt,
                                                                int rows, int K, int N, int total_tiles, unsigned v_records,
-                                                               const GemmDeconvEp ep) {
+                                                               const std::conditional_t<MASK, GemmMaskEp, GemmDeconvEp> ep) {
+    static_assert(!MASK || (DECONV && TN == 4), "the mask epilogue wants one tap's 256 channels in a tile");
     constexpr int BM = 128, BN = 64 * TN, BK = 16, TM = 2;
     constexpr int AF = BM * BK, BF = BK * BN;
     __shared__ __attribute__((aligned(16))) float lds[2 * (AF + BF)];
@@ -893,6 +926,20 @@ __global__ __launch_bounds__(256, 2) void winograd_gemm_kernel(const float* __re
         const int ntile = tile - mtile * ntiles;
         m0 = mtile * BM; n0 = ntile * BN;
         const unsigned wbase = (unsigned)(((long long)(m0 / rows) * K * N + n0) * 4);      // the tile's weight matrix (U [nb][K][N], < 2 GiB)
+        if constexpr (MASK) {
+            // The mask epilogue needs every register beside the 128 accumulators, so this instantiation keeps three offsets, not
+            // six, and none of their lane-only parts across the K loop (the empty asm has them recomputed per tile).  The second A
+            // piece is 64 rows below the first with the same swizzle; with BN = 256 B piece jj is k row wave + 4 jj whole, and
+            // stage() puts those 4 jj rows into the scalar offset (the weights are never addressed out of range).
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int r = wave * 16 + (ln >> 2);
+            const int cl = (ln & 3) ^ ((r >> 2) & 3);
+            a_voff[0] = (unsigned)(((long long)(m0 + r) * K + cl * 4) * 4);
+            a_voff[1] = a_voff[0] + (unsigned)(64 * K * 4);
+            b_voff[0] = wbase + (unsigned)((wave * N + ln * 4) * 4);
+            return;
+        }
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
             const int r = (wave + jj * 4) * 16 + (lane >> 2);
@@ -914,8 +961,13 @@ __global__ __launch_bounds__(256, 2) void winograd_gemm_kernel(const float* __re
         for (int jj = 0; jj < 2; ++jj)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (wino_lds_ptr)(ab + (wave + jj * 4) * 256), 16, a_voff[jj], soff_a, 0, 0);
 #pragma unroll
-        for (int jj = 0; jj < NBP; ++jj)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (wino_lds_ptr)(bb + (wave + jj * 4) * 256), 16, b_voff[jj], soff_b, 0, 0);
+        for (int jj = 0; jj < NBP; ++jj) {
+            if constexpr (MASK)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (wino_lds_ptr)(bb + (wave + jj * 4) * 256), 16, b_voff[0],
+                                                         soff_b + (unsigned)(jj * 16 * N), 0, 0);
+            else
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (wino_lds_ptr)(bb + (wave + jj * 4) * 256), 16, b_voff[jj], soff_b, 0, 0);
+        }
         k0 += BK;
     };
     f32x16 acc[TM][TN];
@@ -945,6 +997,14 @@ __global__ __launch_bounds__(256, 2) void winograd_gemm_kernel(const float* __re
     };
     typedef std::integral_constant<int, 0> I0;
     typedef std::integral_constant<int, 1> I1;
+
+    if constexpr (MASK) {                                  // once per workgroup; the first tile's top-of-loop barrier publishes it
+        extern __shared__ __attribute__((aligned(16))) float wino_mask_w[];   // w_mask as [k][256 co]: 256 C floats of dynamic LDS
+        for (int i = tid; i < 256 * ep.C; i += 256) {
+            const int co = i / ep.C;
+            wino_mask_w[(i - co * ep.C) * 256 + co] = ep.w_mask[i];
+        }
+    }
 
     int tile = blockIdx.x;
     setup(tile);
@@ -982,6 +1042,89 @@ __global__ __launch_bounds__(256, 2) void winograd_gemm_kernel(const float* __re
                         const int m = mw0 + a * 32 + (r & 3) + 8 * (r >> 2);
                         if (m < Mtot) Mt[(long long)m * N + nw0 + b * 32] = acc[a][b][r];
                     }
+        } else if constexpr (MASK) {
+            extern __shared__ __attribute__((aligned(16))) float wino_mask_w[];
+            // Cd = 256 = BN: every column of the tile belongs to tap nw0 / 256; this lane's channels are co0 + 32 b
+            // Lane and wave coordinates are taken back out of the tile's own mw0 / nw0 (m0 % 128 == 0, n0 % 256 == 0), so that what
+            // the epilogue derives from them is computed per tile and does not sit in registers across the K loop.
+            // (The empty asm keeps the compiler from seeing through that: n0 is a multiple of 256 by construction.)
+            int nw0_e = nw0, mw0_e = mw0;
+            asm volatile("" : "+v"(nw0_e), "+v"(mw0_e));
+            const int tap = nw0 >> 8, co0 = nw0_e & 255;
+            const int li_e = nw0_e & 31, lane_e = ((mw0_e >> 2) & 1) * 32 + li_e;
+            const int hw = ep.H * ep.W;
+#pragma unroll
+            for (int b = 0; b < TN; ++b) {
+                const float bi = ep.bias ? ep.bias[co0 + b * 32] : 0.f;
+#pragma unroll
+                for (int a = 0; a < TM; ++a)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float v = acc[a][b][r] + bi;
+                        if (ep.act == MRCNN_ACT_RELU) v = fmaxf(v, 0.f);
+                        acc[a][b][r] = v;
+                    }
+            }
+            if (Mt) {                                                          // the pixel-shuffle store of the DECONV epilogue
+                const int coff = ((tap >> 1) * 2 * ep.W + (tap & 1)) * 256 + co0;
+#pragma unroll
+                for (int a = 0; a < TM; ++a)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int m = mw0 + a * 32 + (r & 3) + 8 * (r >> 2);
+                        if (m >= Mtot) continue;
+                        const int img = (int)fast_div((unsigned)m, ep.d_hw), rem = m - img * hw;
+                        const int h = (int)fast_div((unsigned)rem, ep.d_w), w = rem - h * ep.W;
+                        const long long base = (((long long)img * 2 * ep.H + 2 * h) * 2 * ep.W + 2 * w) * 256;
+#pragma unroll
+                        for (int b = 0; b < TN; ++b) Mt[base + coff + b * 32] = acc[a][b][r];
+                        __builtin_amdgcn_sched_barrier(0);                     // one row's addresses at a time: the 128 accumulators stay live
+                    }
+            }
+            // Partial logits.  The exchange area is stage buffer 1: the K loop's last barrier is behind its last reader and no DMA
+            // into it is outstanding (the next tile's first stage, already issued above, fills buffer 0).
+            float* xch = lds + (AF + BF);                                      // [wn][wm][k < 16][lane]
+#pragma unroll 1
+            for (int k = 0; k < ep.C; ++k) {
+                float wk[TN];
+#pragma unroll
+                for (int b = 0; b < TN; ++b) wk[b] = wino_mask_w[k * 256 + co0 + b * 32];
+                float mine = 0.f;                                              // the sum of this lane's row: block li >> 4, row li & 15
+#pragma unroll
+                for (int g = 0; g < 2 * TM; ++g) {                             // eight rows at a time: rows 8 (g & 1) .. of block g >> 1
+                    float s[8];                                                // this lane's four channels of each
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        s[i] = acc[g >> 1][0][(g & 1) * 8 + i] * wk[0];
+#pragma unroll
+                        for (int b = 1; b < TN; ++b) s[i] = fmaf(acc[g >> 1][b][(g & 1) * 8 + i], wk[b], s[i]);
+                    }
+                    // 8 rows x 32 lanes: three halving exchanges leave row li & 7 summed over 8 lanes, two plain ones finish it
+                    wino_halve<4>(s, li_e); wino_halve<2>(s, li_e); wino_halve<1>(s, li_e);
+                    float t = s[0] + wino_swz_xor<8>(s[0]);
+                    t = t + wino_swz_xor<16>(t);
+                    mine = ((li_e >> 3) == g) ? t : mine;
+                    __builtin_amdgcn_sched_barrier(0);                         // one group after the other: 8 sums live beside the accumulators
+                }
+                xch[((wn * 2 + wm) * 16 + k) * 64 + lane_e] = mine;
+            }
+            __syncthreads();                                                   // both N-waves' partial sums are in LDS
+            if (wn == 0) {
+                const int r = li_e & 15;
+                const int m = mw0 + (li_e >> 4) * 32 + (r & 3) + 8 * (r >> 2);
+                if (m < Mtot) {
+                    const int img = (int)fast_div((unsigned)m, ep.d_hw), rem = m - img * hw;
+                    const int h = (int)fast_div((unsigned)rem, ep.d_w), w = rem - h * ep.W;
+                    float* mo = ep.m + (((long long)img * 2 * ep.H + 2 * h + (tap >> 1)) * 2 * ep.W + 2 * w + (tap & 1)) * ep.C;
+                    for (int k = 0; k < ep.C; ++k) {
+                        const float y = (xch[(wm * 16 + k) * 64 + lane] + xch[((2 + wm) * 16 + k) * 64 + lane]) + (ep.b_mask ? ep.b_mask[k] : 0.f);
+                        mo[k] = 1.f / (1.f + expf(-y));
+                    }
+                }
+            }
+            // This barrier orders the reads of xch above before the next tile's first stage(lds + AF + BF), which overwrites it.
+            // (The loop's top barrier would do the same today; this one keeps the epilogue safe on its own.)
+            __syncthreads();
         } else {
             float bi[TN];
             int coff[TN];                                                      // (a * 2 W + b) * Cd + co of this lane's column in group b
@@ -1301,5 +1444,31 @@ extern "C" int mrcnn_deconv2x2_gemm(const float* x, const float* w_gemm, const f
     const int rows = (int)((M + 127) / 128 * 128);              // one matrix: every tile uses weight matrix 0
     hipLaunchKernelGGL((winograd_gemm_kernel<2, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w_gemm, out, rows, Cin, Nn, (int)tiles,
                        (unsigned)(M * Cin * 4), ep);
+    return mrcnn_launch_status();
+}
+
+/* The mask head's output stage in one launch: the transposed convolution above on the wide tile, with the mrcnn_mask 1 x 1
+ * convolution (Cd -> C), its bias and the sigmoid in the same epilogue -- `up` is not read back.  up [N][2 H][2 W][Cd] may be NULL
+ * (inference: not stored); w_mask [Cd][C], b_mask [C] or NULL, mask_out [N][2 H][2 W][C].  Cd == 256, 1 <= C <= 16. */
+extern "C" int mrcnn_deconv2x2_mask_gemm(const float* x, const float* w_gemm, const float* bias, float* up, const float* w_mask,
+                                         const float* b_mask, float* mask_out, int N, int H, int W, int Cin, int Cd, int C, int act,
+                                         void* stream) {
+    if (!x || !w_gemm || !w_mask || !mask_out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cd <= 0) return MRCNN_ERR_ARG;
+    if (act != MRCNN_ACT_NONE && act != MRCNN_ACT_RELU) return MRCNN_ERR_UNSUPPORTED;
+    if (Cd != 256 || C < 1 || C > 16) return MRCNN_ERR_UNSUPPORTED;
+    const long long M = (long long)N * H * W;
+    const int Nn = 4 * Cd;
+    if (Cin % 16 || M * Cin * 4 >= 0x7FFFFFF0LL || (long long)Cin * Nn * 4 >= 0x7FFFFFF0LL || M >= (1LL << 31) - 128)
+        return MRCNN_ERR_UNSUPPORTED;
+    GemmMaskEp ep = {};
+    ep.bias = bias; ep.Cd = Cd; ep.H = H; ep.W = W; ep.act = act;
+    ep.d_hw = make_fastdiv((unsigned)(H * W)); ep.d_w = make_fastdiv((unsigned)W);
+    ep.w_mask = w_mask; ep.b_mask = b_mask; ep.m = mask_out; ep.C = C;
+    const long long tiles = ((M + 127) / 128) * (Nn / 256);
+    const long long slots = 3LL * mrcnn_num_cus();              // 128 x 256 tiles, as the wide Winograd launch
+    const unsigned grid = (unsigned)(tiles < slots ? tiles : slots);
+    const int rows = (int)((M + 127) / 128 * 128);
+    hipLaunchKernelGGL((winograd_gemm_kernel<4, true, true>), dim3(grid), dim3(256), (size_t)256 * C * sizeof(float), (hipStream_t)stream, x,
+                       w_gemm, up, rows, Cin, Nn, (int)tiles, (unsigned)(M * Cin * 4), ep);
     return mrcnn_launch_status();
 }

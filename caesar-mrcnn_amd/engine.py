@@ -83,6 +83,9 @@ SWITCHES = (
     ("infer_mask_tile", "MRCNN_WINOGRAD_INFER_MASK_TILE", 4, int, "i"),
     # the 16 x 16-tile single-launch kernel for the layers of a few hundred pixels of the inference trunk (see infer)
     ("sk16_infer", "MRCNN_SK16_INFER", True, _on, "i"),
+    # float32 mask head: the mrcnn_mask 1x1 convolution and its sigmoid in the epilogue of the deconvolution's GEMM
+    # (ops.deconv2x2_mask); False: the two launches (A/B)
+    ("fused_mask_out_fwd", "MRCNN_MASK_OUT_FWD_FUSED", True, _on, "ti"),
     ("fused_mask_out_bwd", None, True, None, "t"),              # single-pass backward of the mask-head output stage
     ("fused_dgrad_epilogue", None, True, None, "t"),            # mask-head data-gradient convs apply the lower layer's epilogue bwd
     ("gather_roialign_bwd", "MRCNN_GATHER_ROIALIGN_BWD", True, _on, "t"),   # class-head ROIAlign adjoint in gather form
@@ -990,9 +993,14 @@ class MaskRCNNEngine(object):
                 ctxs.append(Ctx(up, None, m, ACT_SIGMOID, H16) if train else None)
                 return m.view(B, R, m.shape[1], m.shape[2], m.shape[3]), ctxs
             x = ops.cast_from_h16(h)
-        dc = self.op("mrcnn_mask_deconv")
-        up = ops.deconv2x2(x, dc.w.view(dc.wshape[2], dc.wshape[3]), dc.b, ACT_RELU)
-        m, cm = self.op("mrcnn_mask").forward(up, ACT_SIGMOID, train=train)
+        dc, mop = self.op("mrcnn_mask_deconv"), self.op("mrcnn_mask")
+        if self.fused_mask_out_fwd:                # the 1x1 convolution and the sigmoid in the deconvolution's epilogue; inference
+            up, m = ops.deconv2x2_mask(x, dc.w.view(dc.wshape[2], dc.wshape[3]), dc.b, mop.w.view(mop.wshape[2], mop.wshape[3]),
+                                       mop.b, ACT_RELU, want_up=train)             # does not store `up`
+            cm = Ctx(up, None, m, ACT_SIGMOID) if train else None
+        else:
+            up = ops.deconv2x2(x, dc.w.view(dc.wshape[2], dc.wshape[3]), dc.b, ACT_RELU)
+            m, cm = mop.forward(up, ACT_SIGMOID, train=train)
         ctxs.append(Ctx(x, None, up, ACT_RELU) if train else None)
         ctxs.append(cm)
         return m.view(B, R, m.shape[1], m.shape[2], m.shape[3]), ctxs

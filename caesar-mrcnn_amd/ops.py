@@ -217,6 +217,28 @@ def deconv2x2(x, w_gemm, bias, act=ACT_RELU, out=None):
     return out
 
 
+def deconv2x2_mask(x, w_gemm, bias, w_mask, b_mask, act=ACT_RELU, want_up=True):
+    """The mask head's output stage: up = deconv2x2(x, w_gemm, bias, act), m = sigmoid(up . w_mask + b_mask) with w_mask [Cd, C].
+    Returns (up, m), or (None, m) for want_up=False where the single launch ran (mrcnn_deconv2x2_mask_gemm: the 1x1 convolution
+    and the sigmoid in the deconvolution's epilogue, `up` not read back).  Shapes that launch does not take run deconv2x2 and the
+    1x1 convolution as two launches; `up` is returned then whatever want_up says."""
+    _need_cuda(x, w_gemm, bias, w_mask, b_mask)
+    N, H, W, Cin = x.shape
+    Cd, Cm = w_gemm.shape[1] // 4, w_mask.shape[-1]
+    if (_DECONV_GEMM and Cin % 16 == 0 and Cd == 256 and 1 <= Cm <= 16 and act in (ACT_NONE, ACT_RELU) and
+            N * H * W * Cin * 4 < 0x7FFFFFF0 and N * H * W >= _DECONV_GEMM_MIN_ROWS):
+        up = empty((N, 2 * H, 2 * W, Cd), torch.float32, x.device) if want_up else None
+        m = empty((N, 2 * H, 2 * W, Cm), torch.float32, x.device)
+        rc = _hip.lib().mrcnn_deconv2x2_mask_gemm(ptr(x), ptr(w_gemm), ptr(bias), ptr(up), ptr(w_mask), ptr(b_mask), ptr(m), N, H, W, Cin,
+                                                  Cd, Cm, act, current_stream())
+        if rc != ERR_UNSUPPORTED:
+            check(rc, "mrcnn_deconv2x2_mask_gemm")
+            return up, m
+    up = deconv2x2(x, w_gemm, bias, act)
+    m = conv2d(up, w_mask.reshape(1, 1, Cd, Cm), b_mask, act=ACT_SIGMOID)
+    return up, m
+
+
 _ws_cache = {}
 _ws_retired = []
 

@@ -1085,6 +1085,15 @@ int mrcnn_winograd_dw_g(const float* dU, float* dw_hwio, int Cin, int Cout, int 
 int mrcnn_deconv2x2_gemm(const float* x, const float* w_gemm, const float* bias, float* out, int N, int H, int W, int Cin, int Cd,
                          int act, void* stream);
 
+/* The mask head's output stage (model.py:1084-1088) in one launch: the product above on the 128 x 256 tile, and in the same
+ * epilogue KL.Conv2D(num_classes, (1, 1), activation="sigmoid") over the 256 channels the tile holds for each of its output pixels:
+ * mask_out[n][y][x][k] = sigmoid(b_mask[k] + sum_co up[n][y][x][co] w_mask[co][k]) -- the deconvolution's output is not read back.
+ * up [N][2 H][2 W][Cd] is written as mrcnn_deconv2x2_gemm writes `out` (same bits), or not at all when NULL (inference);
+ * w_mask [Cd][C], b_mask [C] or NULL, mask_out [N][2 H][2 W][C].  The sum has a fixed order (no atomics).
+ * Cin % 16 == 0, Cd == 256, 1 <= C <= 16, act NONE or RELU; else MRCNN_ERR_UNSUPPORTED. */
+int mrcnn_deconv2x2_mask_gemm(const float* x, const float* w_gemm, const float* bias, float* up, const float* w_mask,
+                              const float* b_mask, float* mask_out, int N, int H, int W, int Cin, int Cd, int C, int act, void* stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI ---------------------------------------------------------------
  * Replaces the in-graph tower aggregation of mrcnn/parallel_model.py:54-104 (weights shared between towers, gradients
  * summed implicitly by TF, scalar losses averaged :97-99): one process per GPU, each rank sums contiguous ranges

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The Winograd transform launches of the mask-head FORWARD of one training step of a rocprofv3 kernel trace: the window from the
-ProposalLayer to the transposed convolution's GEMM (winograd_gemm_kernel<2, true>), where no backward launch of the same kernels
+ProposalLayer to the transposed convolution's GEMM (winograd_gemm_kernel<.., true, ..>), where no backward launch of the same kernels
 runs; grouped by (kernel, workgroups): launches, summed and mean duration.
 usage: wino_fwd_window.py <kernel_trace.csv> [step index]"""
 import csv, sys, collections
@@ -12,7 +12,7 @@ sgd = [e for e in ev if e[2].startswith('sgd_kernel')]
 t0, t1 = sgd[step][1], sgd[step + 1][1]
 seg = [e for e in ev if e[0] >= t0 and e[1] <= t1]
 p = next(e for e in seg if e[2].startswith('select_sort_decode') or e[2].startswith('topk'))
-d = next(e for e in seg if e[2].startswith('winograd_gemm_kernel<2, true>'))
+d = next(e for e in seg if e[2].startswith(('winograd_gemm_kernel<2, true', 'winograd_gemm_kernel<4, true')))   # DECONV, with or without the mask epilogue
 win = [e for e in seg if e[0] >= p[1] and e[1] <= d[0]]
 print("mask-head forward window (ProposalLayer .. transposed convolution): %.3f ms" % ((d[0] - p[1]) / 1e6))
 names = ('winograd_input_kernel', 'winograd_output_kernel', 'winograd_chain_kernel')
