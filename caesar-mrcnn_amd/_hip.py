@@ -268,6 +268,7 @@ _SIGNATURES = {
     "mrcnn_detection_fwd": (C.c_int, [C.POINTER(DetectionDesc)] + [_P] * 6 + [C.c_size_t, _P]),
     "mrcnn_losses_workspace": (C.c_size_t, [C.POINTER(LossDesc)]),
     "mrcnn_losses_fwd_bwd": (C.c_int, [C.POINTER(LossDesc)] + [_P] * 18 + [C.c_size_t, _P]),
+    "mrcnn_losses_fwd_bwd_weighted": (C.c_int, [C.POINTER(LossDesc)] + [_P] * 19 + [C.c_size_t, _P]),
     "mrcnn_grad_prepare": (C.c_int, [_P, _P, C.c_float, _P, C.c_int64, _P, _P]),
     "mrcnn_sumsq": (C.c_int, [_P, C.c_int64, _P, _P]),
     "mrcnn_sgd_momentum": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, C.c_int64, _P]),

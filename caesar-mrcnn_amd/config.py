@@ -58,6 +58,10 @@ class Config(object):
     TRAIN_BN = False
     GRADIENT_CLIP_NORM = 5.0
     MASK_LOSS_FUNCTION = 'binary_crossentropy'  # or 'dice_coef_loss'
+    # extension (the reference parses --weight_classes and Keras drops the weights): None, or the class weights
+    # of the three head losses -- a dict {class_id: weight} or NUM_CLASSES weights, index 0 the background
+    # (MaskRCNN.set_class_weights); MaskRCNN.train(class_weights=...) overrides it
+    CLASS_WEIGHTS = None
     # extension (not in the reference): build rpn_match / rpn_bbox on the GPU (csrc/rpn_targets.hip) instead of in
     # the NumPy generator; False restores the host path and its np.random.choice stream (model.py:1536-1644)
     DEVICE_RPN_TARGETS = True

@@ -23,6 +23,7 @@ struct LossArgs {
     float* part_heads;                 // [B * T][PART_HEADS] block sums of heads_loss_reduce_kernel
     int B, A, T, C, mh, mw, max_rpn_pos, dice;
     float w0, w1, w2, w3, w4;
+    const float* cw;                   // [C] class weights of the head losses; nullptr = unweighted
 };
 
 __device__ __forceinline__ float block_sum(float v, float* sbuf) {
@@ -135,6 +136,7 @@ __global__ __launch_bounds__(256) void heads_loss_reduce_kernel(const LossArgs p
     const int64_t row = blockIdx.x;
     const int tid = threadIdx.x, C = p.C;
     const int cls = p.tcls[row];
+    const float u = p.cw ? p.cw[cls] : 1.f;              // this row's class weight (uniform branch; cls in [0, C) as for l[cls])
     float* o = p.part_heads + row * PART_HEADS;          // S_C_SUM, S_C_PA, S_B_SUM, S_POS, S_M_SUM, S_D_Y, S_D_P of this row
     if (tid == 0) {
         const float* l = p.cls_logits + row * C;
@@ -154,6 +156,7 @@ __global__ __launch_bounds__(256) void heads_loss_reduce_kernel(const LossArgs p
             o[2] = smooth_l1(t[0], q[0]) + smooth_l1(t[1], q[1]) + smooth_l1(t[2], q[2]) + smooth_l1(t[3], q[3]);
             o[3] = 1.f;
         }
+        if (p.cw) { o[0] *= u; o[2] *= u; }               // o[1], o[3] stay counts: the normalisers are unweighted
     }
     if (cls <= 0) return;
     const int npix = p.mh * p.mw;
@@ -173,6 +176,7 @@ __global__ __launch_bounds__(256) void heads_loss_reduce_kernel(const LossArgs p
     ms = block_sum(ms, sbuf);
     if (p.dice) { sy = block_sum(sy, sbuf); sp = block_sum(sp, sbuf); }
     if (tid == 0) {                                      // the same thread wrote the zeros above
+        if (p.cw) { ms *= u; sy *= u; sp *= u; }
         o[4] = ms;
         if (p.dice) { o[5] = sy; o[6] = sp; }
     }
@@ -243,6 +247,7 @@ __global__ __launch_bounds__(256) void heads_loss_grad_kernel(const LossArgs p) 
     const int64_t row = blockIdx.x;
     const int tid = threadIdx.x, C = p.C;
     const int cls = p.tcls[row];
+    const float u = p.cw ? p.cw[cls] : 1.f;              // this row's class weight, as in heads_loss_reduce_kernel
     const float pa_sum = p.scal[S_C_PA], npos = p.scal[S_POS];
     const int npix = p.mh * p.mw;
     if (row == 0 && tid == 0) {
@@ -265,14 +270,17 @@ __global__ __launch_bounds__(256) void heads_loss_grad_kernel(const LossArgs p) 
         for (int c = 1; c < C; ++c) if (l[c] > mx) { mx = l[c]; am = c; }
         float s = 0.f;
         for (int c = 0; c < C; ++c) s += expf(l[c] - mx);
-        const float k = p.w2 * (float)p.active[am] / pa_sum;
+        float k = p.w2 * (float)p.active[am] / pa_sum;
+        if (p.cw) k *= u;
         for (int c = 0; c < C; ++c)
             p.d_cls_logits[row * C + c] = (expf(l[c] - mx) / s - (c == cls ? 1.f : 0.f)) * k;
     }
+    float kb = p.w3 / (npos * 4.f), kd = p.w4, km = p.w4 / (npos * (float)npix);      // per-row factors of the three gradients
+    if (p.cw) { kb *= u; kd *= u; km *= u; }
     for (int i = tid; i < C * 4; i += 256) {
         float g = 0.f;
         const int c = i >> 2, e = i & 3;
-        if (cls > 0 && c == cls) g = smooth_l1_grad(p.tbbox[row * 4 + e], p.mbbox[(row * C + c) * 4 + e]) * (p.w3 / (npos * 4.f));
+        if (cls > 0 && c == cls) g = smooth_l1_grad(p.tbbox[row * 4 + e], p.mbbox[(row * C + c) * 4 + e]) * kb;
         p.d_mbbox[row * C * 4 + i] = g;
     }
     const float eps = 1e-7f;
@@ -286,7 +294,7 @@ __global__ __launch_bounds__(256) void heads_loss_grad_kernel(const LossArgs p) 
             const float y = p.tmask[row * npix + pix];
             const float q = p.mmask[row * npix * C + i];
             if (p.dice) {
-                g = -(2.f * y * D - I2) / (D * D) * p.w4;
+                g = -(2.f * y * D - I2) / (D * D) * kd;
             } else if (q >= eps && q <= 1.f - eps) {
                 // TF autodiff of max(x,0) - x*y + log1p(exp(-|x|)) with x = log(q/(1-q)):
                 // relu'(0) = 0 and sign(0) = 0, so the value at x == 0 is -y (not sigmoid(0) - y)
@@ -294,7 +302,7 @@ __global__ __launch_bounds__(256) void heads_loss_grad_kernel(const LossArgs p) 
                 const float e = expf(-fabsf(x));
                 const float sg = x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);
                 const float gx = (x > 0.f ? 1.f : 0.f) - y - sg * e / (1.f + e);
-                g = gx / (q * (1.f - q)) * (p.w4 / (npos * (float)npix));
+                g = gx / (q * (1.f - q)) * km;
             }
         }
         p.d_mmask[row * npix * C + i] = g;
@@ -307,14 +315,15 @@ extern "C" size_t mrcnn_losses_workspace(const mrcnn_loss_desc* d) {
     return 256 + S_NUM * sizeof(float) + (size_t)d->B * d->A * sizeof(int32_t) + parts * sizeof(float);
 }
 
-extern "C" int mrcnn_losses_fwd_bwd(const mrcnn_loss_desc* d, const int32_t* rpn_match, const float* rpn_bbox_t,
-                                    const float* rpn_class_logits, const float* rpn_bbox,
-                                    const int32_t* target_class_ids, const float* target_bbox,
-                                    const float* target_mask, const int32_t* active_class_ids,
-                                    const float* mrcnn_class_logits, const float* mrcnn_bbox,
-                                    const float* mrcnn_mask, float* losses, float* d_rpn_class_logits,
-                                    float* d_rpn_bbox, float* d_mrcnn_class_logits, float* d_mrcnn_bbox,
-                                    float* d_mrcnn_mask, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int mrcnn_losses_fwd_bwd_weighted(const mrcnn_loss_desc* d, const int32_t* rpn_match, const float* rpn_bbox_t,
+                                             const float* rpn_class_logits, const float* rpn_bbox,
+                                             const int32_t* target_class_ids, const float* target_bbox,
+                                             const float* target_mask, const int32_t* active_class_ids,
+                                             const float* mrcnn_class_logits, const float* mrcnn_bbox,
+                                             const float* mrcnn_mask, const float* class_weights, float* losses,
+                                             float* d_rpn_class_logits, float* d_rpn_bbox, float* d_mrcnn_class_logits,
+                                             float* d_mrcnn_bbox, float* d_mrcnn_mask, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
     if (!d || !rpn_match || !rpn_bbox_t || !rpn_class_logits || !rpn_bbox || !target_class_ids || !target_bbox ||
         !target_mask || !active_class_ids || !mrcnn_class_logits || !mrcnn_bbox || !mrcnn_mask || !losses ||
         !d_rpn_class_logits || !d_rpn_bbox || !d_mrcnn_class_logits || !d_mrcnn_bbox || !d_mrcnn_mask || !workspace)
@@ -336,6 +345,7 @@ extern "C" int mrcnn_losses_fwd_bwd(const mrcnn_loss_desc* d, const int32_t* rpn
     a.B = d->B; a.A = d->A; a.T = d->T; a.C = d->C; a.mh = d->mask_h; a.mw = d->mask_w;
     a.max_rpn_pos = d->max_rpn_pos; a.dice = d->mask_loss_dice;
     a.w0 = d->w[0]; a.w1 = d->w[1]; a.w2 = d->w[2]; a.w3 = d->w[3]; a.w4 = d->w[4];
+    a.cw = class_weights;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(rpn_loss_reduce_kernel, dim3(d->B), dim3(1024), 0, s, a);
     hipLaunchKernelGGL(heads_loss_reduce_kernel, dim3((unsigned)(d->B * d->T)), dim3(256), 0, s, a);
@@ -344,4 +354,18 @@ extern "C" int mrcnn_losses_fwd_bwd(const mrcnn_loss_desc* d, const int32_t* rpn
     hipLaunchKernelGGL(rpn_loss_grad_kernel, dim3((unsigned)cdiv64(na, 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(heads_loss_grad_kernel, dim3((unsigned)(d->B * d->T)), dim3(256), 0, s, a);
     return mrcnn_launch_status();
+}
+
+extern "C" int mrcnn_losses_fwd_bwd(const mrcnn_loss_desc* d, const int32_t* rpn_match, const float* rpn_bbox_t,
+                                    const float* rpn_class_logits, const float* rpn_bbox,
+                                    const int32_t* target_class_ids, const float* target_bbox,
+                                    const float* target_mask, const int32_t* active_class_ids,
+                                    const float* mrcnn_class_logits, const float* mrcnn_bbox,
+                                    const float* mrcnn_mask, float* losses, float* d_rpn_class_logits,
+                                    float* d_rpn_bbox, float* d_mrcnn_class_logits, float* d_mrcnn_bbox,
+                                    float* d_mrcnn_mask, void* workspace, size_t workspace_bytes, void* stream) {
+    return mrcnn_losses_fwd_bwd_weighted(d, rpn_match, rpn_bbox_t, rpn_class_logits, rpn_bbox, target_class_ids, target_bbox,
+                                         target_mask, active_class_ids, mrcnn_class_logits, mrcnn_bbox, mrcnn_mask, nullptr,
+                                         losses, d_rpn_class_logits, d_rpn_bbox, d_mrcnn_class_logits, d_mrcnn_bbox,
+                                         d_mrcnn_mask, workspace, workspace_bytes, stream);
 }

@@ -228,6 +228,8 @@ class SourceDataset(Dataset):
         return self.image_info[image_id]['metadata']
 
     def compute_class_weights(self):
-        tot = float(sum(self.nobjs_per_class[1:])) or 1.0
-        return {i: (tot / (len(self.nobjs_per_class) - 1) / n if n > 0 else 1.0)
-                for i, n in enumerate(self.nobjs_per_class)}
+        """{class_id: nobjs / (nclasses_with_objects * nobjs_k)}, and 1.0 for a class without objects, the background included
+        (run.py:785-808): the classes that HAVE objects share the total evenly, so the object-weighted mean of the weights is 1."""
+        populated = [n for n in self.nobjs_per_class if n > 0]
+        nobjs, nclasses = float(sum(populated)), float(len(populated))
+        return {i: (nobjs / (nclasses * float(n)) if n > 0 else 1.0) for i, n in enumerate(self.nobjs_per_class)}

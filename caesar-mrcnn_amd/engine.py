@@ -311,6 +311,7 @@ class MaskRCNNEngine(object):
         self.grad_ranges = {"heads": (hd, L.gamma_offset), "tail": (fp, hd), 5: (s5, fp), 4: (s4, s5), 3: (s3, s4),
                             2: (s2, s3), "head": (0, s2), "bn": (L.gamma_offset, L.total)}
         self.grad_ready = None          # callable(start, end) or None
+        self.class_weights = None       # [C] device buffer of set_class_weights, or None: the head losses are unweighted
         self.forced_rpn_rois = None     # test hook: [B, POST_NMS_ROIS_TRAINING, 4] used instead of the ProposalLayer's output
         self.loss_scale = 4096.0
         self.skipped_steps = torch.zeros(1, dtype=torch.int32, device=device)   # steps the guarded optimiser refused (float16)
@@ -808,6 +809,22 @@ class MaskRCNNEngine(object):
             self._train_tapes, self._train_graphs = {}, {}
         self.gran_coef.copy_(coef)           # (the backward pass computes every gradient whatever the mask: the mask acts here only)
 
+    def set_class_weights(self, vector):
+        """Class weights of the three head losses: a float32 [NUM_CLASSES] vector of positive finite weights
+        (utils.class_weight_vector), or None for the unweighted losses."""
+        if vector is None:
+            self.class_weights = None                # (_mode_key: recordings made with weights are not replayed without)
+            return
+        cw = torch.as_tensor(np.asarray(vector, dtype=np.float32))
+        if tuple(cw.shape) != (self.cfg.NUM_CLASSES,):
+            raise ValueError("class weights must have shape [%d] (got %s)" % (self.cfg.NUM_CLASSES, tuple(cw.shape)))
+        # ONE buffer for the life of the engine, refreshed in place like gran_coef: recorded launch tapes and captured step
+        # graphs carry its address in their loss call, so they survive a change of the values
+        if getattr(self, "_class_weights_buf", None) is None:
+            self._class_weights_buf = torch.empty(self.cfg.NUM_CLASSES, dtype=torch.float32, device=self.dev)
+        self._class_weights_buf.copy_(cw)
+        self.class_weights = self._class_weights_buf
+
     # ---- anchors -------------------------------------------------------------------------------
     def anchors(self, image_shape):
         from . import utils
@@ -1147,7 +1164,7 @@ class MaskRCNNEngine(object):
             mmask = full
         out = ops.losses_fwd_bwd(rpn_match, rpn_bbox_t, rpn_logits, rpn_bbox, tcls, tbbox, tmask, active_class_ids,
                                  logits, mbbox, mmask, self.loss_weights(),
-                                 cfg.MASK_LOSS_FUNCTION == "dice_coef_loss")
+                                 cfg.MASK_LOSS_FUNCTION == "dice_coef_loss", class_weights=self.class_weights)
         losses, d_rpn_logits, d_rpn_bbox, d_logits, d_mbbox, d_mmask = out
         _hip_mod.ev_wait(main, prep_ev)
         assert self._wt_gen == self._gen, "the backward pass reads the flipped kernels of the current weights"
@@ -1516,9 +1533,10 @@ class MaskRCNNEngine(object):
         mode it was made in (tests and tools flip these attributes between steps of one engine)."""
         # ... and what a launch bakes in by VALUE: the loss weights and the clip norm are scalar arguments of recorded calls
         # (cfg is mutable: run.py patches it in place).  The trainable mask / weight decay live in gran_coef, a buffer with a
-        # stable address that set_trainable refreshes in place, so recordings survive a change of `layers`.
+        # stable address that set_trainable refreshes in place, so recordings survive a change of `layers`.  The class weights
+        # are such a buffer too (set_class_weights); WHETHER the loss call reads one is baked in (another C-ABI entry).
         return _TRAIN_SWITCHES(self) + (float(self.loss_scale), self.forced_rpn_rois is not None, tuple(self.loss_weights()),
-                                        float(self.cfg.GRADIENT_CLIP_NORM))
+                                        float(self.cfg.GRADIENT_CLIP_NORM), self.class_weights is not None)
 
     @contextlib.contextmanager
     def _rolled_back(self):

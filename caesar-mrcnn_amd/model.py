@@ -171,6 +171,17 @@ class MaskRCNN(object):
                 print('Will not include %s in total loss ...' % name)
         print("Optimizer SGD: lr=%f, momentum=%f, clipnorm=%f" % (learning_rate, momentum, self.config.GRADIENT_CLIP_NORM))
         print("weight_decay=%f" % (self.config.WEIGHT_DECAY))
+        if getattr(self, "class_weights", None) is not None:
+            print("Class weights of the head losses: [%s]" % ", ".join("%g" % v for v in self.class_weights))
+
+    def set_class_weights(self, weights):
+        """Class weights of the three head losses: a dict {class_id: weight} (missing ids weigh 1.0) or a
+        sequence of NUM_CLASSES weights, index 0 the background; None switches them off.  Every ROI row of mrcnn_class_loss,
+        mrcnn_bbox_loss and mrcnn_mask_loss is multiplied by the weight of its target class, the normalisers stay plain counts;
+        the RPN losses do not change."""
+        vec = None if weights is None else utils.class_weight_vector(weights, self.config.NUM_CLASSES)
+        self.engine.set_class_weights(vec)
+        self.class_weights = vec
 
     def set_trainable(self, layer_regex, keras_model=None, indent=0, verbose=1):
         if verbose > 0:
@@ -297,7 +308,11 @@ class MaskRCNN(object):
               custom_callbacks=None, no_augmentation_sources=None, n_worker_threads=-1, class_weights=None,
               draw_loss=False):
         """Training loop (mrcnn/model.py:2395-2517): ``epochs`` is the total target epoch, one weight
-        file per epoch under log_dir, validation losses per epoch; returns None."""
+        file per epoch under log_dir, validation losses per epoch; returns None.
+
+        class_weights (set_class_weights; None: Config.CLASS_WEIGHTS, and when that is None too, whatever set_class_weights
+        left on the model) weigh the head losses of the training steps AND of the validation steps, so that ``loss`` and
+        ``val_loss`` stay comparable."""
         assert self.mode == "training", "Create model in training mode."
         import torch
         from .parallel import GradReducer, allreduce_mean_scalars, init_distributed
@@ -332,6 +347,10 @@ class MaskRCNN(object):
             os.makedirs(self.log_dir)
         log("\nStarting at epoch {}. LR={}\n".format(self.epoch, learning_rate))
         log("Checkpoint Path: {}".format(self.checkpoint_path))
+        if class_weights is None:
+            class_weights = getattr(cfg, "CLASS_WEIGHTS", None)
+        if class_weights is not None:
+            self.set_class_weights(class_weights)
         self.set_trainable(layers, verbose=1 if rank == 0 else 0)
         self.compile(learning_rate, cfg.LEARNING_MOMENTUM)
         reducer = GradReducer(self.engine.grads, world) if world > 1 else None

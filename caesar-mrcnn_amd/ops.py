@@ -639,8 +639,19 @@ def detections(rois, probs, deltas, windows, max_instances, min_confidence, nms_
 
 
 def losses_fwd_bwd(rpn_match, rpn_bbox_t, rpn_logits, rpn_bbox, tcls, tbbox, tmask, active_class_ids, cls_logits,
-                   mbbox, mmask, weights, dice=False):
-    """Returns (losses[5], d_rpn_logits, d_rpn_bbox, d_cls_logits, d_mbbox, d_mmask)."""
+                   mbbox, mmask, weights, dice=False, class_weights=None):
+    """Returns (losses[5], d_rpn_logits, d_rpn_bbox, d_cls_logits, d_mbbox, d_mmask).
+
+    class_weights: None, or a float32 device tensor [C] of positive finite class weights (index 0 the background) that every ROI
+    row of the three head losses carries by its target class.  None takes the unweighted entry."""
+    if class_weights is not None:
+        if not torch.is_tensor(class_weights) or class_weights.dtype != torch.float32:
+            raise ValueError("class_weights must be a float32 tensor (got %s)" % getattr(class_weights, "dtype", type(class_weights)))
+        if tuple(class_weights.shape) != (cls_logits.shape[2],):
+            raise ValueError("class_weights must have shape [%d], one weight per model class (got %s)"
+                             % (cls_logits.shape[2], tuple(class_weights.shape)))
+        if class_weights.device != cls_logits.device or not class_weights.is_contiguous():
+            raise ValueError("class_weights must be a contiguous tensor on %s (got %s)" % (cls_logits.device, class_weights.device))
     _need_cuda(rpn_match, rpn_bbox_t, rpn_logits, rpn_bbox, tcls, tbbox, tmask, active_class_ids, cls_logits, mbbox,
                mmask)
     d = _hip.LossDesc()
@@ -656,6 +667,14 @@ def losses_fwd_bwd(rpn_match, rpn_bbox_t, rpn_logits, rpn_bbox, tcls, tbbox, tma
     g = [empty_like(t) for t in (rpn_logits, rpn_bbox, cls_logits, mbbox, mmask)]
     nbytes = _hip.lib().mrcnn_losses_workspace(C.byref(d))
     ws = workspace(nbytes, dev, "losses")
+    if class_weights is not None:
+        check(_hip.lib().mrcnn_losses_fwd_bwd_weighted(C.byref(d), ptr(rpn_match), ptr(rpn_bbox_t), ptr(rpn_logits), ptr(rpn_bbox),
+                                                       ptr(tcls), ptr(tbbox), ptr(tmask), ptr(active_class_ids), ptr(cls_logits),
+                                                       ptr(mbbox), ptr(mmask), ptr(class_weights), ptr(losses), ptr(g[0]),
+                                                       ptr(g[1]), ptr(g[2]), ptr(g[3]), ptr(g[4]), ptr(ws), ws.numel(),
+                                                       current_stream()),
+              "mrcnn_losses_fwd_bwd_weighted")
+        return (losses,) + tuple(g)
     check(_hip.lib().mrcnn_losses_fwd_bwd(C.byref(d), ptr(rpn_match), ptr(rpn_bbox_t), ptr(rpn_logits), ptr(rpn_bbox),
                                           ptr(tcls), ptr(tbbox), ptr(tmask), ptr(active_class_ids), ptr(cls_logits),
                                           ptr(mbbox), ptr(mmask), ptr(losses), ptr(g[0]), ptr(g[1]), ptr(g[2]),

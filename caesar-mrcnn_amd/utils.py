@@ -403,3 +403,26 @@ def compute_ap_range(gt_box, gt_class_id, gt_mask, pred_box, pred_class_id, pred
     if verbose:
         print("AP @{:.2f}-{:.2f}:\t {:.3f}".format(iou_thresholds[0], iou_thresholds[-1], mean))
     return mean
+
+
+def class_weight_vector(weights, num_classes):
+    """The class weights of the head losses as a float32 [num_classes] vector, index 0 the background.
+    `weights`: a dict {class_id: weight} -- ids it does not name weigh 1.0 -- or a sequence of num_classes weights.
+    ValueError for an id outside [0, num_classes), a sequence of another length, or a weight that is not finite and > 0."""
+    C = int(num_classes)
+    vec = np.ones(C, dtype=np.float64)
+    if isinstance(weights, dict):
+        for cid, w in weights.items():
+            if isinstance(cid, (bool, float)) or int(cid) != cid or not 0 <= int(cid) < C:
+                raise ValueError("class weight for class id %r: the model has the ids 0..%d" % (cid, C - 1))
+            vec[int(cid)] = float(w)
+    else:
+        seq = np.asarray(weights, dtype=np.float64)
+        if seq.shape != (C,):
+            raise ValueError("class weights: %d weights expected, one per model class (got shape %r)" % (C, seq.shape))
+        vec = seq
+    with np.errstate(over="ignore"):
+        vec = vec.astype(np.float32)
+    if not np.all(np.isfinite(vec) & (vec > 0)):           # (as float32: what the kernels read)
+        raise ValueError("class weights must be finite and > 0 (got %s)" % vec.tolist())
+    return vec

@@ -983,6 +983,23 @@ int mrcnn_losses_fwd_bwd(const mrcnn_loss_desc* d, const int32_t* rpn_match, con
                          const float* mrcnn_mask, float* losses, float* d_rpn_class_logits,
                          float* d_rpn_bbox, float* d_mrcnn_class_logits, float* d_mrcnn_bbox,
                          float* d_mrcnn_mask, void* workspace, size_t workspace_bytes, void* stream);
+/* The same with class weights on the three head losses.  class_weights: device, [C] positive finite floats,
+ * index 0 the background; NULL = unweighted, which is mrcnn_losses_fwd_bwd.  Every ROI row r carries
+ * u_r = class_weights[target_class_ids[r]]:
+ *   mrcnn_class = sum(u ce pa) / sum(pa)            mrcnn_bbox = sum_pos(u smooth_l1) / (4 npos)
+ *   mrcnn_mask  = sum_pos(u sum_pix bce) / (npos npix), or with mask_loss_dice
+ *                 1 - (2 sum(u y q) + s) / (sum(u y) + sum(u q) + s)
+ * The normalisers stay plain counts, the two RPN losses and their gradients do not change, and weights of one give the
+ * unweighted result bit for bit.  target_class_ids in [0, C) is the caller's precondition, as it is for the class logits. */
+int mrcnn_losses_fwd_bwd_weighted(const mrcnn_loss_desc* d, const int32_t* rpn_match, const float* rpn_bbox_t,
+                                  const float* rpn_class_logits, const float* rpn_bbox,
+                                  const int32_t* target_class_ids, const float* target_bbox,
+                                  const float* target_mask, const int32_t* active_class_ids,
+                                  const float* mrcnn_class_logits, const float* mrcnn_bbox,
+                                  const float* mrcnn_mask, const float* class_weights, float* losses,
+                                  float* d_rpn_class_logits, float* d_rpn_bbox, float* d_mrcnn_class_logits,
+                                  float* d_mrcnn_bbox, float* d_mrcnn_mask, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 
 /* keras.optimizers.SGD(lr, momentum, clipnorm) + L2/numel regulariser (mrcnn/model.py:2255-2291) on
  * flat buffers of n floats (n % 64 == 0).  gran_coef[n/64] describes each 64-float granule (every

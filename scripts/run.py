@@ -281,6 +281,24 @@ def build_augmentation(args):
     return aug
 
 
+def weight_classes_refusal(class_dict, class_dict_model):
+    """--weight_classes: the weights are indexed by the model's class ids.  The message that refuses a training class
+    dictionary with an id the model does not have, or None."""
+    num_classes = len(class_dict_model) + 1
+    bad = {k: v for k, v in class_dict.items() if not (isinstance(v, int) and 0 <= v < num_classes)}
+    if not bad:
+        return None
+    return ("--weight_classes: class id(s) %s of --classdict are outside the model's %d classes (ids 0..%d, --classdict_model): "
+            "their objects would have no weight" % (", ".join("%s=%r" % kv for kv in sorted(bad.items(), key=str)), num_classes,
+                                                    num_classes - 1))
+
+
+def log_class_weights(weights, cfg):
+    names = list(getattr(cfg, "CLASS_NAMES", []))
+    for cid, w in sorted(weights.items()):
+        logger.info("Class weight of %s (id %d): %g" % (names[cid] if cid < len(names) else "?", cid, w))
+
+
 def train(args, model, cfg):
     src = args.datadir if args.dataloader == 'datadir_json' else (args.datalist_train or args.datalist)
     ds_train = make_dataset(args, src)
@@ -291,8 +309,12 @@ def train(args, model, cfg):
     cfg.STEPS_PER_EPOCH = args.epoch_length or max(1, len(ds_train.image_ids) // (cfg.IMAGES_PER_GPU * world))
     cfg.VALIDATION_STEPS = args.nvalidation_steps or max(1, len(ds_val.image_ids) // (cfg.IMAGES_PER_GPU * world))
     aug = build_augmentation(args)
+    class_weights = None
+    if args.weight_classes:                # (main() has refused a training dictionary with ids the model does not have)
+        class_weights = ds_train.compute_class_weights()
+        log_class_weights(class_weights, cfg)
     model.train(ds_train, ds_val, learning_rate=cfg.LEARNING_RATE, epochs=args.nepochs, layers='all', augmentation=aug,
-                n_worker_threads=args.nthreads, class_weights=ds_train.compute_class_weights() if args.weight_classes else None)
+                n_worker_threads=args.nthreads, class_weights=class_weights)
     return 0
 
 
@@ -466,6 +488,11 @@ def main(argv=None):
     except Exception:
         logger.error("Failed to convert class dict string to dict!")
         return 1
+    if args.command == "train" and args.weight_classes:
+        refusal = weight_classes_refusal(class_dict, class_dict_model)
+        if refusal:
+            logger.error(refusal)
+            return 1
     if not (args.command == "detect" and args.split_img_in_tiles and args.merge_tile_sources):
         mosaic_settings(args)                    # the one warning for flags that mean nothing here
     from caesar_mrcnn_amd import model as modellib
